@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """bench.py — env-steps/s of the batched gym-auv step() hot path on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
 
 `python bench.py --gpus N` without a launcher starts its N ranks itself (one process per GPU).
@@ -21,7 +21,11 @@ chains on K streams, no ordering between them inside the timed region (the actio
 GPU -- one chain's sweeps run under another's dynamics chain and navigation tail.  Same envs, same results as K = 1,
 bit for bit (tests/test_gpu_parity.py::test_sub_batches_bitwise).
 
-Prints ONE JSON line (rank 0) with the driver's contract plus
+Prints ONE JSON line (rank 0): metric, value (env-steps/s), unit, higher_is_better, dtype, steps, warmup, ms_per_step (one timed
+step) and `config` (what was timed).  A plain run does nothing else: set-up (world bank, the shape calibration below), warm-up, the
+timed steps, --dump-outputs.  `--dump-outputs DIR` writes what the last timed step returned (obs, reward, done, info) as
+DIR/<name>.npy; the inputs (worlds, actions) depend on the arguments only, so two builds compare output for output.
+--full measures more after the timed region (figures of their own, never mixed into `value`) and adds to the line
   roofline      the step's dominant kernel: k_step_multi (T steps per launch: `avg_ms` = a run of back-to-back launches between one
                 pair of HIP events on the chain's stream / their number, `alone_ms` = one launch by itself) or k_step_roles (one
                 step per launch).  `kernels[...]`: its launch duration by HIP events on its own
@@ -34,6 +38,8 @@ Prints ONE JSON line (rank 0) with the driver's contract plus
                 committed SQ pass / (1024 SIMDs x clock x measured time per step), `wait_frac` = SQ_WAIT_ANY /
                 SQ_WAVE_CYCLES; both carry the sha256 of the library they were measured on and `stale: true` when this
                 process runs another one.  `bound`: the larger leg, or "latency" when neither reaches 0.6.
+  comparison    rank 0 at N = 1: the same envs driven the other ways (one chain, the VecEnv rendezvous, one-step chains, 64 steps
+                per launch, the policy in the loop; with --fresh-worlds the bank-cycling rate of the same loop)
   cpu_baseline  the CPU oracle (a C port of the reference algorithm) timed on this box's host cores on a bounded sample of
                 the same workload (median of 5 repeats of 500 steps), plus the reference's own
                 Python step() as measured in the build container (a stated constant, never run here).
@@ -53,6 +59,7 @@ import torch  # noqa: E402
 HBM_PEAK_GBS = 8000.0          # MI355X HBM3E spec peak (MI355X_MICROARCH.md)
 N_SIMD = 256 * 4               # 256 CUs x 4 SIMD-32 (MI355X_MICROARCH.md)
 CLOCK_PEAK_GHZ = 2.4           # max shader clock (MI355X_MICROARCH.md): the VALU leg's peak is N_SIMD x this
+DUMP_BUDGET = 64 << 20         # --dump-outputs: bytes at most, over all ranks
 
 
 def parse():
@@ -111,7 +118,13 @@ def parse():
     ap.add_argument("--probe-streams", type=int, default=1,
                     help="0: take any K streams for the sub-batch chains instead of K that were measured to run side by side "
                          "(for runs under a counter-collecting profiler, which serialises dispatches)")
-    ap.add_argument("--cpu-baseline", type=int, default=1)
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: the roofline (per-kernel timing, counter legs), the other "
+                         "ways of driving the same envs (`comparison`) and the CPU baseline.  Off: set up, warm up, time, report")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="write what the timed loop's last step returned (obs, reward, done, info) as DIR/<name>.npy (float32 / float64, "
+                         "a fixed sample of the envs beyond %d MB), so that two builds can be compared output for output" % (DUMP_BUDGET >> 20))
+    ap.add_argument("--cpu-baseline", type=int, default=1, help="--full: 0 skips the CPU baseline")
     ap.add_argument("--procs", type=int, default=0, help="world-generation worker processes (0 = auto)")
     ap.add_argument("--bank-cache", default="auto",
                     help="path prefix: save / load the rank's generated world bank (.npz, keyed by workload, shard and bank size).  "
@@ -261,6 +274,24 @@ def device_bank_summary(env):
     M = env.m_max if env._gen.n_moving else 0
     return dict(n_worlds=W, poly_off=np.r_[0, np.cumsum(cnt)], obs_off=np.arange(W + 1, dtype=np.int64) * K,
                 mv_off=np.arange(W + 1, dtype=np.int64) * M, obs_meta=meta.reshape(W * K, 4))
+
+
+def dump_outputs(env, path, rank, world):
+    """--dump-outputs: what a caller of the timed loop holds after its last step -- obs [n, obs_dim] f32, reward [n] f32, done [n]
+    (as f32) and info [n, 4] f64 (collision, reached_goal, goal_distance, progress) -- as <path>/<name>.npy, <name>_rank<r>.npy with
+    several ranks.  Beyond DUMP_BUDGET the same fixed sample of envs (RandomState(0), sorted) from every array, its indices in
+    env_index.npy."""
+    arrays = dict(obs=env.obs.float(), reward=env.reward.float(), done=env.done.float(), info=env.read("STEP_INFO"))
+    arrays = {k: v.cpu().numpy() for k, v in arrays.items()}
+    n = env.n_envs
+    per_env = sum(a.nbytes for a in arrays.values()) // n
+    cap = DUMP_BUDGET // world // (per_env + 8)
+    if n > cap:
+        rows = np.sort(np.random.RandomState(0).choice(n, cap, replace=False))
+        arrays = dict({k: a[rows] for k, a in arrays.items()}, env_index=rows.astype(np.float64))
+    os.makedirs(path, exist_ok=True)
+    for k, a in arrays.items():
+        np.save(os.path.join(path, "%s%s.npy" % (k, "_rank%d" % rank if world > 1 else "")), a)
 
 
 def world_seeds(lo, n_local, total_envs, worlds_per_env):
@@ -556,6 +587,8 @@ def main():
     D.barrier()
     torch.cuda.synchronize(dev)
     elapsed = D.max_over_ranks(elapsed, dev)
+    if args.dump_outputs:
+        dump_outputs(env, args.dump_outputs, rank, world)
     # the only exchange of the path: episode returns for reporting, RCCL all_gather over xGMI -- timed on its own (second call:
     # the first one pays the communicator's lazy set-up), outside the timed region
     ep_stats = env.episode_stats()
@@ -571,92 +604,95 @@ def main():
         api = "step"
     per_rank = D.gather_floats([t_gen, t_probe, float(bank_from_cache), float(sub), 1e3 * elapsed_local / args.steps, 1e3 * t_ag], dev)
 
-    world_of_env = env.read("WORLD_IDX").cpu().numpy()
-    nearby = env.read("NEARBY").cpu().numpy()
+    # ---- --full: the roofline (per-kernel timing after the timed region, committed counter legs)
+    roofline = None
+    if args.full:
+        world_of_env = env.read("WORLD_IDX").cpu().numpy()
+        nearby = env.read("NEARBY").cpu().numpy()
 
-    # ---- per-kernel timing with HIP events on the launch stream(s) (same workload, same process)
-    n_prof = min(max(args.steps, 20), 100)
-    alg = algorithmic_bytes(bank, S, world_of_env, nearby)
-    step_bytes = sum(alg[ph] for ph in ("k1", "lidar", "nav", "reward"))
-    pipelined = sub > 1 and env.effective_step_mode(max(1, n_local // sub)) == "one_launch"
-    if api == "multi":
-        # a run of back-to-back launches of multi_T steps bracketed by ONE pair of HIP events per chain, on that chain's stream (the
-        # stream is in order: the pair encloses exactly those launches, as the timed region issues them) => average launch duration;
-        # `alone_ms`: one launch between its own pair of events (its ramp and drain not hidden under its neighbours)
-        n_launch = max(4, min(max(args.steps, 1024) // multi_T, 24))      # (16 launches of 64 steps; the driver's 20 steps: 24 launches of 20)
-        evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in env._sub_streams]
-        ev1 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in env._sub_streams]
-        for (a, _), stq in zip(evs, env._sub_streams):
-            a.record(stq)
-        for j in range(n_launch):
-            env.step_multi(pool, (j * multi_T) % n_pool, multi_T)
-        for (_, b), stq in zip(evs, env._sub_streams):
-            b.record(stq)
-        torch.cuda.synchronize(dev)
-        for (a, _), stq in zip(ev1, env._sub_streams):
-            a.record(stq)
-        env.step_multi(pool, 0, multi_T)
-        for (_, b), stq in zip(ev1, env._sub_streams):
-            b.record(stq)
-        torch.cuda.synchronize(dev)
-        lms = np.array([a.elapsed_time(b) / n_launch for a, b in evs])      # ms per launch, per chain
-        alone = np.array([a.elapsed_time(b) for a, b in ev1])
-        names = ["k_step_multi"]
-        kms = np.array([lms.mean(), 0.0, 0.0, lms.max()])
-        launch_bytes = step_bytes / env.sub_batches * multi_T
-        per_kernel = {"k_step_multi": dict(avg_ms=round(float(lms.mean()), 5), steps_per_launch=multi_T, launches_per_step=round(env.sub_batches / multi_T, 4),
-                                           algorithmic_bytes=int(launch_bytes),
-                                           achieved_GBs=round(launch_bytes / (lms.mean() * 1e-3) / 1e9, 1),
-                                           frac=round(launch_bytes / (lms.mean() * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                           per_slice_ms=[round(float(x), 5) for x in lms], launches_timed=n_launch,
-                                           alone_ms=round(float(alone.mean()), 5),
-                                           avg_ms_per_step=round(float(lms.mean()) / multi_T, 5))}
-    elif pipelined:
-        # every sub-batch launch stamped on its own stream while the other chains run beside it
-        lms = np.zeros(env.sub_batches)
-        for i in range(n_prof):
-            lms += np.array(env.step_pipelined_timed(pool[i % n_pool]))
-        lms /= n_prof
-        names = ["k_step_roles"]
-        kms = np.array([lms.mean(), 0.0, 0.0, lms.max()])
-        launch_bytes = step_bytes / env.sub_batches
-        per_kernel = {"k_step_roles": dict(avg_ms=round(float(lms.mean()), 5), launches_per_step=env.sub_batches,
-                                           algorithmic_bytes=int(launch_bytes),
-                                           achieved_GBs=round(launch_bytes / (lms.mean() * 1e-3) / 1e9, 1),
-                                           frac=round(launch_bytes / (lms.mean() * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
-                                           per_slice_ms=[round(float(x), 5) for x in lms])}
-    else:
-        kms = np.zeros(4)
-        for i in range(n_prof):
-            kms += np.array(env.step_timed(pool[i % n_pool]))
-        kms /= n_prof
-        names = env.timed_kernel_names()
-        per_kernel = {}
-        for j, nm in enumerate(names):
-            b = sum(alg[ph] for ph in KERNEL_PHASES[nm])
-            gbs = b / (kms[j] * 1e-3) / 1e9 if kms[j] > 0 else 0.0
-            per_kernel[nm] = dict(avg_ms=round(float(kms[j]), 5), launches_per_step=1, algorithmic_bytes=int(b),
-                                  achieved_GBs=round(gbs, 1), frac=round(gbs / HBM_PEAK_GBS, 4))
-    dom = max(names, key=lambda nm: per_kernel[nm]["avg_ms"])
-    per_kernel[dom].update(lidar_bytes=int(alg["lidar"]), nav_bytes=int(alg["nav"]),
-                           nearby_segments_per_env=round(alg["nearby_segments_per_env"], 1),
-                           all_segments_per_env=round(alg["all_segments_per_env"], 1),
-                           nav_bruteforce_bytes=int(alg["nav_bruteforce"]))
-    # HBM leg.  One chain: algorithmic bytes of the dominant launch / its HIP-event duration.  Sub-batch chains: the
-    # launches of a step run CONCURRENTLY, so one launch's bytes / duration is a quarter of what the chip moves; the
-    # leg is then all launches' bytes of a step / the measured time per step of the timed region (gaps included).
-    ms_step = 1e3 * elapsed / args.steps
-    if sub > 1:
-        achieved = step_bytes / (ms_step * 1e-3) / 1e9
-    else:
-        achieved = per_kernel[dom]["achieved_GBs"]
-    hbm_frac = round(achieved / HBM_PEAK_GBS, 4)
+        # ---- per-kernel timing with HIP events on the launch stream(s) (same workload, same process)
+        n_prof = min(max(args.steps, 20), 100)
+        alg = algorithmic_bytes(bank, S, world_of_env, nearby)
+        step_bytes = sum(alg[ph] for ph in ("k1", "lidar", "nav", "reward"))
+        pipelined = sub > 1 and env.effective_step_mode(max(1, n_local // sub)) == "one_launch"
+        if api == "multi":
+            # a run of back-to-back launches of multi_T steps bracketed by ONE pair of HIP events per chain, on that chain's stream (the
+            # stream is in order: the pair encloses exactly those launches, as the timed region issues them) => average launch duration;
+            # `alone_ms`: one launch between its own pair of events (its ramp and drain not hidden under its neighbours)
+            n_launch = max(4, min(max(args.steps, 1024) // multi_T, 24))      # (16 launches of 64 steps; a 20-step run: 24 launches of 20)
+            evs = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in env._sub_streams]
+            ev1 = [(torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)) for _ in env._sub_streams]
+            for (a, _), stq in zip(evs, env._sub_streams):
+                a.record(stq)
+            for j in range(n_launch):
+                env.step_multi(pool, (j * multi_T) % n_pool, multi_T)
+            for (_, b), stq in zip(evs, env._sub_streams):
+                b.record(stq)
+            torch.cuda.synchronize(dev)
+            for (a, _), stq in zip(ev1, env._sub_streams):
+                a.record(stq)
+            env.step_multi(pool, 0, multi_T)
+            for (_, b), stq in zip(ev1, env._sub_streams):
+                b.record(stq)
+            torch.cuda.synchronize(dev)
+            lms = np.array([a.elapsed_time(b) / n_launch for a, b in evs])      # ms per launch, per chain
+            alone = np.array([a.elapsed_time(b) for a, b in ev1])
+            names = ["k_step_multi"]
+            kms = np.array([lms.mean(), 0.0, 0.0, lms.max()])
+            launch_bytes = step_bytes / env.sub_batches * multi_T
+            per_kernel = {"k_step_multi": dict(avg_ms=round(float(lms.mean()), 5), steps_per_launch=multi_T, launches_per_step=round(env.sub_batches / multi_T, 4),
+                                               algorithmic_bytes=int(launch_bytes),
+                                               achieved_GBs=round(launch_bytes / (lms.mean() * 1e-3) / 1e9, 1),
+                                               frac=round(launch_bytes / (lms.mean() * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                               per_slice_ms=[round(float(x), 5) for x in lms], launches_timed=n_launch,
+                                               alone_ms=round(float(alone.mean()), 5),
+                                               avg_ms_per_step=round(float(lms.mean()) / multi_T, 5))}
+        elif pipelined:
+            # every sub-batch launch stamped on its own stream while the other chains run beside it
+            lms = np.zeros(env.sub_batches)
+            for i in range(n_prof):
+                lms += np.array(env.step_pipelined_timed(pool[i % n_pool]))
+            lms /= n_prof
+            names = ["k_step_roles"]
+            kms = np.array([lms.mean(), 0.0, 0.0, lms.max()])
+            launch_bytes = step_bytes / env.sub_batches
+            per_kernel = {"k_step_roles": dict(avg_ms=round(float(lms.mean()), 5), launches_per_step=env.sub_batches,
+                                               algorithmic_bytes=int(launch_bytes),
+                                               achieved_GBs=round(launch_bytes / (lms.mean() * 1e-3) / 1e9, 1),
+                                               frac=round(launch_bytes / (lms.mean() * 1e-3) / 1e9 / HBM_PEAK_GBS, 4),
+                                               per_slice_ms=[round(float(x), 5) for x in lms])}
+        else:
+            kms = np.zeros(4)
+            for i in range(n_prof):
+                kms += np.array(env.step_timed(pool[i % n_pool]))
+            kms /= n_prof
+            names = env.timed_kernel_names()
+            per_kernel = {}
+            for j, nm in enumerate(names):
+                b = sum(alg[ph] for ph in KERNEL_PHASES[nm])
+                gbs = b / (kms[j] * 1e-3) / 1e9 if kms[j] > 0 else 0.0
+                per_kernel[nm] = dict(avg_ms=round(float(kms[j]), 5), launches_per_step=1, algorithmic_bytes=int(b),
+                                      achieved_GBs=round(gbs, 1), frac=round(gbs / HBM_PEAK_GBS, 4))
+        dom = max(names, key=lambda nm: per_kernel[nm]["avg_ms"])
+        per_kernel[dom].update(lidar_bytes=int(alg["lidar"]), nav_bytes=int(alg["nav"]),
+                               nearby_segments_per_env=round(alg["nearby_segments_per_env"], 1),
+                               all_segments_per_env=round(alg["all_segments_per_env"], 1),
+                               nav_bruteforce_bytes=int(alg["nav_bruteforce"]))
+        # HBM leg.  One chain: algorithmic bytes of the dominant launch / its HIP-event duration.  Sub-batch chains: the
+        # launches of a step run CONCURRENTLY, so one launch's bytes / duration is a quarter of what the chip moves; the
+        # leg is then all launches' bytes of a step / the measured time per step of the timed region (gaps included).
+        ms_step = 1e3 * elapsed / args.steps
+        if sub > 1:
+            achieved = step_bytes / (ms_step * 1e-3) / 1e9
+        else:
+            achieved = per_kernel[dom]["achieved_GBs"]
+        hbm_frac = round(achieved / HBM_PEAK_GBS, 4)
 
     # ---- the same envs through the OTHER ways of driving them, beside the headline (rank 0 at N = 1; short, outside
     # the timed region): the headline loop is open-loop chain throughput, a VecEnv consumer that waits for every step
     # sees the rendezvous figure
     comparison = None
-    if rank == 0 and world == 1 and args.actions == "uniform" and not K and args.steps >= 20 and args.probe_streams:
+    if args.full and rank == 0 and world == 1 and args.actions == "uniform" and not K and args.steps >= 20 and args.probe_streams:
         n_cmp = 300
 
         def rate(fn):
@@ -748,7 +784,7 @@ def main():
     if fresh:
         torch.cuda.synchronize(dev)
         fresh_stats = env.fresh_stats()
-        if rank == 0 and world == 1 and not K and args.probe_streams:
+        if args.full and rank == 0 and world == 1 and not K and args.probe_streams:
             # beside it: the SAME loop (same steps, same chains) over a device-built bank of the same shape that just cycles
             # (w + N) % W -- the difference is what a fresh world per reset costs, generator and refill bookkeeping included
             from gym_auv_amd.devgen import GeneratedWorlds
@@ -775,60 +811,61 @@ def main():
                               bank_cycling_episodes=int(cyc.episode_stats()["episodes"].sum().item()))
             cyc.close()
 
-    lib_sha = library_sha256()
-    # the committed counter passes: of this very shape ("polygons50/sub1_T64": MULTI=64 tools/pmc_workload.sh) when there is one,
-    # otherwise of one step per launch over as many chains (k_step_roles: the device functions k_step_multi runs)
-    cfg_key = "%s/sub%d" % (args.workload, sub)
-    cfg_key_T = cfg_key + ("_T%d" % multi_T if multi_T > 1 else "")
+    if args.full:
+        lib_sha = library_sha256()
+        # the committed counter passes: of this very shape ("polygons50/sub1_T64": MULTI=64 tools/pmc_workload.sh) when there is one,
+        # otherwise of one step per launch over as many chains (k_step_roles: the device functions k_step_multi runs)
+        cfg_key = "%s/sub%d" % (args.workload, sub)
+        cfg_key_T = cfg_key + ("_T%d" % multi_T if multi_T > 1 else "")
 
-    def committed(name):
-        """per-STEP counters of the step's launches from the committed rocprofv3 passes (4096 envs per GPU, this
-        workload and sub-batch count), with the sha256 of the library they were measured on"""
-        path = os.path.join(ROOT, "profiles", name)
-        if n_local != 4096 or not os.path.exists(path):
-            return None
-        try:
-            tab = json.load(open(path))
-            k = cfg_key_T if cfg_key_T in tab else cfg_key
-            if multi_T > 1 and cfg_key_T not in tab:
-                # (no pass of this very launch length: the counters per STEP of another length of the same kernel, nearest first)
-                others = sorted((abs(int(x.rsplit("_T", 1)[1]) - multi_T), x) for x in tab if x.startswith(cfg_key + "_T"))
-                if others:
-                    k = others[0][1]
-            return dict(tab[k], key=k) if k in tab else None
-        except Exception:
-            return None
+        def committed(name):
+            """per-STEP counters of the step's launches from the committed rocprofv3 passes (4096 envs per GPU, this
+            workload and sub-batch count), with the sha256 of the library they were measured on"""
+            path = os.path.join(ROOT, "profiles", name)
+            if n_local != 4096 or not os.path.exists(path):
+                return None
+            try:
+                tab = json.load(open(path))
+                k = cfg_key_T if cfg_key_T in tab else cfg_key
+                if multi_T > 1 and cfg_key_T not in tab:
+                    # (no pass of this very launch length: the counters per STEP of another length of the same kernel, nearest first)
+                    others = sorted((abs(int(x.rsplit("_T", 1)[1]) - multi_T), x) for x in tab if x.startswith(cfg_key + "_T"))
+                    if others:
+                        k = others[0][1]
+                return dict(tab[k], key=k) if k in tab else None
+            except Exception:
+                return None
 
-    traffic = committed("pmc_traffic.json")
-    sq = committed("pmc_sq.json")
-    valu = None
-    if traffic is not None:
-        traffic = dict(traffic, stale=traffic.get("lib_sha256") != lib_sha)
-    if sq:
-        # SQ_ACTIVE_INST_VALU counts quad-cycles (4 shader cycles) in which a wave executes a VALU instruction, summed over
-        # waves and (here) over the launches of one step.  Issue capacity of a step = 1024 SIMDs x shader clock x time per
-        # step; the clock is the counter pass's own SQ_BUSY_CYCLES / 32 shader engines / kernel duration.
-        # `frac` prices the step against the PEAK clock (a lower bound of the share: the clock under load is lower);
-        # `frac_at_measured_clock` against the counter pass's own SQ_BUSY_CYCLES / 32 shader engines / dispatch duration
-        # (an upper bound: short launches do not keep every shader engine busy from first to last cycle).
-        issue = 4.0 * sq["SQ_ACTIVE_INST_VALU"]
-        cyc_step = CLOCK_PEAK_GHZ * 1e9 * ms_step * 1e-3
-        valu = dict(insts=int(sq["SQ_INSTS_VALU"]), issue_cycles=int(issue), step_cycles=int(cyc_step), clock_ghz=CLOCK_PEAK_GHZ,
-                    frac=round(issue / (N_SIMD * cyc_step), 4),
-                    frac_at_measured_clock=round(issue / (N_SIMD * sq["clock_ghz"] * 1e9 * ms_step * 1e-3), 4), measured_clock_ghz=sq["clock_ghz"],
-                    wait_frac=round(sq["SQ_WAIT_ANY"] / sq["SQ_WAVE_CYCLES"], 4) if sq.get("SQ_WAVE_CYCLES") else None,
-                    source="profiles/pmc_sq.json [%s]" % sq["key"], lib_sha256=sq.get("lib_sha256"),
-                    stale=sq.get("lib_sha256") != lib_sha)
-    legs = dict(hbm=hbm_frac, valu=valu["frac"] if valu else 0.0)
-    bound = max(legs, key=legs.get)
-    if max(legs.values()) < 0.6:
-        bound = "latency"      # neither leg saturated: the step is bound by dependent chains / occupancy, not by a pipe
-    # (achieved / peak / unit / frac are ALWAYS the HBM leg -- algorithmic bytes over measured time against 8 TB/s; `bound` names the
-    # larger of `legs`, or "latency" when neither reaches 0.6)
-    roofline = dict(bound=bound, kernel=dom, achieved=round(achieved, 1), peak=HBM_PEAK_GBS, unit="GB/s", frac=hbm_frac, frac_is_leg="hbm",
-                    traffic=traffic, valu=valu, wait_frac=valu["wait_frac"] if valu else None, legs=legs,
-                    step_bytes=int(step_bytes), concurrent_launches=sub if (pipelined or api == "multi") else 1, kernels=per_kernel,
-                    lib_sha256=lib_sha)
+        traffic = committed("pmc_traffic.json")
+        sq = committed("pmc_sq.json")
+        valu = None
+        if traffic is not None:
+            traffic = dict(traffic, stale=traffic.get("lib_sha256") != lib_sha)
+        if sq:
+            # SQ_ACTIVE_INST_VALU counts quad-cycles (4 shader cycles) in which a wave executes a VALU instruction, summed over
+            # waves and (here) over the launches of one step.  Issue capacity of a step = 1024 SIMDs x shader clock x time per
+            # step; the clock is the counter pass's own SQ_BUSY_CYCLES / 32 shader engines / kernel duration.
+            # `frac` prices the step against the PEAK clock (a lower bound of the share: the clock under load is lower);
+            # `frac_at_measured_clock` against the counter pass's own SQ_BUSY_CYCLES / 32 shader engines / dispatch duration
+            # (an upper bound: short launches do not keep every shader engine busy from first to last cycle).
+            issue = 4.0 * sq["SQ_ACTIVE_INST_VALU"]
+            cyc_step = CLOCK_PEAK_GHZ * 1e9 * ms_step * 1e-3
+            valu = dict(insts=int(sq["SQ_INSTS_VALU"]), issue_cycles=int(issue), step_cycles=int(cyc_step), clock_ghz=CLOCK_PEAK_GHZ,
+                        frac=round(issue / (N_SIMD * cyc_step), 4),
+                        frac_at_measured_clock=round(issue / (N_SIMD * sq["clock_ghz"] * 1e9 * ms_step * 1e-3), 4), measured_clock_ghz=sq["clock_ghz"],
+                        wait_frac=round(sq["SQ_WAIT_ANY"] / sq["SQ_WAVE_CYCLES"], 4) if sq.get("SQ_WAVE_CYCLES") else None,
+                        source="profiles/pmc_sq.json [%s]" % sq["key"], lib_sha256=sq.get("lib_sha256"),
+                        stale=sq.get("lib_sha256") != lib_sha)
+        legs = dict(hbm=hbm_frac, valu=valu["frac"] if valu else 0.0)
+        bound = max(legs, key=legs.get)
+        if max(legs.values()) < 0.6:
+            bound = "latency"      # neither leg saturated: the step is bound by dependent chains / occupancy, not by a pipe
+        # (achieved / peak / unit / frac are ALWAYS the HBM leg -- algorithmic bytes over measured time against 8 TB/s; `bound` names the
+        # larger of `legs`, or "latency" when neither reaches 0.6)
+        roofline = dict(bound=bound, kernel=dom, achieved=round(achieved, 1), peak=HBM_PEAK_GBS, unit="GB/s", frac=hbm_frac, frac_is_leg="hbm",
+                        traffic=traffic, valu=valu, wait_frac=valu["wait_frac"] if valu else None, legs=legs,
+                        step_bytes=int(step_bytes), concurrent_launches=sub if (pipelined or api == "multi") else 1, kernels=per_kernel,
+                        lib_sha256=lib_sha)
 
     loops = {"pipelined": "open loop: %d chains, no ordering between them or with a consumer (auv_step_pipelined)" % sub,
              "multi": "open loop: %d chains, %d consecutive steps per launch and chain (auv_step_multi; bit-identical to single-step launches)" % (sub, multi_T),
@@ -863,11 +900,13 @@ def main():
         cfg_out["lib_override"] = os.environ["AUV_HIP_LIB"]      # (the loader's A/B hook: say so when it is in use)
     out = dict(metric="env-steps/sec", value=round(value, 1), unit="env-steps/s", n_gpus=n_devices_used, steps=args.steps,
                warmup=args.warmup, ms_per_step=round(1e3 * elapsed / args.steps, 5), higher_is_better=True,
-               scaling="weak", vs_baseline=None, dtype="f64", data="synthetic", config=cfg_out, roofline=roofline)
+               scaling="weak", vs_baseline=None, dtype="f64", data="synthetic", config=cfg_out)
+    if roofline:
+        out["roofline"] = roofline
     if comparison:
         out["comparison"] = comparison
 
-    if rank == 0 and world == 1 and args.cpu_baseline:
+    if args.full and rank == 0 and world == 1 and args.cpu_baseline:
         if fresh:
             # (the oracle steps host-built worlds of the same scenario: the reference's generator through scenarios.py)
             cpu_bank = build_bank_parallel(gen, world_seeds(0, 1024, 1024, 2), procs=procs, **kwargs)

@@ -7,7 +7,7 @@ OUT=${OUT:-gpurun_out/r04/sweep_api.jsonl}
 mkdir -p "$(dirname "$OUT")"; : > "$OUT"
 run() {
   echo "== $*" >&2
-  timeout -k 10 300 python bench.py --steps "$STEPS" --warmup "$WARM" --cpu-baseline 0 "$@" 2>>"$OUT.err" | tail -n 1 |
+  timeout -k 10 300 python bench.py --full --steps "$STEPS" --warmup "$WARM" --cpu-baseline 0 "$@" 2>>"$OUT.err" | tail -n 1 |
     python -c "
 import json,sys
 l=sys.stdin.readline()

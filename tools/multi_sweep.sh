@@ -2,6 +2,7 @@
 mkdir -p gpurun_out/r05
 one() { # one <tag> <flags...>
   tag=$1; shift
+  set -- --full "$@"      # (the line's roofline is read below)
   timeout -k 10 200 python bench.py --bank-cache /tmp/bank --cpu-baseline 0 "$@" > gpurun_out/r05/sweep_$tag.json 2>/dev/null
   python -c "
 import json; d=json.load(open('gpurun_out/r05/sweep_$tag.json')); k=list(d['roofline']['kernels'].values())[0]

@@ -26,10 +26,10 @@ run() {   # run <name> <stdout file> <command ...>
   [ $rc = 0 ] || tail -3 $ERR
   return 0
 }
-B="python bench.py --bank-cache /tmp/bank"
+B="python bench.py --full --bank-cache /tmp/bank"
 run bench_polygons50 $OUT/bench_polygons50.json $B
 echo "headline: $(cut -c1-140 $OUT/bench_polygons50.json)"
-run bench_driver_command $OUT/bench_driver_command.json python bench.py --gpus 1 --steps 20 --warmup 5 --bank-cache /tmp/bank --cpu-baseline 0
+run bench_driver_command $OUT/bench_driver_command.json python bench.py --full --gpus 1 --steps 20 --warmup 5 --bank-cache /tmp/bank --cpu-baseline 0
 # several steps per launch (round 5): one chain x 64 / 16 steps, two chains x 64, one step per launch on four chains; the rate table by order
 run bench_polygons50_multi64_sub1 $OUT/bench_polygons50_multi64_sub1.json $B --multi 64 --sub-batches 1 --cpu-baseline 0
 run bench_polygons50_multi16_sub1 $OUT/bench_polygons50_multi16_sub1.json $B --multi 16 --sub-batches 1 --cpu-baseline 0
@@ -66,7 +66,7 @@ run bench_mixed47_8192_graph16_sub1 $OUT/bench_mixed47_8192_graph16_sub1.json $B
 run bench_mixed47_8192_graph16_chains4 $OUT/bench_mixed47_8192_graph16_chains4.json $B --workload mixed47 --envs 8192 --graph 16 --sub-batches 4 --steps 1920 --warmup 192 --cpu-baseline 0
 run bench_polygons50_32768 $OUT/bench_polygons50_32768.json $B --envs 32768 --steps 100 --warmup 20 --worlds-per-env 1 --cpu-baseline 0
 # two ranks started by bench.py itself, sharing the one GPU of this box (gloo instead of RCCL): the N > 1 code path on hardware
-run bench_2ranks_rehearsal_1gpu $OUT/bench_2ranks_rehearsal_1gpu.json python bench.py --gpus 2 --rehearse 1 --steps 500 --warmup 100 --bank-cache /tmp/bank --cpu-baseline 0
+run bench_2ranks_rehearsal_1gpu $OUT/bench_2ranks_rehearsal_1gpu.json python bench.py --full --gpus 2 --rehearse 1 --steps 500 --warmup 100 --bank-cache /tmp/bank --cpu-baseline 0
 python bench.py --gpus 2 --steps 10 > $OUT/bench_2ranks_refused.out 2>&1; echo "exit code $? (two ranks without --rehearse on a 1-GPU box must be refused)" >> $OUT/bench_2ranks_refused.out
 run policy_bench $OUT/policy_bench.log python tools/policy_bench.py 4096
 run ppo_colav_fused_4096x128 $OUT/ppo_colav_fused_4096x128.log python examples/ppo.py --envs 4096 --updates 6 --rollout 128
@@ -74,7 +74,7 @@ run ppo_colav_fused_4096x128_generated_bank $OUT/ppo_colav_fused_4096x128_genera
 echo "benches done"
 [ "${SKIP_TRACE:-0}" = 1 ] && exit 0
 cd /tmp && export TMPDIR=/tmp
-run bench_under_rocprof $OUT/bench_under_rocprof.json rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --bank-cache /tmp/bank --cpu-baseline 0
+run bench_under_rocprof $OUT/bench_under_rocprof.json rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 $ROOT/bench.py --full --bank-cache /tmp/bank --cpu-baseline 0
 cd $ROOT
 python tools/trace_summary.py $OUT/trace/*/*_kernel_trace.csv > $OUT/kernel_trace_summary.txt
 python tools/trace_overlap.py $OUT/trace/*/*_kernel_trace.csv k_step_roles 4000 > $OUT/kernel_trace_overlap.txt
@@ -83,7 +83,7 @@ cp $OUT/trace/*/*_kernel_stats.csv $OUT/kernel_stats.csv 2>/dev/null
 rm -rf $OUT/trace
 # the same for the driver's own command (20 steps: its calibration issues launches of several lengths; the summary lists k_step_multi per length)
 cd /tmp
-run bench_driver_command_under_rocprof $OUT/bench_driver_command_under_rocprof.json rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_drv -- python3 $ROOT/bench.py --gpus 1 --steps 20 --warmup 5 --bank-cache /tmp/bank --cpu-baseline 0
+run bench_driver_command_under_rocprof $OUT/bench_driver_command_under_rocprof.json rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace_drv -- python3 $ROOT/bench.py --full --gpus 1 --steps 20 --warmup 5 --bank-cache /tmp/bank --cpu-baseline 0
 cd $ROOT
 python tools/trace_summary.py $OUT/trace_drv/*/*_kernel_trace.csv > $OUT/kernel_trace_summary_driver_command.txt
 cp $OUT/trace_drv/*/*_kernel_stats.csv $OUT/kernel_stats_driver_command.csv 2>/dev/null

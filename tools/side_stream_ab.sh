@@ -5,6 +5,7 @@ mkdir -p gpurun_out/r05
 run() {  # run <tag> <env assignments...> -- <bench flags...>
   tag=$1; shift
   envs=(); while [ "$1" != "--" ]; do envs+=("$1"); shift; done; shift
+  set -- --full "$@"      # (the roofline and comparison of the line are read below)
   env "${envs[@]}" timeout -k 10 300 python bench.py --workload moving28 --cpu-baseline 0 "$@" > gpurun_out/r05/side_$tag.json 2>> gpurun_out/r05/side_stderr.log
   python - <<PY
 import json
