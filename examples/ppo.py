@@ -151,7 +151,7 @@ def average_gradients(params, world):
 def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print, worlds="fresh", regen=0, log_every=1,
           task="colav", step_mode=None, graph_rollout=False, sub_batches=4, minibatches=32,
           reward_scale=0.01, reward_clip=0.0, min_cumulative_reward=None, act_space="raw", ret_norm=False, orthogonal=False, ent_coef=0.01, log_std=-0.5, lr=2e-4,
-          fused_policy=True, graph_update=False, policy_bf16=False):
+          fused_policy=True, graph_update=False, policy_bf16=False, feasibility_pooling=False):
     from gym_auv_amd import distributed as D
     from gym_auv_amd.batched_env import BatchedAuvEnv
     from gym_auv_amd.config import effective_reference_config
@@ -163,6 +163,8 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
     # task "pathfollow": PathFollowNoObstacles-v0 (no obstacles, LiDAR off, PathFollowRewarder) -- gym_auv/__init__.py:105-121
     colav = task == "colav"
     cfg = effective_reference_config(use_lidar=colav)
+    # the observation's LiDAR part pooled to n_sectors feasible distances (the gym-auv paper's reduction; ignored without LiDAR)
+    cfg.vessel.sensor_use_feasibility_pooling = bool(feasibility_pooling)
     if min_cumulative_reward is not None:       # (diagnosis only: the reference ends an episode below -2000, config.py:16)
         cfg.episode.min_cumulative_reward = float(min_cumulative_reward)
     nm, ns = (17, 11) if colav else (0, 0)
@@ -491,6 +493,9 @@ if __name__ == "__main__":
     ap.add_argument("--log-every", type=int, default=1)
     ap.add_argument("--task", default="colav", choices=["colav", "pathfollow"])
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--feasibility-pooling", type=int, default=0,
+                    help="1: observe the LiDAR through feasibility pooling, 9 sector closenesses instead of 180 (VesselConfig."
+                         "sensor_use_feasibility_pooling)")
     ap.add_argument("--sub-batches", type=int, default=4, help="rollout chains (BatchedAuvEnv.set_sub_batches)")
     ap.add_argument("--minibatches", type=int, default=32)
     ap.add_argument("--graph-rollout", type=int, default=0, help="1: one captured device graph per chain and rollout step (torch-module policy only)")
@@ -519,4 +524,4 @@ if __name__ == "__main__":
           task=a.task, step_mode=a.step_mode, graph_rollout=bool(a.graph_rollout), fused_policy=bool(a.fused_policy), graph_update=a.graph_update, policy_bf16=bool(a.policy_bf16),
           sub_batches=a.sub_batches, minibatches=a.minibatches, act_space=a.act_space, ret_norm=bool(a.ret_norm),
           orthogonal=bool(a.orthogonal), ent_coef=a.ent_coef, log_std=a.log_std, lr=a.lr, reward_clip=a.reward_clip,
-          min_cumulative_reward=a.min_cumulative_reward)
+          min_cumulative_reward=a.min_cumulative_reward, feasibility_pooling=bool(a.feasibility_pooling))

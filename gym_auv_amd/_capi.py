@@ -14,7 +14,7 @@ from .config import Config
 
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, "csrc", "libauv_hip.so")
-ABI_VERSION = 4
+ABI_VERSION = 5
 
 AUV_REWARD_COLAV, AUV_REWARD_PATHFOLLOW = 0, 1
 AUV_CULL_REFERENCE, AUV_CULL_EXACT = 0, 1
@@ -22,12 +22,13 @@ AUV_F32, AUV_F64 = 0, 1
 AUV_RDV_EVENTS, AUV_RDV_DEVICE, AUV_RDV_CP = 0, 1, 2
 
 FIELDS = dict(STATE=0, LIDAR_D=1, OBS64=2, REWARD64=3, INFO64=4, WORLD_IDX=5, COUNTERS=6,
-              MOVER_STATE=7, NEARBY=8, EPISODE=9, CULL_LIMITS=10, NAV64=11, COLLISION=12, STAMPS=13, STEP_INFO=14, BROKEN=15, FW_STATE=16, FW_SERIAL=17)
+              MOVER_STATE=7, NEARBY=8, EPISODE=9, CULL_LIMITS=10, NAV64=11, COLLISION=12, STAMPS=13, STEP_INFO=14, BROKEN=15, FW_STATE=16, FW_SERIAL=17,
+              SECTOR_D=18)
 FIELD_DTYPES = dict(STATE=np.float64, LIDAR_D=np.float64, OBS64=np.float64, REWARD64=np.float64,
                     INFO64=np.float64, WORLD_IDX=np.int32, COUNTERS=np.int32, MOVER_STATE=np.float64,
                     NEARBY=np.uint8, EPISODE=np.float64, CULL_LIMITS=np.int32, NAV64=np.float64,
                     COLLISION=np.uint8, STAMPS=np.int64, STEP_INFO=np.float64, BROKEN=np.uint8,
-                    FW_STATE=np.int32, FW_SERIAL=np.int32)
+                    FW_STATE=np.int32, FW_SERIAL=np.int32, SECTOR_D=np.float64)
 
 
 class AuvLibraryError(RuntimeError):
@@ -65,9 +66,7 @@ class AuvWorldBank(C.Structure):
 def make_config(cfg: Config, rewarder: str = "colav", test_mode: bool = False,
                 cull: str = "reference", auto_reset: bool = False) -> AuvConfig:
     v, e, s = cfg.vessel, cfg.episode, cfg.simulation
-    if v.sensor_use_feasibility_pooling:
-        raise NotImplementedError("feasibility pooling is not part of step() (its wiring is broken in the reference, "
-                                  "SURVEY 8(f) F3); use BatchedAuvEnv.feasibility_pooling() on the ranges")
+    obs_pooling(cfg)                      # (validates a pooled config; the pooling itself is set per handle: auv_set_obs_pooling)
     if v.sensor_use_velocity_observations and not v.use_lidar:
         raise ValueError("sensor_use_velocity_observations needs use_lidar (the reference raises on [].flatten(), "
                          "environment.py:260,271-272)")
@@ -81,6 +80,27 @@ def make_config(cfg: Config, rewarder: str = "colav", test_mode: bool = False,
         rewarder={"colav": AUV_REWARD_COLAV, "pathfollow": AUV_REWARD_PATHFOLLOW}[rewarder],
         test_mode=int(test_mode), cull_mode={"reference": AUV_CULL_REFERENCE, "exact": AUV_CULL_EXACT}[cull],
         auto_reset=int(auto_reset), obs_channels=3 if v.sensor_use_velocity_observations else 1)
+
+
+def obs_pooling(cfg: Config):
+    """(n_sectors, sector_start int32 [n_sectors + 1], width) of a config whose observation is feasibility-pooled, else
+    None -- the arguments of auv_set_obs_pooling.  Pooling is on when use_lidar and sensor_use_feasibility_pooling; with the
+    LiDAR off the flag is accepted and ignored (the reference's observe() never calls perceive).  When on, raises ValueError
+    for a sector partition with an empty sector or an opening width that is not positive."""
+    from .pooling import sector_starts
+    v = cfg.vessel
+    if not v.feasibility_pooled:
+        return None
+    if not v.n_sectors >= 1 or not v.n_sensors_per_sector >= 1:
+        raise ValueError("feasibility pooling needs n_sectors >= 1 and n_sensors_per_sector >= 1")
+    starts = sector_starts(v.n_sectors, v.n_sensors_per_sector)
+    if (np.diff(starts) <= 0).any():
+        raise ValueError("feasibility pooling: the sector partition of %d sectors x %d sensors has an empty sector (starts %s)"
+                         % (v.n_sectors, v.n_sensors_per_sector, starts.tolist()))
+    width = float(v.vessel_width) * float(v.feasibility_width_multiplier)
+    if not (np.isfinite(width) and width > 0.0):
+        raise ValueError("feasibility pooling: opening width vessel_width * feasibility_width_multiplier = %r is not > 0" % width)
+    return v.n_sectors, starts.astype(np.int32), width
 
 
 def make_bank_struct(bank: Dict[str, np.ndarray]) -> Tuple[AuvWorldBank, list]:
@@ -180,6 +200,7 @@ def load_library(path: str = None) -> C.CDLL:
         "auv_step_timed": (C.c_int, [vp, vp, i32, vp, vp, vp, vp, C.POINTER(C.c_float)]),
         "auv_set_action_ring": (C.c_int, [vp, i32]),
         "auv_set_step_mode": (C.c_int, [vp, i32]),
+        "auv_set_obs_pooling": (C.c_int, [vp, i32, vp, C.c_double]),
         "auv_feasibility_pooling": (C.c_int, [vp, vp, i32, C.c_double, vp, vp, vp]),
         "auv_generate_worlds": (C.c_int, [vp, i32, i32, i32, vp, i32, vp, vp, i32]),
         "auv_fresh_worlds_create": (C.c_int, [vp, i32, i32, i32, C.c_uint64, C.c_int64, i32, i32, vp, vp, i32]),
@@ -211,7 +232,7 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_graph_launch_chains", "auv_policy_param_floats", "auv_policy_act", "auv_gae", "auv_policy_rollout", "auv_step_pipelined_timed", "auv_streams_overlap", "auv_episode_log", "auv_health", "auv_probe_streams", "auv_effective_step_mode",
                     "auv_step_dynamics", "auv_lidar", "auv_nav_reward", "auv_read", "auv_write",
                     "auv_field_bytes", "auv_graph_capture", "auv_graph_launch", "auv_graph_capture_steps", "auv_step_timed",
-                    "auv_set_action_ring", "auv_set_step_mode", "auv_feasibility_pooling",
+                    "auv_set_action_ring", "auv_set_step_mode", "auv_set_obs_pooling", "auv_feasibility_pooling",
                     "auv_generate_worlds", "auv_bank_bytes", "auv_read_bank",
                     "auv_fresh_worlds_create", "auv_fresh_worlds_refill", "auv_fresh_worlds_stats", "auv_fresh_worlds_draws", "auv_fresh_worlds_set_stream",
                     "auv_abi_version", "auv_last_error"]

@@ -18,7 +18,7 @@ import numpy as np
 import torch
 
 from . import _capi
-from ._capi import FIELD_DTYPES, FIELDS, AuvLibraryError, load_library, make_bank_struct, make_config
+from ._capi import FIELD_DTYPES, FIELDS, AuvLibraryError, load_library, make_bank_struct, make_config, obs_pooling
 from .config import Config
 from .devgen import FreshWorlds, GeneratedWorlds
 from .spaces import Box
@@ -54,6 +54,13 @@ class BatchedAuvEnv:
         self._h = C.c_void_p()
         idx = self.device.index if self.device.index is not None else torch.cuda.current_device()
         _check(_LIB.auv_create(C.byref(self._cfg_struct), self.n_envs, idx, C.byref(self._h)), "auv_create")
+        # feasibility-pooled observation rows (VesselConfig.sensor_use_feasibility_pooling): before any bank, whose reset
+        # rows depend on it
+        pool = obs_pooling(config)
+        self.n_sectors = 0 if pool is None else int(pool[0])
+        if pool is not None:
+            ns, starts, width = pool
+            _check(_LIB.auv_set_obs_pooling(self._h, ns, starts.ctypes.data_as(C.c_void_p), width), "auv_set_obs_pooling")
         self._gen = None
         self._fresh = None
         if isinstance(worlds, FreshWorlds):
@@ -616,7 +623,7 @@ class BatchedAuvEnv:
         return dict(STATE=(6, n), LIDAR_D=(n, S), OBS64=(n, 6 + S), REWARD64=(n,), INFO64=(n, 8),
                     WORLD_IDX=(n,), COUNTERS=(n, 4), MOVER_STATE=(n, self.m_max, 4), NEARBY=(n, self.k_max),
                     EPISODE=(n, 4), CULL_LIMITS=(n, self.k_max, 2), NAV64=(n, 8), COLLISION=(n,), STAMPS=(n, 16), STEP_INFO=(n, 4), BROKEN=(n,),
-                    FW_STATE=(self.n_worlds,), FW_SERIAL=(self.n_worlds,))[name]
+                    FW_STATE=(self.n_worlds,), FW_SERIAL=(self.n_worlds,), SECTOR_D=(n, self.n_sectors))[name]
 
     def read(self, name: str) -> torch.Tensor:
         t = torch.empty(self.field_shape(name), dtype=_TORCH_DTYPES[FIELD_DTYPES[name]], device=self.device)

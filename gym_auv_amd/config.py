@@ -52,8 +52,14 @@ class VesselConfig:
         return self.n_sensors_per_sector * self.n_sectors
 
     @property
+    def feasibility_pooled(self) -> bool:
+        """The observation carries one closeness per sector (the feasible distance of feasibility pooling) instead of one
+        per beam: sensor_use_feasibility_pooling with the LiDAR on (with it off there is nothing to pool)."""
+        return bool(self.use_lidar and self.sensor_use_feasibility_pooling)
+
+    @property
     def lidar_shape(self) -> Tuple[int, int]:
-        return (3 if self.sensor_use_velocity_observations else 1, self.n_sensors)
+        return (3 if self.sensor_use_velocity_observations else 1, self.n_sectors if self.feasibility_pooled else self.n_sensors)
 
     @property
     def n_lidar_observations(self) -> int:

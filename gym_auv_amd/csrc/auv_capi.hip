@@ -77,6 +77,8 @@ struct auv_handle {
   AuvDev d;
   int device;
   bool worlds_loaded;
+  bool bank_seen = false;        // a bank has been loaded or generated once: the observation's layout is fixed from then on
+  std::vector<uint32_t> pool_word_host;   // auv_set_obs_pooling: [S] sector word per sensor (AuvDev::pool_word), empty when off
   std::vector<void*> env_allocs, bank_allocs;
   hipStream_t cap_stream;
   hipGraph_t graph;
@@ -267,6 +269,7 @@ static int finish_bank(auv_handle* h, bool alloc_env) {
   const int W = d.n_worlds, k_max = d.k_max, m_max = d.m_max;
   const size_t n = (size_t)d.n, S = (size_t)d.cfg.n_sensors;
   int rc = 0;
+  h->bank_seen = true;
   if (alloc_env) {
   free_pool(h->env_allocs);
   auto& ep = h->env_allocs;
@@ -320,6 +323,11 @@ static int finish_bank(auv_handle* h, bool alloc_env) {
   rc |= dev_alloc(ep, &d.w_nearby, (size_t)W * k_max);
   rc |= dev_alloc(ep, &d.w_limits, (size_t)W * k_max);
   rc |= dev_alloc(ep, &d.w_collision, (size_t)W);
+  if (d.pool_ns) {
+    rc |= dev_upload(ep, &d.pool_word, h->pool_word_host.data(), S);
+    rc |= dev_alloc(ep, &d.sector_d, n * (size_t)d.pool_ns);
+    rc |= dev_alloc(ep, &d.w_sector_d, (size_t)W * d.pool_ns);
+  }
   if (rc) return AUV_EHIP;
   }
   HIP_TRY(hipMemset(d.ep_log_count, 0, sizeof(unsigned long long)));   // the episode log restarts with every bank
@@ -999,6 +1007,7 @@ int auv_fresh_worlds_create(auv_handle_t* h, int32_t depth, int32_t n_moving, in
   rc |= dev_alloc(ap, &sh.stamps, c * 16);
   rc |= dev_alloc(ap, &sh.rew_path, c);
   rc |= dev_alloc(ap, &sh.rew_lidar, c);
+  if (d.pool_ns) rc |= dev_alloc(ap, &sh.sector_d, c * (size_t)d.pool_ns);   // (w_sector_d: the handle's own, like w_obs64)
   if (rc) {
     fw_disable(h);
     return AUV_ENOMEM;
@@ -1691,6 +1700,7 @@ static void* field_ptr(const auv_handle_t* h, int32_t field, size_t* bytes) {
     case AUV_FIELD_BROKEN: *bytes = n; return d.broken;
     case AUV_FIELD_FW_STATE: *bytes = d.fw_state ? 4 * (size_t)d.n_worlds : 0; return d.fw_state;
     case AUV_FIELD_FW_SERIAL: *bytes = d.fw_serial ? 4 * (size_t)d.n_worlds : 0; return d.fw_serial;
+    case AUV_FIELD_SECTOR_D: *bytes = d.pool_ns ? 8 * n * (size_t)d.pool_ns : 0; return d.pool_ns ? d.sector_d : nullptr;
   }
   *bytes = 0;
   return nullptr;
@@ -1722,6 +1732,32 @@ int auv_write(auv_handle_t* h, int32_t field, const void* src_dev, size_t bytes,
   return AUV_OK;
 }
 
+int auv_set_obs_pooling(auv_handle_t* h, int32_t n_sectors, const int32_t* sector_start_host, double width) {
+  if (!h) return fail(AUV_EINVAL, "null handle");
+  if (h->bank_seen) return fail(AUV_ESTATE, "auv_set_obs_pooling: only before the first bank is loaded (the reset rows depend on it)");
+  const int S = h->d.cfg.n_sensors;
+  if (n_sectors == 0) {
+    h->d.pool_ns = 0, h->d.pool_width = 0.0;
+    h->pool_word_host.clear();
+    return AUV_OK;
+  }
+  if (n_sectors < 1 || !sector_start_host) return fail(AUV_EINVAL, "auv_set_obs_pooling: n_sectors must be >= 1 (0: off) with a table");
+  if (!std::isfinite(width) || !(width > 0.0)) return fail(AUV_EINVAL, "auv_set_obs_pooling: width must be finite and > 0");
+  if (sector_start_host[0] != 0 || sector_start_host[n_sectors] != S)
+    return fail(AUV_EINVAL, "auv_set_obs_pooling: the sector table must run from 0 to n_sensors (%d)", S);
+  for (int k = 0; k < n_sectors; k++)
+    if (sector_start_host[k + 1] <= sector_start_host[k]) return fail(AUV_EINVAL, "auv_set_obs_pooling: sector %d is empty", k);
+  // with the LiDAR off the observation has no LiDAR columns to pool (the reference never calls perceive): accepted, ignored
+  if (!h->d.cfg.use_lidar) return AUV_OK;
+  h->pool_word_host.assign((size_t)S, 0u);
+  for (int k = 0; k < n_sectors; k++) {
+    const int s0 = sector_start_host[k], s1 = sector_start_host[k + 1];
+    for (int i = s0; i < s1; i++) h->pool_word_host[(size_t)i] = (uint32_t)s0 | ((uint32_t)(s1 - s0) << 16);   // (S <= 4096)
+  }
+  h->d.pool_ns = n_sectors, h->d.pool_width = width;
+  return AUV_OK;
+}
+
 int auv_feasibility_pooling(auv_handle_t* h, const int32_t* sector_start_dev, int32_t n_sectors, double width,
                             double* out_dist_dev, float* out_closeness_dev, void* stream) {
   REQUIRE_READY(h);
@@ -1736,8 +1772,7 @@ size_t auv_policy_param_floats(int32_t obs_dim) { return obs_dim > 0 ? auv_polic
 
 static int check_policy_io(const auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const char* who) {
   if (!io) return fail(AUV_EINVAL, "%s: null io", who);
-  const auv_config_t& c = h->d.cfg;
-  const int D = 6 + (c.use_lidar ? c.n_sensors * (c.obs_channels == 3 ? 3 : 1) : 0);
+  const int D = auv_obs_cols(h->d.cfg, h->d.pool_ns);
   if (io->obs_dim != D) return fail(AUV_EINVAL, "%s: obs_dim %d, the handle's observation has %d columns", who, io->obs_dim, D);
   if (e0 < 0 || ne < 1 || (int64_t)e0 + ne > h->d.n) return fail(AUV_EINVAL, "%s: slice [%d, %d) outside [0, %d)", who, e0, e0 + ne, h->d.n);
   if (io->T < 1) return fail(AUV_EINVAL, "%s: T must be >= 1", who);

@@ -133,7 +133,57 @@ struct AuvDev {
   unsigned int* fw_ctl;  // [8] [0] tail (producers: finish waves of any chain), [1] head (the refill pass), [2] episodes that had to
                          //     start in the world they had just finished because the next slot was not READY yet (stale re-use)
   int32_t fw_cap;
+  // ---- feasibility-pooled observations (auv_set_obs_pooling): the observation row carries one closeness per
+  //      sector -- of the sector's feasible distance (LidarPreprocessor._feasibility_pooling, sensor.py:251-296) -- instead of one
+  //      per beam.  Computed by the LiDAR wave itself (k2_back), so every step shape gets it.  Rows stay at stride 6 + S in
+  //      obs64 / w_obs64 (the pooled row fills the first 6 + pool_ns columns, the rest stay 0); the caller's float32 row is
+  //      6 + c pool_ns wide (auv_obs_cols).  Fields are read where a role uses them; an unpooled run reads pool_ns only ----
+  int32_t pool_ns;             // sectors (0: off, the default)
+  double pool_width;           // opening width: vessel_width * feasibility_width_multiplier
+  const uint32_t* pool_word;   // [S] per sensor: first sensor of its sector | sector size << 16 (from the host's sector table)
+  double* sector_d;            // [N][pool_ns] the feasible distances behind the current observation row (AUV_FIELD_SECTOR_D)
+  double* w_sector_d;          // [W][pool_ns] the same of every world's reset row
 };
+
+// LiDAR columns of the observation row (closeness per beam, or per sector when pooled) and the width of the caller's float32 row:
+// 6 navigation features + those columns, times three with the velocity channels (zero, sensor.py:159)
+__host__ __device__ __forceinline__ int auv_obs_lidar_cols(const int n_sensors, const int pool_ns) { return pool_ns ? pool_ns : n_sensors; }
+template <class Cfg> __host__ __device__ __forceinline__ int auv_obs_cols(const Cfg& c, const int pool_ns) {
+  return 6 + (c.use_lidar ? auv_obs_lidar_cols(c.n_sensors, pool_ns) * (c.obs_channels == 3 ? 3 : 1) : 0);
+}
+
+// The opening scan of feasibility pooling for one threshold (sensor.py:268-291): does the sector [s0, s0 + N) of the ranges
+// x (spacing theta) have an opening wider than `width` -- centred within a quarter of the sector -- among the sensors whose
+// range exceeds xi + width?  The feasible distance of the sector is the least xi without one (else its largest range).
+// Shared by the post-kernel (k4_pooling) and the LiDAR wave (k2_back): the same fp64 operations in the same order.
+__device__ __forceinline__ bool auv_pool_opening(const double* x, const int s0, const int N, const double xi, const double width,
+                                                 const double theta) {
+  const double dd = xi * theta;
+  double opening_width = 0, opening_span = 0, opening_start = -theta * (N - 1) / 2;
+  bool found = false;
+  for (int j = 0; j < N; j++) {
+    const bool survives = x[s0 + j] > xi + width;
+    if (survives) {
+      opening_width += dd;
+      opening_span += theta;
+      if (opening_width > width) {
+        const double centre = opening_start + opening_span / 2;
+        if (fabs(centre) < theta * (N - 1) / 4) found = true;
+      }
+    } else {
+      opening_width += 0.5 * dd;
+      opening_span += 0.5 * theta;
+      if (opening_width > width) {
+        const double centre = opening_start + opening_span / 2;
+        if (fabs(centre) < theta * (N - 1) / 4) found = true;
+      }
+      opening_width = 0;
+      opening_span = 0;
+      opening_start = -theta * (N - 1) / 2 + j * theta;
+    }
+  }
+  return found;
+}
 
 enum { AUV_FW_READY = 0, AUV_FW_IN_USE = 1, AUV_FW_STALE = 2 };
 

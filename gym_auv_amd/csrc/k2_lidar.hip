@@ -889,6 +889,68 @@ __device__ __forceinline__ void k2_stage_and_pairs(const AuvDev& d, const Slice&
 #endif
 }
 
+// ---- feasibility pooling of the sweep's ranges (auv_set_obs_pooling): the observation row's closeness per sector ----
+// Lanes <-> sensors, as in k4_pooling and with its arithmetic (auv_pool_opening): every lane runs the opening scan of its own
+// range over its sector, then a per-sector min / max through LDS (non-negative fp64 ordered as uint64).  The ranges are in
+// L.dbits by then (the returns' distances, R for the free beams); the min / max words, indexed by the sector's first sensor,
+// go into the ray vectors' region, idle once the returns are through.  `w`: the sensor's word of d.pool_word, with bit 31 set
+// when its sector holds a return -- a sector of free beams only pools to exactly R (every threshold is R: the result is R
+// whether an opening is found or not), so its lanes skip the scan and its words start at R.
+#define K2_POOL_HAS 0x80000000u
+__device__ __forceinline__ void k2_pool_init(const Slice& L, const int S, const int i, const unsigned w, const double R) {
+  unsigned long long* mn = (unsigned long long*)L.rayv;
+  if (i < S && (int)(w & 0xffffu) == i) {
+    const bool has = (w & K2_POOL_HAS) != 0u;
+    mn[i] = has ? d2u(1.0e308) : d2u(R), mn[S + i] = has ? 0ull : d2u(R);
+  }
+}
+__device__ __forceinline__ void k2_pool_scan(const Slice& L, const int S, const int i, const unsigned w, const double width,
+                                             const double theta) {
+  unsigned long long* mn = (unsigned long long*)L.rayv;
+  if (i < S && (w & K2_POOL_HAS)) {
+    const int s0 = (int)(w & 0xffffu), N = (int)((w >> 16) & 0x7fffu);
+    const double* x = (const double*)L.dbits;
+    const double xi = x[i];
+    const bool found = auv_pool_opening(x, s0, N, xi, width, theta);
+    atomicMax(&mn[S + s0], d2u(xi));
+    if (!found) atomicMin(&mn[s0], d2u(xi));
+  }
+}
+// the lane of a sector's first sensor stores the sector's distance and closeness; `k0`: sectors that start in earlier passes
+template <bool WT>
+__device__ __forceinline__ void k2_pool_out(const AuvDev& d, const Slice& L, const int e, const int lane, const int S, const int i,
+                                            const unsigned w, int& k0, const double R, const double logR, double* ob, float* oo) {
+  const bool first = i < S && (int)(w & 0xffffu) == i;
+  const unsigned long long fm = __ballot(first);
+  if (first) {
+    const unsigned long long* mn = (const unsigned long long*)L.rayv;
+    const int k = k0 + __popcll(fm & ((1ull << lane) - 1ull));
+    double v = u2d(mn[i]);
+    if (v > 1.0e307) v = u2d(mn[S + i]);                   // every threshold had an opening: np.max
+    v = v > 0.0 ? v : 0.0;                                   // max(0, .)
+    const int ns = d.pool_ns;
+    auv_st<WT>(d.sector_d + (size_t)e * ns + k, v);
+    // the closeness of the feasible distance by the unpooled rule (vessel.py:88-95, :356-363)
+    double cl = d.cfg.sensor_log_transform ? 1 - auv_clip(log(1 + v) / logR, 0.0, 1.0) : 1 - auv_clip(v / R, 0.0, 1.0);
+    cl = auv_clip(cl, -1.0, 1.0);
+    auv_st<WT>(ob + k, cl);
+    if (oo) auv_st<WT>(oo + k, (float)cl);
+  }
+  k0 += __popcll(fm);
+}
+// beams [0, x) with a return, from the wave's hit masks
+template <int NQ>
+__device__ __forceinline__ int k2_hits_below(const unsigned long long (&hm)[NQ], const int x) {
+  int c = 0;
+#pragma unroll
+  for (int q = 0; q < NQ; q++) {
+    const int m = x - q * AUV_WAVE;
+    const unsigned long long below = m <= 0 ? 0ull : (m >= AUV_WAVE ? ~0ull : ((1ull << m) - 1ull));
+    c += __popcll(hm[q] & below);
+  }
+  return c;
+}
+
 // phase E: outputs (vessel.py:88-95, :356-359) and the LiDAR term of the Colav reward
 // (rewarder.py:205-222: sum of gamma_theta-weighted R exp(-0.1 d) over the beams; the velocity channel
 // is identically zero, sensor.py:159) and the float32 closeness columns of the observation row.
@@ -901,13 +963,17 @@ __device__ __forceinline__ void k2_stage_and_pairs(const AuvDev& d, const Slice&
 // every store issued before it (~0.7 us for a write-through one).  So everything this phase reads from memory -- the beam
 // weights, the per-config constants -- is requested before its first store, the returns take their weights along through
 // LDS, and the cull-limit rows of phase B (`lim0`: this lane's row of the first 64 obstacles) are stored here, not there.
-template <bool WT = false>
-__device__ __forceinline__ int k2_back(const AuvDev& d, const int e, const int lane, const Slice& L, const int n_act,
-                       float* __restrict__ obs_out = nullptr, double* rew_lidar_out = nullptr, const int2* lim0 = nullptr) {
+// Pooled (d.pool_ns > 0): the per-beam closeness is not stored; the ranges go to LDS instead and the pooled tail above writes
+// the sectors' distances (sector_d) and closenesses (obs64 / the float32 row, first pool_ns columns) -- all before the caller's
+// drain of this wave's stores, like every other row of the sweep.  Ranges, collision and the reward term are the same either way.
+template <bool WT, bool POOL>
+__device__ __forceinline__ int k2_back_impl(const AuvDev& d, const int e, const int lane, const Slice& L, const int n_act,
+                                            float* __restrict__ obs_out, double* rew_lidar_out, const int2* lim0) {
   const int S = d.cfg.n_sensors;
   const double R = d.cfg.sensor_range, W = d.cfg.vessel_width;
   const bool colav = d.cfg.rewarder == AUV_REWARD_COLAV;
-  const int D = 6 + S * (d.cfg.obs_channels == 3 ? 3 : 1);   // row stride of obs_out (use_lidar is on here)
+  const int ns = POOL ? d.pool_ns : 0;                       // sectors of a pooled observation row (0: off)
+  const int D = auv_obs_cols(d.cfg, ns);                     // row stride of obs_out (use_lidar is on here)
   double* dd = d.lidar_d + (size_t)e * S;
   double* ob = d.obs64 + (size_t)e * (6 + S) + 6;
   float* oo = obs_out ? obs_out + (size_t)e * D + 6 : nullptr;
@@ -915,8 +981,16 @@ __device__ __forceinline__ int k2_back(const AuvDev& d, const int e, const int l
     const double term = colav ? d.derived[3] : 0.0;
     if (lim0 && lane < d.k_max) auv_st<WT>(&d.limits[(size_t)e * d.k_max + lane], *lim0);
     for (int i = lane; i < S; i += AUV_WAVE) {
-      auv_st<WT>(dd + i, R), auv_st<WT>(ob + i, 0.0);
-      if (oo) auv_st<WT>(oo + i, 0.0f);
+      auv_st<WT>(dd + i, R);
+      if (!ns) {
+        auv_st<WT>(ob + i, 0.0);
+        if (oo) auv_st<WT>(oo + i, 0.0f);
+      }
+    }
+    // pooled: every sector of free beams pools to exactly R, closeness 1 - log(1 + R) / log(1 + R) = 0 (or 1 - R / R)
+    for (int k = lane; k < ns; k += AUV_WAVE) {
+      auv_st<WT>(d.sector_d + (size_t)e * ns + k, R), auv_st<WT>(ob + k, 0.0);
+      if (oo) auv_st<WT>(oo + k, 0.0f);
     }
     if (lane == 0) {
       auv_st<WT>(d.collision + e, (uint8_t)0);
@@ -936,10 +1010,12 @@ __device__ __forceinline__ int k2_back(const AuvDev& d, const int e, const int l
     double* hitw = L.hitw;
     constexpr int NQ = K2_HIT_S / AUV_WAVE;
     double bw[NQ];                                         // gamma_theta from the per-config table
+    unsigned pw[NQ];                                       // pooled: the sensors' sector words
 #pragma unroll
     for (int q = 0; q < NQ; q++) {
       const int i = q * AUV_WAVE + lane;
       bw[q] = (colav && i < S) ? d.beam_w[i] : 0.0;
+      pw[q] = (ns && i < S) ? d.pool_word[i] : 0u;
     }
     // ---- which beams have a return; their indices compacted into LDS (no store yet) ----
     unsigned long long hm[NQ];
@@ -967,9 +1043,18 @@ __device__ __forceinline__ int k2_back(const AuvDev& d, const int e, const int l
         const int i = q * AUV_WAVE + lane;
         const bool hit = (hm[q] >> lane) & 1ull;
         if (i < S && !hit) {
-          auv_st<WT>(dd + i, R), auv_st<WT>(ob + i, 0.0);  // sensor.py:156; closeness 1 - clip(x / x) = 0
-          if (oo) auv_st<WT>(oo + i, 0.0f);
+          auv_st<WT>(dd + i, R);                           // sensor.py:156
+          if (!ns) {
+            auv_st<WT>(ob + i, 0.0);                       // closeness 1 - clip(x / x) = 0
+            if (oo) auv_st<WT>(oo + i, 0.0f);
+          } else {
+            L.dbits[i] = d2u(R);                           // (the returns' lanes put their distances there)
+          }
           if (colav) num += bw[q] * raw_free;
+        }
+        if (ns && i < S) {
+          const int s0 = (int)(pw[q] & 0xffffu);
+          if (k2_hits_below(hm, s0 + (int)((pw[q] >> 16) & 0x7fffu)) != k2_hits_below(hm, s0)) pw[q] |= K2_POOL_HAS;
         }
         if (hit) hitw[base + __popcll(hm[q] & ((1ull << lane) - 1ull))] = bw[q];
         base += __popcll(hm[q]);
@@ -990,13 +1075,34 @@ __device__ __forceinline__ int k2_back(const AuvDev& d, const int e, const int l
         const double dx = X - px, dy = Y - py;
         const double di = sqrt(dx * dx + dy * dy);
         auv_st<WT>(dd + i, di);
-        double cl = d.cfg.sensor_log_transform ? 1 - auv_clip(log(1 + di) / logR, 0.0, 1.0) : 1 - auv_clip(di / R, 0.0, 1.0);
-        cl = auv_clip(cl, -1.0, 1.0);
-        auv_st<WT>(ob + i, cl);
-        if (oo) auv_st<WT>(oo + i, (float)cl);
+        if (!ns) {
+          double cl = d.cfg.sensor_log_transform ? 1 - auv_clip(log(1 + di) / logR, 0.0, 1.0) : 1 - auv_clip(di / R, 0.0, 1.0);
+          cl = auv_clip(cl, -1.0, 1.0);
+          auv_st<WT>(ob + i, cl);
+          if (oo) auv_st<WT>(oo + i, (float)cl);
+        } else {
+          L.dbits[i] = d2u(di);
+        }
         if (colav) num += wgt * ((di != R) ? R * exp(-0.1 * di) : raw_free);   // gamma_x
         col |= (di < W);
       }
+    }
+    if (ns) {
+      // ---- pooled tail (the sector words were requested with the beam weights) ----
+      const double width = d.pool_width, theta = 2 * AUV_PI / S;   // vessel.py:63-65
+      auv_wave_lds_sync();                                 // (ranges in place; the ray vectors are idle)
+#pragma unroll
+      for (int q = 0; q < NQ; q++)
+        if (q * AUV_WAVE < S) k2_pool_init(L, S, q * AUV_WAVE + lane, pw[q], R);
+      auv_wave_lds_sync();
+#pragma unroll
+      for (int q = 0; q < NQ; q++)
+        if (q * AUV_WAVE < S) k2_pool_scan(L, S, q * AUV_WAVE + lane, pw[q], width, theta);
+      auv_wave_lds_sync();
+      int k0 = 0;
+#pragma unroll
+      for (int q = 0; q < NQ; q++)
+        if (q * AUV_WAVE < S) k2_pool_out<WT>(d, L, e, lane, S, q * AUV_WAVE + lane, pw[q], k0, R, logR, ob, oo);
     }
   } else {
     // (more beams than the list holds: every pass does everything)
@@ -1011,13 +1117,31 @@ __device__ __forceinline__ int k2_back(const AuvDev& d, const int e, const int l
         di = sqrt(dx * dx + dy * dy);
       }
       auv_st<WT>(dd + i, di);
-      double cl = 0.0;
-      if (t <= 1.0) cl = d.cfg.sensor_log_transform ? 1 - auv_clip(log(1 + di) / logR, 0.0, 1.0) : 1 - auv_clip(di / R, 0.0, 1.0);
-      cl = auv_clip(cl, -1.0, 1.0);
-      auv_st<WT>(ob + i, cl);
-      if (oo) auv_st<WT>(oo + i, (float)cl);
+      if (!ns) {
+        double cl = 0.0;
+        if (t <= 1.0) cl = d.cfg.sensor_log_transform ? 1 - auv_clip(log(1 + di) / logR, 0.0, 1.0) : 1 - auv_clip(di / R, 0.0, 1.0);
+        cl = auv_clip(cl, -1.0, 1.0);
+        auv_st<WT>(ob + i, cl);
+        if (oo) auv_st<WT>(oo + i, (float)cl);
+      } else {
+        L.dbits[i] = d2u(di);
+      }
       if (colav) num += d.beam_w[i] * ((di != R) ? R * exp(-0.1 * di) : raw_free);
       col |= (di < W);
+    }
+    if (ns) {
+      // ---- pooled tail, every sector scanned (this path keeps no hit masks) ----
+      const double width = d.pool_width, theta = 2 * AUV_PI / S;
+      auv_wave_lds_sync();
+      for (int i = lane; i < S; i += AUV_WAVE) k2_pool_init(L, S, i, d.pool_word[i] | K2_POOL_HAS, R);
+      auv_wave_lds_sync();
+      for (int i = lane; i < S; i += AUV_WAVE) k2_pool_scan(L, S, i, d.pool_word[i] | K2_POOL_HAS, width, theta);
+      auv_wave_lds_sync();
+      int k0 = 0;
+      for (int i0 = 0; i0 < S; i0 += AUV_WAVE) {
+        const int i = i0 + lane;
+        k2_pool_out<WT>(d, L, e, lane, S, i, i < S ? (d.pool_word[i] | K2_POOL_HAS) : 0u, k0, R, logR, ob, oo);
+      }
     }
   }
   col = __any(col);
@@ -1029,6 +1153,14 @@ __device__ __forceinline__ int k2_back(const AuvDev& d, const int e, const int l
   }
   if (rew_lidar_out) *rew_lidar_out = term;
   return col != 0;
+}
+// The pooled and the plain form are separate instantiations behind one uniform branch: the plain one is the sweep's tail as
+// it was without pooling (no trace of the pooled path in its code), the pooled one adds the tail above.
+template <bool WT = false>
+__device__ __forceinline__ int k2_back(const AuvDev& d, const int e, const int lane, const Slice& L, const int n_act,
+                                       float* __restrict__ obs_out = nullptr, double* rew_lidar_out = nullptr, const int2* lim0 = nullptr) {
+  if (d.pool_ns) return k2_back_impl<WT, true>(d, e, lane, L, n_act, obs_out, rew_lidar_out, lim0);
+  return k2_back_impl<WT, false>(d, e, lane, L, n_act, obs_out, rew_lidar_out, lim0);
 }
 
 #ifndef AUV_DEVICE_FUNCS_ONLY

@@ -60,6 +60,7 @@ struct StepTabs {
   int32_t* ring_pos;
   const int32_t* fw_serial;   // (fresh worlds: the slot's serial, for the episode log's world column)
   int32_t n;                  // environments of the handle (AuvDev::n)
+  int32_t pool_ns;            // sectors of a pooled observation row (AuvDev::pool_ns; 0: off)
 };
 
 // SciPy PPoly: interval search + power-basis eval.  The knots are near-uniform, so the interval
@@ -238,8 +239,12 @@ __device__ __forceinline__ void restore_env(const AuvDev& d, int e, int w2, int 
   const int S = d.cfg.n_sensors;
   const size_t n = (size_t)d.n;
   const double* ws2 = d.world_scalar + 8 * (size_t)w2;
-  const int D = 6 + (d.cfg.use_lidar ? S * (d.cfg.obs_channels == 3 ? 3 : 1) : 0);   // row stride of obs_out
-  const int DL = 6 + (d.cfg.use_lidar ? S : 0);                                        // columns this path writes
+  const int ns = d.pool_ns;
+  const int D = auv_obs_cols(d.cfg, ns);                                                // row stride of obs_out
+  // columns this path writes: 6 + S (6 without LiDAR) -- pooled, the row's first D of them: the sectors' closenesses, then
+  // zeros from the reset row's unused columns into the velocity channels, which are zero anyway.  (One value formed from D
+  // instead of a second one from the pooling state: the multi-step launch's finish wave has no register to spare here.)
+  const int DL = D < 6 + S ? D : 6 + S;
   if (d.w_ready && 6 + S <= 4 * AUV_WAVE && d.k_max <= AUV_WAVE) {
     // The usual shapes: every row fits four wave passes.  The auto-reset sits on the reward kernel's
     // critical path and the compiler must assume that the rows alias, so the copy is written as:
@@ -285,6 +290,8 @@ __device__ __forceinline__ void restore_env(const AuvDev& d, int e, int w2, int 
     if (lane < 8) d.info64[8 * (size_t)e + lane] = row;
     else if (lane < 16) d.nav64[8 * (size_t)e + lane - 8] = row;
     if (lane < d.k_max) auv_st<WTM>(&d.nearby[(size_t)e * d.k_max + lane], nb), d.limits[(size_t)e * d.k_max + lane] = lm;
+    // pooled: the sectors' distances of the reset row (last: an unpooled restore keeps its load-then-store order untouched)
+    for (int k = lane; k < ns; k += AUV_WAVE) d.sector_d[(size_t)e * ns + k] = auv_ld<COH>(d.w_sector_d + (size_t)w2 * ns + k);
     return;
   }
   if (lane == 0) {
@@ -311,6 +318,7 @@ __device__ __forceinline__ void restore_env(const AuvDev& d, int e, int w2, int 
     for (int k = lane; k < d.k_max; k += AUV_WAVE) d.nearby[(size_t)e * d.k_max + k] = 0;
     return;
   }
+  for (int k = lane; k < ns; k += AUV_WAVE) d.sector_d[(size_t)e * ns + k] = auv_ld<COH>(d.w_sector_d + (size_t)w2 * ns + k);
   for (int i = lane; i < S; i += AUV_WAVE) d.lidar_d[(size_t)e * S + i] = auv_ld<COH>(d.w_lidar + (size_t)w2 * S + i);
   for (int i = lane; i < 6 + S; i += AUV_WAVE) {
     const double v = auv_ld<COH>(d.w_obs64 + (size_t)w2 * (6 + S) + i);
@@ -587,7 +595,7 @@ __device__ __forceinline__ NavOut nav_tail(const Desc& d, const int e, const int
   double* inf = d.info64 + 8 * (size_t)e;
   double* nv = d.nav64 + 8 * (size_t)e;
   double* ob = d.obs64 + (size_t)e * (6 + S);
-  const int D = 6 + (d.cfg.use_lidar ? S * (d.cfg.obs_channels == 3 ? 3 : 1) : 0);   // row stride of obs_out
+  const int D = auv_obs_cols(d.cfg, d.pool_ns);                                        // row stride of obs_out
   const double2 A = t.nr.A, B = t.nr.B;
   const double cum = t.nr.cum;
   NavOut out;
@@ -832,8 +840,8 @@ __device__ void k3_reward_env(const AuvDev& d, const int e, const int lane, cons
   const int w = d.world_idx[e];
   double* inf = d.info64 + 8 * (size_t)e;
   const double* ob = d.obs64 + (size_t)e * (6 + S);
-  const int D = 6 + (d.cfg.use_lidar ? S * (d.cfg.obs_channels == 3 ? 3 : 1) : 0);   // row stride of obs_out
-  const int DL = 6 + (d.cfg.use_lidar ? S : 0);                                        // columns this path writes
+  const int D = auv_obs_cols(d.cfg, d.pool_ns);                                        // row stride of obs_out
+  const int DL = 6 + (d.cfg.use_lidar ? auv_obs_lidar_cols(S, d.pool_ns) : 0);         // columns this path writes
   const int collision = collision_pre >= 0 ? collision_pre : d.collision[e];
   if (lane == 0) inf[0] = collision;
   if (full) {
@@ -978,6 +986,7 @@ __global__ void __launch_bounds__(AUV_BLOCK) k_harvest(AuvDev d, int count, cons
     d.w_limits[(size_t)w * d.k_max + k] = d.limits[(size_t)e * d.k_max + k];
   }
   if (lane == 0) d.w_collision[w] = d.collision[e];
+  for (int k = lane; k < d.pool_ns; k += AUV_WAVE) d.w_sector_d[(size_t)w * d.pool_ns + k] = d.sector_d[(size_t)e * d.pool_ns + k];
 }
 
 #endif

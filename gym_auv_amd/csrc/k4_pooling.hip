@@ -38,31 +38,7 @@ __global__ void __launch_bounds__(AUV_BLOCK) k4_pooling(AuvDev d, const int32_t*
     while (k + 1 < n_sectors && i >= sector_start[k + 1]) k++;
     const int s0 = sector_start[k], N = sector_start[k + 1] - s0;
     const double xi = x[i];
-    // sensor.py:268-291 for threshold x_i
-    const double dd = xi * theta;
-    double opening_width = 0, opening_span = 0, opening_start = -theta * (N - 1) / 2;
-    bool found = false;
-    for (int j = 0; j < N; j++) {
-      const bool survives = x[s0 + j] > xi + width;
-      if (survives) {
-        opening_width += dd;
-        opening_span += theta;
-        if (opening_width > width) {
-          const double centre = opening_start + opening_span / 2;
-          if (fabs(centre) < theta * (N - 1) / 4) found = true;
-        }
-      } else {
-        opening_width += 0.5 * dd;
-        opening_span += 0.5 * theta;
-        if (opening_width > width) {
-          const double centre = opening_start + opening_span / 2;
-          if (fabs(centre) < theta * (N - 1) / 4) found = true;
-        }
-        opening_width = 0;
-        opening_span = 0;
-        opening_start = -theta * (N - 1) / 2 + j * theta;
-      }
-    }
+    const bool found = auv_pool_opening(x, s0, N, xi, width, theta);   // sensor.py:268-291 for threshold x_i
     atomicMax(&mx[k], pd2u(xi));
     if (!found) atomicMin(&mn[k], pd2u(xi));
   }

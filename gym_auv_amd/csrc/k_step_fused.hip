@@ -304,7 +304,7 @@ __device__ __forceinline__ void roles_finish_wave(const AuvDev& dk, const int f,
   st.cfg.min_path_progress = dc->cfg.min_path_progress, st.cfg.look_ahead_distance = dc->cfg.look_ahead_distance;
   st.cfg.max_timesteps = dc->cfg.max_timesteps, st.cfg.rewarder = dc->cfg.rewarder, st.cfg.test_mode = dc->cfg.test_mode;
   st.cfg.auto_reset = dc->cfg.auto_reset, st.cfg.n_sensors = dc->cfg.n_sensors, st.cfg.use_lidar = dc->cfg.use_lidar;
-  st.cfg.obs_channels = dc->cfg.obs_channels;
+  st.cfg.obs_channels = dc->cfg.obs_channels, st.pool_ns = dc->pool_ns;
   st.knot_s = dc->knot_s, st.knot_coef = dc->knot_coef;
   st.info64 = dc->info64, st.nav64 = dc->nav64, st.obs64 = dc->obs64, st.rew_path = dc->rew_path, st.reward64 = dc->reward64;
   st.step_info = dc->step_info, st.episode = dc->episode, st.ep_log = dc->ep_log, st.ep_log_count = dc->ep_log_count;
@@ -703,7 +703,7 @@ __device__ __forceinline__ void roles_finish_wave_multi(const AuvDev& dk, const 
   st.cfg.min_path_progress = dc->cfg.min_path_progress, st.cfg.look_ahead_distance = dc->cfg.look_ahead_distance;
   st.cfg.max_timesteps = dc->cfg.max_timesteps, st.cfg.rewarder = dc->cfg.rewarder, st.cfg.test_mode = dc->cfg.test_mode;
   st.cfg.auto_reset = dc->cfg.auto_reset, st.cfg.n_sensors = dc->cfg.n_sensors, st.cfg.use_lidar = dc->cfg.use_lidar;
-  st.cfg.obs_channels = dc->cfg.obs_channels;
+  st.cfg.obs_channels = dc->cfg.obs_channels, st.pool_ns = dc->pool_ns;
   st.knot_s = dc->knot_s, st.knot_coef = dc->knot_coef;
   st.info64 = dc->info64, st.nav64 = dc->nav64, st.obs64 = dc->obs64, st.rew_path = dc->rew_path, st.reward64 = dc->reward64;
   st.step_info = dc->step_info, st.episode = dc->episode, st.ep_log = dc->ep_log, st.ep_log_count = dc->ep_log_count;

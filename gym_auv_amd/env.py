@@ -268,10 +268,10 @@ class AuvEnv:
     def _obs(self):
         # the reference returns float64 although the space says float32 (environment.py:276-280)
         v = self.config.vessel
-        S = v.n_sensors
+        L = v.lidar_shape[1]                        # closeness columns: one per beam, or per sector when pooled
         row = self._host[:self._n_obs64]
-        flat = np.concatenate([row[:6 + (S if v.use_lidar else 0)],
-                               np.zeros(2 * S if (v.use_lidar and v.sensor_use_velocity_observations) else 0)])
+        flat = np.concatenate([row[:6 + (L if v.use_lidar else 0)],
+                               np.zeros(2 * L if (v.use_lidar and v.sensor_use_velocity_observations) else 0)])
         if not v.use_dict_observation:
             return flat
         # environment.py:281-288: closeness row stacked over the (zero) velocity rows

@@ -4,9 +4,10 @@ n_sectors "feasible distances" (the dimensionality reduction of the gym-auv pape
 Reference: `LidarPreprocessor._feasibility_pooling`
 (/root/reference/gym_auv/objects/vessel/sensor.py:251-296) and the sigmoid sector partition
 `sector_partition_fun` (utils/sector_partitioning.py:4-9).  The class wiring around them is
-broken at the reference's HEAD (never initialised), so this is offered as an
-optional post-kernel on the ranges (`BatchedAuvEnv.feasibility_pooling()`), not as part of
-`step()`.
+broken at the reference's HEAD (never initialised); its intent is what this package
+implements: with `VesselConfig.sensor_use_feasibility_pooling` every step shape emits the pooled
+observation (the LiDAR wave pools its own ranges), and `BatchedAuvEnv.feasibility_pooling()` runs
+the same arithmetic as a post-kernel on the current ranges.
 
 For one sector the reference walks the sensors in ascending order of range and returns the
 first range x for which the sector has no opening wider than `width` among the sensors whose

@@ -31,7 +31,7 @@
 extern "C" {
 #endif
 
-#define AUV_ABI_VERSION 4
+#define AUV_ABI_VERSION 5
 
 enum {
   AUV_OK = 0,
@@ -117,7 +117,9 @@ typedef struct auv_handle auv_handle_t;
 enum {
   AUV_FIELD_STATE = 0,       /* [6][N]  x, y, psi, u, v, r   (Vessel._state, SoA)          */
   AUV_FIELD_LIDAR_D = 1,     /* [N][S]  Vessel._last_sensor_dist_measurements              */
-  AUV_FIELD_OBS64 = 2,       /* [N][6+S] observation before the float32 cast               */
+  AUV_FIELD_OBS64 = 2,       /* [N][6+S] observation before the float32 cast.  Pooled (auv_set_obs_pooling): the
+                                 stride stays 6+S; columns 6 .. 6+n_sectors-1 hold the sectors' closenesses and
+                                 the rest stay 0                                                 */
   AUV_FIELD_REWARD64 = 3,    /* [N]                                                        */
   AUV_FIELD_INFO64 = 4,      /* [N][8] collision, reached_goal, goal_distance, progress,
                                  cumulative_reward, max_progress, vessel_arclength, sum of |cross-track
@@ -140,6 +142,10 @@ enum {
                                  (all zero except between a hand-over time-out and the call that recovers)     */
   AUV_FIELD_FW_STATE = 16,   /* [W] int32  fresh-world mode only: 0 READY (unseen), 1 IN_USE, 2 STALE (queued / being rebuilt) */
   AUV_FIELD_FW_SERIAL = 17,  /* [W] int32  fresh-world mode only: the slot holds world number `serial` of its environment    */
+  AUV_FIELD_SECTOR_D = 18,   /* [N][n_sectors] pooled observation only (0 bytes otherwise): the feasible distance of every
+                                 sector behind the current observation row (vessel.py:556-557 "feasible_distances");
+                                 after a reset / auto-reset those of the reset row. Read-only in spirit: writing it
+                                 changes no observation                                                              */
   AUV_FIELD_STEP_INFO = 14   /* [N][4] the `info` dict of the last step() as the reference
                                  returns it (environment.py:336-340): collision, reached_goal,
                                  goal_distance, progress -- of the step that was taken, i.e. the
@@ -375,6 +381,22 @@ int auv_probe_streams(auv_handle_t* h, int32_t n_streams, void* const* streams);
  *   AUV_STEP_SIDE_BY_SIDE  K1, [K2 + K3-nav], K3-reward, whole step. */
 int auv_step_timed(auv_handle_t* h, const void* actions_dev, int32_t action_dtype, float* obs_dev,
                    float* reward_dev, uint8_t* done_dev, void* stream, float* out_ms4);
+
+/* Feasibility-pooled observations (VesselConfig.sensor_use_feasibility_pooling; the dimensionality reduction of the
+ * gym-auv paper).  The observation row becomes [6 navigation features | n_sectors closenesses | (velocity channels:
+ * 2 * n_sectors zeros)]: the closeness (sensor_log_transform or linear, vessel.py:88-95) of each sector's feasible distance,
+ * LidarPreprocessor._feasibility_pooling (sensor.py:251-296) over sensors sector_start[k] .. sector_start[k+1]-1 with
+ * opening width `width` (= vessel_width * feasibility_width_multiplier) and sensor spacing 2*pi/S -- bit for bit what
+ * auv_feasibility_pooling computes on the same ranges.  Every step shape produces it (the LiDAR wave pools its own
+ * ranges); the float32 rows the caller passes are 6 + c * n_sectors wide (c = obs_channels), and so is a policy's obs_dim.
+ * Unchanged by pooling: the ranges (LIDAR_D), collision, both rewarders' LiDAR terms, done, info, the episode log and the
+ * state -- they read the full ranges, as in the reference.  OBS64 keeps its stride (see the field).
+ *   sector_start_host [n_sectors + 1] int32, host memory: strictly increasing from 0 to n_sensors (gym_auv_amd.pooling.
+ *   sector_starts gives the reference's sigmoid partition).  n_sectors = 0: off (the default).  width: finite, > 0.
+ * Only between auv_create and the first bank load (auv_load_worlds / auv_generate_worlds / auv_fresh_worlds_create): the
+ * per-world reset rows depend on it -- later calls return AUV_ESTATE; a malformed table AUV_EINVAL.  With use_lidar = 0 the
+ * call is accepted and changes nothing (the observation has no LiDAR columns).                                             */
+int auv_set_obs_pooling(auv_handle_t* h, int32_t n_sectors, const int32_t* sector_start_host, double width);
 
 /* Feasibility pooling (optional post-kernel on the current LiDAR ranges):
  * for every env and sector k (sensors sector_start[k] .. sector_start[k+1]-1) the feasible

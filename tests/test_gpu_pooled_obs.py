@@ -1,0 +1,351 @@
+"""-m gpu: feasibility-pooled observations (VesselConfig.sensor_use_feasibility_pooling) from every step shape.
+
+Ground truth for the pooled values is the oracle's pooling (the reference's _feasibility_pooling, pinned by G6 in
+test_pooling.py) of the device's OWN ranges: pooling picks one of the ranges through threshold comparisons, so pooling the
+oracle's ranges would turn last-bit range differences into large jumps; the ranges themselves are pinned elsewhere.  Everything
+pooling must not change -- ranges, collision, reward, done, info -- is compared bit for bit with an unpooled twin handle."""
+import os
+import sys
+import warnings
+
+import numpy as np
+import pytest
+import torch
+
+from gym_auv_amd import _capi
+from gym_auv_amd._capi import make_config, obs_pooling
+from gym_auv_amd.config import effective_reference_config
+from gym_auv_amd.scenarios import empty_scenario, moving_obstacles_world, polygon_world
+from gym_auv_amd.world import build_world, pack_bank
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+SHAPES = [(180, 9, 20), (64, 8, 8), (256, 16, 16)]
+R = 150.0
+
+
+def _cfg(ns, nps, pooled=True, velocity=False, max_timesteps=37):
+    cfg = effective_reference_config(use_lidar=True)
+    cfg.vessel.n_sectors, cfg.vessel.n_sensors_per_sector = ns, nps
+    cfg.vessel.sensor_use_feasibility_pooling = pooled
+    cfg.vessel.sensor_use_velocity_observations = velocity
+    cfg.episode.max_timesteps = max_timesteps
+    return cfg
+
+
+def _bank(kind, n_worlds, seed=0):
+    if kind == "polygons":
+        ws = [polygon_world(900 + seed + i, n_polygons=50) for i in range(n_worlds)]
+    elif kind == "moving28":
+        ws = [moving_obstacles_world(400 + seed + i) for i in range(n_worlds)]
+    else:                                            # nothing within sensor range: the sweep's n_act == 0 path
+        ws = [empty_scenario() for _ in range(n_worlds)]
+    return pack_bank([build_world(w) for w in ws])
+
+
+def _env(cfg, bank, n, **kw):
+    from gym_auv_amd.batched_env import BatchedAuvEnv
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")
+        return BatchedAuvEnv(cfg, bank, n, device="cuda:0", **kw)
+
+
+def _closeness(v):
+    return 1 - np.clip(np.log(1 + v) / np.log(1 + R), 0.0, 1.0)
+
+
+class _Pool:
+    """The oracle's pooling of given ranges (written into an oracle as test_pooling.py does)."""
+
+    def __init__(self, cfg, n, bank):
+        from oracle.pyoracle import Oracle
+        ns, self.starts, self.width = obs_pooling(cfg)
+        self.o = Oracle(make_config(cfg), n, bank)
+        self.o.reset()
+
+    def __call__(self, lidar_d):
+        self.o.write("LIDAR_D", np.ascontiguousarray(lidar_d))
+        return self.o.feasibility_pooling(self.starts, self.width)
+
+
+def _check_row(env, pool, ns, c):
+    """SECTOR_D == the oracle's pooling of LIDAR_D, bit for bit; the observation's closeness columns are its closeness."""
+    lid = env.read("LIDAR_D").cpu().numpy()
+    sd = env.read("SECTOR_D").cpu().numpy()
+    ref = pool(lid)
+    np.testing.assert_array_equal(sd, ref)
+    o64 = env.read("OBS64").cpu().numpy()
+    S = lid.shape[1]
+    assert o64.shape[1] == 6 + S
+    assert np.abs(o64[:, 6:6 + ns] - _closeness(ref)).max() <= 1e-12
+    assert (o64[:, 6 + ns:] == 0.0).all()
+    obs = env.obs.cpu().numpy()
+    assert obs.shape[1] == 6 + c * ns
+    assert np.abs(obs[:, 6:6 + ns] - _closeness(ref)).max() <= 1e-6
+    assert (obs[:, 6 + ns:] == 0.0).all()            # the velocity channels
+    np.testing.assert_array_equal(obs[:, :6], o64[:, :6].astype(np.float32))
+    return sd
+
+
+CASES = [(shape, kind, rew) for shape in SHAPES for kind in ("polygons", "moving28", "empty") for rew in ("colav", "pathfollow")]
+
+
+@pytest.mark.parametrize("shape,kind,rewarder", CASES, ids=["%d-%s-%s" % (s[0], k, r) for s, k, r in CASES])
+def test_pooled_step_parity(shape, kind, rewarder):
+    S, ns, nps = shape
+    n = 128 if S != 180 else 256
+    velocity = rewarder == "pathfollow"
+    c = 3 if velocity else 1
+    bank = _bank(kind, 2 * n, seed=S)
+    pooled = _env(_cfg(ns, nps, velocity=velocity), bank, n, rewarder=rewarder)
+    plain = _env(_cfg(ns, nps, pooled=False, velocity=velocity), bank, n, rewarder=rewarder)
+    pool = _Pool(_cfg(ns, nps, velocity=velocity), n, bank)
+    assert pooled.obs_dim == 6 + c * ns and plain.obs_dim == 6 + c * S
+    assert pooled.observation_space.shape == (6 + c * ns,)
+    pooled.reset(), plain.reset()
+    _check_row(pooled, pool, ns, c)
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(S + len(kind))
+    scale, shift = torch.tensor([2.0, 0.3], device="cuda:0"), torch.tensor([1.0, 0.15], device="cuda:0")
+    resets = 0
+    for t in range(200):
+        a = torch.rand((n, 2), generator=g, device="cuda:0") * scale - shift
+        op, rp, dp, _ = pooled.step(a)
+        ou, ru, du, _ = plain.step(a)
+        torch.cuda.synchronize()
+        sd = _check_row(pooled, pool, ns, c)
+        # the post-kernel on the same ranges agrees bit for bit
+        dist, _ = pooled.feasibility_pooling()
+        np.testing.assert_array_equal(dist.cpu().numpy(), sd)
+        assert torch.equal(op[:, :6], ou[:, :6]) and torch.equal(rp, ru) and torch.equal(dp, du), t
+        for f in ("LIDAR_D", "COLLISION", "INFO64", "STEP_INFO", "STATE", "REWARD64"):
+            assert torch.equal(pooled.read(f), plain.read(f)), (t, f)
+        resets += int(dp.sum())
+    assert resets > 0
+    if kind == "empty":
+        np.testing.assert_array_equal(pooled.read("SECTOR_D").cpu().numpy(), np.full((n, ns), R))
+    pooled.close(), plain.close()
+
+
+def _shape_run(shape_name, cfg, bank, n, ring, steps):
+    """obs / SECTOR_D / reward / done after every step (multi-step launches: after every launch) of one step shape."""
+    env = _env(cfg, bank, n, auto_reset=True)
+    env.reset()
+    out = {}
+    if shape_name == "side_by_side":
+        env.set_step_mode("side_by_side")
+    if shape_name in ("chains", "async") or shape_name.startswith("multi"):
+        env.set_sub_batches(1 if shape_name.startswith("multi") else 4, strict=shape_name.startswith("multi"))
+    if shape_name == "multi_steps":
+        env.set_multi_order("steps")
+    if shape_name == "graph":
+        env.capture_graph(steps=1)
+
+    def snap(t):
+        torch.cuda.synchronize()
+        out[t] = (env.obs.clone(), env.read("SECTOR_D"), env.reward.clone(), env.done.clone())
+
+    slots = ring.shape[0]
+    if shape_name.startswith("multi"):
+        t = 0
+        lengths = [1, 6, 16, 64]
+        while t < steps:
+            T = min(lengths[len(out) % len(lengths)], steps - t)
+            env.step_multi(ring, t % slots, T)
+            t += T
+            snap(t)
+    else:
+        for t in range(steps):
+            a = ring[t % slots]
+            if shape_name == "one_launch" or shape_name == "side_by_side":
+                env.step(a)
+            elif shape_name == "chains":
+                env.step_pipelined(a)
+            elif shape_name == "async":
+                env.step_async(a)
+                env.step_wait()
+            elif shape_name == "graph":
+                env.step_graph(a)
+            snap(t + 1)
+    env.close()
+    return out
+
+
+@pytest.mark.parametrize("shape_name", ["side_by_side", "chains", "async", "graph", "multi_cohorts", "multi_steps"])
+def test_every_step_shape_pools_bitwise_the_same(shape_name):
+    n, steps = 1024, 96
+    cfg = _cfg(9, 20, max_timesteps=23)
+    bank = _bank("moving28", 48)
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(5)
+    ring = (torch.rand((steps, n, 2), generator=g, device="cuda:0") * torch.tensor([2.0, 0.3], device="cuda:0")
+            - torch.tensor([1.0, 0.15], device="cuda:0")).contiguous()
+    ref = _shape_run("one_launch", cfg, bank, n, ring, steps)
+    got = _shape_run(shape_name, cfg, bank, n, ring, steps)
+    assert len(got) > 0
+    for t, v in got.items():
+        for a, b in zip(ref[t], v):
+            assert torch.equal(a, b), (shape_name, t)
+    assert sum(int(v[3].sum()) for v in ref.values()) > 0          # auto-resets happened inside the compared stretch
+
+
+def test_reset_rows_and_fresh_worlds():
+    from gym_auv_amd.devgen import FreshWorlds
+    cfg = _cfg(9, 20, max_timesteps=25)
+    n = 128
+    env = _env(cfg, FreshWorlds(depth=3, seed=21), n, auto_reset=True)
+    bank = _bank("moving28", 4)
+    pool = _Pool(cfg, n, bank)
+    env.reset()
+    _check_row(env, pool, 9, 1)
+    g = torch.Generator(device="cuda:0")
+    g.manual_seed(2)
+    ended = 0
+    for t in range(120):
+        a = torch.rand((n, 2), generator=g, device="cuda:0") * torch.tensor([2.0, 0.3], device="cuda:0") - torch.tensor([1.0, 0.15], device="cuda:0")
+        _, _, d, _ = env.step(a)
+        torch.cuda.synchronize()
+        _check_row(env, pool, 9, 1)                      # fresh episodes' first rows included
+        ended += int(d.sum())
+    assert ended >= n
+    # reset() puts every environment's reset row back
+    env.reset()
+    _check_row(env, pool, 9, 1)
+    env.close()
+
+
+@pytest.mark.parametrize("velocity", [False, True])
+@pytest.mark.parametrize("dict_obs", [False, True])
+def test_env_and_vecenv_interfaces(velocity, dict_obs):
+    from gym_auv_amd.env import AuvEnv
+    from gym_auv_amd.vec_env import AuvVecEnv
+    c = 3 if velocity else 1
+    cfg = _cfg(9, 20, velocity=velocity, max_timesteps=10000)
+    cfg.vessel.use_dict_observation = dict_obs
+    flat_cfg = _cfg(9, 20, velocity=velocity, max_timesteps=10000)
+    n = 16
+    worlds = [build_world(moving_obstacles_world(60 + i)) for i in range(2 * n)]
+    ve, vf = AuvVecEnv(cfg, worlds, n, track_trajectories=()), AuvVecEnv(flat_cfg, worlds, n, track_trajectories=())
+    o, f = ve.reset(), vf.reset()
+    rs = np.random.RandomState(1)
+    for _ in range(6):
+        a = rs.uniform([0, -0.15], [1, 0.15], (n, 2)).astype(np.float32)
+        o, _, _, _ = ve.step(a)
+        f, _, _, _ = vf.step(a)
+        assert f.shape == (n, 6 + c * 9)
+        if dict_obs:
+            assert o["lidar"].shape == (n, c, 9) and o["proprioceptive"].shape == (n, 6)
+            np.testing.assert_array_equal(o["lidar"][:, 0, :], f[:, 6:6 + 9])
+            np.testing.assert_array_equal(o["proprioceptive"], f[:, :6])
+            assert ve.observation_space["lidar"].shape == (c, 9)
+        else:
+            np.testing.assert_array_equal(o, f)
+            assert ve.observation_space.shape == (6 + c * 9,)
+        assert (f[:, 6 + 9:] == 0.0).all()
+    ve.close(), vf.close()
+    env = AuvEnv(cfg)
+    ob = env.reset()
+    for _ in range(4):
+        ob, _, _, _ = env.step(env.action_space.sample())
+        if dict_obs:
+            assert ob["lidar"].shape == (c, 9) and env.observation_space["lidar"].shape == (c, 9)
+            assert env.observation_space["lidar"].contains(ob["lidar"].astype(np.float32))
+        else:
+            assert ob.shape == (6 + c * 9,) and env.observation_space.contains(ob.astype(np.float32))
+    env.close()
+
+
+def _policy(env, T, seed=0):
+    sys.path.insert(0, os.path.join(ROOT, "examples"))
+    import ppo
+    from gym_auv_amd.policy import FusedActorCritic
+    torch.manual_seed(seed)
+    net = ppo.ActorCritic(env.obs_dim).to("cuda:0")
+    with torch.no_grad():
+        for m in net.modules():
+            if isinstance(m, torch.nn.Linear):
+                m.bias.uniform_(-0.3, 0.3)
+    return net, FusedActorCritic(net, env, rollout=T, debug=True, seed=seed, reward_scale=0.01)
+
+
+def test_policy_on_a_pooled_env():
+    n, T = 512, 8
+    bank = _bank("moving28", 32)
+    env = _env(_cfg(9, 20), bank, n)
+    env.reset()
+    env.set_sub_batches(2, probe_streams=False)
+    assert env.obs_dim == 15
+    net, fused = _policy(env, T)
+    fused.begin_rollout()
+    for t in range(T):
+        obs = env.obs.clone()
+        for i in range(env.sub_batches):
+            fused.act(i)
+        torch.cuda.synchronize()
+        with torch.no_grad():
+            mu_ref = net.pi(obs)
+        assert float((fused.mu - mu_ref).abs().max()) <= 1e-5
+        for i in range(env.sub_batches):
+            env.step_slice(i, fused.actions)
+        torch.cuda.synchronize()
+    env.close()
+    # the rollout call stores the observations env.step gives: the same samples step by step from Python
+    env_a, env_b = _env(_cfg(9, 20), bank, n), _env(_cfg(9, 20), bank, n)
+    for e in (env_a, env_b):
+        e.reset()
+        e.set_sub_batches(2, probe_streams=False)
+    _, fa = _policy(env_a, T, seed=3)
+    _, fb = _policy(env_b, T, seed=3)
+    torch.cuda.synchronize()                             # (the chains are not ordered against the caller's stream)
+    fa.begin_rollout(), fb.begin_rollout()
+    fa.rollout(T)
+    obs_seen = []
+    for t in range(T):
+        torch.cuda.synchronize()
+        obs_seen.append(env_b.obs.clone())
+        for i in range(env_b.sub_batches):
+            fb.act(i)
+            env_b.step_slice(i, fb.actions)
+    for i in range(env_b.sub_batches):
+        fb.act(i)
+    torch.cuda.synchronize()
+    O = fa.buffers()[0]
+    for t in range(T):
+        assert torch.equal(O[t], obs_seen[t]), t
+        assert O[t].shape == (n, 15)
+    for x, y in zip(fa.buffers(), fb.buffers()):
+        assert torch.equal(x, y)
+    env_a.close(), env_b.close()
+
+
+def test_abi_errors():
+    import ctypes as C
+    lib = _capi.load_library()
+    cfg = _cfg(9, 20)
+    st = make_config(cfg)
+    starts = obs_pooling(cfg)[1]
+    h = C.c_void_p()
+    assert lib.auv_create(C.byref(st), 8, 0, C.byref(h)) == 0
+    try:
+        bad = [np.array([0, 54, 54, 180], np.int32), np.array([1, 90, 180], np.int32), np.array([0, 90, 179], np.int32)]
+        for b in bad:
+            assert lib.auv_set_obs_pooling(h, len(b) - 1, b.ctypes.data_as(C.c_void_p), 6.275) == -1
+        assert lib.auv_set_obs_pooling(h, -1, starts.ctypes.data_as(C.c_void_p), 6.275) == -1
+        for w in (0.0, -1.0, float("inf"), float("nan")):
+            assert lib.auv_set_obs_pooling(h, 9, starts.ctypes.data_as(C.c_void_p), w) == -1
+        assert lib.auv_set_obs_pooling(h, 9, starts.ctypes.data_as(C.c_void_p), 6.275) == 0
+        bank = _bank("moving28", 8)
+        bs, keep = _capi.make_bank_struct(bank)
+        assert lib.auv_load_worlds(h, C.byref(bs)) == 0
+        assert lib.auv_field_bytes(h, 18) == 8 * 8 * 9
+        assert lib.auv_set_obs_pooling(h, 9, starts.ctypes.data_as(C.c_void_p), 6.275) == -3       # AUV_ESTATE
+        assert lib.auv_set_obs_pooling(h, 0, None, 0.0) == -3
+    finally:
+        lib.auv_destroy(h)
+    plain = _env(_cfg(9, 20, pooled=False), _bank("moving28", 8), 8)
+    assert _LIB_field_bytes(plain, 18) == 0
+    plain.close()
+
+
+def _LIB_field_bytes(env, field):
+    return _capi.load_library().auv_field_bytes(env._h, field)

@@ -1,6 +1,8 @@
 #!/usr/bin/env python3
 """Open-loop rate with SEVERAL steps per launch (auv_step_multi) against one step per launch, by chains and launch length:
-python tools/multi_bench.py [workload polygons50|moving28] [envs]"""
+python tools/multi_bench.py [workload polygons50|moving28] [envs] [--feasibility-pooling] [--quick]
+--feasibility-pooling: the observation pooled to 9 sectors (VesselConfig.sensor_use_feasibility_pooling);
+--quick: one chain only, one step per launch and 64-step launches in cohort order"""
 import json
 import os
 import sys
@@ -14,10 +16,13 @@ from gym_auv_amd.batched_env import BatchedAuvEnv  # noqa: E402
 from gym_auv_amd.config import effective_reference_config  # noqa: E402
 from gym_auv_amd.world import build_bank_parallel  # noqa: E402
 
-wl = sys.argv[1] if len(sys.argv) > 1 else "polygons50"
-n = int(sys.argv[2]) if len(sys.argv) > 2 else 4096
+POOL, QUICK = "--feasibility-pooling" in sys.argv, "--quick" in sys.argv
+argv = [a for a in sys.argv if not a.startswith("--")]
+wl = argv[1] if len(argv) > 1 else "polygons50"
+n = int(argv[2]) if len(argv) > 2 else 4096
 dev = torch.device("cuda:0")
 cfg = effective_reference_config(use_lidar=True)
+cfg.vessel.sensor_use_feasibility_pooling = POOL
 gen, kw = ("polygon_world", dict(n_polygons=50)) if wl == "polygons50" else ("moving_obstacles_world", dict())
 cache = "/tmp/multi_bench_%s_%d.npz" % (wl, n)
 if os.path.exists(cache):
@@ -28,12 +33,14 @@ else:
     np.savez(cache, **bank)
 slots = 64
 ring = torch.rand((slots, n, 2), device=dev) * torch.tensor([2.0, 0.3], device=dev) - torch.tensor([1.0, 0.15], device=dev)
-for k in (1, 2, 4):
+for k in ((1,) if QUICK else (1, 2, 4)):
     env = BatchedAuvEnv(cfg, bank, n, device=dev, auto_reset=True)
     env.reset()
     env.set_sub_batches(k, strict=True)
     steps = 1920
-    for T, order in ((0, "-"), (8, "steps"), (64, "steps"), (8, "cohorts"), (16, "cohorts"), (64, "cohorts"), (64, "cohorts:6:16"), (64, "cohorts:20:40")):
+    shapes = ((0, "-"), (64, "cohorts")) if QUICK else \
+        ((0, "-"), (8, "steps"), (64, "steps"), (8, "cohorts"), (16, "cohorts"), (64, "cohorts"), (64, "cohorts:6:16"), (64, "cohorts:20:40"))
+    for T, order in shapes:
         if T:
             o = order.split(":")
             env.set_multi_order(o[0], *([int(o[1]), int(o[2])] if len(o) > 1 else []))
@@ -50,6 +57,6 @@ for k in (1, 2, 4):
         run(steps)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        print(json.dumps(dict(workload=wl, envs=n, chains=k, steps_per_launch=T or 1, order=order, rate_M=round(n * steps / dt / 1e6, 1), us_per_step=round(1e6 * dt / steps, 2),
+        print(json.dumps(dict(workload=wl, envs=n, pooled=POOL, obs_dim=env.obs_dim, chains=k, steps_per_launch=T or 1, order=order, rate_M=round(n * steps / dt / 1e6, 1), us_per_step=round(1e6 * dt / steps, 2),
                               health=env.health())), flush=True)
     env.close()

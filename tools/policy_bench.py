@@ -1,5 +1,7 @@
 #!/usr/bin/env python3
-"""Time of the fused policy launch alone (csrc/k6_policy.hip) and of policy + environment step chains: tools/policy_bench.py [envs]"""
+"""Time of the fused policy launch alone (csrc/k6_policy.hip) and of policy + environment step chains:
+tools/policy_bench.py [envs] [bf16] [--feasibility-pooling] [--quick]
+--feasibility-pooling: the observation pooled to 9 sectors (obs_dim 15 instead of 186); --quick: one chain only"""
 import os
 import sys
 import time
@@ -15,10 +17,13 @@ from gym_auv_amd.config import effective_reference_config  # noqa: E402
 from gym_auv_amd.devgen import GeneratedWorlds  # noqa: E402
 from gym_auv_amd.policy import FusedActorCritic  # noqa: E402
 
-n = int(sys.argv[1]) if len(sys.argv) > 1 else 4096
+POOL, QUICK = "--feasibility-pooling" in sys.argv, "--quick" in sys.argv
+argv = [a for a in sys.argv if not a.startswith("--")]
+n = int(argv[1]) if len(argv) > 1 else 4096
 cfg = effective_reference_config(use_lidar=True)
-BF16 = len(sys.argv) > 2 and sys.argv[2] == "bf16"
-for k in (1, 2, 4):
+cfg.vessel.sensor_use_feasibility_pooling = POOL
+BF16 = len(argv) > 2 and argv[2] == "bf16"
+for k in ((1,) if QUICK else (1, 2, 4)):
     env = BatchedAuvEnv(cfg, GeneratedWorlds(2 * n, 17, 11, seed=1), n, device="cuda:0")
     env.reset()
     env.set_sub_batches(k)
@@ -50,6 +55,6 @@ for k in (1, 2, 4):
     t_host = time.perf_counter() - t0
     torch.cuda.synchronize()
     t_roll = (time.perf_counter() - t0) / T
-    print("envs %d chains %d: policy launches alone %.1f us per full step; policy + env step %.1f us per step = %.1f M env-steps/s "
-          "(host enqueue %.1f us per step)" % (n, env.sub_batches, 1e6 * t_pol, 1e6 * t_roll, n / t_roll / 1e6, 1e6 * t_host / T), flush=True)
+    print("envs %d obs_dim %d chains %d: policy launches alone %.1f us per full step; policy + env step %.1f us per step = %.1f M env-steps/s "
+          "(host enqueue %.1f us per step)" % (n, env.obs_dim, env.sub_batches, 1e6 * t_pol, 1e6 * t_roll, n / t_roll / 1e6, 1e6 * t_host / T), flush=True)
     env.close()
