@@ -67,6 +67,11 @@ def make_config(cfg: Config, rewarder: str = "colav", test_mode: bool = False,
                 cull: str = "reference", auto_reset: bool = False) -> AuvConfig:
     v, e, s = cfg.vessel, cfg.episode, cfg.simulation
     obs_pooling(cfg)                      # (validates a pooled config; the pooling itself is set per handle: auv_set_obs_pooling)
+    for name, x, positive in (("simulation.t_step_size (dt)", s.t_step_size, True), ("sensor_range", v.sensor_range, True),
+                              ("vessel_width", v.vessel_width, False), ("thrust_max_auv", v.thrust_max_auv, False),
+                              ("moment_max_auv", v.moment_max_auv, False), ("look_ahead_distance", v.look_ahead_distance, False)):
+        if not np.isfinite(float(x)) or (positive and not float(x) > 0.0):
+            raise ValueError("%s = %r: must be finite%s (auv_create refuses it)" % (name, x, " and > 0" if positive else ""))
     if v.sensor_use_velocity_observations and not v.use_lidar:
         raise ValueError("sensor_use_velocity_observations needs use_lidar (the reference raises on [].flatten(), "
                          "environment.py:260,271-272)")

@@ -647,6 +647,15 @@ int auv_create(const auv_config_t* cfg, int32_t n_envs, int32_t device_id, auv_h
   if (cfg->n_sensors < 0 || cfg->n_sensors > 4096) return fail(AUV_EINVAL, "n_sensors out of range");
   if (cfg->sensor_interval_load_obstacles <= 0) return fail(AUV_EINVAL, "sensor_interval_load_obstacles <= 0");
   if (cfg->obs_channels != 1 && cfg->obs_channels != 3) return fail(AUV_EINVAL, "obs_channels must be 1 or 3");
+  // k_derive's per-handle constants (log(1 + R), R exp(-0.1 R), 2 pi / S, ...) and the dynamics would turn these into NaN / inf
+  if (!(std::isfinite(cfg->dt) && cfg->dt > 0.0)) return fail(AUV_EINVAL, "dt = %g: not finite and > 0", cfg->dt);
+  if (!(std::isfinite(cfg->sensor_range) && cfg->sensor_range > 0.0))
+    return fail(AUV_EINVAL, "sensor_range = %g: not finite and > 0", cfg->sensor_range);
+  if (!std::isfinite(cfg->vessel_width)) return fail(AUV_EINVAL, "vessel_width = %g: not finite", cfg->vessel_width);
+  if (!std::isfinite(cfg->thrust_max)) return fail(AUV_EINVAL, "thrust_max = %g: not finite", cfg->thrust_max);
+  if (!std::isfinite(cfg->moment_max)) return fail(AUV_EINVAL, "moment_max = %g: not finite", cfg->moment_max);
+  if (!std::isfinite(cfg->look_ahead_distance))
+    return fail(AUV_EINVAL, "look_ahead_distance = %g: not finite", cfg->look_ahead_distance);
   int ndev = 0;
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (device_id < 0 || device_id >= ndev) return fail(AUV_EINVAL, "device %d not present (%d visible)", device_id, ndev);

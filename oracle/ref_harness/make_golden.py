@@ -2,6 +2,7 @@
 """Generate tests/golden/*.npz by EXECUTING THE REFERENCE'S OWN CODE (build container only).
 
     python oracle/ref_harness/make_golden.py          # rewrites tests/golden/*.npz
+    python oracle/ref_harness/make_golden.py --only g7   # rewrites only g7_config_space.npz
 
 The reference package is imported from /root/reference through bootstrap.install()
 (inert gym/pygame/turtle stubs + the numpy GEOS shim in ./shim).  Every expected value
@@ -14,6 +15,8 @@ stored below is produced by a reference function:
     G5 rollouts   BaseEnvironment.reset/step     environment.py:176-366
     G6 pooling    LidarPreprocessor._feasibility_pooling, sector_partition_fun
                                                  sensor.py:251-296, utils/sector_partitioning.py:4-9
+    G7 configs    BaseEnvironment.reset/step under non-default Vessel/Episode/Simulation knobs
+                                                 (one knob per case; G5's recording)
 Each fixture records dt / min_goal_distance / use_lidar explicitly.
 GEOS primitives come from the shim, so GEOS numerics are "parity unpinned" (DESIGN.md).
 """
@@ -73,6 +76,15 @@ def cfg_scalars(cfg):
 CFG_KEYS = ["dt", "min_goal_distance", "use_lidar", "n_sectors", "n_sensors_per_sector",
             "max_timesteps", "min_cumulative_reward", "min_path_progress", "sensor_range",
             "vessel_width", "look_ahead_distance", "sensor_interval_load_obstacles"]
+
+# G7 records the knobs G1-G6 leave at their defaults too (tests/helpers.py::cfg_from_scalars reads them when present)
+CFG_KEYS_EXT = CFG_KEYS + ["thrust_max_auv", "moment_max_auv", "sensor_log_transform", "feasibility_width_multiplier"]
+
+
+def cfg_scalars_ext(cfg):
+    return np.concatenate([cfg_scalars(cfg), [cfg.vessel.thrust_max_auv, cfg.vessel.moment_max_auv,
+                                              float(cfg.vessel.sensor_log_transform),
+                                              cfg.vessel.feasibility_width_multiplier]]).astype(np.float64)
 
 
 def mover_spec(o):
@@ -408,6 +420,23 @@ def gen_reward():
 
 
 # =============================================================================== G5
+def seeded_env(cls, cfg, seed):
+    with quiet():
+        np.random.seed(seed)
+        random.seed(seed)
+        env = cls(env_config=cfg, renderer=None)
+        env.seed(seed)
+        np.random.seed(seed)
+        random.seed(seed)
+        # First-episode semantics: scenarios whose _generate() does not build a rewarder
+        # (envs/testscenario.py) only get one on the FIRST reset (environment.py:219-224) and
+        # afterwards keep rewarding the first episode's stale Vessel object.  Clearing it makes
+        # this seeded reset behave like a fresh environment's first episode.
+        env.rewarder = None
+        env.observe_cache = env.reset()
+    return env
+
+
 def pilot(env, rs, k):
     """Look-ahead pilot + noise; step 7 feeds a NaN action (environment.py:314-315)."""
     he = env.vessel._last_navi_state_dict["heading_error"]
@@ -454,23 +483,7 @@ def gen_rollouts():
            "info_keys": np.array(["collision", "reached_goal", "goal_distance", "progress",
                                   "cumulative_reward", "max_progress"])}
     runs = []
-
-    def make(cls, cfg, seed):
-        with quiet():
-            np.random.seed(seed)
-            random.seed(seed)
-            env = cls(env_config=cfg, renderer=None)
-            env.seed(seed)
-            np.random.seed(seed)
-            random.seed(seed)
-            # First-episode semantics: scenarios whose _generate() does not build a rewarder
-            # (envs/testscenario.py) only get one on the FIRST reset (environment.py:219-224) and
-            # afterwards keep rewarding the first episode's stale Vessel object.  Clearing it makes
-            # this seeded reset behave like a fresh environment's first episode.
-            env.rewarder = None
-            env.observe_cache = env.reset()
-        return env
-
+    make = seeded_env
     rs = np.random.RandomState(5005)
     # r0-r2: MovingObstaclesNoRules, lidar on, S=180, dt 0.5, free pilot
     for seed in (11, 12, 13):
@@ -564,9 +577,88 @@ def gen_pooling():
     print("G6 pooling: sector sizes", {S: np.diff(out["S%d_starts" % S]).tolist() for S in (180, 64, 256)})
 
 
+# =============================================================================== G7
+def gen_config_space():
+    """Rollouts as in G5, each under a config with (mostly) one knob moved off its default.  Values and starts are chosen
+    so that the knob changes the trace (tests/test_oracle_config_space.py checks that it does); the termination knobs are
+    driven into the termination they control."""
+    out = {"cfg_keys": np.array(CFG_KEYS_EXT),
+           "info_keys": np.array(["collision", "reached_goal", "goal_distance", "progress",
+                                  "cumulative_reward", "max_progress"])}
+    full = lambda env, rs, k: np.array([1.0, 0.0])  # noqa: E731
+
+    def on_path(frac=None, before_end=None, speed=0.5):
+        def tp(env):
+            L = env.path.length
+            s0 = frac * L if frac is not None else L - before_end
+            p = env.path(s0)
+            return np.array([p[0], p[1], env.path.get_direction(s0), speed, 0.0, 0.0])
+        return tp
+
+    def at_circle(gap, ang=0.7, farthest=False):
+        def tp(env):
+            circ = [o for o in env.obstacles if isinstance(o, CircularObstacle)]
+            # farthest from the reset pose: outside the nearby list the reset left behind, which only a refresh brings in
+            circ = max(circ, key=lambda o: np.hypot(*(o.position - env.vessel.position))) if farthest else circ[0]
+            start = circ.position + (circ.radius + gap) * np.array([np.cos(ang), np.sin(ang)])
+            return np.array([start[0], start[1], ang + np.pi, 0.4, 0.0, 0.0])
+        return tp
+
+    def cfg_with(dt=0.5, use_lidar=True, n_sectors=9, n_per_sector=20, **knobs):
+        cfg = make_cfg(dt=dt, use_lidar=use_lidar, n_sectors=n_sectors, n_per_sector=n_per_sector)
+        for k, v in knobs.items():
+            sub = cfg.episode if hasattr(cfg.episode, k) else cfg.vessel
+            assert hasattr(sub, k), k
+            setattr(sub, k, v)
+        return cfg
+
+    MO, PF = mo.MovingObstaclesNoRules, mo.PathFollowNoObstacles
+    # (name, scenario, seed, cfg, rewarder, steps, teleport, actions)
+    cases = [
+        ("log_off", MO, 11, cfg_with(sensor_log_transform=False), "colav", 60, None, pilot),
+        ("range60", MO, 12, cfg_with(sensor_range=60.0), "colav", 60, None, pilot),
+        ("range400", MO, 13, cfg_with(sensor_range=400.0), "colav", 40, None, pilot),
+        ("thrust_moment", MO, 14, cfg_with(thrust_max_auv=3.5, moment_max_auv=0.2625), "colav", 60, None, pilot),
+        ("width4", MO, 21, cfg_with(vessel_width=4.0), "colav", 80, at_circle(9.0), full),
+        ("lookahead25", MO, 15, cfg_with(look_ahead_distance=25), "colav", 60, None, pilot),
+        ("lookahead_past_end", MO, 16, cfg_with(look_ahead_distance=5000), "colav", 60, on_path(frac=0.5), pilot),
+        ("interval1", MO, 17, cfg_with(sensor_interval_load_obstacles=1), "colav", 60, None, pilot),
+        ("interval7", MO, 100, cfg_with(sensor_interval_load_obstacles=7), "colav", 60, None, pilot),
+        ("min_cumulative_reward", MO, 20, cfg_with(min_cumulative_reward=-15.0), "colav", 119, None, pilot),
+        ("min_path_progress", MO, 22, cfg_with(min_path_progress=0.05), "colav", 119, on_path(frac=0.03), full),
+        ("min_goal_distance", MO, 24, cfg_with(min_goal_distance=150.0), "colav", 119, on_path(before_end=170.0), full),
+        ("max_timesteps", MO, 24, cfg_with(max_timesteps=40), "colav", 119, None, pilot),
+        ("dt02", MO, 25, cfg_with(dt=0.2), "colav", 60, None, pilot),
+        ("pathfollow_nolidar", PF, 31, cfg_with(dt=1.0, use_lidar=False, thrust_max_auv=1.0, look_ahead_distance=50),
+         "pathfollow", 80, None, pilot),
+        ("s64_bundle", MO, 26, cfg_with(n_sectors=8, n_per_sector=8, sensor_range=90.0, sensor_log_transform=False,
+                                        vessel_width=2.0, sensor_interval_load_obstacles=3), "colav", 80,
+         at_circle(7.0, farthest=True), full),
+    ]
+    out["names"] = np.array([c[0] for c in cases])
+    out["rewarder"] = np.array([c[4] for c in cases])
+    for k, (name, cls, seed, cfg, rew, steps, tp_fn, act_fn) in enumerate(cases):
+        env = seeded_env(cls, cfg, seed)
+        rs = np.random.RandomState(7000 + seed)          # (per case: retuning one case leaves the others alone)
+        world, rec = rollout(env, steps, rs, teleport=None if tp_fn is None else tp_fn(env), act_fn=act_fn)
+        pre = "r%d_" % k
+        out[pre + "cfg"] = cfg_scalars_ext(cfg)
+        out.update(pack_world(pre + "w_", world))
+        for key, val in rec.items():
+            out[pre + key] = val
+        print("  rollout", name, "steps", len(rec["reward"]), "done", bool(rec["done"][-1]),
+              "collision", bool(rec["info"][-1, 0]), "goal", bool(rec["info"][-1, 1]),
+              "min d", rec["d"].min().round(3) if rec["d"].size else None, "reward sum", rec["reward"].sum().round(2),
+              "path length", round(env.path.length, 1))
+    np.savez_compressed(os.path.join(OUT, "g7_config_space.npz"), **out)
+
+
 if __name__ == "__main__":
     os.makedirs(OUT, exist_ok=True)
-    which = sys.argv[1:] or ["g1", "g2", "g3", "g4", "g5", "g6"]
+    args = sys.argv[1:]
+    if args[:1] == ["--only"]:
+        args = args[1:]
+    which = args or ["g1", "g2", "g3", "g4", "g5", "g6", "g7"]
     if "g1" in which:
         gen_dynamics()
     if "g2" in which:
@@ -579,5 +671,7 @@ if __name__ == "__main__":
         gen_rollouts()
     if "g6" in which:
         gen_pooling()
+    if "g7" in which:
+        gen_config_space()
     for f in sorted(os.listdir(OUT)):
         print(f, os.path.getsize(os.path.join(OUT, f)) // 1024, "KiB")

@@ -17,6 +17,7 @@ from gym_auv_amd._capi import make_config, obs_pooling
 from gym_auv_amd.config import effective_reference_config
 from gym_auv_amd.scenarios import empty_scenario, moving_obstacles_world, polygon_world
 from gym_auv_amd.world import build_world, pack_bank
+from helpers import shape_run
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -50,8 +51,12 @@ def _env(cfg, bank, n, **kw):
         return BatchedAuvEnv(cfg, bank, n, device="cuda:0", **kw)
 
 
-def _closeness(v):
-    return 1 - np.clip(np.log(1 + v) / np.log(1 + R), 0.0, 1.0)
+def _closeness(v, cfg=None):
+    """The reference's closeness (vessel.py:88-95) under cfg's sensor_range / sensor_log_transform (default: R = 150, log)."""
+    r = R if cfg is None else cfg.vessel.sensor_range
+    if cfg is None or cfg.vessel.sensor_log_transform:
+        return 1 - np.clip(np.log(1 + v) / np.log(1 + r), 0.0, 1.0)
+    return 1 - np.clip(v / r, 0.0, 1.0)
 
 
 class _Pool:
@@ -77,11 +82,11 @@ def _check_row(env, pool, ns, c):
     o64 = env.read("OBS64").cpu().numpy()
     S = lid.shape[1]
     assert o64.shape[1] == 6 + S
-    assert np.abs(o64[:, 6:6 + ns] - _closeness(ref)).max() <= 1e-12
+    assert np.abs(o64[:, 6:6 + ns] - _closeness(ref, env.config)).max() <= 1e-12
     assert (o64[:, 6 + ns:] == 0.0).all()
     obs = env.obs.cpu().numpy()
     assert obs.shape[1] == 6 + c * ns
-    assert np.abs(obs[:, 6:6 + ns] - _closeness(ref)).max() <= 1e-6
+    assert np.abs(obs[:, 6:6 + ns] - _closeness(ref, env.config)).max() <= 1e-6
     assert (obs[:, 6 + ns:] == 0.0).all()            # the velocity channels
     np.testing.assert_array_equal(obs[:, :6], o64[:, :6].astype(np.float32))
     return sd
@@ -127,50 +132,6 @@ def test_pooled_step_parity(shape, kind, rewarder):
     pooled.close(), plain.close()
 
 
-def _shape_run(shape_name, cfg, bank, n, ring, steps):
-    """obs / SECTOR_D / reward / done after every step (multi-step launches: after every launch) of one step shape."""
-    env = _env(cfg, bank, n, auto_reset=True)
-    env.reset()
-    out = {}
-    if shape_name == "side_by_side":
-        env.set_step_mode("side_by_side")
-    if shape_name in ("chains", "async") or shape_name.startswith("multi"):
-        env.set_sub_batches(1 if shape_name.startswith("multi") else 4, strict=shape_name.startswith("multi"))
-    if shape_name == "multi_steps":
-        env.set_multi_order("steps")
-    if shape_name == "graph":
-        env.capture_graph(steps=1)
-
-    def snap(t):
-        torch.cuda.synchronize()
-        out[t] = (env.obs.clone(), env.read("SECTOR_D"), env.reward.clone(), env.done.clone())
-
-    slots = ring.shape[0]
-    if shape_name.startswith("multi"):
-        t = 0
-        lengths = [1, 6, 16, 64]
-        while t < steps:
-            T = min(lengths[len(out) % len(lengths)], steps - t)
-            env.step_multi(ring, t % slots, T)
-            t += T
-            snap(t)
-    else:
-        for t in range(steps):
-            a = ring[t % slots]
-            if shape_name == "one_launch" or shape_name == "side_by_side":
-                env.step(a)
-            elif shape_name == "chains":
-                env.step_pipelined(a)
-            elif shape_name == "async":
-                env.step_async(a)
-                env.step_wait()
-            elif shape_name == "graph":
-                env.step_graph(a)
-            snap(t + 1)
-    env.close()
-    return out
-
-
 @pytest.mark.parametrize("shape_name", ["side_by_side", "chains", "async", "graph", "multi_cohorts", "multi_steps"])
 def test_every_step_shape_pools_bitwise_the_same(shape_name):
     n, steps = 1024, 96
@@ -180,8 +141,8 @@ def test_every_step_shape_pools_bitwise_the_same(shape_name):
     g.manual_seed(5)
     ring = (torch.rand((steps, n, 2), generator=g, device="cuda:0") * torch.tensor([2.0, 0.3], device="cuda:0")
             - torch.tensor([1.0, 0.15], device="cuda:0")).contiguous()
-    ref = _shape_run("one_launch", cfg, bank, n, ring, steps)
-    got = _shape_run(shape_name, cfg, bank, n, ring, steps)
+    ref = shape_run("one_launch", cfg, bank, n, ring, steps, fields=("SECTOR_D",))
+    got = shape_run(shape_name, cfg, bank, n, ring, steps, fields=("SECTOR_D",))
     assert len(got) > 0
     for t, v in got.items():
         for a, b in zip(ref[t], v):
