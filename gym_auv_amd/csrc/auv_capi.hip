@@ -13,6 +13,7 @@
 
 #include "auv_device.h"
 #include "auv_generate.h"
+#include "auv_multi_geom.h"
 
 void auv_launch_k1(const AuvDev& d, const void* actions, int dtype, hipStream_t st, hipEvent_t ev0 = nullptr,
                    hipEvent_t ev1 = nullptr);
@@ -1288,8 +1289,12 @@ int auv_step_multi(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, voi
   for (int i = 0; i < n_slices; i++) {
     const int ne = bounds[i + 1] - bounds[i];
     if (effective_mode(h, ne) != AUV_STEP_ONE_LAUNCH) return fail(AUV_ESTATE, "auv_step_multi: needs the one-launch shape for every slice");
-    const long long wg = (long long)n_steps * (2 * (8 * ((ne + 63) / 64)) + 2 * (8 * ((ne + 7) / 8)));
-    if (wg > 0x7fffffffll) return fail(AUV_EINVAL, "auv_step_multi: %lld workgroups in one launch", wg);
+    // the grid that will be launched, in work-items: the dispatch packet holds a 32-bit count (checked before anything launches
+    // and before the step numbers move)
+    const AuvMultiGeom g = auv_multi_geom(ne, n_steps, h->multi_order, h->multi_lead, h->multi_lag);
+    if (!auv_multi_fits(g))
+      return fail(AUV_EINVAL, "auv_step_multi: %llu work-items in one launch of %d environments x %d steps (at most 2^32 - 1)",
+                  auv_multi_grid(g) * AUV_MULTI_WG_LANES, ne, (int)n_steps);
   }
   PAIR_CHECK(h, obs_dev);
   const unsigned long long seq0 = h->multi_seq;

@@ -17,6 +17,7 @@
 #include <hip/hip_ext.h>
 
 #define AUV_DEVICE_FUNCS_ONLY
+#include "auv_multi_geom.h"
 #include "k1_dynamics.hip"
 #include "k2_lidar.hip"
 #include "k3_nav_reward.hip"
@@ -907,9 +908,8 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_multi(AuvD
 #endif
   const int lane = threadIdx.x;
   const int ne = d.ne;
-  const int nk = 8 * ((ne + 63) / 64), nb = 8 * ((ne + 7) / 8);
-  const int per = 2 * nk + 2 * nb;
-  // role: 0 dynamics, 1 sweep, 2 search, 3 finish; bi: the wave's index within its role and step.
+  // role: 0 dynamics, 1 sweep, 2 search, 3 finish; bi: the wave's index within its role and step (auv_multi_geom.h: the decode,
+  // the launcher's grid and the host's checks have this one source).
   // Two workgroup orders (both computed, one selected: a run-time branch around this index arithmetic makes this compiler emit a
   // vector-to-scalar copy it then rejects):
   //   step-major: all of step t's workgroups, role by role, then step t + 1's;
@@ -921,23 +921,13 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_multi(AuvD
   //   they poll for it (the step-major order makes step t + 1's sweeps wait, resident, for a finish wave that is dispatched last
   //   of all of step t).  lead + lag < C keeps every producer ahead of its consumer in index order, also across steps: the
   //   dynamics of q + C sit at position q + C, behind the finish waves of q at q + lead + lag.
+  // A workgroup outside the launch -- past the last step, or past its role's count (a slice that is not a multiple of 8
+  // environments) -- decodes to step == n_steps and ends here.
   const bool cohorts = lead_dyn >= 0;
-  const int bx = (int)blockIdx.x;
-  // step-major
-  const int step_a = bx / per, b_a = bx - step_a * per;
-  const int role_a = b_a < nk ? 0 : (b_a < nk + nb ? 1 : (b_a < nk + 2 * nb ? 2 : 3));
-  const int bi_a = b_a - (role_a == 0 ? 0 : (role_a == 1 ? nk : (role_a == 2 ? nk + nb : nk + 2 * nb)));
-  // cohort-pipelined
-  const int C = nk / 8;
-  const int p = bx / 144, r = bx - 144 * p;
-  const int role_c = r < 8 ? 0 : (r < 72 ? 1 : (r < 136 ? 2 : 3));
-  const int q = p - (role_c == 0 ? 0 : (role_c == 3 ? lead_dyn + lag_fin : lead_dyn));
-  const bool q_ok = q >= 0 && q < n_steps * C;
-  const int step_c = (int)__umulhi((unsigned)(q_ok ? q : 0), magic_c);      // q / C by the host's multiplier ceil(2^32 / C): exact for q < 2^32 / C
-  const int c = (q_ok ? q : 0) - step_c * C;
-  const int bi_c = (role_c == 0 ? r : (role_c == 1 ? r - 8 : (role_c == 2 ? r - 72 : r - 136))) + ((role_c == 0 || role_c == 3) ? 8 * c : 64 * c);
-  int step = auv_uniform(cohorts ? (q_ok ? step_c : n_steps) : step_a);      // (a position outside the launch: ends below)
-  int role = auv_uniform(cohorts ? role_c : role_a), bi = auv_uniform(cohorts ? bi_c : bi_a);
+  const AuvMultiWave wa = auv_multi_decode_steps(blockIdx.x, ne, n_steps);
+  const AuvMultiWave wc = auv_multi_decode_cohorts(blockIdx.x, ne, n_steps, lead_dyn, lag_fin, magic_c);
+  const int step = auv_uniform(cohorts ? wc.step : wa.step);
+  const int role = auv_uniform(cohorts ? wc.role : wa.role), bi = auv_uniform(cohorts ? wc.bi : wa.bi);
   if (step >= n_steps) return;
   const unsigned long long tagmix = roles_tagmix(seq0 + (unsigned long long)step + 1ull), tagmix_prev = roles_tagmix(seq0 + (unsigned long long)step);
 #ifdef AUV_STAMPS_MULTI
@@ -945,7 +935,6 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_multi(AuvD
 #endif
   if (role == 0) {
     // ---- Vessel.step of eight environments ----
-    if (bi >= nk) return;
     __builtin_amdgcn_s_setprio(3);
     const int b = bi;
     const int g = lane / K1_GROUP, c = lane % K1_GROUP;
@@ -1003,7 +992,6 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_multi(AuvD
   EnvDesc ed;
   if (role == 1) {
     // ---- _update + Vessel.perceive of one environment ----
-    if (bi >= ne) return;
     const int e = auv_uniform(d.e0 + bi);
     MSTAMP(e, 0);
     // three requests in flight before the first wait: the abort flag, this step's state packet (dispatched `lead` cohorts behind
@@ -1050,9 +1038,7 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_multi(AuvD
 #endif
   } else if (role == 2) {
     // ---- Vessel.navigate of one environment: the nearest-point search ----
-    const int el = bi;
-    if (el >= ne) return;
-    const int e = auv_uniform(d.e0 + el);
+    const int e = auv_uniform(d.e0 + bi);
     MSTAMP(e, 6);
     const unsigned long long pk_first = __hip_atomic_load(d.k1_pkt + 8 * (size_t)e + (lane & 7), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     if (step == 0) {
@@ -1076,7 +1062,6 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_multi(AuvD
   } else {
     // ---- navigation tail + reward / done / auto-reset of eight environments ----
     const int f = bi;
-    if (f >= nk) return;
     __builtin_amdgcn_s_setprio(2);
 #ifdef AUV_STAMPS_MULTI
     const int fer = 8 * (8 * (f / 8) + lane / K1_GROUP) + (f % 8);
@@ -1263,30 +1248,16 @@ void auv_launch_step_roles(const AuvDev& d0, const void* actions, int dtype, flo
   hipExtLaunchKernelGGL(k_step_roles, grid, block, lds, st, ev0, ev1, 0, d, actions, obs, reward, done);
 }
 
-// order: 0 step-major; 1 cohort-pipelined (lead / lag chosen here: as long as the slice has cohorts for them)
+// order: 0 step-major; 1 cohort-pipelined where the slice has whole cohorts for it (lead / lag clamped: auv_multi_geom.h)
 void auv_launch_step_multi(const AuvDev& d0, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, int n_steps,
                            int first_slot, int n_slots, unsigned long long seq0, int order, int lead, int lag, hipStream_t st) {
   AuvDev d = d0;
   d.act_f64 = dtype == AUV_F64;
   d.ring_slots = 1;
   const uint32_t lds = (uint32_t)k2_slice_bytes(d);
-  const int nk = 8 * ((d.ne + 63) / 64), nb = 8 * ((d.ne + 7) / 8);
-  const int C = nk / 8;
-  if (order == 1 && C >= 3 && d.ne % 64 == 0) {
-    if (lead < 1) lead = 1;
-    if (lag < 1) lag = 1;
-    while (lead + lag > C - 1) {                          // every producer ahead of its consumer, also across steps
-      if (lag > lead && lag > 1) lag--;
-      else if (lead > 1) lead--;
-      else lag--;
-    }
-    const dim3 grid((unsigned)(n_steps * C + lead + lag) * 144u), block(AUV_WAVE);
-    const unsigned magic = (unsigned)((0x100000000ull + (unsigned)C - 1) / (unsigned)C);
-    hipLaunchKernelGGL(k_step_multi, grid, block, lds, st, d, actions, obs, reward, done, n_steps, first_slot, n_slots, seq0, lead, lag, magic);
-    return;
-  }
-  const dim3 grid((unsigned)n_steps * (unsigned)(2 * nk + 2 * nb)), block(AUV_WAVE);
-  hipLaunchKernelGGL(k_step_multi, grid, block, lds, st, d, actions, obs, reward, done, n_steps, first_slot, n_slots, seq0, -1, 0, 0u);
+  const AuvMultiGeom g = auv_multi_geom(d.ne, n_steps, order, lead, lag);      // (the host has checked that the grid fits)
+  const dim3 grid((unsigned)auv_multi_grid(g)), block(AUV_WAVE);
+  hipLaunchKernelGGL(k_step_multi, grid, block, lds, st, d, actions, obs, reward, done, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic);
 }
 
 // The stage's capacity for a bank (S, k_max, m_max known): the largest that gives the one-launch step its best occupancy (see

@@ -196,7 +196,10 @@ int auv_step_pipelined(auv_handle_t* h, int32_t n_slices, const int32_t* bounds,
  * k_step_fused.hip, k_step_multi.  obs / reward / done hold the LAST step's values afterwards; everything else -- state, counters,
  * episode log, auto-reset -- is bit for bit what n_steps calls of auv_step_pipelined leave (tests/test_gpu_multi.py).  Needs the
  * one-launch shape for every slice and at most 64 obstacles per world; refused with a fresh world per reset.  Polls are bounded and
- * report like the one-launch step's (auv_health).                                                                     */
+ * report like the one-launch step's (auv_health).  1 <= n_steps <= 1024, and every slice's launch within the dispatch limit of
+ * 2^32 - 1 work-items (64 per workgroup): step-major, n_steps * (2 * 8 * ceil(ne / 64) + 2 * 8 * ceil(ne / 8)) workgroups;
+ * cohort order, (n_steps * ne / 64 + lead + lag) * 144 with lead / lag as clamped (auv_set_multi_order).  A call past either is
+ * refused with AUV_EINVAL before anything is launched or any step number is spent.                                    */
 int auv_step_multi(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const void* actions_dev,
                    int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev, float* reward_dev,
                    uint8_t* done_dev);

@@ -48,3 +48,10 @@ def test_side_by_side_kernel_fits_its_register_budget():
     assert all(int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", b).group(1)) == 0 for b in blk)
     # one instantiation per kernel: the action dtype is a launch-time flag, not a template parameter (build time)
     assert len(usage("k_step_roles")) == 1
+    # k_step_multi (several steps per launch): no more than it needed before its launch geometry moved to auv_multi_geom.h
+    # (127 VGPRs, no spill, 16 bytes of private segment)
+    blk = [b for b in blocks if re.search(r"\.name:\s+\S*k_step_multi", b)]
+    assert len(blk) == 1
+    for vgpr, spill, lds_static in usage("k_step_multi"):
+        assert vgpr <= 127 and spill == 0 and lds_static == 0, (vgpr, spill, lds_static)
+    assert int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", blk[0]).group(1)) <= 16
