@@ -295,19 +295,63 @@ class BatchedAuvEnv:
                                        C.c_void_p(self.obs.data_ptr()), C.c_void_p(self.reward.data_ptr()),
                                        C.c_void_p(self.done.data_ptr())), "auv_step_pipelined")
 
-    def step_multi(self, ring: torch.Tensor, first_slot: int, n_steps: int):
+    def step_multi(self, ring: torch.Tensor, first_slot: int, n_steps: int, record=None):
         """`n_steps` consecutive steps of every sub-batch in ONE launch per sub-batch (auv_step_multi): step k reads the actions
         of ring slot (first_slot + k) % slots.  `ring`: [slots, N, 2] float32 / float64, resident on the device.  Open loop, like
-        step_pipelined (nothing orders the chains against the caller's stream); bit-identical to n_steps step_pipelined calls."""
+        step_pipelined (nothing orders the chains against the caller's stream); bit-identical to n_steps step_pipelined calls.
+
+        `record`: keep EVERY step's outputs (auv_step_multi_record) -- row k of the record is what the k-th of n_steps one-step
+        calls returns; a row with done = 1 holds the terminal reward and (auto-reset) the new episode's first observation.
+            None       nothing is recorded (the call above), returns None
+            True       allocates and returns (obs [T, N, obs_dim] float32, reward [T, N] float32, done [T, N] uint8)
+            "reward"   no observation record: returns (None, reward, done)
+            (obs_or_None, reward, done)   the caller's tensors of those shapes and dtypes, contiguous, on this device -- e.g. a
+                       slice buf[t0:t0 + T] of a rollout buffer; returned as passed
+        `self.obs / reward / done` hold the last step's values either way.  Action repeat needs nothing else: a ring of ONE slot
+        repeats its action for n_steps steps ((first_slot + k) % 1 == 0); sum the reward record up to the first done."""
         if self._slices is None:
             self.set_sub_batches(1)
         if ring.dim() != 3 or tuple(ring.shape[1:]) != (self.n_envs, 2) or ring.device != self.device or not ring.is_contiguous() \
                 or ring.dtype not in (torch.float32, torch.float64):
             raise ValueError("ring must be a contiguous [slots, %d, 2] float32 / float64 tensor on %s" % (self.n_envs, self.device))
         dt = _capi.AUV_F64 if ring.dtype == torch.float64 else _capi.AUV_F32
-        _check(_LIB.auv_step_multi(self._h, self.sub_batches, self._bounds_c, self._streams_c, C.c_void_p(ring.data_ptr()), dt,
-                                   int(ring.shape[0]), int(first_slot), int(n_steps), C.c_void_p(self.obs.data_ptr()),
-                                   C.c_void_p(self.reward.data_ptr()), C.c_void_p(self.done.data_ptr())), "auv_step_multi")
+        if record is None:
+            _check(_LIB.auv_step_multi(self._h, self.sub_batches, self._bounds_c, self._streams_c, C.c_void_p(ring.data_ptr()), dt,
+                                       int(ring.shape[0]), int(first_slot), int(n_steps), C.c_void_p(self.obs.data_ptr()),
+                                       C.c_void_p(self.reward.data_ptr()), C.c_void_p(self.done.data_ptr())), "auv_step_multi")
+            return None
+        T, n = int(n_steps), self.n_envs
+        if isinstance(record, (tuple, list)):
+            if len(record) != 3:
+                raise ValueError("record must be True, \"reward\" or a tuple (obs_or_None, reward, done)")
+            rec = tuple(record)
+            for name, t, shape, dtype in (("obs", rec[0], (T, n, self.obs_dim), torch.float32), ("reward", rec[1], (T, n), torch.float32),
+                                          ("done", rec[2], (T, n), torch.uint8)):
+                if t is None and name == "obs":
+                    continue
+                if not isinstance(t, torch.Tensor) or tuple(t.shape) != shape or t.dtype != dtype or t.device != self.device or not t.is_contiguous():
+                    raise ValueError("record: %s must be a contiguous %s tensor of shape %s on %s" % (name, dtype, shape, self.device))
+        elif record is True or record == "reward":
+            with torch.cuda.device(self.device):
+                rec = (torch.empty((T, n, self.obs_dim), dtype=torch.float32, device=self.device) if record is True else None,
+                       torch.empty((T, n), dtype=torch.float32, device=self.device), torch.empty((T, n), dtype=torch.uint8, device=self.device))
+            # (the chains' streams write the new tensors: whatever the allocating stream still has pending on their memory goes
+            # first, and the allocator must not hand the memory on while a chain may still write it)
+            cur = torch.cuda.current_stream(self.device)
+            for st in self._sub_streams:
+                if st != cur:
+                    st.wait_stream(cur)
+                    for t in rec:
+                        if t is not None:
+                            t.record_stream(st)
+        else:
+            raise ValueError("record must be None, True, \"reward\" or a tuple (obs_or_None, reward, done)")
+        _check(_LIB.auv_step_multi_record(self._h, self.sub_batches, self._bounds_c, self._streams_c, C.c_void_p(ring.data_ptr()), dt,
+                                          int(ring.shape[0]), int(first_slot), T, C.c_void_p(self.obs.data_ptr()),
+                                          C.c_void_p(self.reward.data_ptr()), C.c_void_p(self.done.data_ptr()),
+                                          None if rec[0] is None else C.c_void_p(rec[0].data_ptr()), C.c_void_p(rec[1].data_ptr()),
+                                          C.c_void_p(rec[2].data_ptr())), "auv_step_multi_record")
+        return rec
 
     def set_multi_order(self, order: str = "cohorts", lead: int = 16, lag: int = 30):
         """Workgroup order of step_multi's launches: "cohorts" (default: cohort-pipelined, see include/auv_hip.h) or "steps"."""

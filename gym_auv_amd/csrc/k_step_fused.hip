@@ -902,175 +902,36 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_multi(AuvD
                                                                            const int n_steps, const int first_slot, const int n_slots,
                                                                            const unsigned long long seq0, const int lead_dyn, const int lag_fin, const unsigned magic_c) {
   AUV_KERNARG_DESC(d);
-  extern __shared__ __align__(16) unsigned char smem[];
-#ifdef AUV_STAMPS_MULTI
-  const unsigned long long t_entry = wall_clock64();      // the wave's first instruction
-#endif
-  const int lane = threadIdx.x;
-  const int ne = d.ne;
-  // role: 0 dynamics, 1 sweep, 2 search, 3 finish; bi: the wave's index within its role and step (auv_multi_geom.h: the decode,
-  // the launcher's grid and the host's checks have this one source).
-  // Two workgroup orders (both computed, one selected: a run-time branch around this index arithmetic makes this compiler emit a
-  // vector-to-scalar copy it then rejects):
-  //   step-major: all of step t's workgroups, role by role, then step t + 1's;
-  //   COHORT-PIPELINED (lead_dyn >= 0).  A cohort = 64 consecutive environments = 8 dynamics + 64 sweep + 64 search + 8 finish
-  //   workgroups (every run a multiple of 8: an environment's waves still share an XCD).  Cohort-steps are numbered
-  //   q = step * C + cohort; position p of the grid holds the dynamics of q = p, the sweeps and searches of q = p - lead and the
-  //   finish waves of q = p - lead - lag: a sweep is dispatched `lead` positions behind its dynamics -- which have finished by
-  //   then -- and a finish wave `lag` positions behind its sweeps, so waves find what they need instead of holding a slot while
-  //   they poll for it (the step-major order makes step t + 1's sweeps wait, resident, for a finish wave that is dispatched last
-  //   of all of step t).  lead + lag < C keeps every producer ahead of its consumer in index order, also across steps: the
-  //   dynamics of q + C sit at position q + C, behind the finish waves of q at q + lead + lag.
-  // A workgroup outside the launch -- past the last step, or past its role's count (a slice that is not a multiple of 8
-  // environments) -- decodes to step == n_steps and ends here.
-  const bool cohorts = lead_dyn >= 0;
-  const AuvMultiWave wa = auv_multi_decode_steps(blockIdx.x, ne, n_steps);
-  const AuvMultiWave wc = auv_multi_decode_cohorts(blockIdx.x, ne, n_steps, lead_dyn, lag_fin, magic_c);
-  const int step = auv_uniform(cohorts ? wc.step : wa.step);
-  const int role = auv_uniform(cohorts ? wc.role : wa.role), bi = auv_uniform(cohorts ? wc.bi : wa.bi);
-  if (step >= n_steps) return;
-  const unsigned long long tagmix = roles_tagmix(seq0 + (unsigned long long)step + 1ull), tagmix_prev = roles_tagmix(seq0 + (unsigned long long)step);
-#ifdef AUV_STAMPS_MULTI
-  unsigned long long* const stamp = d.stamps + (step == n_steps / 2 ? (size_t)0 : (size_t)16 * (size_t)d.n);
-#endif
-  if (role == 0) {
-    // ---- Vessel.step of eight environments ----
-    __builtin_amdgcn_s_setprio(3);
-    const int b = bi;
-    const int g = lane / K1_GROUP, c = lane % K1_GROUP;
-    const int er = 8 * (8 * (b / 8) + g) + (b % 8);
-    const bool live = er < ne;
-    const int eg = d.e0 + (live ? er : ne - 1);
-    int y, gave_up = 0;
-    double y0 = 0.0;
-    MSTAMP_IF(live && c == 0, eg, 10);
-    // requested ahead of the wait for the carry record (this wave is on every environment's critical path): the flag and the action
-    const int ab_early = __hip_atomic_load(d.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    double act0, act1;
-    k1_action(d, actions, eg, &act0, &act1, (first_slot + step) % n_slots);
-    if (step == 0) {
-      y = d.counters[eg].y + 1;
-    } else {
-      // this environment's state and counters after the previous step: the first line of its carry record
-      const unsigned long long* cw = d.carry + CARRY_WORDS * (size_t)eg;
-      unsigned long long v = 0ull;
-      bool ok = !live;
-      for (int polls = 0;; polls++) {
-        if (!ok) v = __hip_atomic_load(cw + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        ok = !live || roles_record_ok(v, c, tagmix_prev);
-        if (!__any(!ok)) break;
-        if ((polls & 31) == 31 && auv_uniform(__hip_atomic_load(d.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
-          gave_up = 1;                                                              // (ABORT packets below)
-          break;
-        }
-        if (polls == (AUV_HOOK_FAULT(d) ? (1 << 12) : PAIR_POLL_LIMIT)) {
-          if (live && c == 0) auv_st<true>(d.broken + eg, (uint8_t)1);
-          roles_give_up(d, d.e0, d.ne, 6, lane);
-          gave_up = 1;                                                              // (the flag is up now: ABORT packets below)
-          break;
-        }
-        __builtin_amdgcn_s_sleep(ROLES_POLL_SLEEP);
-      }
-      y0 = __longlong_as_double((long long)v);
-      y = (int)(unsigned)(roles_group_word(v, 6) >> 32) + 1;
-    }
-    const int aborted = gave_up | auv_uniform(ab_early);
-    double t = 0.0;
-    MSTAMP_IF(live && c == 0, eg, 11);
-    const double2 act = make_double2(act0, act1);
-    if (!aborted) t = k1_group(d, actions, eg, lane, step == 0 ? nullptr : &y0, (first_slot + step) % n_slots, &act);
-    unsigned long long* pk = d.k1_pkt + 8 * (size_t)eg;
-    const unsigned long long word = aborted ? (c == 6 ? (unsigned long long)ROLES_ABORT_COUNTER : 0ull)
-                                            : (c < 6 ? (unsigned long long)__double_as_longlong(t) : (c == 6 ? (unsigned long long)(unsigned)y : 0ull));
-    const unsigned long long mark = roles_mark(roles_group_xor(word) ^ tagmix);
-    if (live && !(AUV_HOOK_FAULT(d) == 2 && eg == d.e0 && step == 0))
-      __hip_atomic_store(pk + c, c < 7 ? word : mark, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    MSTAMP_IF(live && c == 0, eg, 12);
-    return;
-  }
-  EnvPre pre;
-  EnvDesc ed;
-  if (role == 1) {
-    // ---- _update + Vessel.perceive of one environment ----
-    const int e = auv_uniform(d.e0 + bi);
-    MSTAMP(e, 0);
-    // three requests in flight before the first wait: the abort flag, this step's state packet (dispatched `lead` cohorts behind
-    // its dynamics, the wave usually finds it there), the carry record
-    const int ab_early = __hip_atomic_load(d.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const unsigned long long pk_first = __hip_atomic_load(d.k1_pkt + 8 * (size_t)e + (lane & 7), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const Slice L = carve(smem, d);
-    K2Pre kp;
-    if (step == 0) {
-      ed = d.env_desc[e];
-      pre.cnt = d.counters[e];
-      pre.ed = &ed;
-      if (auv_uniform(ab_early)) return;
-      k2_movers<true>(d, e, lane, L, ed, 1);
-      kp = k2_prefetch(d, e, lane, ed);
-    } else {
-      if (carry_wait_wave(d, e, lane, tagmix_prev, ed, pre.cnt)) return;
-      if (auv_uniform(ab_early)) return;
-      pre.ed = &ed;
-      k2_movers<true, true>(d, e, lane, L, ed, 1);
-      kp = k2_prefetch<true>(d, e, lane, ed);
-    }
-    k2_stage_beams(d, lane, L);
-    {
-      const int ws = roles_wait_state(d, e, lane, pre, tagmix, true, pk_first);
-      if (ws) {
-        if (ws == 2 && ed.M > 0 && lane == 0) auv_st<true>(d.broken + e, (uint8_t)1);
-        return;
-      }
-    }
-    MSTAMP(e, 2);
-    int2 lim0 = make_int2(INT32_MIN, INT32_MIN);
-    const int n_act = k2_front<true>(d, e, lane, L, 1, &pre, 1, &kp, true, &lim0);
-    k2_stage_and_pairs(d, L, lane, n_act, pre.s[2]);
-    MSTAMP(e, 4);
-    double term = 0.0;
-    const int collision = k2_back<true>(d, e, lane, L, n_act, obs_out, &term, &lim0);
-    pair_publish_lidar(d, e, lane, collision, term);
-    MSTAMP(e, 5);
-#ifdef AUV_STAMPS_MULTI
-    if (lane == 0) stamp[(size_t)e * 16 + 1] = t_entry;
-    __builtin_amdgcn_s_waitcnt(0x0F70);                    // every store of this wave has been acknowledged
-    MSTAMP(e, 3);
-#endif
-  } else if (role == 2) {
-    // ---- Vessel.navigate of one environment: the nearest-point search ----
-    const int e = auv_uniform(d.e0 + bi);
-    MSTAMP(e, 6);
-    const unsigned long long pk_first = __hip_atomic_load(d.k1_pkt + 8 * (size_t)e + (lane & 7), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    if (step == 0) {
-      ed = d.env_desc[e];
-      pre.cnt = d.counters[e];
-    } else if (carry_wait_wave(d, e, lane, tagmix_prev, ed, pre.cnt)) {
-      return;
-    }
-#ifdef AUV_STAMPS_MULTI
-    if (lane == 0) stamp[(size_t)e * 16 + 7] = t_entry;
-#endif
-    pre.ed = &ed;
-    if (roles_wait_state(d, e, lane, pre, tagmix, true, pk_first)) return;
-    MSTAMP(e, 8);
-    NavNear nr;
-    int* list = (int*)smem;
-    const NavSpec sp = nav_bounds(d, e, lane, list, pre.s[0], pre.s[1], &ed);
-    nr = nav_nearest(d, e, lane, list, pre.s[0], pre.s[1], sp);
-    roles_publish_search(d, e, lane, nr, tagmix);
-    MSTAMP(e, 9);
-  } else {
-    // ---- navigation tail + reward / done / auto-reset of eight environments ----
-    const int f = bi;
-    __builtin_amdgcn_s_setprio(2);
-#ifdef AUV_STAMPS_MULTI
-    const int fer = 8 * (8 * (f / 8) + lane / K1_GROUP) + (f % 8);
-    const bool fst = fer < ne && lane % K1_GROUP == 0;
-#endif
-    MSTAMP_IF(fst, d.e0 + fer, 13);
-    roles_finish_wave_multi<true>(d, f, lane, obs_out, reward_out, done_out, step, step == n_steps - 1, tagmix, tagmix_prev MSTAMP_ARG);
-    MSTAMP_IF(fst, d.e0 + fer, 15);
-  }
+#define STEP_MULTI_REC 0
+#include "k_step_multi_body.inc"
+#undef STEP_MULTI_REC
+}
+
+// The recording launch (auv_step_multi_record): k_step_multi with the three output rows of step k at k * stride.  A kernel of its
+// own, so that the plain launch keeps its argument list and its code (the body is the same text: k_step_multi_body.inc).
+__global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_record(AuvDev dk, const void* __restrict__ actions, float* __restrict__ obs_out,
+                                                                            float* __restrict__ reward_out, uint8_t* __restrict__ done_out,
+                                                                            const int n_steps, const int first_slot, const int n_slots,
+                                                                            const unsigned long long seq0, const int lead_dyn, const int lag_fin, const unsigned magic_c,
+                                                                            const unsigned long long obs_stride, const unsigned long long reward_stride,
+                                                                            const unsigned long long done_stride) {
+  AUV_KERNARG_DESC(d);
+#define STEP_MULTI_REC 1
+#include "k_step_multi_body.inc"
+#undef STEP_MULTI_REC
+}
+
+// Behind a recording launch, on its stream: the record's LAST row of the slice [e0, e0 + ne) into the handle-wide obs / reward / done
+// buffers, which hold the last step's values after every kind of step.  obs_last == nullptr: the launch kept no observation record
+// and wrote obs itself.  Nothing is copied behind an aborted launch (rows that were not reached hold what the caller passed).
+__global__ void __launch_bounds__(256) k_record_last(const float* __restrict__ obs_last, const float* __restrict__ reward_last,
+                                                     const uint8_t* __restrict__ done_last, float* __restrict__ obs, float* __restrict__ reward,
+                                                     uint8_t* __restrict__ done, const int e0, const int ne, const int D, const int32_t* __restrict__ abort_flag) {
+  if (*abort_flag) return;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t o0 = (size_t)e0 * (size_t)D;
+  if (obs_last && i < (size_t)ne * (size_t)D) obs[o0 + i] = obs_last[o0 + i];
+  if (i < (size_t)ne) reward[e0 + i] = reward_last[e0 + i], done[e0 + i] = done_last[e0 + i];
 }
 
 // ---- inside a captured graph of several steps: reward / done / auto-reset of step t and Vessel.step of step t + 1
@@ -1260,6 +1121,26 @@ void auv_launch_step_multi(const AuvDev& d0, const void* actions, int dtype, flo
   hipLaunchKernelGGL(k_step_multi, grid, block, lds, st, d, actions, obs, reward, done, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic);
 }
 
+// the recording form: step k's rows at obs_rec + k N D, reward_rec + k N, done_rec + k N (obs_rec == nullptr: no observation record,
+// every step writes `obs`); then the last row into obs / reward / done
+void auv_launch_step_record(const AuvDev& d0, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, float* obs_rec,
+                            float* reward_rec, uint8_t* done_rec, int n_steps, int first_slot, int n_slots, unsigned long long seq0, int order,
+                            int lead, int lag, hipStream_t st) {
+  AuvDev d = d0;
+  d.act_f64 = dtype == AUV_F64;
+  d.ring_slots = 1;
+  const uint32_t lds = (uint32_t)k2_slice_bytes(d);
+  const AuvMultiGeom g = auv_multi_geom(d.ne, n_steps, order, lead, lag);      // (the host has checked that the grid fits)
+  const dim3 grid((unsigned)auv_multi_grid(g)), block(AUV_WAVE);
+  const int D = auv_obs_cols(d.cfg, d.pool_ns);
+  const unsigned long long n = (unsigned long long)d.n, obs_stride = obs_rec ? n * (unsigned long long)D : 0ull;
+  hipLaunchKernelGGL(k_step_record, grid, block, lds, st, d, actions, obs_rec ? obs_rec : obs, reward_rec, done_rec, n_steps, first_slot, n_slots, seq0,
+                     g.lead, g.lag, g.magic, obs_stride, n, n);
+  const size_t last = (size_t)(n_steps - 1), items = (size_t)d.ne * (size_t)(obs_rec ? D : 1);
+  hipLaunchKernelGGL(k_record_last, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, obs_rec ? obs_rec + last * obs_stride : nullptr,
+                     reward_rec + last * n, done_rec + last * n, obs, reward, done, d.e0, d.ne, D, d.abort_flag);
+}
+
 // The stage's capacity for a bank (S, k_max, m_max known): the largest that gives the one-launch step its best occupancy (see
 // k2_lidar.hip) and still leaves room for the search role's chunk list; asked of the runtime, not computed (allocation granule).
 int auv_pick_seg_cap(const AuvDev& d0) {
@@ -1284,6 +1165,8 @@ hipError_t auv_step_fused_prepare(const AuvDev& d) {
   hipError_t e = hipFuncSetAttribute((const void*)k23_lidar_nav, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void*)k_step_multi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute((const void*)k_step_record, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)k_step_roles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
 }

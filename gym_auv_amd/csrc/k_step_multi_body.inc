@@ -1,0 +1,187 @@
+// k_step_multi_body.inc -- the body of a launch of several steps, included by csrc/k_step_fused.hip once per kernel:
+//   STEP_MULTI_REC 0   k_step_multi   every step writes the same obs / reward / done rows (the last step's remain)
+//   STEP_MULTI_REC 1   k_step_record  step k of the launch writes its rows `k * stride` elements further on: a [T][N] record
+// The includer has declared `d` (AUV_KERNARG_DESC) and the kernel's parameters: actions, obs_out, reward_out, done_out, n_steps,
+// first_slot, n_slots, seq0, lead_dyn, lag_fin, magic_c -- and, recording, obs_stride, reward_stride, done_stride (elements; 0: no
+// record of that output).  The record's offset is wave-uniform (the step is, the strides are kernel arguments): 64-bit scalar
+// arithmetic once per wave, and every writer -- the sweep's closeness columns, the tail's navigation features, the reward phase, a
+// restored environment's row -- keeps its code and its GLOBAL environment index.
+// (Text, not a function template on `bool REC` inlined into two wrappers: that was tried first and k_step_multi's code came out
+// different -- same register counts, other allocation and block layout -- where this change is meant to leave it alone.)
+  extern __shared__ __align__(16) unsigned char smem[];
+#ifdef AUV_STAMPS_MULTI
+  const unsigned long long t_entry = wall_clock64();      // the wave's first instruction
+#endif
+  const int lane = threadIdx.x;
+  const int ne = d.ne;
+  // role: 0 dynamics, 1 sweep, 2 search, 3 finish; bi: the wave's index within its role and step (auv_multi_geom.h: the decode,
+  // the launcher's grid and the host's checks have this one source).
+  // Two workgroup orders (both computed, one selected: a run-time branch around this index arithmetic makes this compiler emit a
+  // vector-to-scalar copy it then rejects):
+  //   step-major: all of step t's workgroups, role by role, then step t + 1's;
+  //   COHORT-PIPELINED (lead_dyn >= 0).  A cohort = 64 consecutive environments = 8 dynamics + 64 sweep + 64 search + 8 finish
+  //   workgroups (every run a multiple of 8: an environment's waves still share an XCD).  Cohort-steps are numbered
+  //   q = step * C + cohort; position p of the grid holds the dynamics of q = p, the sweeps and searches of q = p - lead and the
+  //   finish waves of q = p - lead - lag: a sweep is dispatched `lead` positions behind its dynamics -- which have finished by
+  //   then -- and a finish wave `lag` positions behind its sweeps, so waves find what they need instead of holding a slot while
+  //   they poll for it (the step-major order makes step t + 1's sweeps wait, resident, for a finish wave that is dispatched last
+  //   of all of step t).  lead + lag < C keeps every producer ahead of its consumer in index order, also across steps: the
+  //   dynamics of q + C sit at position q + C, behind the finish waves of q at q + lead + lag.
+  // A workgroup outside the launch -- past the last step, or past its role's count (a slice that is not a multiple of 8
+  // environments) -- decodes to step == n_steps and ends here.
+  const bool cohorts = lead_dyn >= 0;
+  const AuvMultiWave wa = auv_multi_decode_steps(blockIdx.x, ne, n_steps);
+  const AuvMultiWave wc = auv_multi_decode_cohorts(blockIdx.x, ne, n_steps, lead_dyn, lag_fin, magic_c);
+  const int step = auv_uniform(cohorts ? wc.step : wa.step);
+  const int role = auv_uniform(cohorts ? wc.role : wa.role), bi = auv_uniform(cohorts ? wc.bi : wa.bi);
+  if (step >= n_steps) return;
+#if STEP_MULTI_REC
+  {
+    // this step's rows of the record (a stride of 0: no record of that output, every step writes the one row)
+    obs_out += (unsigned long long)(unsigned)step * obs_stride;
+    reward_out += (unsigned long long)(unsigned)step * reward_stride;
+    done_out += (unsigned long long)(unsigned)step * done_stride;
+  }
+#endif
+  const unsigned long long tagmix = roles_tagmix(seq0 + (unsigned long long)step + 1ull), tagmix_prev = roles_tagmix(seq0 + (unsigned long long)step);
+#ifdef AUV_STAMPS_MULTI
+  unsigned long long* const stamp = d.stamps + (step == n_steps / 2 ? (size_t)0 : (size_t)16 * (size_t)d.n);
+#endif
+  if (role == 0) {
+    // ---- Vessel.step of eight environments ----
+    __builtin_amdgcn_s_setprio(3);
+    const int b = bi;
+    const int g = lane / K1_GROUP, c = lane % K1_GROUP;
+    const int er = 8 * (8 * (b / 8) + g) + (b % 8);
+    const bool live = er < ne;
+    const int eg = d.e0 + (live ? er : ne - 1);
+    int y, gave_up = 0;
+    double y0 = 0.0;
+    MSTAMP_IF(live && c == 0, eg, 10);
+    // requested ahead of the wait for the carry record (this wave is on every environment's critical path): the flag and the action
+    const int ab_early = __hip_atomic_load(d.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    double act0, act1;
+    k1_action(d, actions, eg, &act0, &act1, (first_slot + step) % n_slots);
+    if (step == 0) {
+      y = d.counters[eg].y + 1;
+    } else {
+      // this environment's state and counters after the previous step: the first line of its carry record
+      const unsigned long long* cw = d.carry + CARRY_WORDS * (size_t)eg;
+      unsigned long long v = 0ull;
+      bool ok = !live;
+      for (int polls = 0;; polls++) {
+        if (!ok) v = __hip_atomic_load(cw + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ok = !live || roles_record_ok(v, c, tagmix_prev);
+        if (!__any(!ok)) break;
+        if ((polls & 31) == 31 && auv_uniform(__hip_atomic_load(d.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
+          gave_up = 1;                                                              // (ABORT packets below)
+          break;
+        }
+        if (polls == (AUV_HOOK_FAULT(d) ? (1 << 12) : PAIR_POLL_LIMIT)) {
+          if (live && c == 0) auv_st<true>(d.broken + eg, (uint8_t)1);
+          roles_give_up(d, d.e0, d.ne, 6, lane);
+          gave_up = 1;                                                              // (the flag is up now: ABORT packets below)
+          break;
+        }
+        __builtin_amdgcn_s_sleep(ROLES_POLL_SLEEP);
+      }
+      y0 = __longlong_as_double((long long)v);
+      y = (int)(unsigned)(roles_group_word(v, 6) >> 32) + 1;
+    }
+    const int aborted = gave_up | auv_uniform(ab_early);
+    double t = 0.0;
+    MSTAMP_IF(live && c == 0, eg, 11);
+    const double2 act = make_double2(act0, act1);
+    if (!aborted) t = k1_group(d, actions, eg, lane, step == 0 ? nullptr : &y0, (first_slot + step) % n_slots, &act);
+    unsigned long long* pk = d.k1_pkt + 8 * (size_t)eg;
+    const unsigned long long word = aborted ? (c == 6 ? (unsigned long long)ROLES_ABORT_COUNTER : 0ull)
+                                            : (c < 6 ? (unsigned long long)__double_as_longlong(t) : (c == 6 ? (unsigned long long)(unsigned)y : 0ull));
+    const unsigned long long mark = roles_mark(roles_group_xor(word) ^ tagmix);
+    if (live && !(AUV_HOOK_FAULT(d) == 2 && eg == d.e0 && step == 0))
+      __hip_atomic_store(pk + c, c < 7 ? word : mark, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    MSTAMP_IF(live && c == 0, eg, 12);
+    return;
+  }
+  EnvPre pre;
+  EnvDesc ed;
+  if (role == 1) {
+    // ---- _update + Vessel.perceive of one environment ----
+    const int e = auv_uniform(d.e0 + bi);
+    MSTAMP(e, 0);
+    // three requests in flight before the first wait: the abort flag, this step's state packet (dispatched `lead` cohorts behind
+    // its dynamics, the wave usually finds it there), the carry record
+    const int ab_early = __hip_atomic_load(d.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const unsigned long long pk_first = __hip_atomic_load(d.k1_pkt + 8 * (size_t)e + (lane & 7), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const Slice L = carve(smem, d);
+    K2Pre kp;
+    if (step == 0) {
+      ed = d.env_desc[e];
+      pre.cnt = d.counters[e];
+      pre.ed = &ed;
+      if (auv_uniform(ab_early)) return;
+      k2_movers<true>(d, e, lane, L, ed, 1);
+      kp = k2_prefetch(d, e, lane, ed);
+    } else {
+      if (carry_wait_wave(d, e, lane, tagmix_prev, ed, pre.cnt)) return;
+      if (auv_uniform(ab_early)) return;
+      pre.ed = &ed;
+      k2_movers<true, true>(d, e, lane, L, ed, 1);
+      kp = k2_prefetch<true>(d, e, lane, ed);
+    }
+    k2_stage_beams(d, lane, L);
+    {
+      const int ws = roles_wait_state(d, e, lane, pre, tagmix, true, pk_first);
+      if (ws) {
+        if (ws == 2 && ed.M > 0 && lane == 0) auv_st<true>(d.broken + e, (uint8_t)1);
+        return;
+      }
+    }
+    MSTAMP(e, 2);
+    int2 lim0 = make_int2(INT32_MIN, INT32_MIN);
+    const int n_act = k2_front<true>(d, e, lane, L, 1, &pre, 1, &kp, true, &lim0);
+    k2_stage_and_pairs(d, L, lane, n_act, pre.s[2]);
+    MSTAMP(e, 4);
+    double term = 0.0;
+    const int collision = k2_back<true>(d, e, lane, L, n_act, obs_out, &term, &lim0);
+    pair_publish_lidar(d, e, lane, collision, term);
+    MSTAMP(e, 5);
+#ifdef AUV_STAMPS_MULTI
+    if (lane == 0) stamp[(size_t)e * 16 + 1] = t_entry;
+    __builtin_amdgcn_s_waitcnt(0x0F70);                    // every store of this wave has been acknowledged
+    MSTAMP(e, 3);
+#endif
+  } else if (role == 2) {
+    // ---- Vessel.navigate of one environment: the nearest-point search ----
+    const int e = auv_uniform(d.e0 + bi);
+    MSTAMP(e, 6);
+    const unsigned long long pk_first = __hip_atomic_load(d.k1_pkt + 8 * (size_t)e + (lane & 7), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (step == 0) {
+      ed = d.env_desc[e];
+      pre.cnt = d.counters[e];
+    } else if (carry_wait_wave(d, e, lane, tagmix_prev, ed, pre.cnt)) {
+      return;
+    }
+#ifdef AUV_STAMPS_MULTI
+    if (lane == 0) stamp[(size_t)e * 16 + 7] = t_entry;
+#endif
+    pre.ed = &ed;
+    if (roles_wait_state(d, e, lane, pre, tagmix, true, pk_first)) return;
+    MSTAMP(e, 8);
+    NavNear nr;
+    int* list = (int*)smem;
+    const NavSpec sp = nav_bounds(d, e, lane, list, pre.s[0], pre.s[1], &ed);
+    nr = nav_nearest(d, e, lane, list, pre.s[0], pre.s[1], sp);
+    roles_publish_search(d, e, lane, nr, tagmix);
+    MSTAMP(e, 9);
+  } else {
+    // ---- navigation tail + reward / done / auto-reset of eight environments ----
+    const int f = bi;
+    __builtin_amdgcn_s_setprio(2);
+#ifdef AUV_STAMPS_MULTI
+    const int fer = 8 * (8 * (f / 8) + lane / K1_GROUP) + (f % 8);
+    const bool fst = fer < ne && lane % K1_GROUP == 0;
+#endif
+    MSTAMP_IF(fst, d.e0 + fer, 13);
+    roles_finish_wave_multi<true>(d, f, lane, obs_out, reward_out, done_out, step, step == n_steps - 1, tagmix, tagmix_prev MSTAMP_ARG);
+    MSTAMP_IF(fst, d.e0 + fer, 15);
+  }

@@ -132,6 +132,48 @@ class AuvVecEnv:
         self.step_async(actions)
         return self.step_wait()
 
+    def step_sequence(self, actions):
+        """`actions` [T, N, 2]: T consecutive step() calls with known actions as ONE launch (BatchedAuvEnv.step_multi with a
+        record).  Returns (obs, rewards, dones) with a leading T axis -- row t is what the t-th step() returns, in step_wait's
+        formats (flat or Dict observations; NumPy float32 / bool, or device tensors with numpy=False): a row with done carries the
+        terminal reward and the new episode's first observation.  T = 1 equals step().  No per-step infos (the episode log and
+        get_attr('history') see every episode all the same), and the poses between the first and the last step of the sequence
+        are not tracked: `last_episode`'s path_taken holds NaN rows for them."""
+        if self._waiting:
+            raise RuntimeError("step_sequence() between step_async() and step_wait()")
+        env = self.env
+        a = torch.as_tensor(np.asarray(actions) if isinstance(actions, (list, tuple)) else actions).to(env.device)
+        if a.dim() != 3 or tuple(a.shape[1:]) != (self.num_envs, 2):
+            raise ValueError("actions must have shape (T, %d, 2), got %s" % (self.num_envs, tuple(a.shape)))
+        if a.dtype not in (torch.float32, torch.float64):
+            a = a.to(torch.float32)
+        a = a.contiguous()
+        T = int(a.shape[0])
+        if env._slices is None:
+            env.set_sub_batches(1, inline_first=True)
+        # the chains run behind whatever produced the actions on the caller's stream, and the caller's stream behind the chains
+        cur = torch.cuda.current_stream(env.device)
+        side = [st for st in env._sub_streams if st != cur]
+        for st in side:
+            st.wait_stream(cur)
+            a.record_stream(st)
+        obs, rew, done = env.step_multi(a, 0, T, record=True)
+        for st in side:
+            cur.wait_stream(st)
+        if self._track and T > 1:
+            idx = (self._traj_n + torch.arange(T - 1, device=env.device)) % self._traj_cap
+            self._traj[idx] = float("nan")
+            self._traj_n += T - 1
+        self._record_pose()
+        if not self._dict_obs:
+            o = self._out(obs)
+        else:
+            c, S = self.config.vessel.lidar_shape
+            o = {"proprioceptive": self._out(obs[:, :, :6]), "lidar": self._out(obs[:, :, 6:6 + c * S].reshape(T, -1, c, S))}
+        if not self.numpy:
+            return o, rew, done
+        return o, self._out(rew), self._out(done).astype(bool)
+
     def seed(self, seed: Optional[int] = None):
         """VecEnv.seed: environment i gets seed + i.  The scenarios of this adapter are the worlds handed to it (the
         bank), so the seeds are only recorded (`get_attr('seed_value')`), as for a gym env whose scenario is fixed."""

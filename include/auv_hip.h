@@ -204,6 +204,28 @@ int auv_step_multi(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, voi
                    int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev, float* reward_dev,
                    uint8_t* done_dev);
 
+/* auv_step_multi with EVERY step's outputs kept: n_steps consecutive step() calls (environment.py:325-384) of every slice in one launch
+ * per slice, step k of the call writing
+ *     its observation rows to  obs_rec    + k * N * obs_dim      [n_steps][N][obs_dim] f32   (may be NULL: no observation record)
+ *     its rewards to           reward_rec + k * N                [n_steps][N] f32            (required)
+ *     its done flags to        done_rec   + k * N                [n_steps][N] u8             (required)
+ * with N the handle's environments -- what n_steps one-step calls hand their caller, row for row and bit for bit (tests/
+ * test_gpu_multi_record.py).  An episode that ends inside the launch leaves, in the row of the step that ended it, the terminal
+ * reward, done = 1 and (auto-reset) the NEW episode's first observation: the VecEnv convention.  A caller that fills a longer rollout
+ * buffer in pieces passes pointers already offset to its row.  The launch is k_step_multi's (csrc/k_step_fused.hip, k_step_record:
+ * the same roles, carry records, marks, workgroup order and polls; only the base address of the three outputs depends on the step),
+ * so state, counters, episode log and every readable field are what auv_step_multi with the same arguments leaves.  obs_dev /
+ * reward_dev / done_dev hold the LAST step's values afterwards: a small copy kernel behind the launch, on the slice's stream, copies
+ * the record's last row of the slice into them (with obs_rec == NULL the launch itself writes every step's observation to obs_dev,
+ * as auv_step_multi does, and only reward and done are copied).  Preconditions and refusals are auv_step_multi's, checked before
+ * anything launches or any step number is spent, plus AUV_EINVAL for a NULL reward_rec / done_rec and for an obs_rec that is not
+ * 8-byte aligned when obs_dim is even (the navigation features of a row are stored as float pairs then; 4 bytes when it is odd).
+ * Workgroup order: auv_set_multi_order.  Eager only.  After a hand-over time-out (auv_health) the rows of steps that were not reached
+ * are left as the caller passed them, and nothing is copied into obs_dev / reward_dev / done_dev; recovery is the usual one.      */
+int auv_step_multi_record(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const void* actions_dev,
+                          int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev, float* reward_dev,
+                          uint8_t* done_dev, float* obs_rec, float* reward_rec, uint8_t* done_rec);
+
 /* Workgroup order of auv_step_multi's launches (same results either way).  order 0: step-major (all of step t, role by role, then
  * step t + 1).  order 1 (default): cohort-pipelined -- cohorts of 64 environments; the sweeps of a cohort-step are dispatched `lead`
  * cohort positions behind its dynamics and its finish waves `lag` positions behind the sweeps, so a wave finds its inputs instead of

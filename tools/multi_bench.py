@@ -1,8 +1,11 @@
 #!/usr/bin/env python3
 """Open-loop rate with SEVERAL steps per launch (auv_step_multi) against one step per launch, by chains and launch length:
-python tools/multi_bench.py [workload polygons50|moving28] [envs] [--feasibility-pooling] [--quick]
+python tools/multi_bench.py [workload polygons50|moving28] [envs] [--feasibility-pooling] [--quick] [--record | --record=reward]
 --feasibility-pooling: the observation pooled to 9 sectors (VesselConfig.sensor_use_feasibility_pooling);
---quick: one chain only, one step per launch and 64-step launches in cohort order"""
+--quick: one chain only, one step per launch and 64-step launches in cohort order;
+--record: the launches of several steps keep every step's obs / reward / done in a preallocated [T][N] buffer
+(auv_step_multi_record); --record=reward: reward and done only.  The one-step-per-launch row is the same loop either way: it
+hands out every step already."""
 import json
 import os
 import sys
@@ -17,6 +20,7 @@ from gym_auv_amd.config import effective_reference_config  # noqa: E402
 from gym_auv_amd.world import build_bank_parallel  # noqa: E402
 
 POOL, QUICK = "--feasibility-pooling" in sys.argv, "--quick" in sys.argv
+RECORD = "obs" if "--record" in sys.argv else ("reward" if "--record=reward" in sys.argv else None)
 argv = [a for a in sys.argv if not a.startswith("--")]
 wl = argv[1] if len(argv) > 1 else "polygons50"
 n = int(argv[2]) if len(argv) > 2 else 4096
@@ -38,6 +42,11 @@ for k in ((1,) if QUICK else (1, 2, 4)):
     env.reset()
     env.set_sub_batches(k, strict=True)
     steps = 1920
+    rec = None
+    if RECORD:
+        rec = (torch.zeros((64, n, env.obs_dim), dtype=torch.float32, device=dev) if RECORD == "obs" else None,
+               torch.zeros((64, n), dtype=torch.float32, device=dev), torch.zeros((64, n), dtype=torch.uint8, device=dev))
+        torch.cuda.synchronize()
     shapes = ((0, "-"), (64, "cohorts")) if QUICK else \
         ((0, "-"), (8, "steps"), (64, "steps"), (8, "cohorts"), (16, "cohorts"), (64, "cohorts"), (64, "cohorts:6:16"), (64, "cohorts:20:40"))
     for T, order in shapes:
@@ -50,13 +59,13 @@ for k in ((1,) if QUICK else (1, 2, 4)):
                     env.step_pipelined(ring[i % slots])
             else:
                 for i in range(0, m, T):
-                    env.step_multi(ring, i % slots, T)
+                    env.step_multi(ring, i % slots, T, record=rec and (rec[0] if rec[0] is None else rec[0][:T], rec[1][:T], rec[2][:T]))
         run(steps // 2)
         torch.cuda.synchronize()
         t0 = time.perf_counter()
         run(steps)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        print(json.dumps(dict(workload=wl, envs=n, pooled=POOL, obs_dim=env.obs_dim, chains=k, steps_per_launch=T or 1, order=order, rate_M=round(n * steps / dt / 1e6, 1), us_per_step=round(1e6 * dt / steps, 2),
+        print(json.dumps(dict(workload=wl, envs=n, pooled=POOL, obs_dim=env.obs_dim, chains=k, steps_per_launch=T or 1, order=order, record=RECORD if T else None, rate_M=round(n * steps / dt / 1e6, 1), us_per_step=round(1e6 * dt / steps, 2),
                               health=env.health())), flush=True)
     env.close()
