@@ -216,6 +216,12 @@ def load_library(path: str = None) -> C.CDLL:
         "auv_fresh_worlds_draws": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), i32, vp, vp]),
         "auv_bank_bytes": (sz, [vp, i32]),
         "auv_read_bank": (C.c_int, [vp, i32, vp, sz, vp]),
+        "auv_snapshot_row_bytes": (sz, [vp]),
+        "auv_snapshot_layout": (C.c_uint64, [vp]),
+        "auv_snapshot": (C.c_int, [vp, vp, i32, vp, vp]),
+        "auv_restore": (C.c_int, [vp, C.c_uint64, vp, i32, vp, vp, i32, vp, vp]),
+        "auv_snapshot_skipped": (C.c_int, [vp, C.POINTER(C.c_int64), vp]),
+        "auv_plan_score": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp]),
         "auv_abi_version": (i32, []),
         "auv_last_error": (C.c_char_p, []),
     }
@@ -241,6 +247,7 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_set_action_ring", "auv_set_step_mode", "auv_set_obs_pooling", "auv_feasibility_pooling",
                     "auv_generate_worlds", "auv_bank_bytes", "auv_read_bank",
                     "auv_fresh_worlds_create", "auv_fresh_worlds_refill", "auv_fresh_worlds_stats", "auv_fresh_worlds_draws", "auv_fresh_worlds_set_stream",
+                    "auv_snapshot_row_bytes", "auv_snapshot_layout", "auv_snapshot", "auv_restore", "auv_snapshot_skipped", "auv_plan_score",
                     "auv_abi_version", "auv_last_error"]
 
 # tables of a generated bank (auv_read_bank): id, dtype, trailing shape ('P' = AUV_GEN_POLY_CAP,

@@ -21,6 +21,7 @@ from . import _capi
 from ._capi import FIELD_DTYPES, FIELDS, AuvLibraryError, load_library, make_bank_struct, make_config, obs_pooling
 from .config import Config
 from .devgen import FreshWorlds, GeneratedWorlds
+from .snapshot import Snapshot, check_restore, resolve_pairs
 from .spaces import Box
 from .world import BuiltWorld, build_world, pack_bank
 from .worldspec import WorldSpec
@@ -63,6 +64,9 @@ class BatchedAuvEnv:
             _check(_LIB.auv_set_obs_pooling(self._h, ns, starts.ctypes.data_as(C.c_void_p), width), "auv_set_obs_pooling")
         self._gen = None
         self._fresh = None
+        # what a second batch on the same config and bank is built from (planning.ShootingPlanner)
+        self._ctor_args = dict(rewarder=rewarder, test_mode=test_mode, cull=cull, auto_reset=auto_reset)
+        self._worlds_arg = None
         if isinstance(worlds, FreshWorlds):
             # a fresh world on every reset: `depth` slots per environment, regenerated on the device as they are left
             self.fresh_worlds(worlds)
@@ -80,6 +84,7 @@ class BatchedAuvEnv:
             bs, keep = make_bank_struct(bank)
             _check(_LIB.auv_load_worlds(self._h, C.byref(bs)), "auv_load_worlds")
             del keep
+            self._worlds_arg = bank
         if auto_reset and self.n_worlds <= self.n_envs and self._fresh is None:
             # auto-reset rebinds env e to world (w + n_envs) % n_worlds: with no more worlds than envs that is the
             # world it has just finished (the reference draws a new scenario on every reset, movingobstacles.py:28-95)
@@ -131,6 +136,7 @@ class BatchedAuvEnv:
         del keep
         self._gen = None
         self._fresh = None
+        self._worlds_arg = bank
         self.n_worlds = int(bank["n_worlds"])
         self.k_max = max(1, int(bank["k_max"]))
         self.m_max = max(1, int(bank["m_max"]))
@@ -563,6 +569,7 @@ class BatchedAuvEnv:
         """(Re)build the whole world bank on the device (auv_generate_worlds) and reset every
         environment.  `draws` overrides the spec's seeded draws ([W, n_draws] float64, device)."""
         from . import devgen
+        seeded = draws is None
         if draws is None:
             draws = devgen.sample_draws(spec.n_worlds, spec.n_moving, spec.n_static, seed=spec.seed, device=self.device)
         draws = draws.to(device=self.device, dtype=torch.float64).contiguous()
@@ -578,6 +585,7 @@ class BatchedAuvEnv:
                                         nseg.ctypes.data_as(C.c_void_p), len(nseg)), "auv_generate_worlds")
         self._gen = spec
         self._fresh = None
+        self._worlds_arg = spec if seeded else None   # (explicit draws: a second batch cannot rebuild the bank from the spec alone)
         self._log_first = 0
         self.n_worlds = spec.n_worlds
         self.k_max = max(1, spec.n_moving + spec.n_static)
@@ -600,6 +608,7 @@ class BatchedAuvEnv:
                                             unit.ctypes.data_as(C.c_void_p), nseg.ctypes.data_as(C.c_void_p), len(nseg)),
                "auv_fresh_worlds_create")
         self._fresh = spec
+        self._worlds_arg = None
         # the passes' stream: one that runs side by side with the caller's current stream (set_sub_batches picks again for chains)
         pair = self._concurrent_streams(2, first=torch.cuda.current_stream(self.device))
         if len(pair) == 2:
@@ -660,6 +669,79 @@ class BatchedAuvEnv:
         nbytes = t.numel() * t.element_size()
         _check(_LIB.auv_read_bank(self._h, tid, C.c_void_p(t.data_ptr()), nbytes, self._stream()), "auv_read_bank(%s)" % name)
         return t
+
+    # ------------------------------------------------------------------------------ snapshot / restore
+    def _join_chains(self):
+        """The caller's current stream waits for everything enqueued on the sub-batch chains' streams (events, no host sync)."""
+        cur = torch.cuda.current_stream(self.device)
+        for st in (self._sub_streams if self._slices is not None else ()):
+            if st != cur:
+                cur.wait_stream(st)
+
+    def _fork_chains(self):
+        """The sub-batch chains' streams wait for everything enqueued on the caller's current stream so far."""
+        cur = torch.cuda.current_stream(self.device)
+        for st in (self._sub_streams if self._slices is not None else ()):
+            if st != cur:
+                st.wait_stream(cur)
+
+    def _index_arg(self, x) -> torch.Tensor:
+        return torch.as_tensor(x).to(device=self.device, dtype=torch.int32).contiguous().reshape(-1)
+
+    @property
+    def snapshot_layout(self) -> int:
+        """Fingerprint of this batch's snapshot-row layout (auv_snapshot_layout): snapshots move between batches that agree on it."""
+        return int(_LIB.auv_snapshot_layout(self._h))
+
+    @property
+    def snapshot_row_bytes(self) -> int:
+        return int(_LIB.auv_snapshot_row_bytes(self._h))
+
+    def snapshot(self, envs=None) -> Snapshot:
+        """Copy the environments `envs` (default: all) out of the batch: everything a later step or read() can observe, one packed
+        row each (auv_snapshot; one launch on the caller's stream, ordered behind the sub-batch chains; no host synchronisation).
+        Not with FreshWorlds (RuntimeError)."""
+        idx = torch.arange(self.n_envs, dtype=torch.int32, device=self.device) if envs is None else self._index_arg(envs)
+        m = int(idx.numel())
+        with torch.cuda.device(self.device):
+            rows = torch.empty((m, self.snapshot_row_bytes), dtype=torch.uint8, device=self.device)
+        self._join_chains()
+        _check(_LIB.auv_snapshot(self._h, C.c_void_p(idx.data_ptr()), m, C.c_void_p(rows.data_ptr()), self._stream()), "auv_snapshot")
+        return Snapshot(rows, self.snapshot_layout, idx)
+
+    def restore(self, snap: Snapshot, rows=None, envs=None, validate: bool = True):
+        """Put rows of a snapshot into environments of this batch (auv_restore): environment envs[j] <- row rows[j].  rows=None:
+        0 .. m - 1; envs=None: where the rows were taken from.  One row may feed many environments (a fork).  The snapshot may come
+        from another batch with the same layout and the same world bank (that the banks agree is the caller's promise).  `self.obs`
+        is refreshed for the restored environments; reward / done keep the last step's values.
+        validate=True: the layout, the index ranges and that no environment is written twice are checked on the host (reads index
+        tensors back: may synchronise) -> ValueError.  validate=False: no host read-back at all; a pair with an index out of range is
+        skipped on the device and counted (`snapshot_skipped()`), a foreign layout is still refused (RuntimeError)."""
+        r, e = resolve_pairs(snap.envs, snap.n_rows, rows, envs)
+        if validate:
+            check_restore(snap.layout, self.snapshot_layout, snap.n_rows, self.n_envs, r, e)
+        if snap.device != self.device:
+            snap = snap.to(self.device)
+        r, e = self._index_arg(r), self._index_arg(e)
+        if r.numel() != e.numel():
+            raise ValueError("rows and envs must have the same length, got %d and %d" % (r.numel(), e.numel()))
+        self._join_chains()
+        _check(_LIB.auv_restore(self._h, C.c_uint64(snap.layout), C.c_void_p(snap.rows.data_ptr()), snap.n_rows, C.c_void_p(r.data_ptr()),
+                                C.c_void_p(e.data_ptr()), int(e.numel()), C.c_void_p(self.obs.data_ptr()), self._stream()), "auv_restore")
+        self._fork_chains()
+        return self.obs
+
+    def fork(self, src, dst, validate: bool = True):
+        """Environments dst[j] become copies of environments src[j] (a snapshot of `src`, restored into `dst`); a source may be
+        named several times."""
+        return self.restore(self.snapshot(src), rows=None, envs=dst, validate=validate)
+
+    def snapshot_skipped(self) -> int:
+        """Pairs snapshot() / restore() skipped on the device because an index was out of range, since the bank was loaded.
+        One small device-to-host copy (synchronises the current stream)."""
+        out = C.c_int64(0)
+        _check(_LIB.auv_snapshot_skipped(self._h, C.byref(out), self._stream()), "auv_snapshot_skipped")
+        return int(out.value)
 
     # ------------------------------------------------------------------------------ field access
     def field_shape(self, name: str):

@@ -14,6 +14,7 @@
 #include "auv_device.h"
 #include "auv_generate.h"
 #include "auv_multi_geom.h"
+#include "auv_snapshot.h"
 
 void auv_launch_k1(const AuvDev& d, const void* actions, int dtype, hipStream_t st, hipEvent_t ev0 = nullptr,
                    hipEvent_t ev1 = nullptr);
@@ -58,6 +59,10 @@ void auv_launch_gae(const float* R, const float* V, const float* Dn, const float
                     int T, int N, hipStream_t st);
 void auv_launch_k4(const AuvDev& d, const int32_t* sector_start, int n_sectors, double width, double* out_dist,
                    float* out_closeness, hipStream_t st);
+void auv_launch_snapshot(const AuvSnapArgs& a, const int32_t* env_idx, int m, void* rows, hipStream_t st);
+void auv_launch_restore(const AuvSnapArgs& a, const AuvDev& d, const void* rows, int n_rows, const int32_t* row_idx, const int32_t* env_idx, int m,
+                        float* obs, hipStream_t st);
+void auv_launch_plan_score(const float* reward, const uint8_t* done, int T, int n, int group, float gamma, float* score, int32_t* best, hipStream_t st);
 
 static thread_local char g_err[512] = "";
 
@@ -117,6 +122,7 @@ struct auv_handle {
   int chain_steps = 1, graph_steps = 1;    // steps per replay of the captured chains / of the one graph
   unsigned long long multi_seq = 0;        // auv_step_multi: step numbers handed out so far (every mark of a step carries its number)
   int multi_order = 1, multi_lead = 16, multi_lag = 30;   // auv_set_multi_order: workgroup order of a launch of several steps
+  unsigned int* snap_skipped = nullptr;    // [1] device: pairs auv_snapshot / auv_restore skipped for an index out of range (restarts with every bank)
   // on-device generation (auv_generate_worlds): shape of the slot bank, 0 = packed upload
   int gen_worlds, gen_moving, gen_static, gen_grid;
   GenOut gen;
@@ -368,6 +374,8 @@ static int finish_bank(auv_handle* h, bool alloc_env) {
   HIP_TRY(hipMemset(h->rdv, 0, AUV_RDV_BYTES));
   h->rdv_seq = h->rdv_target = 0;
   h->async_pending = 0;
+  if (!h->snap_skipped) HIP_TRY(hipMalloc((void**)&h->snap_skipped, 4 * sizeof(unsigned int)));   // (here: auv_snapshot / auv_restore never allocate)
+  HIP_TRY(hipMemset(h->snap_skipped, 0, 4 * sizeof(unsigned int)));
   d.w_ready = 0;
   auv_launch_derive(d, nullptr);
   std::vector<int32_t> wi(n);
@@ -710,6 +718,7 @@ int auv_destroy(auv_handle_t* h) {
   for (auto& e : h->ev_chain) (void)hipEventDestroy(e);
   if (h->ev_actions) (void)hipEventDestroy(h->ev_actions);
   if (h->rdv) (void)hipFree(h->rdv);
+  if (h->snap_skipped) (void)hipFree(h->snap_skipped);
   for (auto& g : h->chain_exec) (void)hipGraphExecDestroy(g);
   for (auto& g : h->chain_graph) (void)hipGraphDestroy(g);
   for (auto& st : h->fork_streams) (void)hipStreamDestroy(st);
@@ -1852,6 +1861,109 @@ int auv_gae(auv_handle_t* h, const float* R, const float* V, const float* Dn, co
   if (!R || !V || !Dn || !last_v || !adv_out || !ret_out || T < 1 || N < 1) return fail(AUV_EINVAL, "auv_gae: bad arguments");
   HIP_TRY(hipSetDevice(h->device));
   auv_launch_gae(R, V, Dn, last_v, gamma, lam, adv_out, ret_out, T, N, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+// ---- snapshot / restore of environments (layout: include/auv_hip.h; kernels: k7_snapshot.hip) ----
+static void snap_args(const auv_handle_t* h, AuvSnapArgs* a) {
+  const AuvDev& d = h->d;
+  const uint32_t S = (uint32_t)d.cfg.n_sensors, K = (uint32_t)d.k_max, M = (uint32_t)d.m_max, ns = (uint32_t)d.pool_ns;
+  const struct { void* base; uint32_t bytes; } rows[AUV_SNAP_SEGS] = {
+      {d.info64, 64}, {d.nav64, 64}, {d.step_info, 32}, {d.episode, 32}, {d.lidar_d, 8 * S}, {d.obs64, 8 * (6 + S)},
+      {d.mover, 32 * M}, {d.limits, 8 * K}, {d.nearby, K}, {ns ? d.sector_d : nullptr, 8 * ns}};
+  uint32_t off = AUV_SNAP_HEAD;
+  for (int i = 0; i < AUV_SNAP_SEGS; i++) {
+    a->seg[i].base = (char*)rows[i].base, a->seg[i].bytes = rows[i].bytes, a->seg[i].off = off;
+    if (i == 5) a->obs_off = off;
+    off += (rows[i].bytes + 15u) & ~15u;
+  }
+  a->row_bytes = off;
+  a->counters = d.counters, a->state = (unsigned long long*)d.state, a->reward64 = (unsigned long long*)d.reward64;
+  a->rew_path = (unsigned long long*)d.rew_path, a->rew_lidar = (unsigned long long*)d.rew_lidar;
+  a->world_idx = d.world_idx, a->collision = d.collision, a->skipped = h->snap_skipped;
+  a->n = d.n, a->n_worlds = d.n_worlds;
+}
+
+size_t auv_snapshot_row_bytes(const auv_handle_t* h) {
+  if (!h || !h->worlds_loaded) return 0;
+  AuvSnapArgs a;
+  snap_args(h, &a);
+  return a.row_bytes;
+}
+
+uint64_t auv_snapshot_layout(const auv_handle_t* h) {
+  if (!h || !h->worlds_loaded) return 0;
+  const AuvDev& d = h->d;
+  const uint64_t v[11] = {AUV_ABI_VERSION, AUV_SNAP_FORMAT, (uint64_t)d.cfg.n_sensors, (uint64_t)d.k_max, (uint64_t)d.m_max, (uint64_t)d.pool_ns,
+                          (uint64_t)d.cfg.obs_channels, (uint64_t)(d.cfg.use_lidar != 0), (uint64_t)d.n_worlds, (uint64_t)auv_snapshot_row_bytes(h), 0};
+  uint64_t x = 0xcbf29ce484222325ull;                    // FNV-1a over the bytes of the ten numbers
+  for (int i = 0; i < 10; i++)
+    for (int b = 0; b < 8; b++) x = (x ^ ((v[i] >> (8 * b)) & 0xff)) * 0x100000001b3ull;
+  return x ? x : 1;                                      // (0 is "no bank yet")
+}
+
+// what auv_snapshot and auv_restore refuse, before anything is enqueued
+static int snap_check(auv_handle_t* h, void* stream, float* obs, const char* who) {
+  REQUIRE_READY(h);
+  if (h->fw.on)
+    return fail(AUV_ESTATE, "%s: not with a fresh world per reset (a bank slot belongs to ONE environment and is rebuilt when that environment "
+                            "leaves it: a copy of the environment would share the slot)", who);
+  if (h->async_pending) return fail(AUV_ESTATE, "%s: a step_async is pending (auv_step_wait first)", who);
+  PAIR_CHECK_ON(h, stream, true, obs);
+  return AUV_OK;
+}
+
+int auv_snapshot(auv_handle_t* h, const int32_t* env_idx_dev, int32_t m, void* rows_dev, void* stream) {
+  int rc = snap_check(h, stream, nullptr, "auv_snapshot");
+  if (rc) return rc;
+  if (m < 0 || !rows_dev || ((uintptr_t)rows_dev & 15)) return fail(AUV_EINVAL, "auv_snapshot: m >= 0 and rows_dev 16-byte aligned");
+  if (!env_idx_dev && m > h->d.n) return fail(AUV_EINVAL, "auv_snapshot: %d rows of %d environments (env_idx_dev == NULL: row j is environment j)", m, h->d.n);
+  if (m == 0) return AUV_OK;
+  AuvSnapArgs a;
+  snap_args(h, &a);
+  auv_launch_snapshot(a, env_idx_dev, m, rows_dev, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+int auv_restore(auv_handle_t* h, uint64_t layout, const void* rows_dev, int32_t n_rows, const int32_t* row_idx_dev, const int32_t* env_idx_dev,
+                int32_t m, float* obs_dev, void* stream) {
+  int rc = snap_check(h, stream, obs_dev, "auv_restore");
+  if (rc) return rc;
+  if (layout != auv_snapshot_layout(h))
+    return fail(AUV_EINVAL, "auv_restore: layout %016llx is not this handle's (%016llx): the rows were taken from a handle of another shape",
+                (unsigned long long)layout, (unsigned long long)auv_snapshot_layout(h));
+  if (m < 0 || n_rows < 0 || !rows_dev || ((uintptr_t)rows_dev & 15)) return fail(AUV_EINVAL, "auv_restore: m, n_rows >= 0 and rows_dev 16-byte aligned");
+  if ((!row_idx_dev && m > n_rows) || (!env_idx_dev && m > h->d.n))
+    return fail(AUV_EINVAL, "auv_restore: %d pairs, %d rows, %d environments (a NULL index array stands for 0 .. m - 1)", m, n_rows, h->d.n);
+  const int D = auv_obs_cols(h->d.cfg, h->d.pool_ns);
+  if (obs_dev && ((uintptr_t)obs_dev & 3)) return fail(AUV_EINVAL, "auv_restore: obs_dev must be 4-byte aligned (rows of %d floats)", D);
+  if (m == 0) return AUV_OK;
+  AuvSnapArgs a;
+  snap_args(h, &a);
+  auv_launch_restore(a, h->d, rows_dev, n_rows, row_idx_dev, env_idx_dev, m, obs_dev, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+int auv_snapshot_skipped(auv_handle_t* h, int64_t* out_skipped, void* stream) {
+  REQUIRE_READY(h);
+  if (!out_skipped) return fail(AUV_EINVAL, "auv_snapshot_skipped: null output");
+  unsigned int v = 0;
+  HIP_TRY(hipMemcpyAsync(&v, h->snap_skipped, sizeof(v), hipMemcpyDeviceToHost, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  *out_skipped = (int64_t)v;
+  return AUV_OK;
+}
+
+int auv_plan_score(auv_handle_t* h, const float* reward_rec, const uint8_t* done_rec, int32_t n_steps, int32_t n, int32_t group, float gamma,
+                   float* score_dev, int32_t* best_dev, void* stream) {
+  if (!h) return fail(AUV_EINVAL, "null handle");
+  if (!reward_rec || !done_rec || !score_dev || !best_dev || n_steps < 1 || n < 1 || group < 1 || n % group)
+    return fail(AUV_EINVAL, "auv_plan_score: bad arguments (n_steps, n, group >= 1; n a multiple of group)");
+  HIP_TRY(hipSetDevice(h->device));
+  auv_launch_plan_score(reward_rec, done_rec, n_steps, n, group, gamma, score_dev, best_dev, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }

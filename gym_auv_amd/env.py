@@ -295,6 +295,32 @@ class AuvEnv:
                 "goal_distance": self.goal_distance, "progress": self.progress}
         return self._obs(), reward, bool(self._host[n + 23] != 0.0), info
 
+    _HOST_STATE = ("t_step", "cumulative_reward", "last_reward", "collision", "reached_goal", "progress", "_max_progress",
+                   "goal_distance")
+
+    def get_state(self) -> dict:
+        """Everything that makes this environment what it is inside the current episode: the device-side snapshot row
+        (BatchedAuvEnv.snapshot, moved to the host) and the adapter's own bookkeeping.  `set_state` puts it back -- to replay a
+        stretch, or to try an action and take it back.  Valid until the next reset() (which builds a new world)."""
+        if self._env is None:
+            raise RuntimeError("get_state() before reset()")
+        host = {k: getattr(self, k, None) for k in self._HOST_STATE}
+        return dict(episode=self.episode, snapshot=self._env.snapshot().cpu(), host=host, cte=list(self._cte),
+                    trajectory=[p.copy() for p in self._trajectory], done=float(self._host[self._n_obs64 + 23]))
+
+    def set_state(self, state: dict) -> np.ndarray:
+        """Back to a state of get_state() of the SAME episode; returns the observation of that state."""
+        if self._env is None or state["episode"] != self.episode:
+            raise ValueError("set_state(): the state belongs to another episode (every reset() builds a new world)")
+        self._env.restore(state["snapshot"])
+        self._env.done.fill_(int(state["done"]))
+        for k, v in state["host"].items():
+            setattr(self, k, v)
+        self._cte = list(state["cte"])
+        self._read_pack()
+        self._trajectory = [p.copy() for p in state["trajectory"]]
+        return self._obs()
+
     def render(self, mode="rgb_array", **kwargs):
         return None
 

@@ -587,6 +587,54 @@ int auv_policy_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds,
 int auv_gae(auv_handle_t* h, const float* R, const float* V, const float* Dn, const float* last_v, float gamma, float lam,
             float* adv_out, float* ret_out, int32_t T, int32_t N, void* stream);
 
+/* ---- snapshot / restore: copy environments out of a handle and back in, on the device ------------------------------------
+ * (The reference has no such call: its environment is a Python object, copied with copy.deepcopy.  Here an environment is rows of a
+ * dozen device buffers plus a binding to a world of the bank.)  A SNAPSHOT ROW is everything that makes environment e what it is
+ * between two calls, packed into auv_snapshot_row_bytes(h) bytes of caller-owned device memory.  Opaque to the caller; the layout,
+ * for the record (offsets in bytes; every part starts on a multiple of 16 and is padded with zero bytes to the next one):
+ *      0  counters      int32[4]   t_step, vessel step counter, episodes, pad            (AUV_FIELD_COUNTERS)
+ *     16  state         f64[6]     x, y, psi, u, v, r -- the environment's column of the [6][N] array
+ *     64  reward64, path-following term, LiDAR term of the reward   f64[3]
+ *     88  world index   int32;  92  collision  uint8;  93..95 zero
+ *     96  info64 f64[8] | nav64 f64[8] | step_info f64[4] | episode f64[4]
+ *    288  lidar_d f64[S] | obs64 f64[6 + S] | mover f64[Mmax][4] | cull limits int32[Kmax][2] | nearby uint8[Kmax] |
+ *         sector_d f64[n_sectors] (pooled observations only)
+ * i.e. every per-environment buffer a later step, or a later auv_read of any field, can observe.  NOT in a row: the hand-over records
+ * of the one-launch and multi-step shapes (their marks are down between launches), AUV_FIELD_BROKEN, the episode log, the position in
+ * the action ring, the diagnostic stamps, and anything per WORLD -- a row names its world by index only.
+ *   auv_snapshot   row j of rows_dev <- environment env_idx_dev[j]  (env_idx_dev == NULL: environment j, m <= N).  rows_dev: m rows,
+ *                  16-byte aligned.
+ *   auv_restore    environment env_idx_dev[j] <- row row_idx_dev[j] of the n_rows rows at rows_dev (either NULL: j), for j < m.  One row
+ *                  may feed many environments (a FORK); an environment named twice gets one of its rows, which one is not defined.  The
+ *                  environment's world descriptor is rebuilt from the row's world index and THIS handle's bank, so a row is valid in any
+ *                  handle with the same layout.  obs_dev (nullable): the caller's [N][obs_dim] float32 observation buffer; the rows of
+ *                  the restored environments are written exactly as the step that produced the snapshot state wrote them.
+ *   auv_snapshot_layout   fingerprint of the layout: a hash of AUV_ABI_VERSION, the snapshot format number, n_sensors, Kmax, Mmax,
+ *                  n_sectors, obs_channels, use_lidar, the number of worlds and the row size (0 before a bank is loaded).  auv_restore
+ *                  returns AUV_EINVAL for a `layout` that is not the handle's own: that check is what makes a restore memory-safe.
+ *                  Whether two banks with the same fingerprint hold the same WORLDS is the caller's promise.
+ * One launch each, stream-ordered, no allocation, no host synchronisation; one wave per row (csrc/k7_snapshot.hip).  A pair whose
+ * environment, row or world index is out of range is skipped -- never accessed -- and counted: auv_snapshot_skipped reads the count
+ * (since the bank was loaded; synchronises `stream`).  Refused before anything is enqueued: no bank (AUV_ESTATE); a fresh world per
+ * reset (AUV_ESTATE: a bank slot belongs to one environment there); a pending auv_step_async (AUV_ESTATE); a pending hand-over
+ * time-out is recovered from first and reported as by the step calls.  Ordering against step launches on OTHER streams is the
+ * caller's, as for auv_read / auv_write.  Eager only.                                                                        */
+size_t auv_snapshot_row_bytes(const auv_handle_t* h);
+uint64_t auv_snapshot_layout(const auv_handle_t* h);
+int auv_snapshot(auv_handle_t* h, const int32_t* env_idx_dev, int32_t m, void* rows_dev, void* stream);
+int auv_restore(auv_handle_t* h, uint64_t layout, const void* rows_dev, int32_t n_rows, const int32_t* row_idx_dev,
+                const int32_t* env_idx_dev, int32_t m, float* obs_dev, void* stream);
+int auv_snapshot_skipped(auv_handle_t* h, int64_t* out_skipped, void* stream);
+
+/* Scores of the candidate action sequences of a shooting planner (gym_auv_amd/planning.py), from the [n_steps][n] record of an
+ * auv_step_multi_record launch: score[e] = sum over t of disc_t * reward_rec[t][e], up to AND INCLUDING the first t with
+ * done_rec[t][e]; disc_0 = 1, disc_{t+1} = disc_t * gamma.  Every product and every sum is rounded to float32, in increasing t,
+ * without contraction: part of the contract, a plain float32 loop gives the same bits.  best[g], g < n / group: the index WITHIN
+ * group g (environments g * group .. (g + 1) * group - 1) of its largest score; the lowest index wins a tie, a NaN score never
+ * wins (all NaN: 0).  One launch on `stream`; n a multiple of group.                                                         */
+int auv_plan_score(auv_handle_t* h, const float* reward_rec, const uint8_t* done_rec, int32_t n_steps, int32_t n, int32_t group,
+                   float gamma, float* score_dev, int32_t* best_dev, void* stream);
+
 int32_t auv_abi_version(void);
 const char* auv_last_error(void);
 
