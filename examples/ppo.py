@@ -151,7 +151,7 @@ def average_gradients(params, world):
 def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print, worlds="fresh", regen=0, log_every=1,
           task="colav", step_mode=None, graph_rollout=False, sub_batches=4, minibatches=32,
           reward_scale=0.01, reward_clip=0.0, min_cumulative_reward=None, act_space="raw", ret_norm=False, orthogonal=False, ent_coef=0.01, log_std=-0.5, lr=2e-4,
-          fused_policy=True, graph_update=False, policy_bf16=False, feasibility_pooling=False):
+          fused_policy=True, graph_update=False, policy_bf16=False, feasibility_pooling=False, fused_update=False):
     from gym_auv_amd import distributed as D
     from gym_auv_amd.batched_env import BatchedAuvEnv
     from gym_auv_amd.config import effective_reference_config
@@ -276,6 +276,19 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
         env.episode_log()                                 # (drop what the warm-up steps logged)
     history = []
     n_total = envs * T
+    upd_fused = None
+    if fused_update:
+        # the minibatch step as a few HIP launches (gym_auv_amd/ppo_update.py, csrc/k8_ppo_update.hip): gather, forward, backward,
+        # loss, the two clips and Adam; the parameters become views of one flat vector, and every step also writes the weights
+        # into the fused policy's packed buffer (no refresh() between update and rollout)
+        from gym_auv_amd.ppo_update import FusedPPOUpdate
+        if policy_bf16:
+            raise ValueError("--fused-update repacks the exact f32 policy weights only: not with --policy-bf16")
+        upd_fused = FusedPPOUpdate(net, lr=lr, clip=clip, vf_coef=0.5, ent_coef=ent_coef, max_norm_pi=0.5, max_norm_v=0.5,
+                                   max_batch=-(-n_total // n_mb))
+        if fused is not None:
+            upd_fused.attach(fused)
+        graph_update = 0
     for upd in range(updates):
         if worlds == "generated" and regen > 0 and upd and upd % regen == 0:
             # fresh scenarios for every environment, built on the device; all envs restart
@@ -284,7 +297,8 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
         t0 = time.time()
         cur = torch.cuda.current_stream(device)
         if fused is not None:
-            fused.refresh()                               # (the update of the previous round moved the weights)
+            if upd_fused is None:
+                fused.refresh()                           # (the update of the previous round moved the weights)
             for i in range(K):
                 streams[i].wait_stream(cur)
             fused.begin_rollout()
@@ -394,6 +408,16 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
         mb_size = n_total // n_mb
         for _ in range(epochs):
             perm = torch.randperm(n_total, device=device)
+            if upd_fused is not None:
+                for mb in perm.chunk(n_mb):               # (a ragged last chunk included: B is a launch argument)
+                    if world > 1:                         # data parallel: ONE all-reduce of the flat gradient
+                        g, _ = upd_fused.grad(O, A, LP, ADV, RETn, mb)
+                        torch.distributed.all_reduce(g)
+                        g /= world
+                        upd_fused.apply(g)
+                    else:
+                        upd_fused.step(O, A, LP, ADV, RETn, mb)
+                continue
             for mb in perm.chunk(n_mb):
                 if not graph_update or mb.numel() != mb_size:      # (a ragged last chunk would RESIZE the static buffers)
                     loss = minibatch_step(O[mb], A[mb], LP[mb], ADV[mb], RETn[mb])
@@ -418,6 +442,17 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
                     torch.index_select(src, 0, mb, out=dst)
                 upd_graph.replay()
                 loss = upd_loss
+        if upd_fused is not None:
+            # the steps' own records (stats[8], the two norms), read once per update, in the columns of `diag`.  Column 6, the eager
+            # step's count of non-finite GRADIENT elements, stays 0: the fused step does not count them; a non-finite gradient
+            # shows as a non-finite norm in column 0 or 1, which `steps_bad` below looks at (as at a non-finite loss)
+            n_rec = epochs * n_mb
+            rec = upd_fused.log[torch.arange(upd_fused.n_steps - n_rec, upd_fused.n_steps, device=device) % upd_fused.LOG_ROWS]
+            row8 = torch.zeros((n_rec, 8), device=device)
+            row8[:, 0], row8[:, 1], row8[:, 2], row8[:, 3], row8[:, 4], row8[:, 5] = rec[:, 8], rec[:, 9], rec[:, 0], rec[:, 3], rec[:, 4], rec[:, 5]
+            diag.index_copy_(0, (diag_pos + torch.arange(n_rec, device=device)) % DIAG, row8)
+            diag_pos.add_(n_rec)
+            loss = rec[-1, 0]
         torch.cuda.synchronize()
         dt_all = time.time() - t0
         # ---- what happened: step rewards of the rollout, and the episodes that ended during it (library's episode log)
@@ -505,6 +540,9 @@ if __name__ == "__main__":
     ap.add_argument("--policy-bf16", type=int, default=0,
                     help="1: the fused policy launch multiplies with bf16 weights on the bf16 matrix cores (faster rollouts, ~1e-2 on the "
                          "action means: the PPO ratio then compares log-probabilities of slightly different policies); default 0 = exact f32")
+    ap.add_argument("--fused-update", type=int, default=0, choices=[0, 1],
+                    help="1: the minibatch step (gather, forward, backward, loss, clips, Adam) as a few HIP launches (gym_auv_amd/ppo_update.py); "
+                         "0 (default): eager torch")
     ap.add_argument("--fused-policy", type=int, default=1,
                     help="1 (default): the policy in the loop is ONE HIP launch per chain and step (gym_auv_amd/policy.py); 0: the torch modules")
     ap.add_argument("--step-mode", default=None, help="launch shape of a step (BatchedAuvEnv.STEP_MODES); default: the library's")
@@ -524,4 +562,4 @@ if __name__ == "__main__":
           task=a.task, step_mode=a.step_mode, graph_rollout=bool(a.graph_rollout), fused_policy=bool(a.fused_policy), graph_update=a.graph_update, policy_bf16=bool(a.policy_bf16),
           sub_batches=a.sub_batches, minibatches=a.minibatches, act_space=a.act_space, ret_norm=bool(a.ret_norm),
           orthogonal=bool(a.orthogonal), ent_coef=a.ent_coef, log_std=a.log_std, lr=a.lr, reward_clip=a.reward_clip,
-          min_cumulative_reward=a.min_cumulative_reward, feasibility_pooling=bool(a.feasibility_pooling))
+          min_cumulative_reward=a.min_cumulative_reward, feasibility_pooling=bool(a.feasibility_pooling), fused_update=bool(a.fused_update))

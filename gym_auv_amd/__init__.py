@@ -9,3 +9,11 @@ from .config import Config, EpisodeConfig, SimulationConfig, VesselConfig, effec
 from .worldspec import WorldSpec, MoverSpec  # noqa: F401
 
 __version__ = "0.1.0"
+
+
+def __getattr__(name):
+    # FusedPPOUpdate loads the HIP library: resolved on first use, so that importing the package still does not
+    if name == "FusedPPOUpdate":
+        from .ppo_update import FusedPPOUpdate
+        return FusedPPOUpdate
+    raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -143,6 +143,22 @@ class AuvPolicyIO(C.Structure):
     ]
 
 
+class AuvPpoBatch(C.Structure):
+    """== auv_ppo_batch_t (include/auv_hip.h): the rows of one PPO minibatch step"""
+    _fields_ = [
+        ("O", C.c_void_p), ("A", C.c_void_p), ("LP", C.c_void_p), ("ADV", C.c_void_p), ("RET", C.c_void_p), ("idx", C.c_void_p),
+        ("B", C.c_int32), ("n_rows", C.c_int32), ("clip", C.c_float), ("vf_coef", C.c_float), ("ent_coef", C.c_float),
+    ]
+
+
+class AuvPpoAdam(C.Structure):
+    """== auv_ppo_adam_t: Adam's hyper-parameters and the bias corrections of this step"""
+    _fields_ = [
+        ("lr", C.c_double), ("beta1", C.c_double), ("beta2", C.c_double), ("eps", C.c_double),
+        ("bc1", C.c_double), ("bc2", C.c_double), ("max_norm_pi", C.c_float), ("max_norm_v", C.c_float),
+    ]
+
+
 _lib = None
 
 
@@ -222,6 +238,13 @@ def load_library(path: str = None) -> C.CDLL:
         "auv_restore": (C.c_int, [vp, C.c_uint64, vp, i32, vp, vp, i32, vp, vp]),
         "auv_snapshot_skipped": (C.c_int, [vp, C.POINTER(C.c_int64), vp]),
         "auv_plan_score": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp]),
+        "auv_ppo_param_floats": (sz, [i32]),
+        "auv_ppo_create": (C.c_int, [i32, i32, i32, C.POINTER(vp)]),
+        "auv_ppo_destroy": (None, [vp]),
+        "auv_ppo_load": (C.c_int, [vp, vp, vp]),
+        "auv_ppo_attach_policy": (C.c_int, [vp, vp]),
+        "auv_ppo_grad": (C.c_int, [vp, C.POINTER(AuvPpoBatch), vp, vp, vp]),
+        "auv_ppo_adam": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(AuvPpoAdam), vp, vp]),
         "auv_abi_version": (i32, []),
         "auv_last_error": (C.c_char_p, []),
     }
@@ -248,6 +271,7 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_generate_worlds", "auv_bank_bytes", "auv_read_bank",
                     "auv_fresh_worlds_create", "auv_fresh_worlds_refill", "auv_fresh_worlds_stats", "auv_fresh_worlds_draws", "auv_fresh_worlds_set_stream",
                     "auv_snapshot_row_bytes", "auv_snapshot_layout", "auv_snapshot", "auv_restore", "auv_snapshot_skipped", "auv_plan_score",
+                    "auv_ppo_param_floats", "auv_ppo_create", "auv_ppo_destroy", "auv_ppo_load", "auv_ppo_attach_policy", "auv_ppo_grad", "auv_ppo_adam",
                     "auv_abi_version", "auv_last_error"]
 
 # tables of a generated bank (auv_read_bank): id, dtype, trailing shape ('P' = AUV_GEN_POLY_CAP,

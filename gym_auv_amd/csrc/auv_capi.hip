@@ -15,6 +15,7 @@
 #include "auv_generate.h"
 #include "auv_multi_geom.h"
 #include "auv_snapshot.h"
+#include "auv_ppo.h"
 
 void auv_launch_k1(const AuvDev& d, const void* actions, int dtype, hipStream_t st, hipEvent_t ev0 = nullptr,
                    hipEvent_t ev1 = nullptr);
@@ -2093,6 +2094,111 @@ int auv_step_timed(auv_handle_t* h, const void* actions_dev, int32_t action_dtyp
   out_ms4[1] = out_ms4[2] = 0.0f;
   for (int i = 0; i < nk; i++) HIP_TRY(hipEventElapsedTime(&out_ms4[i], h->ev[2 * i], h->ev[2 * i + 1]));
   HIP_TRY(hipEventElapsedTime(&out_ms4[3], h->ev[0], h->ev[2 * nk - 1]));   // whole step, first start to last stop
+  return AUV_OK;
+}
+
+// ---- the PPO update (include/auv_hip.h, auv_ppo_*; kernels: k8_ppo_update.hip) ----
+struct auv_ppo {
+  AuvPpoDev d;
+  int device;
+  float* arena;
+};
+
+size_t auv_ppo_param_floats(int32_t obs_dim) { return obs_dim > 0 ? auv_ppo_param_floats_impl(obs_dim) : 0; }
+
+int auv_ppo_create(int32_t device, int32_t obs_dim, int32_t max_batch, auv_ppo_t** out) {
+  if (!out) return fail(AUV_EINVAL, "auv_ppo_create: null out");
+  *out = nullptr;
+  if (obs_dim < 1) return fail(AUV_EINVAL, "auv_ppo_create: obs_dim %d < 1", obs_dim);
+  if (obs_dim > 16384 || auv_ppo_lds_bytes(obs_dim) > 160 * 1024)
+    return fail(AUV_EINVAL, "auv_ppo_create: obs_dim %d is too wide for the row pass' LDS tile", obs_dim);
+  if (max_batch < 1 || max_batch > (1 << 24)) return fail(AUV_EINVAL, "auv_ppo_create: max_batch %d outside [1, 2^24]", max_batch);
+  if (device < 0) return fail(AUV_EINVAL, "auv_ppo_create: device %d", device);
+  int ndev = 0;
+  HIP_TRY(hipGetDeviceCount(&ndev));
+  if (device >= ndev) return fail(AUV_EINVAL, "auv_ppo_create: device %d not present (%d visible)", device, ndev);
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(auv_ppo_prepare(obs_dim));
+  auv_ppo* p = new auv_ppo();
+  p->device = device;
+  AuvPpoDev& d = p->d;
+  d.obs_dim = obs_dim, d.k0p = (obs_dim + 31) & ~31, d.max_batch = max_batch, d.rt_max = (max_batch + 15) / 16;
+  const size_t rows = (size_t)d.rt_max * 16, fwd = auv_ppo_fwd_floats(obs_dim), tr = auv_ppo_tr_floats();
+  // one allocation, carved into parts of a multiple of four floats each (16-byte aligned)
+  const size_t n_part = (size_t)AUV_PPO_MAX_SPLIT * (fwd - 4);
+  size_t total = fwd + tr + 256 + rows * d.k0p + 2 * rows * (2 * (256 + 128 + 64) + 16) + n_part + (size_t)d.rt_max * 8 + 4 * AUV_PPO_NORM_BLOCKS;
+  hipError_t e = hipMalloc((void**)&p->arena, total * sizeof(float));
+  if (e != hipSuccess) {
+    delete p;
+    return fail(AUV_ENOMEM, "auv_ppo_create: %zu bytes of scratch for batches of %d rows: %s", total * sizeof(float), max_batch, hipGetErrorString(e));
+  }
+  float* q = p->arena;
+  auto take = [&q](size_t n) { float* r = q; q += n; return r; };
+  d.fwd = take(fwd), d.tr = take(tr), d.zero = take(256);
+  d.sqpart = (double*)take(4 * AUV_PPO_NORM_BLOCKS);
+  d.X = take(rows * d.k0p);
+  for (int net = 0; net < 2; net++) {
+    d.Y[net][0] = take(rows * 256), d.Y[net][1] = take(rows * 128), d.Y[net][2] = take(rows * 64);
+    d.dZ[net][0] = take(rows * 256), d.dZ[net][1] = take(rows * 128), d.dZ[net][2] = take(rows * 64), d.dZ[net][3] = take(rows * 16);
+  }
+  d.part = take(n_part), d.tstat = take((size_t)d.rt_max * 8);
+  d.pol = nullptr;
+  e = hipMemset(p->arena, 0, total * sizeof(float));
+  if (e == hipSuccess) e = hipDeviceSynchronize();
+  if (e != hipSuccess) {
+    (void)hipFree(p->arena);
+    delete p;
+    return fail(AUV_EHIP, "auv_ppo_create: %s", hipGetErrorString(e));
+  }
+  *out = p;
+  return AUV_OK;
+}
+
+void auv_ppo_destroy(auv_ppo_t* p) {
+  if (!p) return;
+  (void)hipSetDevice(p->device);
+  (void)hipDeviceSynchronize();
+  (void)hipFree(p->arena);
+  delete p;
+}
+
+int auv_ppo_load(auv_ppo_t* p, const float* theta, void* stream) {
+  if (!p || !theta) return fail(AUV_EINVAL, "auv_ppo_load: null %s", !p ? "updater" : "theta");
+  HIP_TRY(hipSetDevice(p->device));
+  auv_launch_ppo_load(p->d, theta, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+int auv_ppo_attach_policy(auv_ppo_t* p, float* policy_params) {
+  if (!p) return fail(AUV_EINVAL, "auv_ppo_attach_policy: null updater");
+  if ((uintptr_t)policy_params & 15) return fail(AUV_EINVAL, "auv_ppo_attach_policy: policy_params must be 16-byte aligned");
+  p->d.pol = policy_params;
+  return AUV_OK;
+}
+
+int auv_ppo_grad(auv_ppo_t* p, const auv_ppo_batch_t* b, float* grad, float* stats, void* stream) {
+  if (!p || !b || !grad || !stats) return fail(AUV_EINVAL, "auv_ppo_grad: null argument");
+  if (!b->O || !b->A || !b->LP || !b->ADV || !b->RET) return fail(AUV_EINVAL, "auv_ppo_grad: null batch buffer");
+  if (b->B < 1 || b->B > p->d.max_batch) return fail(AUV_EINVAL, "auv_ppo_grad: B = %d outside [1, max_batch = %d]", b->B, p->d.max_batch);
+  if (b->n_rows < 1 || (!b->idx && b->B > b->n_rows)) return fail(AUV_EINVAL, "auv_ppo_grad: B = %d rows of n_rows = %d", b->B, b->n_rows);
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(auv_ppo_prepare(p->d.obs_dim));
+  auv_launch_ppo_grad(p->d, *b, grad, stats, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+int auv_ppo_adam(auv_ppo_t* p, float* theta, float* m, float* v, const float* grad, const auv_ppo_adam_t* a, float* norms_out, void* stream) {
+  if (!p || !theta || !m || !v || !grad || !a || !norms_out) return fail(AUV_EINVAL, "auv_ppo_adam: null argument");
+  if (!(a->bc1 > 0.0) || !(a->bc2 > 0.0)) return fail(AUV_EINVAL, "auv_ppo_adam: bias corrections must be > 0 (step >= 1)");
+  AuvPpoAdamDev h;
+  h.w1 = (float)(1.0 - a->beta1), h.b2 = (float)a->beta2, h.w2 = (float)(1.0 - a->beta2);
+  h.step_size = (float)(a->lr / a->bc1), h.bc2_sqrt = (float)std::sqrt(a->bc2), h.eps = (float)a->eps;
+  h.max_norm_pi = a->max_norm_pi, h.max_norm_v = a->max_norm_v;
+  HIP_TRY(hipSetDevice(p->device));
+  auv_launch_ppo_adam(p->d, theta, m, v, grad, h, norms_out, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
   return AUV_OK;
 }
 

@@ -1,0 +1,43 @@
+// The PPO update object behind auv_ppo_* (include/auv_hip.h): what auv_capi.hip allocates and k8_ppo_update.hip launches on.
+#ifndef AUV_PPO_H
+#define AUV_PPO_H
+#include <hip/hip_runtime.h>
+#include <stdint.h>
+
+#include "../../include/auv_hip.h"
+
+#define AUV_PPO_MAX_SPLIT 16       // split-K factor of the weight-gradient pass (workgroups per output unit), at most
+#define AUV_PPO_NORM_BLOCKS 64     // partial sums of squares per gradient-norm launch
+
+// Device memory of one updater.  Every matrix of the row pass' scratch is stored in 16 x 16 blocks [row tile][column tile][256]:
+// element (r, c) of a block at ((r / 4) * 16 + c) * 4 + r % 4 -- the float4 a lane of the weight-gradient pass loads, and the
+// four registers a lane of an MFMA result holds.
+struct AuvPpoDev {
+  int32_t obs_dim, k0p, max_batch, rt_max;
+  float* fwd;          // forward copy: the layout of auv_policy_io::params (two nets, log_std[2], two floats of padding)
+  float* tr;           // transposed copy, per net: W2^T [256][128] | W3^T [128][64] | W4^T [64][32], fragment order
+  float* zero;         // [256] zeros: the "bias" of a backward layer
+  float* X;            // [rt][k0p / 16][256]   the gathered, zero-padded observations (written by the policy net's workgroups)
+  float* Y[2][3];      // per net: Y1 [rt][16][256], Y2 [rt][8][256], Y3 [rt][4][256]
+  float* dZ[2][4];     // per net: dZ1 [rt][16][256], dZ2 [rt][8][256], dZ3 [rt][4][256], dZ4 [rt][1][256]
+  float* part;         // [AUV_PPO_MAX_SPLIT][2][net floats]: split-K partials of dW (row-major, padded like the forward copy) and db
+  float* tstat;        // [rt][8]: per row tile sum pg, sum vf, max |adv|, max ratio, non-finite inputs, clipped rows, d log_std[2]
+  double* sqpart;      // [AUV_PPO_NORM_BLOCKS][2]: partial sums of squares of the policy and the value group
+  float* pol;          // attached auv_policy_io::params buffer (nullable)
+};
+
+struct AuvPpoAdamDev {
+  float w1, b2, w2;    // 1 - beta1, beta2, 1 - beta2: each rounded once from double
+  float step_size, bc2_sqrt, eps, max_norm_pi, max_norm_v;
+};
+
+size_t auv_ppo_param_floats_impl(int obs_dim);
+size_t auv_ppo_fwd_floats(int obs_dim);
+size_t auv_ppo_tr_floats();
+size_t auv_ppo_lds_bytes(int obs_dim);
+hipError_t auv_ppo_prepare(int obs_dim);
+void auv_launch_ppo_load(const AuvPpoDev& d, const float* theta, hipStream_t st);
+void auv_launch_ppo_grad(const AuvPpoDev& d, const auv_ppo_batch_t& b, float* grad, float* stats, hipStream_t st);
+void auv_launch_ppo_adam(const AuvPpoDev& d, float* theta, float* m, float* v, const float* grad, const AuvPpoAdamDev& a, float* norms_out,
+                         hipStream_t st);
+#endif /* AUV_PPO_H */

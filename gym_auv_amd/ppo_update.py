@@ -1,0 +1,157 @@
+"""FusedPPOUpdate -- one PPO minibatch step of examples/ppo.py as a few HIP launches (csrc/k8_ppo_update.hip, auv_ppo_*).
+
+The reference trains PPO2 with `MlpPolicy`, net_arch [256, 128, 64] for policy and value function, tanh, a diagonal Gaussian with a
+free log_std (the reference's scripts/run.py:332-357).  `minibatch_step` of examples/ppo.py evaluates that update with stock tensor
+operations: two MLPs forward and backward, the loss, two global-norm clips, a diagnostics row and Adam -- more than a hundred small
+launches behind five gathers.  This class runs the same arithmetic as five launches: the row pass (gather, forward, backward through
+the activations), the weight-gradient pass, the fixed-order reduction, the norm and clip + Adam, which also scatters every updated
+weight into the packed buffer of an attached FusedActorCritic (so `refresh()` is not needed between update and rollout).
+
+    upd = FusedPPOUpdate(net, lr=2e-4, clip=0.2, vf_coef=0.5, ent_coef=0.01, max_batch=16384)
+    upd.attach(fused)                              # optional: the rollout policy's packed weights follow every step
+    stats = upd.step(O, A, LP, ADV, RET, idx)      # [10]: loss, pg, vf, max |adv|, max ratio, non-finite inputs, clipped fraction, 0,
+                                                   #       |g_pi|, |g_v| before clipping -- a device tensor, nothing synchronises
+    g, stats = upd.grad(O, A, LP, ADV, RET, idx)   # or in two halves, e.g. around an all-reduce of g
+    upd.apply(g)
+
+The module's parameters become views of ONE flat tensor (`upd.theta`, torch layout: pi W1 b1 .. W4 b4, v W1 .. b4, log_std); the torch
+modules stay usable and stay the owners -- `net.v(obs)` sees every step.  Deterministic: the same inputs give the same bits.
+"""
+import ctypes as C
+from typing import Optional, Tuple
+
+import torch
+import torch.nn as nn
+
+from . import _capi
+
+HIDDEN = (256, 128, 64)
+_LIB = _capi.load_library()
+
+
+def _check(rc: int, what: str):
+    if rc != 0:
+        raise RuntimeError("%s failed (%d): %s" % (what, rc, _LIB.auv_last_error().decode()))
+
+
+class FusedPPOUpdate:
+    LOG_ROWS = 8192
+
+    def __init__(self, net: nn.Module, lr: float = 2e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, clip: float = 0.2,
+                 vf_coef: float = 0.5, ent_coef: float = 0.01, max_norm_pi: float = 0.5, max_norm_v: float = 0.5, max_batch: int = 16384):
+        tensors = []
+        for seq, out in ((net.pi, 2), (net.v, 1)):
+            lin = [m for m in seq if isinstance(m, nn.Linear)]
+            act = [m for m in seq if not isinstance(m, nn.Linear)]
+            dims = tuple(l.out_features for l in lin[:-1])
+            if (dims != HIDDEN or lin[-1].out_features != out or lin[0].in_features != net.pi[0].in_features
+                    or not all(isinstance(a, nn.Tanh) for a in act) or any(l.bias is None for l in lin)):
+                raise ValueError("FusedPPOUpdate trains the reference's architecture: obs -> %s tanh -> %d (scripts/run.py:332-357); "
+                                 "got %s -> %d" % (list(HIDDEN), out, list(dims), lin[-1].out_features))
+            for l in lin:
+                tensors += [l.weight, l.bias]
+        if tuple(net.log_std.shape) != (2,):
+            raise ValueError("FusedPPOUpdate: log_std must have two elements")
+        tensors.append(net.log_std)
+        self.net, self.obs_dim = net, int(net.pi[0].in_features)
+        self.device = tensors[0].device
+        if self.device.type != "cuda" or any(t.device != self.device or t.dtype != torch.float32 for t in tensors):
+            raise ValueError("FusedPPOUpdate: the module must hold float32 parameters on one GPU")
+        n = int(_LIB.auv_ppo_param_floats(self.obs_dim))
+        assert n == sum(t.numel() for t in tensors)
+        # ONE flat tensor; every parameter becomes a view of it (the modules stay the owners of the weights)
+        self.theta = torch.empty(n, dtype=torch.float32, device=self.device)
+        off = 0
+        with torch.no_grad():
+            for t in tensors:
+                view = self.theta[off:off + t.numel()].view_as(t)
+                view.copy_(t)
+                t.data = view
+                off += t.numel()
+        self.m, self.v = torch.zeros_like(self.theta), torch.zeros_like(self.theta)
+        self.g = torch.zeros_like(self.theta)
+        self.t = 0                                                  # Adam's step count
+        self.lr, self.betas, self.eps = float(lr), (float(betas[0]), float(betas[1])), float(eps)
+        self.clip, self.vf_coef, self.ent_coef = float(clip), float(vf_coef), float(ent_coef)
+        self.max_norm_pi, self.max_norm_v = float(max_norm_pi), float(max_norm_v)
+        self.max_batch = int(max_batch)
+        # the record of every step, written by the launches themselves: row = stats[8] + the two norms; read it once per update
+        self.log = torch.zeros((self.LOG_ROWS, 10), dtype=torch.float32, device=self.device)
+        self.n_steps = 0
+        self._fused = None
+        h = C.c_void_p()
+        _check(_LIB.auv_ppo_create(self.device.index or 0, self.obs_dim, self.max_batch, C.byref(h)), "auv_ppo_create")
+        self._h = h
+        self.load()
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h:
+            _LIB.auv_ppo_destroy(h)
+
+    def _stream(self):
+        return C.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def load(self):
+        """Pack the kernels' copies of the weights (and the attached policy buffer) from `theta`: after construction, and after
+        anything else has written the parameters (a broadcast, a checkpoint)."""
+        _check(_LIB.auv_ppo_load(self._h, C.c_void_p(self.theta.data_ptr()), self._stream()), "auv_ppo_load")
+
+    def attach(self, fused=None):
+        """Hand the packed weight buffer of a FusedActorCritic (exact f32 path) to the updater: every step then writes the updated
+        weights there too, in the policy launch's layout.  None detaches."""
+        if fused is None:
+            _check(_LIB.auv_ppo_attach_policy(self._h, None), "auv_ppo_attach_policy")
+            self._fused = None
+            return
+        if fused.bf16:
+            raise ValueError("FusedPPOUpdate.attach: the bf16 policy keeps a second copy of the weights that only refresh() packs")
+        if fused.env.obs_dim != self.obs_dim or fused.params.device != self.device:
+            raise ValueError("FusedPPOUpdate.attach: the policy has another observation width or device")
+        _check(_LIB.auv_ppo_attach_policy(self._h, C.c_void_p(fused.params.data_ptr())), "auv_ppo_attach_policy")
+        self._fused = fused                                         # (keeps the buffer alive)
+        self.load()
+
+    def _row(self):
+        return self.log[self.n_steps % self.LOG_ROWS]
+
+    def grad(self, O, A, LP, ADV, RET, idx: Optional[torch.Tensor] = None, B: Optional[int] = None):
+        """The flat gradient of minibatch_step's loss over rows `idx` (int64; None: rows 0 .. B - 1, B default: all rows) of the stored
+        transitions, and the statistics row.  Returns (grad, stats): the updater's own buffers, overwritten by the next call."""
+        n_rows = int(O.shape[0])
+        for x, shape in ((O, (n_rows, self.obs_dim)), (A, (n_rows, 2)), (LP, (n_rows,)), (ADV, (n_rows,)), (RET, (n_rows,))):
+            if tuple(x.shape) != shape or x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device:
+                raise ValueError("FusedPPOUpdate: expected a contiguous float32 tensor of shape %s on %s, got %s %s"
+                                 % (shape, self.device, tuple(x.shape), x.dtype))
+        if idx is not None:
+            if idx.dtype != torch.int64 or idx.dim() != 1 or not idx.is_contiguous() or idx.device != self.device:
+                raise ValueError("FusedPPOUpdate: idx must be a contiguous int64 vector on %s" % self.device)
+            B = int(idx.numel())
+        elif B is None:
+            B = n_rows
+        b = _capi.AuvPpoBatch(O.data_ptr(), A.data_ptr(), LP.data_ptr(), ADV.data_ptr(), RET.data_ptr(),
+                              idx.data_ptr() if idx is not None else None, int(B), n_rows, self.clip, self.vf_coef, self.ent_coef)
+        row = self._row()
+        _check(_LIB.auv_ppo_grad(self._h, C.byref(b), C.c_void_p(self.g.data_ptr()), C.c_void_p(row.data_ptr()), self._stream()), "auv_ppo_grad")
+        return self.g, row[:8]
+
+    def apply(self, grad: Optional[torch.Tensor] = None):
+        """Clip per group, one Adam step, and the repack of every weight.  Returns the two norms before clipping ([2], device)."""
+        g = self.g if grad is None else grad
+        if g.numel() != self.theta.numel() or g.dtype != torch.float32 or not g.is_contiguous() or g.device != self.device:
+            raise ValueError("FusedPPOUpdate.apply: the gradient must be a contiguous float32 vector of %d elements" % self.theta.numel())
+        self.t += 1
+        b1, b2 = self.betas
+        a = _capi.AuvPpoAdam(self.lr, b1, b2, self.eps, 1.0 - b1 ** self.t, 1.0 - b2 ** self.t, self.max_norm_pi, self.max_norm_v)
+        row = self._row()
+        _check(_LIB.auv_ppo_adam(self._h, C.c_void_p(self.theta.data_ptr()), C.c_void_p(self.m.data_ptr()), C.c_void_p(self.v.data_ptr()),
+                                 C.c_void_p(g.data_ptr()), C.byref(a), C.c_void_p(row[8:].data_ptr()), self._stream()), "auv_ppo_adam")
+        self.n_steps += 1
+        return row[8:]
+
+    def step(self, O, A, LP, ADV, RET, idx: Optional[torch.Tensor] = None):
+        """grad then apply on the current stream.  Returns the step's record [10] (see the module's docstring)."""
+        row = self._row()
+        self.grad(O, A, LP, ADV, RET, idx)
+        self.apply()
+        return row

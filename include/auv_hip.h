@@ -635,6 +635,54 @@ int auv_snapshot_skipped(auv_handle_t* h, int64_t* out_skipped, void* stream);
 int auv_plan_score(auv_handle_t* h, const float* reward_rec, const uint8_t* done_rec, int32_t n_steps, int32_t n, int32_t group,
                    float gamma, float* score_dev, int32_t* best_dev, void* stream);
 
+/* ---- the PPO update (scripts/run.py:332-357: PPO2 with MlpPolicy, net_arch [256, 128, 64] for policy and value
+ * function, tanh, a diagonal Gaussian with a free log_std[2]): one minibatch step of examples/ppo.py (minibatch_step) as a few
+ * launches -- forward and backward of both nets on the matrix cores in exact f32, the clipped-surrogate / value / entropy loss, the
+ * two global-norm clips and Adam (csrc/k8_ppo_update.hip).  The updater is an object of its own: it needs no environment handle.
+ *   auv_ppo_param_floats   length of the flat parameter / gradient / moment vectors, in TORCH layout: the policy net's W1 [256][D] b1
+ *                    [256] W2 [128][256] b2 W3 [64][128] b3 W4 [2][64] b4 [2], the value net's W1 .. W4 [1][64] b4 [1], log_std[2].
+ *   auv_ppo_create   allocates the packed weight copies and the scratch of batches up to max_batch rows (about 8.5 KB per row at
+ *                    obs_dim 186).  AUV_EINVAL for obs_dim < 1 or an observation too wide for the row pass' LDS tile.
+ *   auv_ppo_load     packs the forward (the layout of auv_policy_io::params) and the transposed fragment-order copy from theta, and the
+ *                    attached policy buffer: after initialisation, and after any change of theta made elsewhere.
+ *   auv_ppo_attach_policy   policy_params: a buffer of auv_policy_param_floats(obs_dim) floats, 16-byte aligned, whose padding is zero
+ *                    (NULL: detach).  auv_ppo_load and every auv_ppo_adam then write each weight into it as well: what
+ *                    FusedActorCritic.refresh() does with a permuted copy per layer.
+ *   auv_ppo_grad     grad (flat layout) <- d loss / d theta over the B rows idx[0 .. B) of the n_rows stored transitions.  An index
+ *                    outside [0, n_rows) is the caller's error: it is not checked.  stats[8]: loss, pg, vf, max |adv|, max ratio, the
+ *                    number of non-finite inputs among the gathered rows, the fraction of rows on the clipped branch, 0.
+ *   auv_ppo_adam     coef = min(1, max_norm / (norm + 1e-6)) per group (policy net + log_std | value net; norms_out[2]: the norms before
+ *                    clipping), then Adam as torch.optim.Adam formulates it (amsgrad off, no weight decay) on theta, m, v, and the
+ *                    scatter of every updated weight into the packed copies and the attached buffer.  `grad` is not modified.
+ * grad and adam are separate so that data-parallel training can all-reduce the flat gradient in between.  Deterministic: no
+ * floating-point atomics, every reduction in an order fixed by B; two calls on the same inputs give the same bits.  Everything is
+ * enqueued on `stream`, nothing synchronises; all pointers except the two structs are device pointers.                      */
+typedef struct auv_ppo auv_ppo_t;
+typedef struct auv_ppo_batch {
+  const float* O;            /* [n_rows][obs_dim]                                                            */
+  const float* A;            /* [n_rows][2]                                                                  */
+  const float* LP;           /* [n_rows]  log-probability under the policy that collected the rows           */
+  const float* ADV;          /* [n_rows]  (normalised) advantages                                            */
+  const float* RET;          /* [n_rows]  value targets                                                      */
+  const int64_t* idx;        /* [B] rows of the minibatch; NULL: rows 0 .. B - 1                             */
+  int32_t B, n_rows;
+  float clip, vf_coef, ent_coef;
+} auv_ppo_batch_t;
+typedef struct auv_ppo_adam {
+  double lr, beta1, beta2, eps;      /* double: 1 - beta2 is rounded to float once, from here, as torch rounds it */
+  double bc1, bc2;                   /* 1 - beta1^t, 1 - beta2^t of this step t >= 1, computed on the host; double for the same
+                                        reason: lr / bc1 and sqrt(bc2) reach the kernel as the floats torch.optim.Adam uses      */
+  float max_norm_pi, max_norm_v;     /* <= 0: no clipping                                                     */
+} auv_ppo_adam_t;
+size_t auv_ppo_param_floats(int32_t obs_dim);
+int auv_ppo_create(int32_t device, int32_t obs_dim, int32_t max_batch, auv_ppo_t** out);
+void auv_ppo_destroy(auv_ppo_t* p);
+int auv_ppo_load(auv_ppo_t* p, const float* theta, void* stream);
+int auv_ppo_attach_policy(auv_ppo_t* p, float* policy_params);
+int auv_ppo_grad(auv_ppo_t* p, const auv_ppo_batch_t* batch, float* grad, float* stats, void* stream);
+int auv_ppo_adam(auv_ppo_t* p, float* theta, float* m, float* v, const float* grad, const auv_ppo_adam_t* adam, float* norms_out,
+                 void* stream);
+
 int32_t auv_abi_version(void);
 const char* auv_last_error(void);
 
