@@ -7,6 +7,7 @@ episode ends.  Prints the return of every vessel and the plans per second.
 
     python examples/mpc.py --scenario TestScenario1 --vessels 4 --candidates 64 --horizon 16
     python examples/mpc.py --scenario moving --vessels 16 --iterations 3          # CEM
+    python examples/mpc.py --value policy.pt --value-scale 100 --prior policy.pt  # a learned critic beyond the horizon, the actor as the mean
 """
 import argparse
 import os
@@ -16,6 +17,7 @@ import time
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
 from gym_auv_amd import scenarios  # noqa: E402
 from gym_auv_amd.batched_env import BatchedAuvEnv  # noqa: E402
 from gym_auv_amd.config import effective_reference_config  # noqa: E402
@@ -36,6 +38,13 @@ def main():
     ap.add_argument("--gamma", type=float, default=0.99)
     ap.add_argument("--max-steps", type=int, default=400)
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--value", default=None, metavar="CKPT",
+                    help="state_dict of examples/ppo.py's ActorCritic: its critic is the terminal value beyond the horizon (one fused launch per plan)")
+    ap.add_argument("--value-scale", type=float, default=100.0, help="terminal = value * scale + shift (the critic lives in scaled-reward "
+                                                                      "units: 1 / reward_scale of the training run)")
+    ap.add_argument("--value-shift", type=float, default=0.0)
+    ap.add_argument("--prior", default=None, metavar="CKPT", help="state_dict of an ActorCritic: its deterministic action, held over the horizon, is "
+                                                                  "the mean the candidates are drawn around")
     args = ap.parse_args()
     cfg = effective_reference_config(use_lidar=True)
     B = args.vessels
@@ -46,7 +55,16 @@ def main():
     bank = pack_bank([build_world(w) for w in worlds])
     env = BatchedAuvEnv(cfg, bank, B, auto_reset=False, test_mode=True)
     env.reset()
-    planner = ShootingPlanner(env, candidates=args.candidates, horizon=args.horizon, gamma=args.gamma, iterations=args.iterations, seed=args.seed)
+    nets = {}
+
+    def fused_of(ckpt):
+        if ckpt and ckpt not in nets:
+            from evaluate import load_policy
+            from gym_auv_amd.policy import FusedActorCritic
+            nets[ckpt] = FusedActorCritic(load_policy(ckpt, env.obs_dim, env.device), env, rollout=1)
+        return nets.get(ckpt)
+    planner = ShootingPlanner(env, candidates=args.candidates, horizon=args.horizon, gamma=args.gamma, iterations=args.iterations, seed=args.seed,
+                              value=fused_of(args.value), value_scale=args.value_scale, value_shift=args.value_shift, prior=fused_of(args.prior))
     ret = torch.zeros(B, dtype=torch.float64, device=env.device)
     running = torch.ones(B, dtype=torch.bool, device=env.device)
     torch.cuda.synchronize()

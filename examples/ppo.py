@@ -151,7 +151,8 @@ def average_gradients(params, world):
 def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print, worlds="fresh", regen=0, log_every=1,
           task="colav", step_mode=None, graph_rollout=False, sub_batches=4, minibatches=32,
           reward_scale=0.01, reward_clip=0.0, min_cumulative_reward=None, act_space="raw", ret_norm=False, orthogonal=False, ent_coef=0.01, log_std=-0.5, lr=2e-4,
-          fused_policy=True, graph_update=False, policy_bf16=False, feasibility_pooling=False, fused_update=False):
+          fused_policy=True, graph_update=False, policy_bf16=False, feasibility_pooling=False, fused_update=False,
+          fused_bootstrap=False):
     from gym_auv_amd import distributed as D
     from gym_auv_amd.batched_env import BatchedAuvEnv
     from gym_auv_amd.config import effective_reference_config
@@ -335,7 +336,11 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
                 V = torch.cat([b["V"] for b in buf], 1) * ret_std + ret_mean        # value head predicts normalised returns
                 R = torch.cat([b["R"] for b in buf], 1)
                 Dn = torch.cat([b["Dn"] for b in buf], 1)
-            last_v = net.v(env.obs).squeeze(-1) * ret_std + ret_mean
+            if fused_bootstrap and fused is not None:
+                # the bootstrap value through the fused critic (one launch, FusedActorCritic.value): the weights the rollout used
+                last_v = fused.value() * ret_std + ret_mean
+            else:
+                last_v = net.v(env.obs).squeeze(-1) * ret_std + ret_mean
             if fused is not None:
                 adv, RET = fused.gae(V, last_v, gamma, lam)            # one launch (auv_gae) instead of T x 6 small ones
             else:
@@ -545,6 +550,9 @@ if __name__ == "__main__":
                          "0 (default): eager torch")
     ap.add_argument("--fused-policy", type=int, default=1,
                     help="1 (default): the policy in the loop is ONE HIP launch per chain and step (gym_auv_amd/policy.py); 0: the torch modules")
+    ap.add_argument("--fused-bootstrap", type=int, default=0, choices=[0, 1],
+                    help="1: the GAE bootstrap value of the last observation comes from the fused critic (FusedActorCritic.value, one launch); "
+                         "0 (default): the torch module")
     ap.add_argument("--step-mode", default=None, help="launch shape of a step (BatchedAuvEnv.STEP_MODES); default: the library's")
     ap.add_argument("--act-space", default="raw", choices=["raw", "normalized"])
     ap.add_argument("--ret-norm", type=int, default=0)
@@ -562,4 +570,5 @@ if __name__ == "__main__":
           task=a.task, step_mode=a.step_mode, graph_rollout=bool(a.graph_rollout), fused_policy=bool(a.fused_policy), graph_update=a.graph_update, policy_bf16=bool(a.policy_bf16),
           sub_batches=a.sub_batches, minibatches=a.minibatches, act_space=a.act_space, ret_norm=bool(a.ret_norm),
           orthogonal=bool(a.orthogonal), ent_coef=a.ent_coef, log_std=a.log_std, lr=a.lr, reward_clip=a.reward_clip,
-          min_cumulative_reward=a.min_cumulative_reward, feasibility_pooling=bool(a.feasibility_pooling), fused_update=bool(a.fused_update))
+          min_cumulative_reward=a.min_cumulative_reward, feasibility_pooling=bool(a.feasibility_pooling), fused_update=bool(a.fused_update),
+          fused_bootstrap=bool(a.fused_bootstrap))

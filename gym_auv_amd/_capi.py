@@ -143,6 +143,16 @@ class AuvPolicyIO(C.Structure):
     ]
 
 
+class AuvPolicyEval(C.Structure):
+    """== auv_policy_eval_t (include/auv_hip.h): one evaluation of M observation rows (auv_policy_eval)"""
+    _fields_ = [
+        ("params", C.c_void_p), ("X", C.c_void_p), ("idx", C.c_void_p), ("A", C.c_void_p),
+        ("mu", C.c_void_p), ("action", C.c_void_p), ("value", C.c_void_p), ("logp", C.c_void_p),
+        ("ldx", C.c_int64), ("action_ld", C.c_int32), ("obs_dim", C.c_int32), ("M", C.c_int32),
+        ("act_mid", C.c_float * 2), ("act_half", C.c_float * 2), ("clip_lo", C.c_float * 2), ("clip_hi", C.c_float * 2),
+    ]
+
+
 class AuvPpoBatch(C.Structure):
     """== auv_ppo_batch_t (include/auv_hip.h): the rows of one PPO minibatch step"""
     _fields_ = [
@@ -238,6 +248,8 @@ def load_library(path: str = None) -> C.CDLL:
         "auv_restore": (C.c_int, [vp, C.c_uint64, vp, i32, vp, vp, i32, vp, vp]),
         "auv_snapshot_skipped": (C.c_int, [vp, C.POINTER(C.c_int64), vp]),
         "auv_plan_score": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp]),
+        "auv_plan_score_v": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, vp]),
+        "auv_policy_eval": (C.c_int, [i32, C.POINTER(AuvPolicyEval), vp]),
         "auv_ppo_param_floats": (sz, [i32]),
         "auv_ppo_create": (C.c_int, [i32, i32, i32, C.POINTER(vp)]),
         "auv_ppo_destroy": (None, [vp]),
@@ -271,6 +283,7 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_generate_worlds", "auv_bank_bytes", "auv_read_bank",
                     "auv_fresh_worlds_create", "auv_fresh_worlds_refill", "auv_fresh_worlds_stats", "auv_fresh_worlds_draws", "auv_fresh_worlds_set_stream",
                     "auv_snapshot_row_bytes", "auv_snapshot_layout", "auv_snapshot", "auv_restore", "auv_snapshot_skipped", "auv_plan_score",
+                    "auv_plan_score_v", "auv_policy_eval",
                     "auv_ppo_param_floats", "auv_ppo_create", "auv_ppo_destroy", "auv_ppo_load", "auv_ppo_attach_policy", "auv_ppo_grad", "auv_ppo_adam",
                     "auv_abi_version", "auv_last_error"]
 

@@ -64,6 +64,10 @@ void auv_launch_snapshot(const AuvSnapArgs& a, const int32_t* env_idx, int m, vo
 void auv_launch_restore(const AuvSnapArgs& a, const AuvDev& d, const void* rows, int n_rows, const int32_t* row_idx, const int32_t* env_idx, int m,
                         float* obs, hipStream_t st);
 void auv_launch_plan_score(const float* reward, const uint8_t* done, int T, int n, int group, float gamma, float* score, int32_t* best, hipStream_t st);
+hipError_t auv_policy_eval_prepare(int obs_dim);
+void auv_launch_policy_eval(const auv_policy_eval_t& ev, bool want_pi, bool want_v, hipStream_t st);
+void auv_launch_plan_score_v(const float* reward, const uint8_t* done, const float* terminal, int T, int n, int group, float gamma, float* score,
+                             int32_t* best, hipStream_t st);
 
 static thread_local char g_err[512] = "";
 
@@ -1965,6 +1969,45 @@ int auv_plan_score(auv_handle_t* h, const float* reward_rec, const uint8_t* done
     return fail(AUV_EINVAL, "auv_plan_score: bad arguments (n_steps, n, group >= 1; n a multiple of group)");
   HIP_TRY(hipSetDevice(h->device));
   auv_launch_plan_score(reward_rec, done_rec, n_steps, n, group, gamma, score_dev, best_dev, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+int auv_plan_score_v(auv_handle_t* h, const float* reward_rec, const uint8_t* done_rec, int32_t n_steps, int32_t n, int32_t group, float gamma,
+                     const float* terminal_value, float* score_dev, int32_t* best_dev, void* stream) {
+  if (!terminal_value) return auv_plan_score(h, reward_rec, done_rec, n_steps, n, group, gamma, score_dev, best_dev, stream);
+  if (!h) return fail(AUV_EINVAL, "null handle");
+  if (!reward_rec || !done_rec || !score_dev || !best_dev || n_steps < 1 || n < 1 || group < 1 || n % group)
+    return fail(AUV_EINVAL, "auv_plan_score_v: bad arguments (n_steps, n, group >= 1; n a multiple of group)");
+  if ((uintptr_t)terminal_value & 3) return fail(AUV_EINVAL, "auv_plan_score_v: terminal_value must be 4-byte aligned");
+  HIP_TRY(hipSetDevice(h->device));
+  auv_launch_plan_score_v(reward_rec, done_rec, terminal_value, n_steps, n, group, gamma, score_dev, best_dev, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+// ---- the policy on arbitrary rows (include/auv_hip.h, auv_policy_eval; kernel: k9_policy_eval.hip) ----
+int auv_policy_eval(int32_t device, const auv_policy_eval_t* ev, void* stream) {
+  if (!ev) return fail(AUV_EINVAL, "auv_policy_eval: null ev");
+  if (device < 0) return fail(AUV_EINVAL, "auv_policy_eval: device %d", device);
+  if (ev->obs_dim < 1) return fail(AUV_EINVAL, "auv_policy_eval: obs_dim %d < 1", ev->obs_dim);
+  if (ev->obs_dim > 16384 || auv_policy_lds_bytes(ev->obs_dim) > 160 * 1024)
+    return fail(AUV_EINVAL, "auv_policy_eval: obs_dim %d is too wide for the policy kernel's LDS tile", ev->obs_dim);
+  if (ev->M < 0) return fail(AUV_EINVAL, "auv_policy_eval: M = %d < 0", ev->M);
+  const bool want_pi = ev->mu || ev->action || ev->logp, want_v = ev->value != nullptr;
+  if (!want_pi && !want_v) return fail(AUV_EINVAL, "auv_policy_eval: no output asked for (mu, action, value, logp are all NULL)");
+  if (ev->logp && !ev->A) return fail(AUV_EINVAL, "auv_policy_eval: logp needs the actions A");
+  if (!ev->params || !ev->X) return fail(AUV_EINVAL, "auv_policy_eval: null %s", !ev->params ? "params" : "X");
+  if (ev->ldx < ev->obs_dim) return fail(AUV_EINVAL, "auv_policy_eval: ldx %lld < obs_dim %d", (long long)ev->ldx, ev->obs_dim);
+  if (ev->action && ev->action_ld < 2) return fail(AUV_EINVAL, "auv_policy_eval: action_ld %d < 2", ev->action_ld);
+  if ((uintptr_t)ev->params & 15) return fail(AUV_EINVAL, "auv_policy_eval: params must be 16-byte aligned");
+  if (((uintptr_t)ev->X & 3) || ((uintptr_t)ev->A & 3) || ((uintptr_t)ev->mu & 3) || ((uintptr_t)ev->action & 3) || ((uintptr_t)ev->value & 3) ||
+      ((uintptr_t)ev->logp & 3) || ((uintptr_t)ev->idx & 7))
+    return fail(AUV_EINVAL, "auv_policy_eval: float buffers must be 4-byte, idx 8-byte aligned");
+  if (ev->M == 0) return AUV_OK;
+  HIP_TRY(hipSetDevice(device));
+  HIP_TRY(auv_policy_eval_prepare(ev->obs_dim));
+  auv_launch_policy_eval(*ev, want_pi, want_v, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }

@@ -31,6 +31,17 @@ __host__ __device__ inline size_t pol_net_floats(int obs_dim) {
   return POL_H1 * k0 + POL_H1 + (size_t)POL_H2 * POL_H1 + POL_H2 + (size_t)POL_H3 * POL_H2 + POL_H3 + (size_t)POL_OUT * POL_H3 + POL_OUT;
 }
 
+// LDS of a forward workgroup (k6_policy_act, k9_policy_eval): X [ROWS][K0p + 8] | Y1 [ROWS][H1 + 8]; Y2 [ROWS][H2 + 8] re-uses X's
+// place (dead after layer 1), Y3 [ROWS][H3 + 8] Y1's (dead after layer 2).  Row strides = 8 mod 64 floats: the 16-byte reads of an
+// A operand -- 16 rows x 4 k-groups -- then touch every bank once.
+__host__ __device__ inline size_t pol_lds_x_floats(int obs_dim) {
+  const size_t x = (size_t)pol_pad16(obs_dim) + 8, y2 = POL_H2 + 8;
+  return POL_ROWS * (x > y2 ? x : y2);
+}
+__host__ __device__ inline size_t pol_lds_bytes(int obs_dim) {
+  return sizeof(float) * (pol_lds_x_floats(obs_dim) + (size_t)POL_ROWS * (POL_H1 + 8));
+}
+
 // tanh: 1 - 2 / (exp(2 x) + 1) with the hardware's exp2 and reciprocal (absolute error ~2e-7, far inside the 1e-5 of the
 // parity test; saturates correctly: exp -> inf gives 1, exp -> 0 gives -1) instead of the library's ~40-instruction tanhf
 __device__ __forceinline__ float pol_tanh(const float x) {

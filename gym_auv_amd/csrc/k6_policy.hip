@@ -26,17 +26,7 @@
 
 namespace {
 
-// LDS: X [ROWS][K0p + 8] | Y1 [ROWS][H1 + 8]; Y2 [ROWS][H2 + 8] re-uses X's place (dead after layer 1), Y3 [ROWS][H3 + 8]
-// Y1's (dead after layer 2).  Row strides = 8 mod 64 floats: the 16-byte reads of an A operand -- 16 rows x 4 k-groups --
-// then touch every bank once.
-__host__ __device__ inline size_t pol_lds_x_floats(int obs_dim) {
-  const size_t x = (size_t)pol_pad16(obs_dim) + 8, y2 = POL_H2 + 8;
-  return POL_ROWS * (x > y2 ? x : y2);
-}
-__host__ __device__ inline size_t pol_lds_bytes(int obs_dim) {
-  return sizeof(float) * (pol_lds_x_floats(obs_dim) + (size_t)POL_ROWS * (POL_H1 + 8));
-}
-
+// (LDS: pol_lds_x_floats / pol_lds_bytes in auv_policy_mfma.h -- shared with k9_policy_eval.hip)
 struct PolicyArgs {
   auv_policy_io_t io;
   int32_t e0, ne;

@@ -64,8 +64,48 @@ def reference_plan_score(reward, done, group: int, gamma: float) -> Tuple[np.nda
     return score, best
 
 
-def plan_score(env, reward: torch.Tensor, done: torch.Tensor, group: int, gamma: float) -> Tuple[torch.Tensor, torch.Tensor]:
-    """auv_plan_score on the caller's current stream: (score [n] float32, best [n / group] int32) of a [T, n] reward / done record."""
+def reference_plan_score_terminal(reward, done, group: int, gamma: float, terminal) -> Tuple[np.ndarray, np.ndarray]:
+    """auv_plan_score_v's contract as a plain float32 loop: reference_plan_score, and in addition an environment with NO done in
+    [0, T) adds float32(disc_T * terminal[e]), disc_T the same running product after T multiplications -- one more rounded product
+    and one more rounded sum, last in order.  An environment that saw a done never reads its terminal value.  terminal [n] float32."""
+    reward = np.asarray(reward, dtype=np.float32)
+    done = np.asarray(done) != 0
+    terminal = np.asarray(terminal, dtype=np.float32).reshape(-1)
+    T, n = reward.shape
+    if n % group:
+        raise ValueError("n = %d is not a multiple of group = %d" % (n, group))
+    if terminal.shape[0] != n:
+        raise ValueError("terminal has %d entries, n = %d" % (terminal.shape[0], n))
+    score = np.zeros(n, dtype=np.float32)
+    g32 = np.float32(gamma)
+    with np.errstate(all="ignore"):
+        for e in range(n):
+            s, disc, ended = np.float32(0.0), np.float32(1.0), False
+            for t in range(T):
+                s = np.float32(s + np.float32(disc * reward[t, e]))
+                if done[t, e]:
+                    ended = True
+                    break
+                disc = np.float32(disc * g32)
+            if not ended:
+                s = np.float32(s + np.float32(disc * terminal[e]))
+            score[e] = s
+    best = np.zeros(n // group, dtype=np.int32)
+    for g in range(n // group):
+        have, bs = False, np.float32(0.0)
+        for k in range(group):
+            s = score[g * group + k]
+            if s != s:
+                continue
+            if not have or s > bs:
+                have, bs, best[g] = True, s, k
+    return score, best
+
+
+def plan_score(env, reward: torch.Tensor, done: torch.Tensor, group: int, gamma: float,
+               terminal: Optional[torch.Tensor] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    """auv_plan_score on the caller's current stream: (score [n] float32, best [n / group] int32) of a [T, n] reward / done record.
+    `terminal` [n] float32: auv_plan_score_v -- a candidate without a done adds disc_T * terminal[e] (reference_plan_score_terminal)."""
     from . import batched_env as be
     if reward.dim() != 2 or reward.dtype != torch.float32 or done.dtype != torch.uint8 or tuple(done.shape) != tuple(reward.shape) \
             or not reward.is_contiguous() or not done.is_contiguous() or reward.device != env.device or done.device != env.device:
@@ -73,9 +113,17 @@ def plan_score(env, reward: torch.Tensor, done: torch.Tensor, group: int, gamma:
     T, n = int(reward.shape[0]), int(reward.shape[1])
     if group < 1 or n % group:
         raise ValueError("n = %d is not a multiple of group = %d" % (n, group))
+    if terminal is not None and (terminal.dtype != torch.float32 or tuple(terminal.shape) != (n,) or not terminal.is_contiguous()
+                                 or terminal.device != env.device):
+        raise ValueError("terminal must be a contiguous [%d] float32 tensor on %s" % (n, env.device))
     with torch.cuda.device(env.device):
         score = torch.empty((n,), dtype=torch.float32, device=env.device)
         best = torch.empty((n // group,), dtype=torch.int32, device=env.device)
+    if terminal is not None:
+        be._check(be._LIB.auv_plan_score_v(env._h, C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()), T, n, int(group), C.c_float(gamma),
+                                           C.c_void_p(terminal.data_ptr()), C.c_void_p(score.data_ptr()), C.c_void_p(best.data_ptr()),
+                                           env._stream()), "auv_plan_score_v")
+        return score, best
     be._check(be._LIB.auv_plan_score(env._h, C.c_void_p(reward.data_ptr()), C.c_void_p(done.data_ptr()), T, n, int(group), C.c_float(gamma),
                                      C.c_void_p(score.data_ptr()), C.c_void_p(best.data_ptr()), env._stream()), "auv_plan_score")
     return score, best
@@ -90,7 +138,7 @@ class ShootingPlanner:
         snapshot of the B real environments -> restored K-fold into the planner's batch (environment b * K + k = real b)
         -> [T, B * K, 2] action ring: candidate 0 of every group is the mean sequence, the others Gaussian around it
            (per-dimension `sigma`), clipped to the action space
-        -> step_multi(ring, 0, T, record="reward") -> auv_plan_score
+        -> step_multi(ring, 0, T, record="reward") -> auv_plan_score (auv_plan_score_v with a terminal `value`)
         -> (CEM) mean and sigma refitted from the best `elite_frac` of every group, again from the restore
     and returns (first actions [B, 2], chosen sequences [T, B, 2], their predicted scores [B]) as device tensors.  The sampler
     is a seeded torch.Generator on the device: the same seed and the same states give the same plan (`plan(seed=...)` re-seeds).
@@ -100,7 +148,7 @@ class ShootingPlanner:
 
     def __init__(self, real_env, candidates: int = 64, horizon: int = 16, gamma: float = 0.99, iterations: int = 1,
                  elite_frac: float = 0.125, sigma: Union[float, Sequence[float], None] = None, seed: int = 0, worlds=None,
-                 sigma_min: float = 1e-3):
+                 sigma_min: float = 1e-3, value=None, value_scale: float = 1.0, value_shift: float = 0.0, prior=None):
         from .batched_env import BatchedAuvEnv
         from .devgen import FreshWorlds
         K, T = int(candidates), int(horizon)
@@ -143,6 +191,30 @@ class ShootingPlanner:
         self._gen.manual_seed(self.seed)
         self.last = None
         self.plans = 0
+        for name, f in (("value", value), ("prior", prior)):
+            if f is not None and hasattr(f, "params") and f.env.obs_dim != real_env.obs_dim:
+                raise ValueError("ShootingPlanner: %s was built for observations of %d columns, the planner's have %d" % (name, f.env.obs_dim, real_env.obs_dim))
+        if value is not None and not (hasattr(value, "params") or callable(value)):
+            raise ValueError("ShootingPlanner: value must be a FusedActorCritic or a callable obs [n, D] -> [n]")
+        if prior is not None and not hasattr(prior, "params"):
+            raise ValueError("ShootingPlanner: prior must be a FusedActorCritic")
+        self.value, self.prior = value, prior
+        self.value_scale, self.value_shift = float(value_scale), float(value_shift)
+
+    def _terminal(self) -> torch.Tensor:
+        """value(sim.obs) * value_scale + value_shift of the planner's batch after the launch, [B * K] float32."""
+        from .policy import policy_eval
+        obs = self.sim.obs
+        if hasattr(self.value, "params"):
+            v = policy_eval(self.value.params, self.sim.obs_dim, obs, want=("value",))["value"]
+        else:
+            v = self.value(obs)
+            if not isinstance(v, torch.Tensor) or v.numel() != obs.shape[0] or v.device != obs.device:
+                raise ValueError("ShootingPlanner: value(obs) must return %d values on %s" % (obs.shape[0], obs.device))
+            v = v.reshape(-1).to(torch.float32)
+        if self.value_scale != 1.0 or self.value_shift != 0.0:
+            v = v * self.value_scale + self.value_shift
+        return v.contiguous()
 
     def plan(self, seed: Optional[int] = None):
         """One decision for every real environment: (actions [B, 2], sequences [T, B, 2], predicted scores [B]).  `self.last` keeps
@@ -152,7 +224,13 @@ class ShootingPlanner:
         B, K, T, sim = self.B, self.K, self.T, self.sim
         snap = self.real.snapshot()
         mean, sigma = self._mean0, self._sigma0
+        terminal = None
         with torch.cuda.device(self.device):
+            if self.prior is not None:
+                # the policy's deterministic action at the real observation, held over the horizon
+                from .policy import policy_eval
+                a0 = policy_eval(self.prior.params, self.real.obs_dim, self.real.obs, want=("action",), action_map=self.prior.action_map)["action"]
+                mean = a0.reshape(1, B, 2).expand(T, B, 2).contiguous()
             for it in range(self.iterations):
                 sim.restore(snap, rows=self._rows, envs=self._envs, validate=False)
                 noise = torch.randn((T, B, K, 2), generator=self._gen, device=self.device, dtype=torch.float32)
@@ -162,7 +240,9 @@ class ShootingPlanner:
                 ring = cand.reshape(T, B * K, 2)
                 _, rew, done = sim.step_multi(ring, 0, T, record="reward")
                 sim._join_chains()
-                score, best = plan_score(sim, rew, done, K, self.gamma)
+                if self.value is not None:
+                    terminal = self._terminal()
+                score, best = plan_score(sim, rew, done, K, self.gamma, terminal)
                 if it + 1 < self.iterations:
                     # cross-entropy refit: mean and spread of the elite sequences of every group
                     elite = torch.nan_to_num(score, nan=float("-inf")).view(B, K).topk(self.n_elite, dim=1).indices      # [B, E]
@@ -173,6 +253,8 @@ class ShootingPlanner:
             chosen = cand[:, self._groups, bl, :].contiguous()                # [T, B, 2]
             predicted = score.view(B, K).gather(1, bl[:, None]).squeeze(1)
         self.last = dict(ring=ring, reward=rew, done=done, score=score, best=best)
+        if terminal is not None:
+            self.last["terminal"] = terminal                              # (only with a `value`: the last iteration's terminal values)
         self.plans += 1
         return chosen[0], chosen, predicted
 

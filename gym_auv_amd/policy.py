@@ -15,7 +15,7 @@ and value into the rollout buffers; reward / done of the previous step are store
     O, A, LP, V, R, Dn = fused.buffers()           # [T, N, ...] views for the update
 """
 import ctypes as C
-from typing import List, Optional
+from typing import Dict, List, Optional, Sequence
 
 import torch
 import torch.nn as nn
@@ -45,6 +45,131 @@ def pack_linear_bf16(weight: torch.Tensor, out_pad: int, in_pad: int) -> torch.T
     w = torch.zeros((out_pad, in_pad), dtype=torch.float32, device=weight.device)
     w[:weight.shape[0], :weight.shape[1]].copy_(weight)
     return w.view(out_pad // 16, 16, in_pad // 32, 4, 8).permute(0, 2, 3, 1, 4).contiguous().view(-1).to(torch.bfloat16)
+
+
+@torch.no_grad()
+def pack_policy_params(net: nn.Module, obs_dim: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The packed f32 weight buffer of auv_policy_io::params for `net` (net.pi / net.v: Linear-Tanh x 3 + Linear, net.log_std) without
+    an environment: what FusedActorCritic.refresh() writes into `self.params`.  For policy_eval on rows that come from elsewhere."""
+    k0p = _pad16(int(obs_dim))
+    dev = net.log_std.device
+    n_float = int(_LIB.auv_policy_param_floats(int(obs_dim)))
+    p = torch.zeros(n_float, dtype=torch.float32, device=dev) if out is None else out
+    off = 0
+    for seq, n_out in ((net.pi, 2), (net.v, 1)):
+        lin = [m for m in seq if isinstance(m, nn.Linear)]
+        if tuple(l.out_features for l in lin[:-1]) != HIDDEN or lin[-1].out_features != n_out or lin[0].in_features != int(obs_dim):
+            raise ValueError("pack_policy_params: the fused kernels evaluate obs[%d] -> %s tanh -> %d" % (int(obs_dim), list(HIDDEN), n_out))
+        for j, l in enumerate(lin):
+            out_p = l.out_features if j < 3 else 16
+            in_p = k0p if j == 0 else l.in_features
+            p[off:off + out_p * in_p].copy_(pack_linear(l.weight, out_p, in_p))
+            off += out_p * in_p
+            p[off:off + out_p].zero_()
+            p[off:off + l.out_features].copy_(l.bias)
+            off += out_p
+    p[off:off + 2].copy_(net.log_std)
+    assert off + 4 == p.numel()
+    return p
+
+
+_EVAL_OUTPUTS = ("mu", "action", "value", "logp")
+
+
+def _eval_check(name: str, t, device, shape_tail, dtype=torch.float32):
+    if not isinstance(t, torch.Tensor) or t.dtype != dtype or t.device != device:
+        raise ValueError("policy_eval: %s must be a %s tensor on %s" % (name, str(dtype).replace("torch.", ""), device))
+    if t.dim() != 1 + len(shape_tail) or tuple(t.shape[1:]) != tuple(shape_tail):
+        raise ValueError("policy_eval: %s must have shape [M%s], got %s" % (name, "".join(", %d" % x for x in shape_tail), tuple(t.shape)))
+
+
+def policy_eval(params: torch.Tensor, obs_dim: int, X: torch.Tensor, idx: Optional[torch.Tensor] = None,
+                actions: Optional[torch.Tensor] = None, want: Sequence[str] = ("mu", "value"), action_map=None,
+                out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+    """auv_policy_eval (csrc/k9_policy_eval.hip) on the caller's current stream: M observation rows through the policy net, the
+    value net, or both, in ONE launch -- no environment, no rollout position, no sampling.
+
+    params      a packed weight buffer (FusedActorCritic.params, or the buffer a FusedPPOUpdate is attached to)
+    X           [R, obs_dim] float32; rows may be strided (a column window of a wider buffer), columns may not
+    idx         [M] int64 rows of X to evaluate, repeats allowed (None: all R rows, M = R); an index outside [0, R) is the
+                caller's error: it is not checked (as auv_ppo_batch::idx)
+    actions     [M, 2] float32, contiguous: needed for "logp"
+    want        any of "mu" [M, 2], "action" [M, 2], "value" [M], "logp" [M]; only the nets they need are launched
+    action_map  (act_mid, act_half, clip_lo, clip_hi), each two floats: action = mid + half * clip(mu, lo, hi); None: the identity
+                map without clipping
+    out         tensors to write into instead of new ones, by name; "action" may be a row-strided [M, 2] view (rows of an
+                environment's action buffer)
+    Returns a dict of the tensors asked for.  Raises ValueError for anything the launch would refuse."""
+    want = tuple(want)
+    out = dict(out or {})
+    for w in want:
+        if w not in _EVAL_OUTPUTS:
+            raise ValueError("policy_eval: unknown output %r (one of %s)" % (w, ", ".join(_EVAL_OUTPUTS)))
+    for w in out:
+        if w not in want:
+            raise ValueError("policy_eval: out[%r] given but %r is not in want" % (w, w))
+    if not want:
+        raise ValueError("policy_eval: no output asked for")
+    obs_dim = int(obs_dim)
+    if obs_dim < 1:
+        raise ValueError("policy_eval: obs_dim must be >= 1")
+    if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or not params.is_cuda or not params.is_contiguous() \
+            or params.numel() != int(_LIB.auv_policy_param_floats(obs_dim)) or params.data_ptr() % 16:
+        raise ValueError("policy_eval: params must be a contiguous, 16-byte aligned float32 device tensor of auv_policy_param_floats(%d) = %d "
+                         "elements" % (obs_dim, int(_LIB.auv_policy_param_floats(obs_dim))))
+    dev = params.device
+    _eval_check("X", X, dev, (obs_dim,))
+    if X.stride(1) != 1 and X.shape[0] > 0:
+        raise ValueError("policy_eval: the columns of X must be contiguous (rows may be strided)")
+    ldx = int(X.stride(0)) if X.shape[0] > 1 else obs_dim
+    if ldx < obs_dim:
+        raise ValueError("policy_eval: row stride of X %d < obs_dim %d" % (ldx, obs_dim))
+    if idx is not None:
+        _eval_check("idx", idx, dev, (), torch.int64)
+        if not idx.is_contiguous():
+            raise ValueError("policy_eval: idx must be contiguous")
+        if idx.numel() and X.shape[0] == 0:
+            raise ValueError("policy_eval: idx names rows of an empty X")
+    M = int(X.shape[0] if idx is None else idx.numel())
+    if "logp" in want and actions is None:
+        raise ValueError("policy_eval: logp needs the actions")
+    if actions is not None:
+        _eval_check("actions", actions, dev, (2,))
+        if actions.shape[0] != M or not actions.is_contiguous():
+            raise ValueError("policy_eval: actions must be a contiguous [%d, 2] tensor" % M)
+    ev = _capi.AuvPolicyEval()
+    res = {}
+    with torch.cuda.device(dev):
+        for w in want:
+            tail = (2,) if w in ("mu", "action") else ()
+            t = out.get(w)
+            if t is None:
+                t = torch.empty((M,) + tail, dtype=torch.float32, device=dev)
+            else:
+                _eval_check("out[%r]" % w, t, dev, tail)
+                if t.shape[0] != M:
+                    raise ValueError("policy_eval: out[%r] has %d rows, M = %d" % (w, t.shape[0], M))
+                if w == "action":
+                    if M > 0 and (t.stride(1) != 1 or (M > 1 and t.stride(0) < 2)):
+                        raise ValueError("policy_eval: out['action'] must have contiguous columns and a row stride >= 2")
+                elif not t.is_contiguous():
+                    raise ValueError("policy_eval: out[%r] must be contiguous" % w)
+            res[w] = t
+            setattr(ev, w, t.data_ptr() if M else None)
+        if M == 0:
+            return res
+        ev.params, ev.X, ev.ldx = params.data_ptr(), X.data_ptr(), ldx
+        ev.idx = idx.data_ptr() if idx is not None else None
+        ev.A = actions.data_ptr() if actions is not None else None
+        ev.action_ld = int(res["action"].stride(0)) if "action" in res and M > 1 else 2
+        ev.obs_dim, ev.M = obs_dim, M
+        mid, half, lo, hi = ((0.0, 0.0), (1.0, 1.0), (float("-inf"),) * 2, (float("inf"),) * 2) if action_map is None else action_map
+        for k in range(2):
+            ev.act_mid[k], ev.act_half[k], ev.clip_lo[k], ev.clip_hi[k] = float(mid[k]), float(half[k]), float(lo[k]), float(hi[k])
+        st = torch.cuda.current_stream(dev)
+        _check(_LIB.auv_policy_eval(dev.index if dev.index is not None else torch.cuda.current_device(), C.byref(ev),
+                                    C.c_void_p(st.cuda_stream)), "auv_policy_eval")
+    return res
 
 
 class FusedActorCritic:
@@ -83,6 +208,7 @@ class FusedActorCritic:
         clo = lo_t.tolist() if clip_lo is None else [float(x) for x in clip_lo]
         chi = hi_t.tolist() if clip_hi is None else [float(x) for x in clip_hi]
         self.actions = torch.zeros((env.n_envs, 2), dtype=torch.float32, device=self.device)
+        self.action_map = (tuple(mid), tuple(half), tuple(clo), tuple(chi))            # (what predict() maps the mean through, too)
         N = env.n_envs
         z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)   # noqa: E731
         # ONE set of rollout buffers [T, N, ...] for the whole batch: every chain writes its own columns, nothing is
@@ -184,3 +310,32 @@ class FusedActorCritic:
                             C.c_void_p(last_v.data_ptr()), float(gamma), float(lam), C.c_void_p(adv.data_ptr()),
                             C.c_void_p(ret.data_ptr()), self.T, self.env.n_envs, C.c_void_p(st.cuda_stream)), "auv_gae")
         return adv, ret
+
+    # ------------------------------------------------------------------------------ evaluation outside a rollout
+    def _rows(self, obs):
+        return self.env.obs if obs is None else obs
+
+    def predict(self, obs: Optional[torch.Tensor] = None, deterministic: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The deterministic action of the policy -- the reference's agent.predict(obs, deterministic=True) of its enjoy / play /
+        test modes (scripts/run.py:175, 273, 567): act_mid + act_half * clip(mu(obs)), one launch (auv_policy_eval) on the caller's
+        current stream, written into `out` (default: `self.actions`, which env.step takes as is).  obs = None: the environment's
+        observation buffer.  Reads `self.params`: refresh() after optimiser steps, as for rollouts.  Touches no rollout buffer and
+        no counter."""
+        if not deterministic:
+            raise ValueError("predict(deterministic=False): sampling lives where its counters are -- use act(i) / rollout()")
+        X = self._rows(obs)
+        if out is None:
+            if X.dim() != 2 or X.shape[0] != self.env.n_envs:
+                raise ValueError("predict: %s rows do not fit self.actions [%d, 2]; pass out=" % (tuple(X.shape[:1]), self.env.n_envs))
+            out = self.actions
+        return policy_eval(self.params, self.env.obs_dim, X, want=("action",), action_map=self.action_map, out={"action": out})["action"]
+
+    def value(self, obs: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """The critic's value of every row of `obs` (None: the environment's observation buffer), [M] float32 in the units the
+        critic was trained in (scaled rewards): one launch of the value net alone, on the caller's current stream."""
+        return policy_eval(self.params, self.env.obs_dim, self._rows(obs), want=("value",))["value"]
+
+    def evaluate(self, obs: torch.Tensor, actions: torch.Tensor):
+        """(log pi(actions | obs) [M], value [M], mu [M, 2]) in one launch on the caller's current stream."""
+        r = policy_eval(self.params, self.env.obs_dim, obs, actions=actions, want=("logp", "value", "mu"))
+        return r["logp"], r["value"], r["mu"]

@@ -582,6 +582,36 @@ int auv_policy_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds,
                        const auv_policy_io_t* ios, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps,
                        int32_t flush, const int64_t* t0, const int64_t* gstep0);
 
+/* ---- the policy outside the rollout (scripts/run.py:175, 273, 567: agent.predict(obs, deterministic=True) of the enjoy / play /
+ * test modes; csrc/k9_policy_eval.hip) --------------------------------------------------------------------------------------------
+ * auv_policy_eval evaluates M observation rows through the policy net, the value net, or both, with ONE launch on `stream`: no
+ * environment handle, no rollout position, no counters, no sampling.  The matrix chains are those of auv_policy_act's exact-f32
+ * path, so for the same row and the same `params` the mean and the value have the same bits as the rollout launch gives.
+ *   rows      row j < M is X[(idx ? idx[j] : j) * ldx .. + obs_dim): ldx >= obs_dim, in floats; 4-byte alignment is enough.  idx as
+ *             auv_ppo_batch::idx: an index that names a row outside X is the caller's error, it is not checked.
+ *   outputs   each nullable, written for rows < M only:  mu[j][2] the policy mean;  action[j * action_ld + c] = act_mid[c] +
+ *             act_half[c] * clip(mu[c], clip_lo[c], clip_hi[c]), the deterministic action (action_ld >= 2 floats: 2 writes straight
+ *             into rows of an environment's [N][2] float32 action buffer);  value[j];  logp[j] = log pi(A[j] | row j) for the GIVEN
+ *             actions A[M][2] (indexed by j, not through idx), the expression auv_policy_act stores in LP.
+ *   nets      only the nets whose outputs are asked for are launched (value alone never reads the policy weights).
+ * AUV_EINVAL, before anything is enqueued: logp without A; no output at all; obs_dim < 1 or too wide for the kernel's LDS tile;
+ * ldx < obs_dim; action with action_ld < 2; M < 0; params not 16-byte or another pointer not 4-byte aligned.  M == 0 succeeds and
+ * launches nothing.  Enqueued on `stream`; no synchronisation, no allocation.  All pointers except `ev` are device pointers.      */
+typedef struct auv_policy_eval {
+  const float* params;       /* the layout of auv_policy_io::params (auv_policy_param_floats(obs_dim) floats)   */
+  const float* X;            /* observation rows, row stride ldx floats                                         */
+  const int64_t* idx;        /* [M] rows of X to evaluate; NULL: rows 0 .. M - 1                                */
+  const float* A;            /* [M][2] actions whose log-probability is asked for (needed with logp)            */
+  float* mu;                 /* [M][2]        (nullable)                                                        */
+  float* action;             /* [M][action_ld] (nullable)                                                       */
+  float* value;              /* [M]           (nullable)                                                        */
+  float* logp;               /* [M]           (nullable)                                                        */
+  int64_t ldx;
+  int32_t action_ld, obs_dim, M;
+  float act_mid[2], act_half[2], clip_lo[2], clip_hi[2];   /* action = mid + half * clip(mu, lo, hi)          */
+} auv_policy_eval_t;
+int auv_policy_eval(int32_t device, const auv_policy_eval_t* ev, void* stream);
+
 /* Generalised advantage estimation over a rollout of T steps x N environments (row-major [T][N] device buffers; V and
  * last_v in the same units as R): adv and ret = adv + V, one launch on `stream`.                                       */
 int auv_gae(auv_handle_t* h, const float* R, const float* V, const float* Dn, const float* last_v, float gamma, float lam,
@@ -634,6 +664,12 @@ int auv_snapshot_skipped(auv_handle_t* h, int64_t* out_skipped, void* stream);
  * wins (all NaN: 0).  One launch on `stream`; n a multiple of group.                                                         */
 int auv_plan_score(auv_handle_t* h, const float* reward_rec, const uint8_t* done_rec, int32_t n_steps, int32_t n, int32_t group,
                    float gamma, float* score_dev, int32_t* best_dev, void* stream);
+/* The same with a terminal value (MPC with a learned critic): auv_plan_score's contract, word for word, and in addition an
+ * environment with NO done in [0, n_steps) adds float32(disc_T * terminal_value[e]), disc_T being the same running product after
+ * n_steps multiplications -- one more rounded product and one more rounded sum, last in order.  A candidate that saw a done never
+ * reads its terminal value (a NaN there cannot reach its score).  terminal_value [n] float32 on the device; NULL: auv_plan_score. */
+int auv_plan_score_v(auv_handle_t* h, const float* reward_rec, const uint8_t* done_rec, int32_t n_steps, int32_t n, int32_t group,
+                     float gamma, const float* terminal_value, float* score_dev, int32_t* best_dev, void* stream);
 
 /* ---- the PPO update (scripts/run.py:332-357: PPO2 with MlpPolicy, net_arch [256, 128, 64] for policy and value
  * function, tanh, a diagonal Gaussian with a free log_std[2]): one minibatch step of examples/ppo.py (minibatch_step) as a few
