@@ -188,10 +188,13 @@ template <int K> __device__ __forceinline__ int k1_group_bcast32(const int x) {
 template <int K> __device__ __forceinline__ double k1_group_bcast(const double t) {
   return __hiloint2double(k1_group_bcast32<K>(__double2hiint(t)), k1_group_bcast32<K>(__double2loint(t)));
 }
-// `y_in` (nullable): component c of the state to start from, in the lane that owns it (else the STATE rows); `slot`: see k1_action;
-// `a_in` (nullable): the action, fetched by the caller already (k1_action)
+// `have_y`: `y_val` is component c of the state to start from, in the lane that owns it (else the STATE rows) -- by value: a pointer
+// that is null in one step and a local's address in the others kept that local in scratch memory (16 bytes of private segment for
+// every wave of k_step_multi, stored and never read); `slot`: see k1_action; `a_in` (nullable): the action, fetched by the caller
+// already (k1_action)
 __device__ __forceinline__ double k1_group(const AuvDev& d, const void* __restrict__ actions, const int e, const int lane,
-                                           const double* y_in = nullptr, const int slot = -1, const double2* a_in = nullptr) {
+                                           const bool have_y = false, const double y_val = 0.0, const int slot = -1,
+                                           const double2* a_in = nullptr) {
   const int c = lane % K1_GROUP, gbase = lane - c;
   const size_t n = (size_t)d.n;
   const bool own = c < 6;
@@ -202,7 +205,7 @@ __device__ __forceinline__ double k1_group(const AuvDev& d, const void* __restri
   const double tu = auv_clip(a0, 0.0, 1.0) * d.cfg.thrust_max;
   const double tr = auv_clip(a1, -1.0, 1.0) * d.cfg.moment_max;
   const double h = d.cfg.dt;
-  const double y = y_in ? *y_in : d.state[(size_t)(own ? c : 0) * n + e];
+  const double y = have_y ? y_val : d.state[(size_t)(own ? c : 0) * n + e];
   (void)gbase;
   const Heading0 h0 = heading0(k1_group_bcast<2>(y));
   // _state_dot of the stage vector whose component c this lane holds in `t`; returns component c

@@ -152,7 +152,8 @@ __device__ __forceinline__ MoverSegs mover_segs(const double4 rot, const double 
   return ms;
 }
 
-__device__ __forceinline__ Slice carve(unsigned char* p, int S, int k_max, int m_max, int cap) {
+// the slice without k2_back's lists (`hits` / `hitw` null: carve_hits places them)
+__device__ __forceinline__ Slice carve_base(unsigned char* p, int S, int k_max, int m_max, int cap) {
   Slice s;
   s.hdr = (EnvHdr*)p;
   s.mvrot = (double4*)(s.hdr + 1);
@@ -169,14 +170,24 @@ __device__ __forceinline__ Slice carve(unsigned char* p, int S, int k_max, int m
   s.owner = (unsigned short*)(s.par + k_max);
   s.ioff = s.owner + cap;
   s.cap = cap;
-  // k2_back's lists, 4 B of beam index + 8 B of weight per beam, in what is idle once the pair sweep is through: both in
-  // R1 = [mvrot, rayv) = the movers' rotations + the stage if they fit there, else the indices in R1 and the weights in
-  // R2 = [mvw, end of the slice) = everything behind the beams' distance words
+  s.hits = nullptr, s.hitw = nullptr;
+  return s;
+}
+// k2_back's lists, 4 B of beam index + 8 B of weight per beam, in what is idle once the pair sweep is through: both in
+// R1 = [mvrot, rayv) = the movers' rotations + the stage if they fit there, else the indices in R1 and the weights in
+// R2 = [mvw, end of the slice) = everything behind the beams' distance words
+// (apart from carve_base: the multi-step sweep places them when it reaches k2_back -- two pointers chosen by branches, alive from
+// the wave's first instructions on, were scalar spills in each of those branches)
+__device__ __forceinline__ void carve_hits(Slice& s, int S, int m_max, int cap) {
   const size_t r1 = 32 * (size_t)(m_max + cap), r2 = (size_t)((unsigned char*)(s.ioff + cap + 2) - (unsigned char*)s.mvw);
   const size_t hb = ((size_t)4 * S + 7) & ~(size_t)7;
   s.hits = nullptr, s.hitw = nullptr;
   if (S <= K2_HIT_S && hb + (size_t)8 * S <= r1) s.hits = (int*)s.mvrot, s.hitw = (double*)((unsigned char*)s.mvrot + hb);
   else if (S <= K2_HIT_S && hb <= r1 && (size_t)8 * S <= r2) s.hits = (int*)s.mvrot, s.hitw = s.mvw;
+}
+__device__ __forceinline__ Slice carve(unsigned char* p, int S, int k_max, int m_max, int cap) {
+  Slice s = carve_base(p, S, k_max, m_max, cap);
+  carve_hits(s, S, m_max, cap);
   return s;
 }
 __device__ __forceinline__ Slice carve(unsigned char* p, const AuvDev& d) { return carve(p, d.cfg.n_sensors, d.k_max, d.m_max, d.seg_cap); }
@@ -255,6 +266,31 @@ __device__ __forceinline__ int inside_flag_wave(double px, double py, SegPtr g, 
 __device__ __forceinline__ void k2_stage_beams(const AuvDev& d, const int lane, const Slice& L) {
   const int S = d.cfg.n_sensors;
   for (int i = lane; i < S; i += AUV_WAVE) L.rayv[i] = d.beam_cs[i];
+}
+
+// The same, straight from memory into LDS (gfx950's global_load_lds, 16 bytes per lane): no register holds an entry while the
+// request is out, so the multi-step sweep can issue it among its first requests, beside the loads of its hand-over records.  The LDS
+// address of such a load is wave-uniform (the pointer given here: the pass's first slot) plus lane x 16 bytes -- lanes past the
+// table in the last pass are masked and write nothing (the movers' cull circles follow the rays in the slice); `rayv` is 16-byte
+// aligned and a pass is 64 consecutive slots.
+// Ordering rests on the compiler: it counts these loads as pending LDS writes and waits for them before any later access to LDS
+// that may alias them.  The number of passes is not known at compile time, so that wait is a vmcnt(0), and it sits where the
+// first result of the loads issued around these is used (the first look at the carry record) -- not at the slots' first read in
+// k2_rays.  That early wait is also what covers the path without rays (n_act == 0: k2_rays is skipped and k2_back reuses `rayv`).
+// Do not replace it by a hand-placed, counted wait further down.
+__device__ __forceinline__ void k2_stage_beams_direct(const AuvDev& d, const int lane, const Slice& L) {
+  // (the beam count and the table's address through a laundered copy of the descriptor's address: read here for these few
+  // instructions only, not held in scalar registers from the wave's first instruction to the sweep's last use of them)
+  const AuvDev* dp = &d;
+  asm volatile("" : "+s"(dp));
+  const __attribute__((address_space(4))) AuvDev* dc = (const __attribute__((address_space(4))) AuvDev*)dp;
+  const int S = dc->cfg.n_sensors;
+  const double2* src = dc->beam_cs + lane;
+  typedef __attribute__((address_space(1))) const void* gptr_t;
+  typedef __attribute__((address_space(3))) void* lptr_t;
+#pragma nounroll
+  for (int q = 0; q < S; q += AUV_WAVE)
+    if (q + lane < S) __builtin_amdgcn_global_load_lds((gptr_t)(src + q), (lptr_t)(L.rayv + q), 16, 0, 0);
 }
 
 __device__ __forceinline__ void k2_rays(const AuvDev& d, const int lane, const Slice& L, const bool staged = false) {

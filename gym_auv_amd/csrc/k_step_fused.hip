@@ -628,6 +628,8 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_roles(AuvD
 //   sweep wave   0 role begins  1 the wave's first instruction  2 state packet here  3 all its stores acknowledged  4 pair sweep done  5 word published
 //   search wave  6 role begins  7 the wave's first instruction  8 state packet here  9 record published
 //   dynamics    10 has its slot 11 carry record here 12 packet stored      finish 13 has its slot 14 sweeps' words here 15 done
+// s_waitcnt with vmcnt = 0 and the other counters left open (gfx9 encoding): every load and store of the wave has completed
+#define AUV_WAITCNT_VMCNT0 0x0F70
 #ifdef AUV_STAMPS_MULTI
 #define MSTAMP(e, k) do { if (lane == 0) stamp[(size_t)(e) * 16 + (k)] = wall_clock64(); } while (0)
 #define MSTAMP_IF(cond, e, k) do { if (cond) stamp[(size_t)(e) * 16 + (k)] = wall_clock64(); } while (0)
@@ -658,13 +660,20 @@ __device__ __forceinline__ void carry_ed_from(EnvDesc& ed, const unsigned long l
   ed.nk = (int)(unsigned)w[7], ed.w = (int)(unsigned)(w[7] >> 32);
 }
 
+// a first look at the carry record, requested by the caller ahead of work that must not sit between the wave's start and this
+// request (the multi-step sweep: carving its slice, staging the beam table); this lane's word goes to carry_wait_wave as `v_first`
+__device__ __forceinline__ unsigned long long carry_request(const AuvDev& d, const int e, const int lane) {
+  return lane < CARRY_WORDS ? __hip_atomic_load(d.carry + CARRY_WORDS * (size_t)e + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0ull;
+}
 // one wave, one environment (sweep, search): the carry of the previous step.  0: here it is; 1: gave up (reported, environment
 // marked); 2: the abort flag went up meanwhile -- the wave ends without touching anything
-__device__ __forceinline__ int carry_wait_wave(const AuvDev& d, const int e, const int lane, const unsigned long long tagmix, EnvDesc& ed, int4& cnt) {
+__device__ __forceinline__ int carry_wait_wave(const AuvDev& d, const int e, const int lane, const unsigned long long tagmix, EnvDesc& ed, int4& cnt,
+                                               const bool have_first = false, const unsigned long long v_first = 0ull) {
   const unsigned long long* cw = d.carry + CARRY_WORDS * (size_t)e;
   unsigned long long v = 0ull;
   for (int polls = 0;; polls++) {
-    if (lane < CARRY_WORDS) v = __hip_atomic_load(cw + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    if (have_first && polls == 0) v = v_first;
+    else if (lane < CARRY_WORDS) v = __hip_atomic_load(cw + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned long long ma = roles_lane_word(v, 7), mb = roles_lane_word(v, 20);
     if (ma != 0ull && mb != 0ull) {
       unsigned long long xa = roles_lane_word(v, 0), xb = roles_lane_word(v, 8);

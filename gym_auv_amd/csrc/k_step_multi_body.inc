@@ -92,7 +92,7 @@
     double t = 0.0;
     MSTAMP_IF(live && c == 0, eg, 11);
     const double2 act = make_double2(act0, act1);
-    if (!aborted) t = k1_group(d, actions, eg, lane, step == 0 ? nullptr : &y0, (first_slot + step) % n_slots, &act);
+    if (!aborted) t = k1_group(d, actions, eg, lane, step != 0, y0, (first_slot + step) % n_slots, &act);
     unsigned long long* pk = d.k1_pkt + 8 * (size_t)eg;
     const unsigned long long word = aborted ? (c == 6 ? (unsigned long long)ROLES_ABORT_COUNTER : 0ull)
                                             : (c < 6 ? (unsigned long long)__double_as_longlong(t) : (c == 6 ? (unsigned long long)(unsigned)y : 0ull));
@@ -108,11 +108,19 @@
     // ---- _update + Vessel.perceive of one environment ----
     const int e = auv_uniform(d.e0 + bi);
     MSTAMP(e, 0);
-    // three requests in flight before the first wait: the abort flag, this step's state packet (dispatched `lead` cohorts behind
-    // its dynamics, the wave usually finds it there), the carry record
+    // four requests in flight before the first wait: the abort flag, this step's state packet (dispatched `lead` cohorts behind
+    // its dynamics, the wave usually finds it there), the first look at the carry record (step 0 reads the arrays and drops it), and
+    // behind those -- its addresses take two scalar loads more -- the beam table on its way straight into the ray slots (no
+    // register waits for it: k2_stage_beams_direct).
+    // (The wait in front of them finds nothing outstanding: a wave has requested nothing from memory before its role begins.  It
+    // is there for the compiler, which otherwise assumes loads of the other roles still in flight here and waits for them, that is
+    // for the abort flag's whole trip, in the middle of these requests.)
+    __builtin_amdgcn_s_waitcnt(AUV_WAITCNT_VMCNT0);       // (a later toolchain may not need it: the sweep's head in the assembly tells)
     const int ab_early = __hip_atomic_load(d.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned long long pk_first = __hip_atomic_load(d.k1_pkt + 8 * (size_t)e + (lane & 7), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    const Slice L = carve(smem, d);
+    const unsigned long long cw_first = carry_request(d, e, lane);
+    Slice L = carve_base(smem, d.cfg.n_sensors, d.k_max, d.m_max, d.seg_cap);   // (k2_back's lists: placed in front of k2_back)
+    k2_stage_beams_direct(d, lane, L);
     K2Pre kp;
     if (step == 0) {
       ed = d.env_desc[e];
@@ -122,13 +130,12 @@
       k2_movers<true>(d, e, lane, L, ed, 1);
       kp = k2_prefetch(d, e, lane, ed);
     } else {
-      if (carry_wait_wave(d, e, lane, tagmix_prev, ed, pre.cnt)) return;
+      if (carry_wait_wave(d, e, lane, tagmix_prev, ed, pre.cnt, true, cw_first)) return;
       if (auv_uniform(ab_early)) return;
       pre.ed = &ed;
       k2_movers<true, true>(d, e, lane, L, ed, 1);
       kp = k2_prefetch<true>(d, e, lane, ed);
     }
-    k2_stage_beams(d, lane, L);
     {
       const int ws = roles_wait_state(d, e, lane, pre, tagmix, true, pk_first);
       if (ws) {
@@ -142,12 +149,18 @@
     k2_stage_and_pairs(d, L, lane, n_act, pre.s[2]);
     MSTAMP(e, 4);
     double term = 0.0;
+    {
+      const AuvDev* dp = &d;
+      asm volatile("" : "+s"(dp));                         // (fetched here: nothing of this is held across the sweep)
+      const __attribute__((address_space(4))) AuvDev* dc = (const __attribute__((address_space(4))) AuvDev*)dp;
+      carve_hits(L, dc->cfg.n_sensors, dc->m_max, dc->seg_cap);
+    }
     const int collision = k2_back<true>(d, e, lane, L, n_act, obs_out, &term, &lim0);
     pair_publish_lidar(d, e, lane, collision, term);
     MSTAMP(e, 5);
 #ifdef AUV_STAMPS_MULTI
     if (lane == 0) stamp[(size_t)e * 16 + 1] = t_entry;
-    __builtin_amdgcn_s_waitcnt(0x0F70);                    // every store of this wave has been acknowledged
+    __builtin_amdgcn_s_waitcnt(AUV_WAITCNT_VMCNT0);                    // every store of this wave has been acknowledged
     MSTAMP(e, 3);
 #endif
   } else if (role == 2) {
