@@ -49,12 +49,12 @@ def loss_terms(net, o, a, lp, adv, ret):
     return loss, pg, vf, ratio
 
 
-def make_data(net, obs_dim, seed=1, device=DEV):
-    """O, A, LP, ADV, RET [N_ROWS]: actions sampled from the net, LP from a slightly perturbed copy of it, so that the ratios spread
+def make_data(net, obs_dim, seed=1, device=DEV, n_rows=N_ROWS):
+    """O, A, LP, ADV, RET [n_rows]: actions sampled from the net, LP from a slightly perturbed copy of it, so that the ratios spread
     over both clip boundaries; rows within 1e-4 of a boundary (in fp64) or with |adv| < 1e-6 are replaced by rows at ratio 1."""
     torch.manual_seed(seed)
     with torch.no_grad():
-        O = torch.randn(N_ROWS, obs_dim, device=device)
+        O = torch.randn(n_rows, obs_dim, device=device)
         mu = net.pi(O)
         A = mu + net.log_std.exp() * torch.randn_like(mu)
         old = copy.deepcopy(net)
@@ -62,7 +62,7 @@ def make_data(net, obs_dim, seed=1, device=DEV):
             p.add_(0.15 * torch.randn_like(p) * p.abs().max())
         old.log_std.add_(torch.tensor([0.03, -0.03], device=device))
         LP = old.log_prob(old.pi(O), A)
-        ADV, RET = torch.randn(N_ROWS, device=device), torch.randn(N_ROWS, device=device)
+        ADV, RET = torch.randn(n_rows, device=device), torch.randn(n_rows, device=device)
         n64 = copy.deepcopy(net).double()
 
         def ratio64():
@@ -79,7 +79,7 @@ def make_data(net, obs_dim, seed=1, device=DEV):
 
 def autograd_reference(net, dtype, data, idx):
     n = copy.deepcopy(net).to(dtype)
-    o, a, lp, adv, ret = (x[idx].to(dtype) for x in data)
+    o, a, lp, adv, ret = ((x if idx is None else x[idx]).to(dtype) for x in data)                # (idx None: every stored row)
     loss, pg, vf, ratio = loss_terms(n, o, a, lp, adv, ret)
     loss.backward()
     clipped = ((adv > 0) & (ratio > 1 + CLIP)) | ((adv < 0) & (ratio < 1 - CLIP))
@@ -110,31 +110,44 @@ def err(x, ref):
     return float((x - ref).abs().max() / ref.abs().max())
 
 
-@pytest.mark.parametrize("B", [7, 16, 1000, 4096])
-@pytest.mark.parametrize("obs_dim", [6, 15, 186])
-def test_gradient_and_stats_match_autograd(obs_dim, B):
-    net, data, upd = case(obs_dim)
-    torch.manual_seed(100 + B)
-    idx = torch.randperm(N_ROWS, device=DEV)[:B].contiguous()
+NAMES = ["pi.W1", "pi.b1", "pi.W2", "pi.b2", "pi.W3", "pi.b3", "pi.W4", "pi.b4", "v.W1", "v.b1", "v.W2", "v.b2", "v.W3", "v.b3", "v.W4", "v.b4", "log_std"]
+
+
+def assert_parity(net, data, upd, idx, tag, names=NAMES):
+    """upd.grad on rows idx against autograd in fp64 by the rule of the module's docstring, for the tensors `names` and for the
+    statistics; every figure is printed before it is asserted.  Returns the fused gradient per tensor, the statistics row (copies,
+    as float64) and the reference gradients in fp64 and fp32."""
     g64, s64 = autograd_reference(net, torch.float64, data, idx)
     g32, s32 = autograd_reference(net, torch.float32, data, idx)
     g, stats = upd.grad(*data, idx)
     gf, stats = split(g.clone(), net), stats.clone().double()
-    names = ["pi.W1", "pi.b1", "pi.W2", "pi.b2", "pi.W3", "pi.b3", "pi.W4", "pi.b4", "v.W1", "v.b1", "v.W2", "v.b2", "v.W3", "v.b3", "v.W4", "v.b4", "log_std"]
     worst = []
-    for name, x, a, b in zip(names, gf, g32, g64):
+    for name, x, a, b in zip(NAMES, gf, g32, g64):
+        if name not in names:
+            continue
         ef, e32 = err(x, b), err(a, b)
-        print("obs_dim %3d B %4d %-7s e(fused) %.3e e(g32) %.3e ratio %.2f" % (obs_dim, B, name, ef, e32, ef / max(e32, 1e-30)))
+        print("%s %-7s e(fused) %.3e e(g32) %.3e ratio %.2f" % (tag, name, ef, e32, ef / max(e32, 1e-30)))
         if not ef <= max(8 * e32, 1e-5):
             worst.append((name, ef, e32))
     assert not worst, worst
-    # loss, pg, vf, max |adv|, max ratio, the clipped fraction: the same bound; no non-finite input; the spare slot
+    # loss, pg, vf, max |adv|, max ratio, the clipped fraction: the same bound
     for j, k in enumerate((0, 1, 2, 3, 4, 6)):
         den = max(abs(float(s64[j])), 1e-30)                         # (a clipped fraction of 0 in a small batch: then exactly 0)
         ef, e32 = abs(float(stats[k] - s64[j])) / den, abs(float(s32[j] - s64[j])) / den
-        print("obs_dim %3d B %4d stats[%d] %.9g fp64 %.9g e(fused) %.3e e(g32) %.3e" % (obs_dim, B, k, float(stats[k]), float(s64[j]), ef, e32))
+        print("%s stats[%d] %.9g fp64 %.9g e(fused) %.3e e(g32) %.3e" % (tag, k, float(stats[k]), float(s64[j]), ef, e32))
         assert ef <= max(8 * e32, 1e-5), (k, float(stats[k]), float(s64[j]), ef, e32)
-    assert float(stats[5]) == 0.0 and float(stats[7]) == 0.0
+    return gf, stats, g64, g32
+
+
+@pytest.mark.parametrize("B", [1, 7, 15, 16, 17, 33, 1000, 4095, 4096])
+@pytest.mark.parametrize("obs_dim", [6, 15, 186])
+def test_gradient_and_stats_match_autograd(obs_dim, B):
+    """B = 1, 15, 17, 33, 4095: a batch of one row; last row tiles of 15 rows and of one row after one, two and 255 full tiles."""
+    net, data, upd = case(obs_dim)
+    torch.manual_seed(100 + B)
+    idx = torch.randperm(N_ROWS, device=DEV)[:B].contiguous()
+    _, stats, _, _ = assert_parity(net, data, upd, idx, "obs_dim %3d B %4d" % (obs_dim, B))
+    assert float(stats[5]) == 0.0 and float(stats[7]) == 0.0         # no non-finite input; the spare slot
     if B >= 1000:
         assert 0.0 < float(stats[6]) < 1.0
 
@@ -180,6 +193,30 @@ def expected_policy_buffer(net, obs_dim):
     return p
 
 
+def assert_adam_step(upd, net, tp, opt, before, step, say=True):
+    """One step of the updater against the same step of torch.optim.Adam on the twin's parameters `tp` (`before`: their values in
+    front of the step), by the rules of test_clip_and_adam_match_torch_and_repack_the_policy_buffer.  Returns the largest
+    difference of a parameter element in ulp."""
+    off, worst = 0, 0.0
+    for p, q, p0 in zip(tp, ordered(net), before):
+        sl = slice(off, off + p.numel())
+        off += p.numel()
+        assert q.data_ptr() == upd.theta[sl].data_ptr() and torch.equal(q.detach().reshape(-1), upd.theta[sl])
+        st = opt.state[p]
+        assert torch.allclose(upd.m[sl], st["exp_avg"].reshape(-1), rtol=2e-6, atol=1e-30), step
+        assert torch.allclose(upd.v[sl], st["exp_avg_sq"].reshape(-1), rtol=2e-6, atol=1e-30), step
+        p1 = p.detach()
+        scale = torch.maximum(torch.maximum(p0.abs(), p1.abs()), (p1 - p0).abs())
+        ulp = torch.exp2(torch.floor(torch.log2(scale.double())) - 23)          # float32 spacing at `scale`
+        n_ulp = (q.detach().double() - p1.double()).abs() / ulp
+        if say:
+            print("step %d %-12s largest difference %.2f ulp, %d of %d elements differ" % (step, tuple(p.shape), float(n_ulp.max()), int((n_ulp > 0).sum()), p.numel()))
+        assert float(n_ulp.max()) <= 2.0, (step, tuple(p.shape), float(n_ulp.max()))
+        worst = max(worst, float(n_ulp.max()))
+    assert off == upd.theta.numel()
+    return worst
+
+
 def test_clip_and_adam_match_torch_and_repack_the_policy_buffer():
     """Three steps on a fixed random gradient (policy group clipped, value group not) against examples/ppo.clip_grad_norm +
     torch.optim.Adam on a twin.  Norms rtol 1e-6, m and v rtol 2e-6, every parameter within 2 ulp of the twin's, PER ELEMENT: the ulp
@@ -217,20 +254,7 @@ def test_clip_and_adam_match_torch_and_repack_the_policy_buffer():
         norms = upd.apply(g).clone()
         assert norms_t[0] > 0.5 > norms_t[1]
         assert torch.allclose(norms, norms_t, rtol=1e-6, atol=0), (norms, norms_t)
-        off = 0
-        for p, q, p0 in zip(tp, ordered(net), before):
-            sl = slice(off, off + p.numel())
-            off += p.numel()
-            assert q.data_ptr() == upd.theta[sl].data_ptr() and torch.equal(q.detach().reshape(-1), upd.theta[sl])
-            st = opt.state[p]
-            assert torch.allclose(upd.m[sl], st["exp_avg"].reshape(-1), rtol=2e-6, atol=1e-30), step
-            assert torch.allclose(upd.v[sl], st["exp_avg_sq"].reshape(-1), rtol=2e-6, atol=1e-30), step
-            p1 = p.detach()
-            scale = torch.maximum(torch.maximum(p0.abs(), p1.abs()), (p1 - p0).abs())
-            ulp = torch.exp2(torch.floor(torch.log2(scale.double())) - 23)          # float32 spacing at `scale`
-            n_ulp = (q.detach().double() - p1.double()).abs() / ulp
-            print("step %d %-12s largest difference %.2f ulp, %d of %d elements differ" % (step, tuple(p.shape), float(n_ulp.max()), int((n_ulp > 0).sum()), p.numel()))
-            assert float(n_ulp.max()) <= 2.0, (step, tuple(p.shape), float(n_ulp.max()))
+        assert_adam_step(upd, net, tp, opt, before, step)
         assert torch.equal(buf, expected_policy_buffer(net, obs_dim)), step
     # the updater's own forward copy follows too: a gradient after the steps is the gradient AT the updated weights
     data = make_data(net, obs_dim, seed=2)
