@@ -359,6 +359,50 @@ class BatchedAuvEnv:
                                           C.c_void_p(rec[2].data_ptr())), "auv_step_multi_record")
         return rec
 
+    def step_feedback(self, gains: torch.Tensor, n_steps: int, ring: Optional[torch.Tensor] = None, first_slot: int = 0, record=None,
+                      record_actions: bool = False):
+        """`n_steps` consecutive steps of every sub-batch in ONE launch per sub-batch with the action chosen INSIDE the launch
+        (auv_step_feedback): the action of a step is the affine feedback law of gym_auv_amd/feedback.py applied to the six
+        navigation columns the step before it left -- a[j] = sum over c of gains[e, j, c] * x[c], x = (obs[0..5], 1, ring action[j]).
+        Bit for bit n_steps step() calls fed by feedback.affine_action.
+
+        `gains`: float64 device tensor [N, 2, 8], or [2, 8] for every environment alike.  `ring`: [slots, N, 2] float32 / float64
+        (column 7's input: step k reads slot (first_slot + k) % slots) or None (that input is 0).  `record`, as step_multi's:
+            None       nothing is recorded, returns None
+            True       returns (obs [T, N, obs_dim] float32, reward [T, N] float32, done [T, N] uint8)
+            "reward"   no observation record: returns (None, reward, done)
+        `record_actions`: the call returns (that, actions [T, N, 2] float64) -- every step's action as the law gave it, before the
+        dynamics' NaN rule and clip.  `self.obs / reward / done` hold the last step's values either way.  Chains and slices as
+        in step_multi: nothing orders the chains against the caller's stream."""
+        from .feedback import check_feedback_args
+        if self._slices is None:
+            self.set_sub_batches(1)
+        T, n = int(n_steps), self.n_envs
+        g = check_feedback_args(n, self.device, gains, T, ring, first_slot, record)
+        with torch.cuda.device(self.device):
+            rec = None
+            if record is not None:
+                rec = (torch.empty((T, n, self.obs_dim), dtype=torch.float32, device=self.device) if record is True else None,
+                       torch.empty((T, n), dtype=torch.float32, device=self.device), torch.empty((T, n), dtype=torch.uint8, device=self.device))
+            act = torch.empty((T, n, 2), dtype=torch.float64, device=self.device) if record_actions else None
+        # (the chains' streams read and write tensors made on the current stream: see step_multi)
+        cur = torch.cuda.current_stream(self.device)
+        for st in self._sub_streams:
+            if st != cur:
+                st.wait_stream(cur)
+                for t in (rec or ()) + (act, g):
+                    if t is not None:
+                        t.record_stream(st)
+
+        def ptr(t):
+            return None if t is None else C.c_void_p(t.data_ptr())
+        dt = _capi.AUV_F64 if (ring is not None and ring.dtype == torch.float64) else _capi.AUV_F32
+        _check(_LIB.auv_step_feedback(self._h, self.sub_batches, self._bounds_c, self._streams_c, ptr(g), ptr(ring), dt,
+                                      1 if ring is None else int(ring.shape[0]), int(first_slot), T, ptr(self.obs), ptr(self.reward), ptr(self.done),
+                                      ptr(rec[0]) if rec else None, ptr(rec[1]) if rec else None, ptr(rec[2]) if rec else None, ptr(act)),
+               "auv_step_feedback")
+        return (rec, act) if record_actions else rec
+
     def set_multi_order(self, order: str = "cohorts", lead: int = 16, lag: int = 30):
         """Workgroup order of step_multi's launches: "cohorts" (default: cohort-pipelined, see include/auv_hip.h) or "steps"."""
         _check(_LIB.auv_set_multi_order(self._h, {"steps": 0, "cohorts": 1}[order], int(lead), int(lag)), "auv_set_multi_order")

@@ -46,6 +46,9 @@ void auv_launch_step_multi(const AuvDev& d, const void* actions, int dtype, floa
                            int n_slots, unsigned long long seq0, int order, int lead, int lag, hipStream_t st);
 void auv_launch_step_record(const AuvDev& d, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, float* obs_rec, float* reward_rec,
                             uint8_t* done_rec, int n_steps, int first_slot, int n_slots, unsigned long long seq0, int order, int lead, int lag, hipStream_t st);
+void auv_launch_step_feedback(const AuvDev& d, const double* gains, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, float* obs_rec,
+                              float* reward_rec, uint8_t* done_rec, double* act_rec, int n_steps, int first_slot, int n_slots, unsigned long long seq0,
+                              int order, int lead, int lag, hipStream_t st);
 void auv_launch_spin(unsigned long long ticks, hipStream_t st);
 void auv_launch_rdv_publish(unsigned long long* word, unsigned long long seq, hipStream_t st);
 void auv_launch_rdv_arrive(unsigned long long* word, hipStream_t st);
@@ -1291,20 +1294,22 @@ int auv_step_pipelined(auv_handle_t* h, int32_t n_slices, const int32_t* bounds,
   return AUV_OK;
 }
 
-// what auv_step_multi and auv_step_multi_record refuse, before anything launches and before any step number is spent
+// what auv_step_multi, auv_step_multi_record and auv_step_feedback refuse, before anything launches and before any step number is spent
+// `ring_optional`: a NULL ring is allowed (auv_step_feedback: x_7 = 0); `state_rc`: the code of the refusals that hang on the handle's
+// configuration (auv_step_feedback reports every refusal as AUV_EINVAL)
 static int check_multi(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const void* actions_dev, int32_t action_dtype,
-                       int32_t n_slots, int32_t first_slot, int32_t n_steps, const char* who) {
-  int rc = check_actions(actions_dev, action_dtype, who);
+                       int32_t n_slots, int32_t first_slot, int32_t n_steps, const char* who, bool ring_optional = false, int state_rc = AUV_ESTATE) {
+  int rc = (ring_optional && !actions_dev) ? AUV_OK : check_actions(actions_dev, action_dtype, who);
   if (rc) return rc;
   rc = check_slices(h, n_slices, bounds, streams, who);
   if (rc) return rc;
   if (n_slots < 1 || first_slot < 0 || first_slot >= n_slots || n_steps < 1 || n_steps > 1024)
     return fail(AUV_EINVAL, "%s: n_slots >= 1, 0 <= first_slot < n_slots, 1 <= n_steps <= 1024", who);
-  if (h->fw.on) return fail(AUV_ESTATE, "%s: not with a fresh world per reset (a slot's tables may be rebuilt beside the launch)", who);
-  if (h->d.k_max > AUV_WAVE) return fail(AUV_ESTATE, "%s: more than 64 obstacles per world", who);
+  if (h->fw.on) return fail(state_rc, "%s: not with a fresh world per reset (a slot's tables may be rebuilt beside the launch)", who);
+  if (h->d.k_max > AUV_WAVE) return fail(state_rc, "%s: more than 64 obstacles per world", who);
   for (int i = 0; i < n_slices; i++) {
     const int ne = bounds[i + 1] - bounds[i];
-    if (effective_mode(h, ne) != AUV_STEP_ONE_LAUNCH) return fail(AUV_ESTATE, "%s: needs the one-launch shape for every slice", who);
+    if (effective_mode(h, ne) != AUV_STEP_ONE_LAUNCH) return fail(state_rc, "%s: needs the one-launch shape for every slice", who);
     // the grid that will be launched, in work-items: the dispatch packet holds a 32-bit count
     const AuvMultiGeom g = auv_multi_geom(ne, n_steps, h->multi_order, h->multi_lead, h->multi_lag);
     if (!auv_multi_fits(g))
@@ -1354,6 +1359,34 @@ int auv_step_multi_record(auv_handle_t* h, int32_t n_slices, const int32_t* boun
     d.e0 = bounds[i], d.ne = bounds[i + 1] - bounds[i];
     auv_launch_step_record(d, actions_dev, action_dtype, obs_dev, reward_dev, done_dev, obs_rec, reward_rec, done_rec, n_steps, first_slot, n_slots, seq0,
                            h->multi_order, h->multi_lead, h->multi_lag, (hipStream_t)streams[i]);
+  }
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+int auv_step_feedback(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const double* gains_dev, const void* actions_dev,
+                      int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev, float* reward_dev, uint8_t* done_dev,
+                      float* obs_rec, float* reward_rec, uint8_t* done_rec, double* act_rec) {
+  REQUIRE_READY(h);
+  if (!gains_dev || ((uintptr_t)gains_dev & 7)) return fail(AUV_EINVAL, "auv_step_feedback: gains_dev must be a non-NULL, 8-byte aligned [N][2][8] fp64 table");
+  if (actions_dev && n_slots < 1) return fail(AUV_EINVAL, "auv_step_feedback: n_slots >= 1 with a ring");
+  if (!actions_dev) n_slots = 1, first_slot = 0, action_dtype = AUV_F32;               // no ring: x_7 = 0, nothing is read
+  const int rc = check_multi(h, n_slices, bounds, streams, actions_dev, action_dtype, n_slots, first_slot, n_steps, "auv_step_feedback", true, AUV_EINVAL);
+  if (rc) return rc;
+  if (!obs_dev || !reward_dev || !done_dev) return fail(AUV_EINVAL, "auv_step_feedback: null obs / reward / done buffer");
+  const int D = auv_obs_cols(h->d.cfg, h->d.pool_ns);                                    // (see auv_step_multi_record)
+  if (obs_rec && ((uintptr_t)obs_rec & ((D & 1) ? 3 : 7)))
+    return fail(AUV_EINVAL, "auv_step_feedback: obs_rec must be %d-byte aligned (observation rows of %d floats)", (D & 1) ? 4 : 8, D);
+  if ((uintptr_t)reward_rec & 3) return fail(AUV_EINVAL, "auv_step_feedback: reward_rec must be 4-byte aligned");
+  if ((uintptr_t)act_rec & 7) return fail(AUV_EINVAL, "auv_step_feedback: act_rec must be 8-byte aligned");
+  PAIR_CHECK(h, obs_dev);
+  const unsigned long long seq0 = h->multi_seq;
+  h->multi_seq += (unsigned long long)n_steps;
+  for (int i = 0; i < n_slices; i++) {
+    AuvDev d = h->d;
+    d.e0 = bounds[i], d.ne = bounds[i + 1] - bounds[i];
+    auv_launch_step_feedback(d, gains_dev, actions_dev, action_dtype, obs_dev, reward_dev, done_dev, obs_rec, reward_rec, done_rec, act_rec, n_steps,
+                             first_slot, n_slots, seq0, h->multi_order, h->multi_lead, h->multi_lag, (hipStream_t)streams[i]);
   }
   HIP_TRY(hipGetLastError());
   return AUV_OK;

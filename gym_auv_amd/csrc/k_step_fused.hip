@@ -700,10 +700,43 @@ __device__ __forceinline__ int carry_wait_wave(const AuvDev& d, const int e, con
   return 0;
 }
 
-template <bool MULTI>
+// ---- the affine feedback law of a closed-loop launch (auv_step_feedback, k_step_feedback) ----
+// Per environment e a gain row G[e][2][8] (fp64); output j (0 thrust, 1 rudder) of step t is
+//     x_c = OBS64[e][c], c = 0..5 (the six navigation columns as step t - 1 left them; after an auto-reset the new episode's reset
+//           row; for the launch's first step what the arrays hold),  x_6 = 1.0,
+//     x_7 = component j of the ring's action in slot (first_slot + t) % n_slots, converted as k1_action converts it (no ring: 0.0),
+//     p_c = G[e][j][c] * x_c,   a_j = ((p_0 + p_1) + (p_2 + p_3)) + ((p_4 + p_5) + (p_6 + p_7))
+// in fp64, FMA contraction off, exactly this association (host mirror: gym_auv_amd/feedback.py, affine_action).  `a` goes to
+// k1_group as `a_in`: the NaN rule and the clip to the action range stay in the dynamics.
+// Lane c of a group of eight owns column c.  The group sum is three DPP adds -- quad_perm [1,0,3,2]: p_2k + p_2k+1; quad_perm
+// [2,3,0,1]: the quad's two pairs; row_half_mirror: the two quads -- which IS the association above in group lane 0, operand order
+// included (the other lanes add the same pairs with the operands swapped: the same bits for numbers); every lane then takes group
+// lane 0's bits.  Called by all 64 lanes.
+__device__ __forceinline__ double fb_group_sum(double p) {
+  p += auv_dpp_f64<0xB1>(p);
+  p += auv_dpp_f64<0x4E>(p);
+  p += auv_dpp_f64<0x141>(p);
+  return k1_group_bcast<0>(p);
+}
+// x: column c of the OBS64 row (lanes c < 6); g0 / g1: G[e][0][c], G[e][1][c]; r0 / r1: the ring's action of the step the law is for
+__device__ __forceinline__ double2 fb_law(const int c, const double x, const double g0, const double g1, const double r0, const double r1) {
+  const double x0 = c < 6 ? x : (c == 6 ? 1.0 : r0), x1 = c < 6 ? x : (c == 6 ? 1.0 : r1);
+  return make_double2(fb_group_sum(g0 * x0), fb_group_sum(g1 * x1));
+}
+// lane c of a group holds word 16 + c of a carry record: do the action words (21, 22) and their mark (23) hold together?
+__device__ __forceinline__ bool fb_record_ok(const unsigned long long v2, const int c, const unsigned long long tagmix) {
+  const unsigned long long x = roles_group_xor((c == 5 || c == 6) ? v2 : 0ull), mark = roles_group_word(v2, 7);
+  return mark != 0ull && roles_mark(x ^ tagmix) == mark;
+}
+
+// FB (k_step_feedback): a step that is not the last also forms the NEXT step's action by the feedback law and hands it over in
+// words 21..23 of the carry record (fb_gains: [N][2][8]; fb_actions / fb_slot: the ring and the next step's slot, or nullptr)
+template <bool MULTI, bool FB = false>
 __device__ __forceinline__ void roles_finish_wave_multi(const AuvDev& dk, const int f, const int lane, float* __restrict__ obs_out,
                                                         float* __restrict__ reward_out, uint8_t* __restrict__ done_out, const int step,
-                                                        const bool last_step, const unsigned long long tagmix, const unsigned long long tagmix_prev MSTAMP_PARAM) {
+                                                        const bool last_step, const unsigned long long tagmix, const unsigned long long tagmix_prev MSTAMP_PARAM,
+                                                        const double* __restrict__ fb_gains = nullptr, const void* __restrict__ fb_actions = nullptr,
+                                                        const int fb_slot = 0) {
   // (roles_finish_wave with the previous step's outcome from the carry record instead of the arrays, and its own outcome into
   // the record at the end; the arithmetic in between is the very same code)
   const __attribute__((address_space(4))) AuvDev* dc = (const __attribute__((address_space(4))) AuvDev*)dk.self;
@@ -888,10 +921,34 @@ __device__ __forceinline__ void roles_finish_wave_multi(const AuvDev& dk, const 
   }
   const unsigned long long ma = roles_mark(roles_group_xor(c < 7 ? w0 : 0ull) ^ tagmix);
   const unsigned long long mb = roles_mark(roles_group_xor(w1) ^ roles_group_xor(c < 4 ? w2 : 0ull) ^ tagmix);
+  unsigned long long w2hi = 0ull;                           // words 21..23 (FB; else written as zero)
+  if constexpr (FB) {
+    // the next step's action.  x_0..5 are read back from the OBS64 row: the tail forms them in group lane 0 and keeps them to
+    // itself, a restored environment's come from its reset row -- either way this wave's own stores, complete (above), so one
+    // agent-scope load past L1 serves both cases.  x_7, the ring's action of step t + 1, is known at launch: it is fetched HERE, in
+    // the same trip as the row and the gains, so that p_6 + p_7 is formed inside the one sum and the association is the law's (the
+    // dynamics wave adding p_7 to a finished sum would be another association).
+    // (the environment's index and the tables laundered / fetched HERE: addresses formed ahead of the restore loop are held across
+    // it in vector registers the wave does not have -- two spilled pairs and a private segment for every wave of the launch)
+    int ef = e;
+    asm volatile("" : "+v"(ef));
+    const AuvDev* dp = dk.self;
+    asm volatile("" : "+s"(dp));
+    const AuvDev& df = *(const AuvDev*)(const __attribute__((address_space(4))) AuvDev*)dp;
+    const int S = df.cfg.n_sensors;
+    const double x = c < 6 ? __hip_atomic_load(df.obs64 + (size_t)ef * (6 + S) + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
+    const double g0 = fb_gains[16 * (size_t)ef + c], g1 = fb_gains[16 * (size_t)ef + 8 + c];
+    double r0 = 0.0, r1 = 0.0;
+    if (fb_actions) k1_action(dk, fb_actions, ef, &r0, &r1, fb_slot);
+    const double2 a = fb_law(c, x, g0, g1, r0, r1);
+    const unsigned long long wa = (unsigned long long)__double_as_longlong(a.x), wb = (unsigned long long)__double_as_longlong(a.y);
+    // (the mark is built like the state line's: a checksum of its payload mixed with the step's number, loaded with it in one request)
+    w2hi = c == 5 ? wa : (c == 6 ? wb : (c == 7 ? roles_mark(wa ^ wb ^ tagmix) : 0ull));
+  }
   if (live) {
     __hip_atomic_store(cw + c, c < 7 ? w0 : ma, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(cw + 8 + c, w1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __hip_atomic_store(cw + 16 + c, c < 4 ? w2 : (c == 4 ? mb : 0ull), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __hip_atomic_store(cw + 16 + c, c < 4 ? w2 : (c == 4 ? mb : w2hi), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
 }
 
@@ -912,7 +969,9 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_multi(AuvD
                                                                            const unsigned long long seq0, const int lead_dyn, const int lag_fin, const unsigned magic_c) {
   AUV_KERNARG_DESC(d);
 #define STEP_MULTI_REC 0
+#define STEP_MULTI_FB 0
 #include "k_step_multi_body.inc"
+#undef STEP_MULTI_FB
 #undef STEP_MULTI_REC
 }
 
@@ -926,8 +985,41 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_record(Auv
                                                                             const unsigned long long done_stride) {
   AUV_KERNARG_DESC(d);
 #define STEP_MULTI_REC 1
+#define STEP_MULTI_FB 0
 #include "k_step_multi_body.inc"
+#undef STEP_MULTI_FB
 #undef STEP_MULTI_REC
+}
+
+// The closed-loop launch (auv_step_feedback): k_step_record whose action of step t is the affine feedback law (fb_law, above) of the
+// OBS64 row step t - 1 left, formed by that step's finish wave and handed to this step's dynamics wave in words 21..23 of the carry
+// record.  A third inclusion of the body, so that the open-loop kernels keep their argument lists and their code.  gains: [N][2][8]
+// fp64; actions: the ring (x_7) or nullptr; act_rec: [n_steps][N][2] fp64 or nullptr.
+__global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_feedback(AuvDev dk, const void* __restrict__ actions, float* __restrict__ obs_out,
+                                                                              float* __restrict__ reward_out, uint8_t* __restrict__ done_out,
+                                                                              const int n_steps, const int first_slot, const int n_slots,
+                                                                              const unsigned long long seq0, const int lead_dyn, const int lag_fin, const unsigned magic_c,
+                                                                              const unsigned long long obs_stride, const unsigned long long reward_stride,
+                                                                              const unsigned long long done_stride, const double* __restrict__ gains,
+                                                                              double* __restrict__ act_rec) {
+  AUV_KERNARG_DESC(d);
+#define STEP_MULTI_REC 1
+#define STEP_MULTI_FB 1
+#include "k_step_multi_body.inc"
+#undef STEP_MULTI_FB
+#undef STEP_MULTI_REC
+}
+
+// Behind a closed-loop launch: k_record_last where any of the three records may be missing (a missing one was written in place)
+__global__ void __launch_bounds__(256) k_feedback_last(const float* __restrict__ obs_last, const float* __restrict__ reward_last,
+                                                       const uint8_t* __restrict__ done_last, float* __restrict__ obs, float* __restrict__ reward,
+                                                       uint8_t* __restrict__ done, const int e0, const int ne, const int D, const int32_t* __restrict__ abort_flag) {
+  if (*abort_flag) return;
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  const size_t o0 = (size_t)e0 * (size_t)D;
+  if (obs_last && i < (size_t)ne * (size_t)D) obs[o0 + i] = obs_last[o0 + i];
+  if (reward_last && i < (size_t)ne) reward[e0 + i] = reward_last[e0 + i];
+  if (done_last && i < (size_t)ne) done[e0 + i] = done_last[e0 + i];
 }
 
 // Behind a recording launch, on its stream: the record's LAST row of the slice [e0, e0 + ne) into the handle-wide obs / reward / done
@@ -1150,6 +1242,29 @@ void auv_launch_step_record(const AuvDev& d0, const void* actions, int dtype, fl
                      reward_rec + last * n, done_rec + last * n, obs, reward, done, d.e0, d.ne, D, d.abort_flag);
 }
 
+// the closed-loop form: the record launch with the gain table, an optional ring and an optional action record; each of the three
+// output records may be missing (that output's every step then goes to obs / reward / done, and nothing is copied for it)
+void auv_launch_step_feedback(const AuvDev& d0, const double* gains, const void* actions, int dtype, float* obs, float* reward, uint8_t* done,
+                              float* obs_rec, float* reward_rec, uint8_t* done_rec, double* act_rec, int n_steps, int first_slot, int n_slots,
+                              unsigned long long seq0, int order, int lead, int lag, hipStream_t st) {
+  AuvDev d = d0;
+  d.act_f64 = dtype == AUV_F64;
+  d.ring_slots = 1;
+  const uint32_t lds = (uint32_t)k2_slice_bytes(d);
+  const AuvMultiGeom g = auv_multi_geom(d.ne, n_steps, order, lead, lag);      // (the host has checked that the grid fits)
+  const dim3 grid((unsigned)auv_multi_grid(g)), block(AUV_WAVE);
+  const int D = auv_obs_cols(d.cfg, d.pool_ns);
+  const unsigned long long n = (unsigned long long)d.n, obs_stride = obs_rec ? n * (unsigned long long)D : 0ull;
+  hipLaunchKernelGGL(k_step_feedback, grid, block, lds, st, d, actions, obs_rec ? obs_rec : obs, reward_rec ? reward_rec : reward,
+                     done_rec ? done_rec : done, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic, obs_stride, reward_rec ? n : 0ull,
+                     done_rec ? n : 0ull, gains, act_rec);
+  if (!obs_rec && !reward_rec && !done_rec) return;
+  const size_t last = (size_t)(n_steps - 1), items = (size_t)d.ne * (size_t)(obs_rec ? D : 1);
+  hipLaunchKernelGGL(k_feedback_last, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, obs_rec ? obs_rec + last * obs_stride : nullptr,
+                     reward_rec ? reward_rec + last * n : nullptr, done_rec ? done_rec + last * n : nullptr, obs, reward, done, d.e0, d.ne, D,
+                     d.abort_flag);
+}
+
 // The stage's capacity for a bank (S, k_max, m_max known): the largest that gives the one-launch step its best occupancy (see
 // k2_lidar.hip) and still leaves room for the search role's chunk list; asked of the runtime, not computed (allocation granule).
 int auv_pick_seg_cap(const AuvDev& d0) {
@@ -1176,6 +1291,8 @@ hipError_t auv_step_fused_prepare(const AuvDev& d) {
   e = hipFuncSetAttribute((const void*)k_step_multi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void*)k_step_record, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute((const void*)k_step_feedback, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)k_step_roles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
 }

@@ -1,6 +1,10 @@
 // k_step_multi_body.inc -- the body of a launch of several steps, included by csrc/k_step_fused.hip once per kernel:
 //   STEP_MULTI_REC 0   k_step_multi   every step writes the same obs / reward / done rows (the last step's remain)
 //   STEP_MULTI_REC 1   k_step_record  step k of the launch writes its rows `k * stride` elements further on: a [T][N] record
+//   STEP_MULTI_FB 1    k_step_feedback (recording on)  the action of step t is the affine feedback law of the OBS64 row step t - 1
+//                      left (fb_law, k_step_fused.hip): step 0's dynamics wave forms it from the arrays, every later step's takes it
+//                      from words 21..23 of the carry record, where the previous step's finish wave has put it.  Further
+//                      parameters: gains ([N][2][8] fp64), act_rec ([T][N][2] fp64 or nullptr); `actions` may be nullptr (x_7 = 0).
 // The includer has declared `d` (AUV_KERNARG_DESC) and the kernel's parameters: actions, obs_out, reward_out, done_out, n_steps,
 // first_slot, n_slots, seq0, lead_dyn, lag_fin, magic_c -- and, recording, obs_stride, reward_stride, done_stride (elements; 0: no
 // record of that output).  The record's offset is wave-uniform (the step is, the strides are kernel arguments): 64-bit scalar
@@ -61,17 +65,37 @@
     // requested ahead of the wait for the carry record (this wave is on every environment's critical path): the flag and the action
     const int ab_early = __hip_atomic_load(d.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     double act0, act1;
+#if STEP_MULTI_FB
+    // (only step 0 forms the law here and needs the ring's action, x_7, for it: later steps' came with the carry record)
+    act0 = act1 = 0.0;
+    if (step == 0 && actions) k1_action(d, actions, eg, &act0, &act1, first_slot % n_slots);
+    unsigned long long v2 = 0ull;
+#else
     k1_action(d, actions, eg, &act0, &act1, (first_slot + step) % n_slots);
+#endif
     if (step == 0) {
       y = d.counters[eg].y + 1;
+#if STEP_MULTI_FB
+      // the arrays, behind the kernel boundary: the OBS64 row and the gains
+      const double x = c < 6 ? d.obs64[(size_t)eg * (6 + d.cfg.n_sensors) + c] : 0.0;
+      const double2 a = fb_law(c, x, gains[16 * (size_t)eg + c], gains[16 * (size_t)eg + 8 + c], act0, act1);
+      act0 = a.x, act1 = a.y;
+#endif
     } else {
       // this environment's state and counters after the previous step: the first line of its carry record
       const unsigned long long* cw = d.carry + CARRY_WORDS * (size_t)eg;
       unsigned long long v = 0ull;
       bool ok = !live;
       for (int polls = 0;; polls++) {
+#if STEP_MULTI_FB
+        // words 16 + c with words c, one more load in the same trip: lanes 5, 6, 7 then hold the action and its mark, and the
+        // record is taken only when BOTH marks belong to the previous step
+        if (!ok) v = __hip_atomic_load(cw + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT), v2 = __hip_atomic_load(cw + 16 + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        ok = !live || (roles_record_ok(v, c, tagmix_prev) && fb_record_ok(v2, c, tagmix_prev));
+#else
         if (!ok) v = __hip_atomic_load(cw + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         ok = !live || roles_record_ok(v, c, tagmix_prev);
+#endif
         if (!__any(!ok)) break;
         if ((polls & 31) == 31 && auv_uniform(__hip_atomic_load(d.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) {
           gave_up = 1;                                                              // (ABORT packets below)
@@ -87,12 +111,19 @@
       }
       y0 = __longlong_as_double((long long)v);
       y = (int)(unsigned)(roles_group_word(v, 6) >> 32) + 1;
+#if STEP_MULTI_FB
+      act0 = roles_group_value(v2, 5), act1 = roles_group_value(v2, 6);
+#endif
     }
     const int aborted = gave_up | auv_uniform(ab_early);
     double t = 0.0;
     MSTAMP_IF(live && c == 0, eg, 11);
     const double2 act = make_double2(act0, act1);
     if (!aborted) t = k1_group(d, actions, eg, lane, step != 0, y0, (first_slot + step) % n_slots, &act);
+#if STEP_MULTI_FB
+    // the action record: `a` as the law gives it (the NaN rule and the clip are the dynamics'); a plain store, never waited for
+    if (act_rec && live && !aborted && c < 2) act_rec[2 * ((size_t)step * (size_t)d.n + (size_t)eg) + c] = c == 0 ? act0 : act1;
+#endif
     unsigned long long* pk = d.k1_pkt + 8 * (size_t)eg;
     const unsigned long long word = aborted ? (c == 6 ? (unsigned long long)ROLES_ABORT_COUNTER : 0ull)
                                             : (c < 6 ? (unsigned long long)__double_as_longlong(t) : (c == 6 ? (unsigned long long)(unsigned)y : 0ull));
@@ -195,6 +226,11 @@
     const bool fst = fer < ne && lane % K1_GROUP == 0;
 #endif
     MSTAMP_IF(fst, d.e0 + fer, 13);
+#if STEP_MULTI_FB
+    roles_finish_wave_multi<true, true>(d, f, lane, obs_out, reward_out, done_out, step, step == n_steps - 1, tagmix, tagmix_prev MSTAMP_ARG, gains,
+                                        actions, (first_slot + step + 1) % n_slots);
+#else
     roles_finish_wave_multi<true>(d, f, lane, obs_out, reward_out, done_out, step, step == n_steps - 1, tagmix, tagmix_prev MSTAMP_ARG);
+#endif
     MSTAMP_IF(fst, d.e0 + fer, 15);
   }

@@ -1,0 +1,109 @@
+"""The affine feedback law of a closed-loop launch (auv_step_feedback / k_step_feedback, BatchedAuvEnv.step_feedback).
+
+Per environment e there is a gain row G[e][2][8] in fp64.  For output j in {0 thrust, 1 rudder} of step t:
+
+    x_c = OBS64[e][c] for c = 0..5   the six navigation columns as step t - 1 left them (after an auto-reset the new episode's
+                                     reset row; for the launch's first step what the arrays hold)
+    x_6 = 1.0
+    x_7 = component j of the ring's action in slot (first_slot + t) % n_slots, as fp64; 0.0 when no ring is passed
+    p_c = G[e][j][c] * x_c
+    a_j = ((p_0 + p_1) + (p_2 + p_3)) + ((p_4 + p_5) + (p_6 + p_7))
+
+in fp64, no fused multiply-add, exactly this association.  `a` is the step's action; the NaN rule and the clip to the action range
+stay in the dynamics.  Column 7 = 1 makes the law a residual on an open-loop sequence, column 7 = 0 pure feedback; columns
+0..6 = 0 with column 7 = 1 is the open-loop launch.
+
+The navigation columns (environment.py:276-280, vessel.py:461-541; each clipped to [-1, 1]):
+
+    0  surge velocity u            1  sway velocity v              2  yaw rate r
+    3  look-ahead heading error: direction of the path at the look-ahead point - heading, wrapped to (-pi, pi]
+    4  heading error: direction from the vessel TO the look-ahead point - heading, wrapped to (-pi, pi]
+    5  cross-track error / 100: positive when the path lies to the left of the vessel (seen along the path)
+
+`affine_action` is the host mirror the GPU tests step one-step launches with: NumPy fp64, the same association, bit for bit the
+kernel's.
+"""
+import numpy as np
+
+N_INPUTS = 8
+COL_U, COL_V, COL_R, COL_LOOKAHEAD_ERR, COL_HEADING_ERR, COL_CROSS_TRACK, COL_BIAS, COL_RING = range(8)
+
+
+def affine_action(obs64_nav, gains, ring_action=None) -> np.ndarray:
+    """a[N, 2] of the law above.  obs64_nav: [N, >= 6] fp64 (the first six columns of OBS64 rows); gains: [N, 2, 8] or [2, 8]
+    fp64; ring_action: [N, 2] (any float dtype, converted to fp64 as the kernels convert an action) or None (x_7 = 0)."""
+    x = np.asarray(obs64_nav, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] < 6:
+        raise ValueError("obs64_nav must be [N, >= 6]")
+    n = x.shape[0]
+    g = np.asarray(gains, dtype=np.float64)
+    if g.shape == (2, N_INPUTS):
+        g = np.broadcast_to(g, (n, 2, N_INPUTS))
+    if g.shape != (n, 2, N_INPUTS):
+        raise ValueError("gains must be [%d, 2, 8] or [2, 8], got %s" % (n, g.shape))
+    if ring_action is None:
+        ring = np.zeros((n, 2), dtype=np.float64)
+    else:
+        ring = np.asarray(ring_action).astype(np.float64)
+        if ring.shape != (n, 2):
+            raise ValueError("ring_action must be [%d, 2]" % n)
+    out = np.empty((n, 2), dtype=np.float64)
+    for j in range(2):
+        xs = np.empty((n, N_INPUTS), dtype=np.float64)
+        xs[:, :6] = x[:, :6]
+        xs[:, 6] = 1.0
+        xs[:, 7] = ring[:, j]
+        p = g[:, j, :] * xs                                    # eight products, each rounded once
+        out[:, j] = ((p[:, 0] + p[:, 1]) + (p[:, 2] + p[:, 3])) + ((p[:, 4] + p[:, 5]) + (p[:, 6] + p[:, 7]))
+    return out
+
+
+def los_gains(thrust, k_heading, k_yaw_rate, k_cross_track=0.0) -> np.ndarray:
+    """The line-of-sight autopilot as a [2, 8] gain row: constant thrust, rudder = -k_heading * e_psi - k_yaw_rate * r with the
+    heading error e_psi = heading - direction to the look-ahead point.  Column 4 of the observation holds -e_psi (target - heading,
+    see the module docstring), so its gain is +k_heading: a positive k_heading turns the vessel towards the look-ahead point, a
+    positive k_yaw_rate damps the turn, a positive k_cross_track steers towards the path.
+        thrust row:  [6] = thrust                                   (the bias column)
+        rudder row:  [2] = -k_yaw_rate   [4] = +k_heading   [5] = +k_cross_track   (column 5 is the error / 100)
+    every other entry 0, column 7 included: pure feedback (residual_gains turns it into a residual)."""
+    g = np.zeros((2, N_INPUTS), dtype=np.float64)
+    g[0, COL_BIAS] = thrust
+    g[1, COL_R] = -float(k_yaw_rate)
+    g[1, COL_HEADING_ERR] = float(k_heading)
+    g[1, COL_CROSS_TRACK] = float(k_cross_track)
+    return g
+
+
+def residual_gains(base) -> np.ndarray:
+    """A copy of `base` ([..., 2, 8]) with column 7 = 1: the ring's action is added to what the law gives."""
+    g = np.array(base, dtype=np.float64, copy=True)
+    if g.shape[-2:] != (2, N_INPUTS):
+        raise ValueError("gains must be [..., 2, 8]")
+    g[..., COL_RING] = 1.0
+    return g
+
+
+def check_feedback_args(n_envs, device, gains, n_steps, ring=None, first_slot=0, record=None):
+    """What BatchedAuvEnv.step_feedback checks before the C call (torch tensors; no GPU needed to evaluate it).  Returns the
+    gain table as a contiguous [N, 2, 8] fp64 tensor."""
+    import torch
+    if not isinstance(gains, torch.Tensor) or gains.dtype != torch.float64 or gains.device != device:
+        raise ValueError("gains must be a float64 tensor on %s" % (device,))
+    if tuple(gains.shape) == (2, N_INPUTS):
+        gains = gains.expand(n_envs, 2, N_INPUTS)
+    if tuple(gains.shape) != (n_envs, 2, N_INPUTS):
+        raise ValueError("gains must have shape (%d, 2, 8) or (2, 8), got %s" % (n_envs, tuple(gains.shape)))
+    gains = gains.contiguous()
+    if int(n_steps) < 1 or int(n_steps) > 1024:
+        raise ValueError("1 <= n_steps <= 1024")
+    if ring is not None:
+        if not isinstance(ring, torch.Tensor) or ring.dim() != 3 or tuple(ring.shape[1:]) != (n_envs, 2) or ring.device != device \
+                or not ring.is_contiguous() or ring.dtype not in (torch.float32, torch.float64) or ring.shape[0] < 1:
+            raise ValueError("ring must be a contiguous [slots, %d, 2] float32 / float64 tensor on %s" % (n_envs, device))
+        if not 0 <= int(first_slot) < ring.shape[0]:
+            raise ValueError("0 <= first_slot < %d" % ring.shape[0])
+    elif int(first_slot) != 0:
+        raise ValueError("first_slot without a ring")
+    if not (record is None or record is True or (isinstance(record, str) and record == "reward")):
+        raise ValueError("record must be None, True or \"reward\"")
+    return gains

@@ -226,6 +226,34 @@ int auv_step_multi_record(auv_handle_t* h, int32_t n_slices, const int32_t* boun
                           int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev, float* reward_dev,
                           uint8_t* done_dev, float* obs_rec, float* reward_rec, uint8_t* done_rec);
 
+/* CLOSED-LOOP launch of several steps: n_steps consecutive step() calls (environment.py:292-347) of every slice in one launch per
+ * slice, the action of every step chosen INSIDE the launch by an affine feedback law of the observation the step before it left.
+ * Per environment e there is a gain row G[e][2][8] in fp64 (gains_dev).  For output j in {0 thrust, 1 rudder} of step t:
+ *     x_c = OBS64[e][c] for c = 0..5: the six navigation columns as step t - 1 left them (after an auto-reset the new episode's
+ *           reset row; for the launch's first step what the arrays hold),
+ *     x_6 = 1.0,
+ *     x_7 = component j of the ring's action in slot (first_slot + t) % n_slots, converted to fp64 as every step converts its
+ *           action; 0.0 when no ring is passed (actions_dev == NULL),
+ *     p_c = G[e][j][c] * x_c,
+ *     a_j = ((p_0 + p_1) + (p_2 + p_3)) + ((p_4 + p_5) + (p_6 + p_7)),
+ * in fp64 with FMA contraction off and exactly this association.  `a` is the step's action: the NaN rule and the clip to the action
+ * range stay where they are, in the dynamics (vessel.py:226-247).  Column 7 = 1 makes the law a residual on an open-loop sequence
+ * (exploration noise, CEM candidates around a controller), column 7 = 0 pure feedback; columns 0..6 = 0 with column 7 = 1 reproduce
+ * auv_step_multi_record bit for bit.  Host mirror: gym_auv_amd/feedback.py, affine_action; the launch is bit for bit n_steps
+ * one-step calls fed by it (tests/test_gpu_feedback.py).  The finish wave of step t forms the action of step t + 1 and hands it to that
+ * step's dynamics wave in three further words of the carry record, checksummed like the state (csrc/k_step_fused.hip,
+ * k_step_feedback); everything else is auv_step_multi_record's launch.
+ *     obs_rec / reward_rec / done_rec   as auv_step_multi_record's, but EACH may be NULL: no record of that output (its every step
+ *                                       is then written to obs_dev / reward_dev / done_dev, which hold the last step's values
+ *                                       afterwards either way)
+ *     act_rec                           [n_steps][N][2] f64 or NULL: `a` of every step, before the NaN rule and the clip
+ * Preconditions are auv_step_multi_record's -- the one-launch shape for every slice, at most 64 obstacles per world, no fresh world
+ * per reset, the dispatch limit, obs_rec's alignment -- plus a non-NULL, 8-byte aligned gains_dev and n_slots >= 1 when a ring is
+ * given; every refusal is AUV_EINVAL, before anything launches or any step number is spent.  Eager only.                       */
+int auv_step_feedback(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const double* gains_dev,
+                      const void* actions_dev, int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev,
+                      float* reward_dev, uint8_t* done_dev, float* obs_rec, float* reward_rec, uint8_t* done_rec, double* act_rec);
+
 /* Workgroup order of auv_step_multi's launches (same results either way).  order 0: step-major (all of step t, role by role, then
  * step t + 1).  order 1 (default): cohort-pipelined -- cohorts of 64 environments; the sweeps of a cohort-step are dispatched `lead`
  * cohort positions behind its dynamics and its finish waves `lag` positions behind the sweeps, so a wave finds its inputs instead of

@@ -1,0 +1,112 @@
+#!/usr/bin/env python3
+"""Closed-loop rate with the action chosen INSIDE a launch of several steps (auv_step_feedback) against the open-loop launch and
+against what a caller had before -- one step() per step with the same law as torch ops on env.obs:
+    python tools/feedback_bench.py [--out profiles/feedback] [--envs 4096] [--steps 1920] [--passes 5]
+4096 x 180 beams, 50 polygons, one chain, 64 steps per launch.  `--passes` alternating passes of
+    (a) open_loop   step_multi(ring, record="reward"): the open-loop kernel
+    (b) feedback    step_feedback(los_gains(...), record="reward"): the line-of-sight autopilot, no ring
+    (c) per_step    obs -> six columns -> the same gain row as two torch matrix-vector products -> step(), once per step
+each warmed by half a pass, timed by the host clock around `--steps` steps ended by a device synchronise.  Writes every figure,
+the library's sha256 and the command to feedback_bench.jsonl and a table to README.md under --out (an ARS curve that
+examples/ars.py left in ars_curve.jsonl there is added to the README)."""
+import argparse
+import hashlib
+import json
+import os
+import sys
+import time
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+import numpy as np  # noqa: E402
+import torch  # noqa: E402
+
+from gym_auv_amd import _capi  # noqa: E402
+from gym_auv_amd.batched_env import BatchedAuvEnv  # noqa: E402
+from gym_auv_amd.config import effective_reference_config  # noqa: E402
+from gym_auv_amd.feedback import los_gains  # noqa: E402
+from gym_auv_amd.world import build_bank_parallel  # noqa: E402
+
+ap = argparse.ArgumentParser()
+ap.add_argument("--out", default="profiles/feedback")
+ap.add_argument("--envs", type=int, default=4096)
+ap.add_argument("--steps", type=int, default=1920)
+ap.add_argument("--passes", type=int, default=5)
+ap.add_argument("--launch", type=int, default=64)
+args = ap.parse_args()
+dev = torch.device("cuda:0")
+n, T, steps = args.envs, args.launch, args.steps
+cfg = effective_reference_config(use_lidar=True)
+bank = build_bank_parallel("polygon_world", 1000 + np.arange(2 * n), procs=16, n_polygons=50)
+ring = torch.rand((T, n, 2), device=dev) * torch.tensor([2.0, 0.3], device=dev) - torch.tensor([1.0, 0.15], device=dev)
+g_np = los_gains(0.7, 0.8, 0.4, 0.5)
+gains = torch.as_tensor(np.broadcast_to(g_np, (n, 2, 8)).copy(), device=dev)
+# (c): the same row in float32 on the float32 observation -- a = W obs[:, :6] + b, what a caller writes in torch
+W = torch.as_tensor(g_np[:, :6], dtype=torch.float32, device=dev).t().contiguous()
+b = torch.as_tensor(g_np[:, 6], dtype=torch.float32, device=dev)
+env = BatchedAuvEnv(cfg, bank, n, device=dev, auto_reset=True)
+env.reset()
+env.set_sub_batches(1)
+
+
+def open_loop(m):
+    for i in range(0, m, T):
+        env.step_multi(ring, 0, T, record="reward")
+
+
+def feedback(m):
+    for i in range(0, m, T):
+        env.step_feedback(gains, T, record="reward")
+
+
+def per_step(m):
+    for i in range(m):
+        env.step(torch.addmm(b, env.obs[:, :6], W))
+
+
+FORMS = (("open_loop", open_loop), ("feedback", feedback), ("per_step", per_step))
+sha = hashlib.sha256(open(_capi.LIB_PATH, "rb").read()).hexdigest()
+rows = []
+for p in range(args.passes):
+    for name, run in FORMS:
+        run(steps // 2)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        run(steps)
+        torch.cuda.synchronize()
+        dt = time.perf_counter() - t0
+        row = dict(form=name, pass_=p, envs=n, beams=env.n_sensors, steps=steps, steps_per_launch=1 if name == "per_step" else T,
+                   rate_M=round(n * steps / dt / 1e6, 2), us_per_step=round(1e6 * dt / steps, 2), health=env.health(), lib_sha256=sha,
+                   command=" ".join(sys.argv))
+        rows.append(row)
+        print(json.dumps(row), flush=True)
+env.close()
+
+os.makedirs(args.out, exist_ok=True)
+with open(os.path.join(args.out, "feedback_bench.jsonl"), "w") as f:
+    for r in rows:
+        f.write(json.dumps(r) + "\n")
+rate = {name: [r["rate_M"] for r in rows if r["form"] == name] for name, _ in FORMS}
+with open(os.path.join(args.out, "README.md"), "w") as f:
+    f.write("# Closed-loop launches: the action chosen inside a launch of several steps\n\n`python %s` on one MI355X, one process: %d "
+            "environments x %d beams, 50 polygons, one chain, %d steps per launch; %d alternating passes, each form warmed by half a pass "
+            "and timed by the host clock over %d steps ended by a synchronise.  Library sha256 `%s`.\n\n"
+            "| form | M env-steps/s per pass | min | max |\n|---|---|---|---|\n" % (" ".join(sys.argv), n, env.n_sensors, T, args.passes, steps, sha))
+    what = dict(open_loop="(a) `step_multi(record=\"reward\")`, open loop", feedback="(b) `step_feedback(los_gains, record=\"reward\")`",
+                per_step="(c) one `step()` per step, the law as torch ops on `env.obs`")
+    for name, _ in FORMS:
+        f.write("| %s | %s | %.1f | %.1f |\n" % (what[name], ", ".join("%.1f" % x for x in rate[name]), min(rate[name]), max(rate[name])))
+    f.write("\n(b) / (a), pass by pass: %s.  Every run of (b) above every run of (c): **%s** (min (b) %.1f, max (c) %.1f).\n\nRaw rows: "
+            "`feedback_bench.jsonl`.\n" % (", ".join("%.3f" % (x / y) for x, y in zip(rate["feedback"], rate["open_loop"])),
+                                           "yes" if min(rate["feedback"]) > max(rate["per_step"]) else "NO", min(rate["feedback"]),
+                                           max(rate["per_step"])))
+    curve = os.path.join(args.out, "ars_curve.jsonl")
+    if os.path.exists(curve):
+        pts = [json.loads(x) for x in open(curve) if x.strip()]
+        its = [p for p in pts if "iteration" in p]
+        f.write("\n## ARS (V1) of a 2 x 7 linear policy, PathFollow (`examples/ars.py`)\n\nOne run, as it came out; no learning result is "
+                "claimed.  `%s`\n\n| iteration | mean return | mean progress | M env-steps/s |\n|---|---|---|---|\n" % pts[0].get("command", ""))
+        keep = sorted(set(list(range(0, len(its), max(1, len(its) // 20))) + [len(its) - 1])) if its else []
+        for i in keep:
+            p = its[i]
+            f.write("| %d | %.3f | %.4f | %.1f |\n" % (p["iteration"], p["mean_return"], p["mean_progress"], p.get("rate_M", float("nan"))))
+        f.write("\nEvery iteration: `ars_curve.jsonl`.\n")
