@@ -7,7 +7,11 @@ P = envs / 2 directions d_k, gives environment k the gain row M + nu d_k and env
 from its reset state), runs `horizon` steps in launches of at most 64, takes every environment's return from the reward / done
 record up to and including its first done (auv_plan_score, group 1, gamma 1) and steps
     M += alpha / (b sigma_R) * sum over the b best directions of (r+ - r-) d_k.
-Prints mean return and mean progress per iteration.  No learning result is promised."""
+Prints mean return and mean progress per iteration.  No learning result is promised.
+    python examples/ars.py --sectors [--out profiles/feedback_sectors/ars_curve.jsonl]
+also searches a 2 x 4 matrix Hs on the LiDAR's four sector inputs (the largest closeness in each of the configuration's 4 x 8
+sectors, step_feedback(..., sector_gains=)): the same directions d_k are drawn for (M, Hs) together, both matrices are perturbed
+and stepped alike.  Hs starts at zero."""
 import argparse
 import json
 import os
@@ -34,6 +38,7 @@ ap.add_argument("--alpha", type=float, default=0.02)
 ap.add_argument("--top", type=float, default=0.25, help="share of the directions an update uses")
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--out", default=None)
+ap.add_argument("--sectors", action="store_true", help="also perturb gains on the LiDAR's sector inputs")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 n, H = args.envs, args.horizon
@@ -52,10 +57,12 @@ gen = torch.Generator(device=dev)
 gen.manual_seed(args.seed)
 M = torch.zeros((2, 7), dtype=torch.float64, device=dev)
 M[0, 6] = 0.5                                               # start: half thrust, rudder amidships
+NS = cfg.vessel.n_sectors                                   # 4 sector inputs; the other 12 columns of the sector gains stay 0
+Hs = torch.zeros((2, NS), dtype=torch.float64, device=dev)
 b = max(1, int(args.top * P))
 log = open(args.out, "w") if args.out else None
 if log:
-    log.write(json.dumps(dict(command=" ".join(sys.argv), envs=n, directions=P, horizon=H, nu=args.nu, alpha=args.alpha, top=b,
+    log.write(json.dumps(dict(command=" ".join(sys.argv), envs=n, directions=P, horizon=H, nu=args.nu, alpha=args.alpha, top=b, sectors=bool(args.sectors),
                               baseline_los_gains=los_gains(0.5, 1.0, 0.5).tolist())) + "\n")
 for it in range(args.iterations):
     t0 = time.perf_counter()
@@ -63,10 +70,16 @@ for it in range(args.iterations):
     gains = torch.zeros((n, 2, 8), dtype=torch.float64, device=dev)
     gains[:P, :, :7] = M + args.nu * d
     gains[P:, :, :7] = M - args.nu * d
+    sgains = None
+    if args.sectors:
+        ds = torch.randn((P, 2, NS), generator=gen, dtype=torch.float64, device=dev)
+        sgains = torch.zeros((n, 2, 16), dtype=torch.float64, device=dev)
+        sgains[:P, :, :NS] = Hs + args.nu * ds
+        sgains[P:, :, :NS] = Hs - args.nu * ds
     env.reset(world_idx=worlds)
     rew, done = [], []
     for t in range(0, H, 64):
-        _, r, dn = env.step_feedback(gains, min(64, H - t), record="reward")
+        _, r, dn = env.step_feedback(gains, min(64, H - t), record="reward", sector_gains=sgains)
         rew.append(r), done.append(dn)
     rew, done = torch.cat(rew).contiguous(), torch.cat(done).contiguous()
     ret, _ = planning.plan_score(env, rew, done, 1, 1.0)
@@ -81,6 +94,8 @@ for it in range(args.iterations):
     top = torch.topk(torch.maximum(rp, rm), b).indices
     sigma = torch.cat([rp[top], rm[top]]).std().clamp_min(1e-8)
     M += args.alpha / (b * sigma) * ((rp[top] - rm[top])[:, None, None] * d[top]).sum(dim=0)
+    if args.sectors:
+        Hs += args.alpha / (b * sigma) * ((rp[top] - rm[top])[:, None, None] * ds[top]).sum(dim=0)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     row = dict(iteration=it, mean_return=float(ret.mean()), best_return=float(ret.max()), mean_progress=float(prog.mean()),
@@ -90,6 +105,6 @@ for it in range(args.iterations):
         log.write(json.dumps(row) + "\n")
         log.flush()
 if log:
-    log.write(json.dumps(dict(final_policy=M.tolist())) + "\n")
+    log.write(json.dumps(dict(final_policy=M.tolist(), final_sector_gains=Hs.tolist() if args.sectors else None)) + "\n")
     log.close()
 env.close()

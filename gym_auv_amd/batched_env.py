@@ -360,7 +360,7 @@ class BatchedAuvEnv:
         return rec
 
     def step_feedback(self, gains: torch.Tensor, n_steps: int, ring: Optional[torch.Tensor] = None, first_slot: int = 0, record=None,
-                      record_actions: bool = False):
+                      record_actions: bool = False, sector_gains: Optional[torch.Tensor] = None, sector_bounds=None):
         """`n_steps` consecutive steps of every sub-batch in ONE launch per sub-batch with the action chosen INSIDE the launch
         (auv_step_feedback): the action of a step is the affine feedback law of gym_auv_amd/feedback.py applied to the six
         navigation columns the step before it left -- a[j] = sum over c of gains[e, j, c] * x[c], x = (obs[0..5], 1, ring action[j]).
@@ -373,12 +373,21 @@ class BatchedAuvEnv:
             "reward"   no observation record: returns (None, reward, done)
         `record_actions`: the call returns (that, actions [T, N, 2] float64) -- every step's action as the law gave it, before the
         dynamics' NaN rule and clip.  `self.obs / reward / done` hold the last step's values either way.  Chains and slices as
-        in step_multi: nothing orders the chains against the caller's stream."""
-        from .feedback import check_feedback_args
+        in step_multi: nothing orders the chains against the caller's stream.
+
+        `sector_gains`: None, or a float64 device tensor [N, 2, 16] ([2, 16]: every environment alike) -- the law then also sees
+        the LiDAR: 16 sector inputs z_k, the largest closeness among the row's closeness columns b[k] <= i < b[k + 1], weighted
+        by these gains and added in their own fixed association (auv_step_feedback_sectors; feedback.sector_action is the
+        mirror).  `sector_bounds`: the table b, K + 1 ascending integers within [0, L], K <= 16 (L: n_sensors, or n_sectors in
+        the feasibility-pooled configuration); None: feedback.default_sector_bounds(config)."""
+        from .feedback import check_feedback_args, check_sector_args
         if self._slices is None:
             self.set_sub_batches(1)
         T, n = int(n_steps), self.n_envs
         g = check_feedback_args(n, self.device, gains, T, ring, first_slot, record)
+        if sector_gains is None and sector_bounds is not None:
+            raise ValueError("sector_bounds without sector_gains")
+        sg, sb = (None, None) if sector_gains is None else check_sector_args(self.config, n, self.device, sector_gains, sector_bounds)
         with torch.cuda.device(self.device):
             rec = None
             if record is not None:
@@ -390,17 +399,24 @@ class BatchedAuvEnv:
         for st in self._sub_streams:
             if st != cur:
                 st.wait_stream(cur)
-                for t in (rec or ()) + (act, g):
+                for t in (rec or ()) + (act, g, sg):
                     if t is not None:
                         t.record_stream(st)
 
         def ptr(t):
             return None if t is None else C.c_void_p(t.data_ptr())
         dt = _capi.AUV_F64 if (ring is not None and ring.dtype == torch.float64) else _capi.AUV_F32
-        _check(_LIB.auv_step_feedback(self._h, self.sub_batches, self._bounds_c, self._streams_c, ptr(g), ptr(ring), dt,
-                                      1 if ring is None else int(ring.shape[0]), int(first_slot), T, ptr(self.obs), ptr(self.reward), ptr(self.done),
-                                      ptr(rec[0]) if rec else None, ptr(rec[1]) if rec else None, ptr(rec[2]) if rec else None, ptr(act)),
-               "auv_step_feedback")
+        if sg is None:
+            _check(_LIB.auv_step_feedback(self._h, self.sub_batches, self._bounds_c, self._streams_c, ptr(g), ptr(ring), dt,
+                                          1 if ring is None else int(ring.shape[0]), int(first_slot), T, ptr(self.obs), ptr(self.reward), ptr(self.done),
+                                          ptr(rec[0]) if rec else None, ptr(rec[1]) if rec else None, ptr(rec[2]) if rec else None, ptr(act)),
+                   "auv_step_feedback")
+        else:
+            _check(_LIB.auv_step_feedback_sectors(self._h, self.sub_batches, self._bounds_c, self._streams_c, ptr(g), ptr(ring), dt,
+                                                  1 if ring is None else int(ring.shape[0]), int(first_slot), T, ptr(self.obs), ptr(self.reward),
+                                                  ptr(self.done), ptr(rec[0]) if rec else None, ptr(rec[1]) if rec else None,
+                                                  ptr(rec[2]) if rec else None, ptr(act), ptr(sg), (C.c_int32 * len(sb))(*[int(v) for v in sb]),
+                                                  len(sb) - 1), "auv_step_feedback_sectors")
         return (rec, act) if record_actions else rec
 
     def set_multi_order(self, order: str = "cohorts", lead: int = 16, lag: int = 30):

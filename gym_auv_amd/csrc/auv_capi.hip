@@ -48,7 +48,7 @@ void auv_launch_step_record(const AuvDev& d, const void* actions, int dtype, flo
                             uint8_t* done_rec, int n_steps, int first_slot, int n_slots, unsigned long long seq0, int order, int lead, int lag, hipStream_t st);
 void auv_launch_step_feedback(const AuvDev& d, const double* gains, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, float* obs_rec,
                               float* reward_rec, uint8_t* done_rec, double* act_rec, int n_steps, int first_slot, int n_slots, unsigned long long seq0,
-                              int order, int lead, int lag, hipStream_t st);
+                              int order, int lead, int lag, hipStream_t st, const double* sector_gains, const int32_t* sector_bounds);
 void auv_launch_spin(unsigned long long ticks, hipStream_t st);
 void auv_launch_rdv_publish(unsigned long long* word, unsigned long long seq, hipStream_t st);
 void auv_launch_rdv_arrive(unsigned long long* word, hipStream_t st);
@@ -1364,21 +1364,37 @@ int auv_step_multi_record(auv_handle_t* h, int32_t n_slices, const int32_t* boun
   return AUV_OK;
 }
 
-int auv_step_feedback(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const double* gains_dev, const void* actions_dev,
-                      int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev, float* reward_dev, uint8_t* done_dev,
-                      float* obs_rec, float* reward_rec, uint8_t* done_rec, double* act_rec) {
+// auv_step_feedback (`sectors` false) and auv_step_feedback_sectors: the same checks and the same launch, the second with the sector
+// gains and the bounds table (padded here to 17 entries with its last one: the sectors past n_sectors are empty ranges)
+static int step_feedback_any(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const double* gains_dev, const void* actions_dev,
+                             int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev, float* reward_dev,
+                             uint8_t* done_dev, float* obs_rec, float* reward_rec, uint8_t* done_rec, double* act_rec, const char* who, bool sectors,
+                             const double* sector_gains_dev, const int32_t* sector_bounds_host, int32_t n_sectors) {
   REQUIRE_READY(h);
-  if (!gains_dev || ((uintptr_t)gains_dev & 7)) return fail(AUV_EINVAL, "auv_step_feedback: gains_dev must be a non-NULL, 8-byte aligned [N][2][8] fp64 table");
-  if (actions_dev && n_slots < 1) return fail(AUV_EINVAL, "auv_step_feedback: n_slots >= 1 with a ring");
+  if (!gains_dev || ((uintptr_t)gains_dev & 7)) return fail(AUV_EINVAL, "%s: gains_dev must be a non-NULL, 8-byte aligned [N][2][8] fp64 table", who);
+  int32_t sb[17];
+  if (sectors) {
+    if (!sector_gains_dev || ((uintptr_t)sector_gains_dev & 7))
+      return fail(AUV_EINVAL, "%s: sector_gains_dev must be a non-NULL, 8-byte aligned [N][2][16] fp64 table", who);
+    if (!sector_bounds_host) return fail(AUV_EINVAL, "%s: null sector_bounds_host", who);
+    if (!h->d.cfg.use_lidar) return fail(AUV_EINVAL, "%s: sector inputs need the LiDAR (use_lidar is off)", who);
+    if (n_sectors < 1 || n_sectors > 16) return fail(AUV_EINVAL, "%s: n_sectors must be 1 .. 16, got %d", who, n_sectors);
+    const int L = h->d.pool_ns ? h->d.pool_ns : h->d.cfg.n_sensors;                    // the row's closeness columns
+    for (int k = 0; k <= n_sectors; k++)
+      if (sector_bounds_host[k] < (k ? sector_bounds_host[k - 1] : 0) || sector_bounds_host[k] > L)
+        return fail(AUV_EINVAL, "%s: sector bounds must be ascending within [0, %d] (entry %d is %d)", who, L, k, sector_bounds_host[k]);
+    for (int k = 0; k < 17; k++) sb[k] = sector_bounds_host[k < n_sectors ? k : n_sectors];
+  }
+  if (actions_dev && n_slots < 1) return fail(AUV_EINVAL, "%s: n_slots >= 1 with a ring", who);
   if (!actions_dev) n_slots = 1, first_slot = 0, action_dtype = AUV_F32;               // no ring: x_7 = 0, nothing is read
-  const int rc = check_multi(h, n_slices, bounds, streams, actions_dev, action_dtype, n_slots, first_slot, n_steps, "auv_step_feedback", true, AUV_EINVAL);
+  const int rc = check_multi(h, n_slices, bounds, streams, actions_dev, action_dtype, n_slots, first_slot, n_steps, who, true, AUV_EINVAL);
   if (rc) return rc;
-  if (!obs_dev || !reward_dev || !done_dev) return fail(AUV_EINVAL, "auv_step_feedback: null obs / reward / done buffer");
+  if (!obs_dev || !reward_dev || !done_dev) return fail(AUV_EINVAL, "%s: null obs / reward / done buffer", who);
   const int D = auv_obs_cols(h->d.cfg, h->d.pool_ns);                                    // (see auv_step_multi_record)
   if (obs_rec && ((uintptr_t)obs_rec & ((D & 1) ? 3 : 7)))
-    return fail(AUV_EINVAL, "auv_step_feedback: obs_rec must be %d-byte aligned (observation rows of %d floats)", (D & 1) ? 4 : 8, D);
-  if ((uintptr_t)reward_rec & 3) return fail(AUV_EINVAL, "auv_step_feedback: reward_rec must be 4-byte aligned");
-  if ((uintptr_t)act_rec & 7) return fail(AUV_EINVAL, "auv_step_feedback: act_rec must be 8-byte aligned");
+    return fail(AUV_EINVAL, "%s: obs_rec must be %d-byte aligned (observation rows of %d floats)", who, (D & 1) ? 4 : 8, D);
+  if ((uintptr_t)reward_rec & 3) return fail(AUV_EINVAL, "%s: reward_rec must be 4-byte aligned", who);
+  if ((uintptr_t)act_rec & 7) return fail(AUV_EINVAL, "%s: act_rec must be 8-byte aligned", who);
   PAIR_CHECK(h, obs_dev);
   const unsigned long long seq0 = h->multi_seq;
   h->multi_seq += (unsigned long long)n_steps;
@@ -1386,10 +1402,26 @@ int auv_step_feedback(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, 
     AuvDev d = h->d;
     d.e0 = bounds[i], d.ne = bounds[i + 1] - bounds[i];
     auv_launch_step_feedback(d, gains_dev, actions_dev, action_dtype, obs_dev, reward_dev, done_dev, obs_rec, reward_rec, done_rec, act_rec, n_steps,
-                             first_slot, n_slots, seq0, h->multi_order, h->multi_lead, h->multi_lag, (hipStream_t)streams[i]);
+                             first_slot, n_slots, seq0, h->multi_order, h->multi_lead, h->multi_lag, (hipStream_t)streams[i],
+                             sectors ? sector_gains_dev : nullptr, sectors ? sb : nullptr);
   }
   HIP_TRY(hipGetLastError());
   return AUV_OK;
+}
+
+int auv_step_feedback(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const double* gains_dev, const void* actions_dev,
+                      int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev, float* reward_dev, uint8_t* done_dev,
+                      float* obs_rec, float* reward_rec, uint8_t* done_rec, double* act_rec) {
+  return step_feedback_any(h, n_slices, bounds, streams, gains_dev, actions_dev, action_dtype, n_slots, first_slot, n_steps, obs_dev, reward_dev, done_dev,
+                           obs_rec, reward_rec, done_rec, act_rec, "auv_step_feedback", false, nullptr, nullptr, 0);
+}
+
+int auv_step_feedback_sectors(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const double* gains_dev,
+                              const void* actions_dev, int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev,
+                              float* reward_dev, uint8_t* done_dev, float* obs_rec, float* reward_rec, uint8_t* done_rec, double* act_rec,
+                              const double* sector_gains_dev, const int32_t* sector_bounds_host, int32_t n_sectors) {
+  return step_feedback_any(h, n_slices, bounds, streams, gains_dev, actions_dev, action_dtype, n_slots, first_slot, n_steps, obs_dev, reward_dev, done_dev,
+                           obs_rec, reward_rec, done_rec, act_rec, "auv_step_feedback_sectors", true, sector_gains_dev, sector_bounds_host, n_sectors);
 }
 
 int auv_set_multi_order(auv_handle_t* h, int32_t order, int32_t lead, int32_t lag) {

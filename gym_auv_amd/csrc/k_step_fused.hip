@@ -729,14 +729,84 @@ __device__ __forceinline__ bool fb_record_ok(const unsigned long long v2, const 
   return mark != 0ull && roles_mark(x ^ tagmix) == mark;
 }
 
-// FB (k_step_feedback): a step that is not the last also forms the NEXT step's action by the feedback law and hands it over in
-// words 21..23 of the carry record (fb_gains: [N][2][8]; fb_actions / fb_slot: the ring and the next step's slot, or nullptr)
-template <bool MULTI, bool FB = false>
+
+// ---- LiDAR sector inputs of the law (auv_step_feedback_sectors, k_step_sector_feedback) ----
+// The OBS64 row's closeness columns (from column 6 on: one per beam, or one per sector in the feasibility-pooled configuration) are
+// cut into at most 16 sectors by a bounds table b[0..16] (the host pads it with its last entry: the sectors past the caller's K are
+// empty ranges); z_k = the maximum of columns b[k] <= i < b[k+1] -- from the first element on with m = v > m ? v : m, +0.0 for an
+// empty range -- and with sector gains H[e][2][16]
+//     q_k = H[e][j][k] * z_k,   u_j = ((q_0 + q_1) + (q_2 + q_3)) + ((q_4 + q_5) + (q_6 + q_7)),   w_j = the same over q_8..q_15,
+//     a_j = s_j + (u_j + w_j),  s_j = fb_law's sum
+// fp64, no FMA, this association (host mirror: gym_auv_amd/feedback.py, sector_action).  Lane c of a group of eight owns sectors c
+// and 8 + c: u_j and w_j are fb_group_sum of its two products, the last two adds are made alike in every lane.
+struct FbBounds {
+  int b[17];
+};
+// lane c's two ranges, (b[c], b[c + 1], b[8 + c], b[9 + c]): the table is a kernel argument by value, wave-uniform, and is taken
+// into scalar registers HERE (laundered: left to itself the compiler selects the OFFSET per lane and gathers the four entries from
+// the argument segment with vector loads, a memory trip in front of the first sector load); the lane's entries are then chains of
+// selects on constant indices
+__device__ __forceinline__ int4 fb_ranges(const FbBounds& sb, const int c) {
+  int b[17];
+#pragma unroll
+  for (int i = 0; i < 17; i++) {
+    b[i] = sb.b[i];
+    asm("" : "+s"(b[i]));
+  }
+  int4 r = make_int4(b[0], b[1], b[8], b[9]);
+#pragma unroll
+  for (int i = 1; i < 8; i++) r.x = c == i ? b[i] : r.x, r.y = c == i ? b[i + 1] : r.y, r.z = c == i ? b[8 + i] : r.z, r.w = c == i ? b[9 + i] : r.w;
+  return r;
+}
+#define FB_SECTOR_BATCH 4   // loads in flight per range and trip; what is loaded is consumed at once: no array of a sector's beams
+// z of this lane's two sectors.  row6: column 6 of the environment's OBS64 row.  COH: agent-scope loads (the finish wave, behind the
+// sweep's pair word and its own store drain), else plain loads (step 0: the arrays, behind the kernel boundary).  Both ranges go
+// through one loop, FB_SECTOR_BATCH columns of each per trip; a trip past a range's end (or an empty range) re-reads a column of
+// the row -- its last one, or column 6 -- and drops it, so every address stays inside the row and no load sits under a branch.  The
+// maximum of a range is taken in ascending column order; a column read twice changes nothing.
+template <bool COH>
+__device__ __forceinline__ double2 fb_sector_pair(const double* __restrict__ row6_, const int4 rg) {
+  // (a global address: through the descriptor's generic pointer these would be flat loads, which count against the LDS counter too)
+  const __attribute__((address_space(1))) double* row6 = (const __attribute__((address_space(1))) double*)row6_;
+  const int lo0 = rg.x, hi0 = rg.y, lo1 = rg.z, hi1 = rg.w;
+  double m0 = 0.0, m1 = 0.0;
+  for (int i0 = lo0, i1 = lo1; __any(i0 < hi0 || i1 < hi1); i0 += FB_SECTOR_BATCH, i1 += FB_SECTOR_BATCH) {
+    const bool on0 = i0 < hi0, on1 = i1 < hi1;
+    double v0[FB_SECTOR_BATCH], v1[FB_SECTOR_BATCH];
+#pragma unroll
+    for (int k = 0; k < FB_SECTOR_BATCH; k++) {
+      const int j0 = on0 ? (i0 + k < hi0 ? i0 + k : hi0 - 1) : 0, j1 = on1 ? (i1 + k < hi1 ? i1 + k : hi1 - 1) : 0;
+      if constexpr (COH) {
+        v0[k] = __hip_atomic_load(row6 + j0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        v1[k] = __hip_atomic_load(row6 + j1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      } else {
+        v0[k] = row6[j0], v1[k] = row6[j1];
+      }
+    }
+    double n0 = i0 == lo0 ? v0[0] : (v0[0] > m0 ? v0[0] : m0), n1 = i1 == lo1 ? v1[0] : (v1[0] > m1 ? v1[0] : m1);
+#pragma unroll
+    for (int k = 1; k < FB_SECTOR_BATCH; k++) n0 = v0[k] > n0 ? v0[k] : n0, n1 = v1[k] > n1 ? v1[k] : n1;
+    m0 = on0 ? n0 : m0, m1 = on1 ? n1 : m1;
+  }
+  return make_double2(m0, m1);
+}
+// s: fb_law's sums; z: this lane's two sector inputs; h0 / h1: H[e][0][c], H[e][0][8 + c] / H[e][1][c], H[e][1][8 + c]
+__device__ __forceinline__ double2 fb_law_sectors(const double2 s, const double2 z, const double2 h0, const double2 h1) {
+  const double u0 = fb_group_sum(h0.x * z.x), w0 = fb_group_sum(h0.y * z.y);
+  const double u1 = fb_group_sum(h1.x * z.x), w1 = fb_group_sum(h1.y * z.y);
+  return make_double2(s.x + (u0 + w0), s.y + (u1 + w1));
+}
+
+// FB (k_step_feedback: 1, k_step_sector_feedback: 2): a step that is not the last also forms the NEXT step's action by the feedback
+// law and hands it over in words 21..23 of the carry record (fb_gains: [N][2][8]; fb_actions / fb_slot: the ring and the next step's
+// slot, or nullptr; FB 2: fb_sgains, [N][2][16], and fb_sb, the sector bounds)
+template <bool MULTI, int FB = 0>
 __device__ __forceinline__ void roles_finish_wave_multi(const AuvDev& dk, const int f, const int lane, float* __restrict__ obs_out,
                                                         float* __restrict__ reward_out, uint8_t* __restrict__ done_out, const int step,
                                                         const bool last_step, const unsigned long long tagmix, const unsigned long long tagmix_prev MSTAMP_PARAM,
                                                         const double* __restrict__ fb_gains = nullptr, const void* __restrict__ fb_actions = nullptr,
-                                                        const int fb_slot = 0) {
+                                                        const int fb_slot = 0, const double* __restrict__ fb_sgains = nullptr,
+                                                        const FbBounds* fb_sb = nullptr) {
   // (roles_finish_wave with the previous step's outcome from the carry record instead of the arrays, and its own outcome into
   // the record at the end; the arithmetic in between is the very same code)
   const __attribute__((address_space(4))) AuvDev* dc = (const __attribute__((address_space(4))) AuvDev*)dk.self;
@@ -940,7 +1010,16 @@ __device__ __forceinline__ void roles_finish_wave_multi(const AuvDev& dk, const 
     const double g0 = fb_gains[16 * (size_t)ef + c], g1 = fb_gains[16 * (size_t)ef + 8 + c];
     double r0 = 0.0, r1 = 0.0;
     if (fb_actions) k1_action(dk, fb_actions, ef, &r0, &r1, fb_slot);
-    const double2 a = fb_law(c, x, g0, g1, r0, r1);
+    double2 a = fb_law(c, x, g0, g1, r0, r1);
+    if constexpr (FB == 2) {
+      // the sector inputs: the closeness columns of the same row.  The sweep stored them write-through and drained them before it
+      // published the pair word this wave has polled (k2_back, pair_publish_lidar); a restored environment's are this wave's own
+      // completed stores -- agent-scope loads past L1 serve both, like x above.  Addresses from the laundered index and descriptor.
+      const double* hp = fb_sgains + 32 * (size_t)ef + c;
+      const double2 h0 = make_double2(hp[0], hp[8]), h1 = make_double2(hp[16], hp[24]);      // (requested ahead of the sector loop)
+      const double2 z = fb_sector_pair<true>(df.obs64 + (size_t)ef * (6 + S) + 6, fb_ranges(*fb_sb, c));
+      a = fb_law_sectors(a, z, h0, h1);
+    }
     const unsigned long long wa = (unsigned long long)__double_as_longlong(a.x), wb = (unsigned long long)__double_as_longlong(a.y);
     // (the mark is built like the state line's: a checksum of its payload mixed with the step's number, loaded with it in one request)
     w2hi = c == 5 ? wa : (c == 6 ? wb : (c == 7 ? roles_mark(wa ^ wb ^ tagmix) : 0ull));
@@ -1005,6 +1084,25 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_feedback(A
   AUV_KERNARG_DESC(d);
 #define STEP_MULTI_REC 1
 #define STEP_MULTI_FB 1
+#include "k_step_multi_body.inc"
+#undef STEP_MULTI_FB
+#undef STEP_MULTI_REC
+}
+
+// The closed-loop launch with LiDAR sector inputs (auv_step_feedback_sectors): k_step_feedback whose law also sees the closeness
+// columns of the OBS64 row, as at most 16 sector maxima (fb_sector_pair, fb_law_sectors).  A fourth inclusion of the body: the other
+// three keep their argument lists and their code.  sgains: [N][2][16] fp64; sb: the bounds, by value (wave-uniform: scalar registers).
+__global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_sector_feedback(AuvDev dk, const void* __restrict__ actions, float* __restrict__ obs_out,
+                                                                                      float* __restrict__ reward_out, uint8_t* __restrict__ done_out,
+                                                                                      const int n_steps, const int first_slot, const int n_slots,
+                                                                                      const unsigned long long seq0, const int lead_dyn, const int lag_fin, const unsigned magic_c,
+                                                                                      const unsigned long long obs_stride, const unsigned long long reward_stride,
+                                                                                      const unsigned long long done_stride, const double* __restrict__ gains,
+                                                                                      double* __restrict__ act_rec, const double* __restrict__ sgains,
+                                                                                      const FbBounds sb) {
+  AUV_KERNARG_DESC(d);
+#define STEP_MULTI_REC 1
+#define STEP_MULTI_FB 2
 #include "k_step_multi_body.inc"
 #undef STEP_MULTI_FB
 #undef STEP_MULTI_REC
@@ -1244,9 +1342,11 @@ void auv_launch_step_record(const AuvDev& d0, const void* actions, int dtype, fl
 
 // the closed-loop form: the record launch with the gain table, an optional ring and an optional action record; each of the three
 // output records may be missing (that output's every step then goes to obs / reward / done, and nothing is copied for it)
+// (sector_gains / sector_bounds: nullptr, or [N][2][16] fp64 and the table of 17 -- k_step_sector_feedback is launched instead)
 void auv_launch_step_feedback(const AuvDev& d0, const double* gains, const void* actions, int dtype, float* obs, float* reward, uint8_t* done,
                               float* obs_rec, float* reward_rec, uint8_t* done_rec, double* act_rec, int n_steps, int first_slot, int n_slots,
-                              unsigned long long seq0, int order, int lead, int lag, hipStream_t st) {
+                              unsigned long long seq0, int order, int lead, int lag, hipStream_t st, const double* sector_gains,
+                              const int32_t* sector_bounds) {
   AuvDev d = d0;
   d.act_f64 = dtype == AUV_F64;
   d.ring_slots = 1;
@@ -1255,9 +1355,17 @@ void auv_launch_step_feedback(const AuvDev& d0, const double* gains, const void*
   const dim3 grid((unsigned)auv_multi_grid(g)), block(AUV_WAVE);
   const int D = auv_obs_cols(d.cfg, d.pool_ns);
   const unsigned long long n = (unsigned long long)d.n, obs_stride = obs_rec ? n * (unsigned long long)D : 0ull;
-  hipLaunchKernelGGL(k_step_feedback, grid, block, lds, st, d, actions, obs_rec ? obs_rec : obs, reward_rec ? reward_rec : reward,
-                     done_rec ? done_rec : done, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic, obs_stride, reward_rec ? n : 0ull,
-                     done_rec ? n : 0ull, gains, act_rec);
+  if (sector_gains) {
+    FbBounds sb;
+    for (int i = 0; i < 17; i++) sb.b[i] = sector_bounds[i];
+    hipLaunchKernelGGL(k_step_sector_feedback, grid, block, lds, st, d, actions, obs_rec ? obs_rec : obs, reward_rec ? reward_rec : reward,
+                       done_rec ? done_rec : done, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic, obs_stride, reward_rec ? n : 0ull,
+                       done_rec ? n : 0ull, gains, act_rec, sector_gains, sb);
+  } else {
+    hipLaunchKernelGGL(k_step_feedback, grid, block, lds, st, d, actions, obs_rec ? obs_rec : obs, reward_rec ? reward_rec : reward,
+                       done_rec ? done_rec : done, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic, obs_stride, reward_rec ? n : 0ull,
+                       done_rec ? n : 0ull, gains, act_rec);
+  }
   if (!obs_rec && !reward_rec && !done_rec) return;
   const size_t last = (size_t)(n_steps - 1), items = (size_t)d.ne * (size_t)(obs_rec ? D : 1);
   hipLaunchKernelGGL(k_feedback_last, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, obs_rec ? obs_rec + last * obs_stride : nullptr,
@@ -1293,6 +1401,8 @@ hipError_t auv_step_fused_prepare(const AuvDev& d) {
   e = hipFuncSetAttribute((const void*)k_step_record, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void*)k_step_feedback, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute((const void*)k_step_sector_feedback, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)k_step_roles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
 }

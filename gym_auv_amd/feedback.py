@@ -22,10 +22,31 @@ The navigation columns (environment.py:276-280, vessel.py:461-541; each clipped 
 
 `affine_action` is the host mirror the GPU tests step one-step launches with: NumPy fp64, the same association, bit for bit the
 kernel's.
+
+LiDAR sector inputs (auv_step_feedback_sectors / k_step_sector_feedback, step_feedback(..., sector_gains=)).  The same OBS64 row
+carries L closeness columns from column 6 on: L = n_sensors in the plain configuration, n_sectors in the feasibility-pooled one.
+A bounds table b[0..K], 1 <= K <= 16, 0 <= b[0] <= b[1] <= ... <= b[K] <= L, cuts them into sectors:
+
+    z_k = max of OBS64[e][6 + i] over b[k] <= i < b[k+1]    the closeness of the nearest return in sector k, k < K: from the first
+                                                            element on with m = v > m ? v : m (a closeness is never NaN);
+                                                            +0.0 for an empty range
+    z_k = +0.0 for K <= k < 16
+
+Default bounds: plain, pooling.sector_starts(n_sectors, n_sensors_per_sector) -- the reference's own sigmoid partition, needs
+n_sectors <= 16; pooled, arange(n_sectors + 1): z_k is the pooled column itself.  With sector gains H[e][2][16] in fp64, output j is
+
+    s_j = the eight-term sum above (unchanged, same association)
+    q_k = H[e][j][k] * z_k
+    u_j = ((q_0 + q_1) + (q_2 + q_3)) + ((q_4 + q_5) + (q_6 + q_7))
+    w_j = the same association over q_8 ... q_15
+    a_j = s_j + (u_j + w_j)
+
+fp64, no fused multiply-add, exactly this association.  `sector_action` is its host mirror.
 """
 import numpy as np
 
 N_INPUTS = 8
+N_SECTOR_INPUTS = 16
 COL_U, COL_V, COL_R, COL_LOOKAHEAD_ERR, COL_HEADING_ERR, COL_CROSS_TRACK, COL_BIAS, COL_RING = range(8)
 
 
@@ -55,6 +76,77 @@ def affine_action(obs64_nav, gains, ring_action=None) -> np.ndarray:
         xs[:, 7] = ring[:, j]
         p = g[:, j, :] * xs                                    # eight products, each rounded once
         out[:, j] = ((p[:, 0] + p[:, 1]) + (p[:, 2] + p[:, 3])) + ((p[:, 4] + p[:, 5]) + (p[:, 6] + p[:, 7]))
+    return out
+
+
+def _lidar_columns(cfg) -> int:
+    """L: the LiDAR closeness columns of an OBS64 row."""
+    v = cfg.vessel
+    return int(v.n_sectors if v.feasibility_pooled else v.n_sensors)
+
+
+def default_sector_bounds(cfg) -> np.ndarray:
+    """The bounds table [K + 1] (int32) a closed-loop launch with sector inputs uses when its caller gives none: the reference's
+    sigmoid sector partition over the beams (plain), one pooled column per sector (feasibility-pooled)."""
+    from .pooling import sector_starts
+    v = cfg.vessel
+    if not v.use_lidar:
+        raise ValueError("sector inputs need the LiDAR (use_lidar is off)")
+    if not 1 <= v.n_sectors <= N_SECTOR_INPUTS:
+        raise ValueError("default sector bounds need 1 <= n_sectors <= %d, got %d" % (N_SECTOR_INPUTS, v.n_sectors))
+    if v.feasibility_pooled:
+        return np.arange(v.n_sectors + 1, dtype=np.int32)
+    return sector_starts(v.n_sectors, v.n_sensors_per_sector).astype(np.int32)
+
+
+def check_sector_bounds(bounds, n_columns) -> np.ndarray:
+    """`bounds` as an int32 array [K + 1], 1 <= K <= 16, ascending within [0, n_columns]; ValueError otherwise."""
+    b = np.asarray(bounds)
+    if b.ndim != 1 or not np.issubdtype(b.dtype, np.integer) or not 2 <= b.size <= N_SECTOR_INPUTS + 1:
+        raise ValueError("sector_bounds must be a 1-D integer table of K + 1 entries, 1 <= K <= %d" % N_SECTOR_INPUTS)
+    b = b.astype(np.int64)
+    if b[0] < 0 or b[-1] > int(n_columns) or (np.diff(b) < 0).any():
+        raise ValueError("sector_bounds must be ascending within [0, %d], got %s" % (int(n_columns), b.tolist()))
+    return b.astype(np.int32)
+
+
+def sector_inputs(obs64_rows, bounds) -> np.ndarray:
+    """z[N, 16] of the module docstring.  obs64_rows: [N, 6 + L] fp64 (whole OBS64 rows, or their first 6 + L columns); bounds:
+    [K + 1]."""
+    x = np.asarray(obs64_rows, dtype=np.float64)
+    if x.ndim != 2 or x.shape[1] < 6:
+        raise ValueError("obs64_rows must be [N, >= 6]")
+    b = check_sector_bounds(bounds, x.shape[1] - 6)
+    z = np.zeros((x.shape[0], N_SECTOR_INPUTS), dtype=np.float64)
+    for k in range(b.size - 1):
+        lo, hi = int(b[k]), int(b[k + 1])
+        if lo < hi:
+            m = x[:, 6 + lo].copy()
+            for i in range(lo + 1, hi):
+                v = x[:, 6 + i]
+                m = np.where(v > m, v, m)
+            z[:, k] = m
+    return z
+
+
+def sector_action(obs64_rows, gains, sector_gains, bounds, ring_action=None) -> np.ndarray:
+    """a[N, 2] of the law with sector inputs: NumPy fp64, the same association, bit for bit the kernel's.  sector_gains:
+    [N, 2, 16] or [2, 16] fp64; the rest as affine_action's and sector_inputs'."""
+    x = np.asarray(obs64_rows, dtype=np.float64)
+    z = sector_inputs(x, bounds)
+    n = x.shape[0]
+    h = np.asarray(sector_gains, dtype=np.float64)
+    if h.shape == (2, N_SECTOR_INPUTS):
+        h = np.broadcast_to(h, (n, 2, N_SECTOR_INPUTS))
+    if h.shape != (n, 2, N_SECTOR_INPUTS):
+        raise ValueError("sector_gains must be [%d, 2, 16] or [2, 16], got %s" % (n, h.shape))
+    s = affine_action(x, gains, ring_action)
+    out = np.empty((n, 2), dtype=np.float64)
+    for j in range(2):
+        q = h[:, j, :] * z                                     # sixteen products, each rounded once
+        u = ((q[:, 0] + q[:, 1]) + (q[:, 2] + q[:, 3])) + ((q[:, 4] + q[:, 5]) + (q[:, 6] + q[:, 7]))
+        w = ((q[:, 8] + q[:, 9]) + (q[:, 10] + q[:, 11])) + ((q[:, 12] + q[:, 13]) + (q[:, 14] + q[:, 15]))
+        out[:, j] = s[:, j] + (u + w)
     return out
 
 
@@ -107,3 +199,19 @@ def check_feedback_args(n_envs, device, gains, n_steps, ring=None, first_slot=0,
     if not (record is None or record is True or (isinstance(record, str) and record == "reward")):
         raise ValueError("record must be None, True or \"reward\"")
     return gains
+
+
+def check_sector_args(cfg, n_envs, device, sector_gains, sector_bounds=None):
+    """What BatchedAuvEnv.step_feedback checks of its sector arguments before the C call (no GPU needed to evaluate it).  Returns
+    (the sector gains as a contiguous [N, 2, 16] fp64 tensor, the bounds as an int32 array [K + 1])."""
+    import torch
+    if not cfg.vessel.use_lidar:
+        raise ValueError("sector_gains need the LiDAR (use_lidar is off)")
+    if not isinstance(sector_gains, torch.Tensor) or sector_gains.dtype != torch.float64 or sector_gains.device != device:
+        raise ValueError("sector_gains must be a float64 tensor on %s" % (device,))
+    if tuple(sector_gains.shape) == (2, N_SECTOR_INPUTS):
+        sector_gains = sector_gains.expand(n_envs, 2, N_SECTOR_INPUTS)
+    if tuple(sector_gains.shape) != (n_envs, 2, N_SECTOR_INPUTS):
+        raise ValueError("sector_gains must have shape (%d, 2, 16) or (2, 16), got %s" % (n_envs, tuple(sector_gains.shape)))
+    bounds = default_sector_bounds(cfg) if sector_bounds is None else check_sector_bounds(sector_bounds, _lidar_columns(cfg))
+    return sector_gains.contiguous(), bounds

@@ -254,6 +254,30 @@ int auv_step_feedback(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, 
                       const void* actions_dev, int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev,
                       float* reward_dev, uint8_t* done_dev, float* obs_rec, float* reward_rec, uint8_t* done_rec, double* act_rec);
 
+/* auv_step_feedback with LiDAR SECTOR inputs in the law: n_steps consecutive step() calls (environment.py:292-347) in one launch per
+ * slice, the action of every step formed inside the launch from the navigation columns AND the closeness columns of the observation
+ * the step before it left (Vessel.perceive's row, sensor.py:140-159; the sectors are the reference's own partition of the beams,
+ * utils/sector_partitioning.py:4-9, sensor.py:197, unless the caller gives another).  The OBS64 row holds L closeness columns from
+ * column 6 on: L = n_sensors, or the number of sectors in the feasibility-pooled configuration.  sector_bounds_host is a table
+ * b[0 .. n_sectors], 1 <= n_sectors <= 16, 0 <= b[0] <= b[1] <= ... <= b[n_sectors] <= L, read during the call (host memory):
+ *     z_k = max of OBS64[e][6 + i] over b[k] <= i < b[k+1]  (from the range's first element on with m = v > m ? v : m; +0.0 for an
+ *           empty range) for k < n_sectors, +0.0 for n_sectors <= k < 16,
+ *     q_k = H[e][j][k] * z_k with the sector gains H[e][2][16] in fp64 (sector_gains_dev),
+ *     u_j = ((q_0 + q_1) + (q_2 + q_3)) + ((q_4 + q_5) + (q_6 + q_7)),   w_j = the same association over q_8 .. q_15,
+ *     a_j = s_j + (u_j + w_j),   s_j = auv_step_feedback's eight-term sum, unchanged,
+ * fp64, FMA contraction off, exactly this association.  Host mirror: gym_auv_amd/feedback.py, sector_action; the launch is bit for
+ * bit n_steps one-step calls fed by it (tests/test_gpu_feedback_sectors.py).  The finish wave of step t reads the closeness columns
+ * where it reads columns 0..5 -- behind the sweep's pair word and its own store drain -- lane c of a group of eight taking the
+ * maxima of sectors c and 8 + c (csrc/k_step_fused.hip, k_step_sector_feedback); the hand-over of the action is
+ * auv_step_feedback's, and so is every other argument.
+ * Preconditions are auv_step_feedback's plus: the LiDAR on (use_lidar), a non-NULL, 8-byte aligned sector_gains_dev, a non-NULL
+ * sector_bounds_host, n_sectors and the bounds as above; every refusal is AUV_EINVAL, before anything launches or any step number
+ * is spent.  Eager only.                                                                                                        */
+int auv_step_feedback_sectors(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const double* gains_dev,
+                              const void* actions_dev, int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps,
+                              float* obs_dev, float* reward_dev, uint8_t* done_dev, float* obs_rec, float* reward_rec, uint8_t* done_rec,
+                              double* act_rec, const double* sector_gains_dev, const int32_t* sector_bounds_host, int32_t n_sectors);
+
 /* Workgroup order of auv_step_multi's launches (same results either way).  order 0: step-major (all of step t, role by role, then
  * step t + 1).  order 1 (default): cohort-pipelined -- cohorts of 64 environments; the sweeps of a cohort-step are dispatched `lead`
  * cohort positions behind its dynamics and its finish waves `lag` positions behind the sweeps, so a wave finds its inputs instead of

@@ -8,7 +8,13 @@ against what a caller had before -- one step() per step with the same law as tor
     (c) per_step    obs -> six columns -> the same gain row as two torch matrix-vector products -> step(), once per step
 each warmed by half a pass, timed by the host clock around `--steps` steps ended by a device synchronise.  Writes every figure,
 the library's sha256 and the command to feedback_bench.jsonl and a table to README.md under --out (an ARS curve that
-examples/ars.py left in ars_curve.jsonl there is added to the README)."""
+examples/ars.py left in ars_curve.jsonl there is added to the README).
+    python tools/feedback_bench.py --sectors [--out profiles/feedback_sectors]
+measures instead, in the same alternating passes, (b) against
+    (d) feedback_sectors   step_feedback(los_gains(...), sector_gains=..., record="reward"): the same autopilot with the LiDAR's
+                           sector inputs in the law (auv_step_feedback_sectors; the reference's 9 x 20 partition, every sector gain
+                           non-zero: the rudder steers away from the side of the nearest return, the thrust drops with it)
+and writes the rows to feedback_sectors_bench.jsonl and the ranges and their ratio to feedback_sectors_bench.md under --out."""
 import argparse
 import hashlib
 import json
@@ -27,12 +33,15 @@ from gym_auv_amd.feedback import los_gains  # noqa: E402
 from gym_auv_amd.world import build_bank_parallel  # noqa: E402
 
 ap = argparse.ArgumentParser()
-ap.add_argument("--out", default="profiles/feedback")
+ap.add_argument("--out", default=None)
+ap.add_argument("--sectors", action="store_true", help="measure the launch with sector inputs against the one without")
 ap.add_argument("--envs", type=int, default=4096)
 ap.add_argument("--steps", type=int, default=1920)
 ap.add_argument("--passes", type=int, default=5)
 ap.add_argument("--launch", type=int, default=64)
 args = ap.parse_args()
+if args.out is None:
+    args.out = "profiles/feedback_sectors" if args.sectors else "profiles/feedback"
 dev = torch.device("cuda:0")
 n, T, steps = args.envs, args.launch, args.steps
 cfg = effective_reference_config(use_lidar=True)
@@ -58,12 +67,28 @@ def feedback(m):
         env.step_feedback(gains, T, record="reward")
 
 
+# (d): every sector gain non-zero -- rudder away from the side of the nearest return (the first sectors are to starboard: the beams
+# run from -pi to pi, sensor.py:110), thrust down with any return
+h_np = np.zeros((2, 16))
+ns = cfg.vessel.n_sectors
+h_np[0, :ns] = -0.3 / ns
+h_np[1, :ns] = np.where(np.arange(ns) < ns / 2.0, 0.1, -0.1)
+sector_gains = torch.as_tensor(np.broadcast_to(h_np, (n, 2, 16)).copy(), device=dev)
+
+
+def feedback_sectors(m):
+    for i in range(0, m, T):
+        env.step_feedback(gains, T, record="reward", sector_gains=sector_gains)
+
+
 def per_step(m):
     for i in range(m):
         env.step(torch.addmm(b, env.obs[:, :6], W))
 
 
 FORMS = (("open_loop", open_loop), ("feedback", feedback), ("per_step", per_step))
+if args.sectors:
+    FORMS = (("feedback", feedback), ("feedback_sectors", feedback_sectors))
 sha = hashlib.sha256(open(_capi.LIB_PATH, "rb").read()).hexdigest()
 rows = []
 for p in range(args.passes):
@@ -82,6 +107,18 @@ for p in range(args.passes):
 env.close()
 
 os.makedirs(args.out, exist_ok=True)
+if args.sectors:
+    with open(os.path.join(args.out, "feedback_sectors_bench.jsonl"), "w") as f:
+        for r in rows:
+            f.write(json.dumps(r) + "\n")
+    a, b_ = [r["rate_M"] for r in rows if r["form"] == "feedback"], [r["rate_M"] for r in rows if r["form"] == "feedback_sectors"]
+    with open(os.path.join(args.out, "feedback_sectors_bench.md"), "w") as f:
+        f.write("`python %s`: %d environments x %d beams, %d steps per launch, %d alternating passes over %d steps.  Library sha256 `%s`.\n\n"
+                "| form | M env-steps/s per pass | min | max |\n|---|---|---|---|\n" % (" ".join(sys.argv), n, env.n_sensors, T, args.passes, steps, sha))
+        f.write("| `step_feedback(los_gains, record=\"reward\")` | %s | %.1f | %.1f |\n" % (", ".join("%.1f" % x for x in a), min(a), max(a)))
+        f.write("| `step_feedback(los_gains, sector_gains=..., record=\"reward\")` | %s | %.1f | %.1f |\n" % (", ".join("%.1f" % x for x in b_), min(b_), max(b_)))
+        f.write("\nsectors / without, pass by pass: %s.\n" % ", ".join("%.3f" % (y / x) for x, y in zip(a, b_)))
+    sys.exit(0)
 with open(os.path.join(args.out, "feedback_bench.jsonl"), "w") as f:
     for r in rows:
         f.write(json.dumps(r) + "\n")

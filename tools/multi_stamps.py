@@ -3,7 +3,9 @@ of the step in the MIDDLE of the last launch leave wall-clock stamps (csrc/k_ste
 holds its slot and how much of that is waiting for a hand-over, and the sum over the roles per step against slots x step time.
 Usage on the GPU box:
     tools/build_variant.sh mstamps "-DAUV_STAMPS_MULTI"
-    AUV_HIP_LIB=gym_auv_amd/csrc_mstamps/libauv_hip.so python tools/multi_stamps.py [workload polygons50|mixed47] [envs] [lead] [lag]"""
+    AUV_HIP_LIB=gym_auv_amd/csrc_mstamps/libauv_hip.so python tools/multi_stamps.py [workload polygons50|mixed47] [envs] [lead] [lag] [form]
+`form`: multi (default: step_multi), feedback (step_feedback, line-of-sight autopilot) or sectors (the same with non-zero gains on
+the LiDAR's sector inputs): the closed-loop launches' finish waves show their law in `reward_and_carry`."""
 import glob
 import json
 import os
@@ -37,12 +39,31 @@ g.manual_seed(0)
 pool = (torch.rand((64, n, 2), generator=g, device="cuda:0", dtype=torch.float64) * torch.tensor([2.0, 0.3], device="cuda:0", dtype=torch.float64)
         - torch.tensor([1.0, 0.15], device="cuda:0", dtype=torch.float64)).contiguous()
 T = 64
+form = sys.argv[5] if len(sys.argv) > 5 else "multi"
+if form != "multi":
+    from gym_auv_amd.feedback import los_gains
+    fb_gains = torch.as_tensor(los_gains(0.7, 0.8, 0.4, 0.5), device="cuda:0")
+    fb_sectors = None
+    if form == "sectors":
+        ns = cfg.vessel.n_sectors
+        fb_sectors = torch.zeros((2, 16), dtype=torch.float64, device="cuda:0")
+        fb_sectors[0, :min(ns, 16)], fb_sectors[1, :min(ns, 16)] = -0.3 / ns, 0.1
+
+
+def launch():
+    if form == "multi":
+        env.step_multi(pool, 0, T)
+    else:
+        env.step_feedback(fb_gains, T, record="reward", sector_gains=fb_sectors, sector_bounds=None if ns_ok else np.arange(17) * (env.n_sensors // 16))
+
+
+ns_ok = cfg.vessel.n_sectors <= 16
 for j in range(4):
-    env.step_multi(pool, 0, T)
+    launch()
 torch.cuda.synchronize()
 t0 = time.perf_counter()
 for j in range(8):
-    env.step_multi(pool, 0, T)
+    launch()
 torch.cuda.synchronize()
 us_step = (time.perf_counter() - t0) / (8 * T) * 1e6
 st = env.read("STAMPS").cpu().numpy().astype(np.float64)[:, :16] / 100.0      # wall_clock64: 100 MHz -> us
@@ -53,7 +74,7 @@ def q(x):
                 p99=round(float(np.percentile(x, 99)), 2), max=round(float(np.max(x)), 2))
 
 
-out = dict(workload=wl, envs=n, steps_per_launch=T, lead=lead, lag=lag, lidar_stage=env.lidar_stage(), us_per_step=round(us_step, 2),
+out = dict(workload=wl, form=form, envs=n, steps_per_launch=T, lead=lead, lag=lag, lidar_stage=env.lidar_stage(), us_per_step=round(us_step, 2),
            rate_M=round(n / us_step, 1))
 sw, se = st[:, 0:6], st[:, 6:10]
 dy = st[::1, 10:13]
