@@ -360,7 +360,8 @@ class BatchedAuvEnv:
         return rec
 
     def step_feedback(self, gains: torch.Tensor, n_steps: int, ring: Optional[torch.Tensor] = None, first_slot: int = 0, record=None,
-                      record_actions: bool = False, sector_gains: Optional[torch.Tensor] = None, sector_bounds=None):
+                      record_actions: bool = False, sector_gains: Optional[torch.Tensor] = None, sector_bounds=None,
+                      hidden: Optional[torch.Tensor] = None, activation: str = "relu"):
         """`n_steps` consecutive steps of every sub-batch in ONE launch per sub-batch with the action chosen INSIDE the launch
         (auv_step_feedback): the action of a step is the affine feedback law of gym_auv_amd/feedback.py applied to the six
         navigation columns the step before it left -- a[j] = sum over c of gains[e, j, c] * x[c], x = (obs[0..5], 1, ring action[j]).
@@ -379,8 +380,14 @@ class BatchedAuvEnv:
         the LiDAR: 16 sector inputs z_k, the largest closeness among the row's closeness columns b[k] <= i < b[k + 1], weighted
         by these gains and added in their own fixed association (auv_step_feedback_sectors; feedback.sector_action is the
         mirror).  `sector_bounds`: the table b, K + 1 ascending integers within [0, L], K <= 16 (L: n_sensors, or n_sectors in
-        the feasibility-pooled configuration); None: feedback.default_sector_bounds(config)."""
-        from .feedback import check_feedback_args, check_sector_args
+        the feasibility-pooled configuration); None: feedback.default_sector_bounds(config).
+
+        `hidden`: None, or a float64 device tensor [N, 16, 28] ([16, 28]: every environment alike), the block
+        feedback.pack_hidden makes -- the law then has one hidden layer of 16 units over its 24 inputs (the six columns, the
+        ring's action, the 16 sector inputs), `activation` "relu" or "hardtanh", added to the affine part as
+        (s + (u + w)) + (ha + hb) (auv_step_feedback_hidden; feedback.hidden_action is the mirror).  Needs `sector_gains`
+        (zeros switch the affine sector terms off)."""
+        from .feedback import check_feedback_args, check_hidden_args, check_sector_args
         if self._slices is None:
             self.set_sub_batches(1)
         T, n = int(n_steps), self.n_envs
@@ -388,6 +395,7 @@ class BatchedAuvEnv:
         if sector_gains is None and sector_bounds is not None:
             raise ValueError("sector_bounds without sector_gains")
         sg, sb = (None, None) if sector_gains is None else check_sector_args(self.config, n, self.device, sector_gains, sector_bounds)
+        hd, act_code = (None, 0) if hidden is None else check_hidden_args(n, self.device, hidden, activation, sector_gains)
         with torch.cuda.device(self.device):
             rec = None
             if record is not None:
@@ -399,7 +407,7 @@ class BatchedAuvEnv:
         for st in self._sub_streams:
             if st != cur:
                 st.wait_stream(cur)
-                for t in (rec or ()) + (act, g, sg):
+                for t in (rec or ()) + (act, g, sg, hd):
                     if t is not None:
                         t.record_stream(st)
 
@@ -411,6 +419,12 @@ class BatchedAuvEnv:
                                           1 if ring is None else int(ring.shape[0]), int(first_slot), T, ptr(self.obs), ptr(self.reward), ptr(self.done),
                                           ptr(rec[0]) if rec else None, ptr(rec[1]) if rec else None, ptr(rec[2]) if rec else None, ptr(act)),
                    "auv_step_feedback")
+        elif hd is not None:
+            _check(_LIB.auv_step_feedback_hidden(self._h, self.sub_batches, self._bounds_c, self._streams_c, ptr(g), ptr(ring), dt,
+                                                 1 if ring is None else int(ring.shape[0]), int(first_slot), T, ptr(self.obs), ptr(self.reward),
+                                                 ptr(self.done), ptr(rec[0]) if rec else None, ptr(rec[1]) if rec else None,
+                                                 ptr(rec[2]) if rec else None, ptr(act), ptr(sg), (C.c_int32 * len(sb))(*[int(v) for v in sb]),
+                                                 len(sb) - 1, ptr(hd), act_code), "auv_step_feedback_hidden")
         else:
             _check(_LIB.auv_step_feedback_sectors(self._h, self.sub_batches, self._bounds_c, self._streams_c, ptr(g), ptr(ring), dt,
                                                   1 if ring is None else int(ring.shape[0]), int(first_slot), T, ptr(self.obs), ptr(self.reward),

@@ -48,7 +48,8 @@ void auv_launch_step_record(const AuvDev& d, const void* actions, int dtype, flo
                             uint8_t* done_rec, int n_steps, int first_slot, int n_slots, unsigned long long seq0, int order, int lead, int lag, hipStream_t st);
 void auv_launch_step_feedback(const AuvDev& d, const double* gains, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, float* obs_rec,
                               float* reward_rec, uint8_t* done_rec, double* act_rec, int n_steps, int first_slot, int n_slots, unsigned long long seq0,
-                              int order, int lead, int lag, hipStream_t st, const double* sector_gains, const int32_t* sector_bounds);
+                              int order, int lead, int lag, hipStream_t st, const double* sector_gains, const int32_t* sector_bounds,
+                              const double* hidden, int activation);
 void auv_launch_spin(unsigned long long ticks, hipStream_t st);
 void auv_launch_rdv_publish(unsigned long long* word, unsigned long long seq, hipStream_t st);
 void auv_launch_rdv_arrive(unsigned long long* word, hipStream_t st);
@@ -1366,10 +1367,12 @@ int auv_step_multi_record(auv_handle_t* h, int32_t n_slices, const int32_t* boun
 
 // auv_step_feedback (`sectors` false) and auv_step_feedback_sectors: the same checks and the same launch, the second with the sector
 // gains and the bounds table (padded here to 17 entries with its last one: the sectors past n_sectors are empty ranges)
+// auv_step_feedback_hidden (`hidden`, with `sectors`): the sector entry's checks plus the hidden block's and the activation's
 static int step_feedback_any(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const double* gains_dev, const void* actions_dev,
                              int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev, float* reward_dev,
                              uint8_t* done_dev, float* obs_rec, float* reward_rec, uint8_t* done_rec, double* act_rec, const char* who, bool sectors,
-                             const double* sector_gains_dev, const int32_t* sector_bounds_host, int32_t n_sectors) {
+                             const double* sector_gains_dev, const int32_t* sector_bounds_host, int32_t n_sectors, bool hidden = false,
+                             const double* hidden_dev = nullptr, int32_t activation = 0) {
   REQUIRE_READY(h);
   if (!gains_dev || ((uintptr_t)gains_dev & 7)) return fail(AUV_EINVAL, "%s: gains_dev must be a non-NULL, 8-byte aligned [N][2][8] fp64 table", who);
   int32_t sb[17];
@@ -1384,6 +1387,11 @@ static int step_feedback_any(auv_handle_t* h, int32_t n_slices, const int32_t* b
       if (sector_bounds_host[k] < (k ? sector_bounds_host[k - 1] : 0) || sector_bounds_host[k] > L)
         return fail(AUV_EINVAL, "%s: sector bounds must be ascending within [0, %d] (entry %d is %d)", who, L, k, sector_bounds_host[k]);
     for (int k = 0; k < 17; k++) sb[k] = sector_bounds_host[k < n_sectors ? k : n_sectors];
+  }
+  if (hidden) {
+    if (!hidden_dev || ((uintptr_t)hidden_dev & 15))
+      return fail(AUV_EINVAL, "%s: hidden_dev must be a non-NULL, 16-byte aligned [N][16][28] fp64 block", who);
+    if (activation != 0 && activation != 1) return fail(AUV_EINVAL, "%s: activation must be 0 (relu) or 1 (hard tanh), got %d", who, activation);
   }
   if (actions_dev && n_slots < 1) return fail(AUV_EINVAL, "%s: n_slots >= 1 with a ring", who);
   if (!actions_dev) n_slots = 1, first_slot = 0, action_dtype = AUV_F32;               // no ring: x_7 = 0, nothing is read
@@ -1403,7 +1411,7 @@ static int step_feedback_any(auv_handle_t* h, int32_t n_slices, const int32_t* b
     d.e0 = bounds[i], d.ne = bounds[i + 1] - bounds[i];
     auv_launch_step_feedback(d, gains_dev, actions_dev, action_dtype, obs_dev, reward_dev, done_dev, obs_rec, reward_rec, done_rec, act_rec, n_steps,
                              first_slot, n_slots, seq0, h->multi_order, h->multi_lead, h->multi_lag, (hipStream_t)streams[i],
-                             sectors ? sector_gains_dev : nullptr, sectors ? sb : nullptr);
+                             sectors ? sector_gains_dev : nullptr, sectors ? sb : nullptr, hidden ? hidden_dev : nullptr, activation);
   }
   HIP_TRY(hipGetLastError());
   return AUV_OK;
@@ -1422,6 +1430,16 @@ int auv_step_feedback_sectors(auv_handle_t* h, int32_t n_slices, const int32_t* 
                               const double* sector_gains_dev, const int32_t* sector_bounds_host, int32_t n_sectors) {
   return step_feedback_any(h, n_slices, bounds, streams, gains_dev, actions_dev, action_dtype, n_slots, first_slot, n_steps, obs_dev, reward_dev, done_dev,
                            obs_rec, reward_rec, done_rec, act_rec, "auv_step_feedback_sectors", true, sector_gains_dev, sector_bounds_host, n_sectors);
+}
+
+int auv_step_feedback_hidden(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const double* gains_dev,
+                             const void* actions_dev, int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev,
+                             float* reward_dev, uint8_t* done_dev, float* obs_rec, float* reward_rec, uint8_t* done_rec, double* act_rec,
+                             const double* sector_gains_dev, const int32_t* sector_bounds_host, int32_t n_sectors, const double* hidden_dev,
+                             int32_t activation) {
+  return step_feedback_any(h, n_slices, bounds, streams, gains_dev, actions_dev, action_dtype, n_slots, first_slot, n_steps, obs_dev, reward_dev, done_dev,
+                           obs_rec, reward_rec, done_rec, act_rec, "auv_step_feedback_hidden", true, sector_gains_dev, sector_bounds_host, n_sectors, true,
+                           hidden_dev, activation);
 }
 
 int auv_set_multi_order(auv_handle_t* h, int32_t order, int32_t lead, int32_t lag) {

@@ -797,16 +797,104 @@ __device__ __forceinline__ double2 fb_law_sectors(const double2 s, const double2
   return make_double2(s.x + (u0 + w0), s.y + (u1 + w1));
 }
 
-// FB (k_step_feedback: 1, k_step_sector_feedback: 2): a step that is not the last also forms the NEXT step's action by the feedback
-// law and hands it over in words 21..23 of the carry record (fb_gains: [N][2][8]; fb_actions / fb_slot: the ring and the next step's
-// slot, or nullptr; FB 2: fb_sgains, [N][2][16], and fb_sb, the sector bounds)
+// ---- one hidden layer on top of the law (auv_step_feedback_hidden, k_step_hidden_feedback) ----
+// Per environment 16 hidden units over 24 inputs, the same for both outputs:
+//     v_0..5 = x_0..5 of fb_law,   v_6, v_7 = the two components of the ring's action of the step the law is for (no ring: 0.0),
+//     v_8..23 = z_0..15 of the sector law (the same bounds, the same maxima)
+//     s = b_h;  for i = 0, 1, ..., 23 in this order  s = s + (w_h[i] * v_i)     (each product and each sum rounded once)
+//     y_h = s > 0.0 ? s : +0.0                                    activation 0, relu (a NaN gives +0.0)
+//     y_h = s > 1.0 ? 1.0 : (s < -1.0 ? -1.0 : s)                 activation 1, hard tanh (a NaN passes)
+//     r_k = V[j][k] * y_k,   ha_j = ((r_0 + r_1) + (r_2 + r_3)) + ((r_4 + r_5) + (r_6 + r_7)),   hb_j = the same over r_8..r_15,
+//     a_j = (s_j + (u_j + w_j)) + (ha_j + hb_j)                   the first bracket: fb_law_sectors' result, unchanged
+// fp64, no FMA, this association (host mirror: gym_auv_amd/feedback.py, hidden_action).  The parameters: [N][16][28] fp64, row h =
+// (w_h[0..23], b_h, V[0][h], V[1][h], pad) -- 224 bytes, so every pair of a row is a 16-byte aligned load.  Lane c of a group of
+// eight owns units c and 8 + c, like the sectors: ha_j and hb_j are fb_group_sum of its two products.  Every lane needs all 24
+// inputs; they sit one (x), or two (z), per lane of the group and are taken from there by DPP moves (k1_group_bcast) at the moment
+// they are multiplied -- no array of inputs, and of the 2 x 27 parameters of a lane only one batch of FB_HIDDEN_BATCH inputs' is
+// in registers at a time.
+#define FB_HIDDEN_BATCH 8   // inputs per batch: 2 units x 4 pairs in flight, consumed at once
+#define FB_HIDDEN_ROW 28    // doubles per unit
+typedef double fb_pair __attribute__((ext_vector_type(2)));   // (a native vector: one 16-byte global load)
+struct FbHiddenBatch {
+  fb_pair p0[FB_HIDDEN_BATCH / 2], p1[FB_HIDDEN_BATCH / 2];     // pairs (w[i], w[i + 1]) of units c and 8 + c
+};
+// hp: row c of the environment's block (row 8 + c is 8 rows on).  Plain loads: nothing in a launch writes the parameters.
+template <int B> __device__ __forceinline__ FbHiddenBatch fb_hidden_request(const double* __restrict__ hp_) {
+  const __attribute__((address_space(1))) fb_pair* hp = (const __attribute__((address_space(1))) fb_pair*)hp_;
+  FbHiddenBatch w;
+#pragma unroll
+  for (int k = 0; k < FB_HIDDEN_BATCH / 2; k++)
+    w.p0[k] = hp[B * (FB_HIDDEN_BATCH / 2) + k], w.p1[k] = hp[8 * (FB_HIDDEN_ROW / 2) + B * (FB_HIDDEN_BATCH / 2) + k];
+  return w;
+}
+// (b_h, V[0][h]) and (V[1][h], pad) of the lane's two units
+struct FbHiddenTail {
+  fb_pair bv0, bv1, vp0, vp1;
+};
+__device__ __forceinline__ FbHiddenTail fb_hidden_request_tail(const double* __restrict__ hp_) {
+  const __attribute__((address_space(1))) fb_pair* hp = (const __attribute__((address_space(1))) fb_pair*)hp_;
+  FbHiddenTail t;
+  static_assert(24 % FB_HIDDEN_BATCH == 0 && FB_HIDDEN_BATCH % 2 == 0, "whole batches of pairs");
+  t.bv0 = hp[12], t.bv1 = hp[8 * (FB_HIDDEN_ROW / 2) + 12], t.vp0 = hp[13], t.vp1 = hp[8 * (FB_HIDDEN_ROW / 2) + 13];
+  return t;
+}
+// input I (a constant) in every lane of the group.  x: column c in lanes c < 6; r0, r1: the ring's action; z: the lane's two sectors
+template <int I> __device__ __forceinline__ double fb_hidden_input(const double x, const double r0, const double r1, const double2 z) {
+  static_assert(I >= 0 && I < 24, "input of the hidden layer");
+  if constexpr (I < 6) return k1_group_bcast<I>(x);
+  else if constexpr (I == 6) return r0;
+  else if constexpr (I == 7) return r1;
+  else if constexpr (I < 16) return k1_group_bcast<I - 8>(z.x);
+  else return k1_group_bcast<I - 16>(z.y);
+}
+// batch B: both units' running sums advanced by one product per input, in the order of the inputs
+template <int B, int K = 0>
+__device__ __forceinline__ void fb_hidden_batch(const FbHiddenBatch& w, const double x, const double r0, const double r1, const double2 z, double& s0, double& s1) {
+  if constexpr (K < FB_HIDDEN_BATCH) {
+    const double v = fb_hidden_input<B * FB_HIDDEN_BATCH + K>(x, r0, r1, z);
+    const fb_pair q0 = w.p0[K / 2], q1 = w.p1[K / 2];
+    s0 = s0 + ((K & 1) ? q0.y : q0.x) * v, s1 = s1 + ((K & 1) ? q1.y : q1.x) * v;
+    fb_hidden_batch<B, K + 1>(w, x, r0, r1, z, s0, s1);
+  }
+}
+// batches B .. the last: each requested when the one before it has been consumed
+template <int B>
+__device__ __forceinline__ void fb_hidden_rest(const double* __restrict__ hp, const double x, const double r0, const double r1, const double2 z, double& s0, double& s1) {
+  if constexpr (B < 24 / FB_HIDDEN_BATCH) {
+    const FbHiddenBatch w = fb_hidden_request<B>(hp);
+    fb_hidden_batch<B>(w, x, r0, r1, z, s0, s1);
+    fb_hidden_rest<B + 1>(hp, x, r0, r1, z, s0, s1);
+  }
+}
+__device__ __forceinline__ double fb_hidden_activation(const double s, const int activation) {
+  const double relu = s > 0.0 ? s : 0.0, ht = s > 1.0 ? 1.0 : (s < -1.0 ? -1.0 : s);
+  return activation ? ht : relu;
+}
+// a: fb_law_sectors' result; x, r0, r1: what fb_law took; z: what fb_law_sectors took; w0 / t: batch 0 and the tail, requested by
+// the caller ahead of its sector loop (they do not depend on the observation); hp: as fb_hidden_request's.  Called by all 64 lanes.
+__device__ __forceinline__ double2 fb_hidden(const double2 a, const double x, const double r0, const double r1, const double2 z,
+                                             const FbHiddenBatch& w0, const FbHiddenTail& t, const double* __restrict__ hp, const int activation) {
+  double s0 = t.bv0.x, s1 = t.bv1.x;
+  fb_hidden_batch<0>(w0, x, r0, r1, z, s0, s1);
+  fb_hidden_rest<1>(hp, x, r0, r1, z, s0, s1);
+  const double y0 = fb_hidden_activation(s0, activation), y1 = fb_hidden_activation(s1, activation);
+  const double ha0 = fb_group_sum(t.bv0.y * y0), hb0 = fb_group_sum(t.bv1.y * y1);
+  const double ha1 = fb_group_sum(t.vp0.x * y0), hb1 = fb_group_sum(t.vp1.x * y1);
+  return make_double2(a.x + (ha0 + hb0), a.y + (ha1 + hb1));
+}
+
+// FB (k_step_feedback: 1, k_step_sector_feedback: 2, k_step_hidden_feedback: 3): a step that is not the last also forms the NEXT
+// step's action by the feedback law and hands it over in words 21..23 of the carry record (fb_gains: [N][2][8]; fb_actions / fb_slot:
+// the ring and the next step's slot, or nullptr; FB >= 2: fb_sgains, [N][2][16], and fb_sb, the sector bounds; FB 3: fb_hidden,
+// [N][16][28], and fb_activation)
 template <bool MULTI, int FB = 0>
 __device__ __forceinline__ void roles_finish_wave_multi(const AuvDev& dk, const int f, const int lane, float* __restrict__ obs_out,
                                                         float* __restrict__ reward_out, uint8_t* __restrict__ done_out, const int step,
                                                         const bool last_step, const unsigned long long tagmix, const unsigned long long tagmix_prev MSTAMP_PARAM,
                                                         const double* __restrict__ fb_gains = nullptr, const void* __restrict__ fb_actions = nullptr,
                                                         const int fb_slot = 0, const double* __restrict__ fb_sgains = nullptr,
-                                                        const FbBounds* fb_sb = nullptr) {
+                                                        const FbBounds* fb_sb = nullptr, const double* __restrict__ fb_hidden_tab = nullptr,
+                                                        const int fb_activation = 0) {
   // (roles_finish_wave with the previous step's outcome from the carry record instead of the arrays, and its own outcome into
   // the record at the end; the arithmetic in between is the very same code)
   const __attribute__((address_space(4))) AuvDev* dc = (const __attribute__((address_space(4))) AuvDev*)dk.self;
@@ -1011,14 +1099,24 @@ __device__ __forceinline__ void roles_finish_wave_multi(const AuvDev& dk, const 
     double r0 = 0.0, r1 = 0.0;
     if (fb_actions) k1_action(dk, fb_actions, ef, &r0, &r1, fb_slot);
     double2 a = fb_law(c, x, g0, g1, r0, r1);
-    if constexpr (FB == 2) {
+    if constexpr (FB >= 2) {
       // the sector inputs: the closeness columns of the same row.  The sweep stored them write-through and drained them before it
       // published the pair word this wave has polled (k2_back, pair_publish_lidar); a restored environment's are this wave's own
       // completed stores -- agent-scope loads past L1 serve both, like x above.  Addresses from the laundered index and descriptor.
       const double* hp = fb_sgains + 32 * (size_t)ef + c;
       const double2 h0 = make_double2(hp[0], hp[8]), h1 = make_double2(hp[16], hp[24]);      // (requested ahead of the sector loop)
-      const double2 z = fb_sector_pair<true>(df.obs64 + (size_t)ef * (6 + S) + 6, fb_ranges(*fb_sb, c));
-      a = fb_law_sectors(a, z, h0, h1);
+      if constexpr (FB == 3) {
+        // the hidden layer: its first batch of weights, the biases and the output rows are requested ahead of the sector loop too
+        // (they do not depend on the observation), the other two batches behind it, where their registers are free
+        const double* wp = fb_hidden_tab + (size_t)(16 * FB_HIDDEN_ROW) * (size_t)ef + FB_HIDDEN_ROW * c;
+        const FbHiddenBatch w0 = fb_hidden_request<0>(wp);
+        const FbHiddenTail wt = fb_hidden_request_tail(wp);
+        const double2 z = fb_sector_pair<true>(df.obs64 + (size_t)ef * (6 + S) + 6, fb_ranges(*fb_sb, c));
+        a = fb_hidden(fb_law_sectors(a, z, h0, h1), x, r0, r1, z, w0, wt, wp, fb_activation);
+      } else {
+        const double2 z = fb_sector_pair<true>(df.obs64 + (size_t)ef * (6 + S) + 6, fb_ranges(*fb_sb, c));
+        a = fb_law_sectors(a, z, h0, h1);
+      }
     }
     const unsigned long long wa = (unsigned long long)__double_as_longlong(a.x), wb = (unsigned long long)__double_as_longlong(a.y);
     // (the mark is built like the state line's: a checksum of its payload mixed with the step's number, loaded with it in one request)
@@ -1103,6 +1201,25 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_sector_fee
   AUV_KERNARG_DESC(d);
 #define STEP_MULTI_REC 1
 #define STEP_MULTI_FB 2
+#include "k_step_multi_body.inc"
+#undef STEP_MULTI_FB
+#undef STEP_MULTI_REC
+}
+
+// The closed-loop launch with one hidden layer in the law (auv_step_feedback_hidden): k_step_sector_feedback whose action also takes
+// 16 hidden units over the 24 inputs the law already holds (fb_hidden).  A fifth inclusion of the body: the other four keep their
+// argument lists and their code.  hidden: [N][16][28] fp64; activation: 0 relu, 1 hard tanh (wave-uniform).
+__global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_hidden_feedback(AuvDev dk, const void* __restrict__ actions, float* __restrict__ obs_out,
+                                                                                      float* __restrict__ reward_out, uint8_t* __restrict__ done_out,
+                                                                                      const int n_steps, const int first_slot, const int n_slots,
+                                                                                      const unsigned long long seq0, const int lead_dyn, const int lag_fin, const unsigned magic_c,
+                                                                                      const unsigned long long obs_stride, const unsigned long long reward_stride,
+                                                                                      const unsigned long long done_stride, const double* __restrict__ gains,
+                                                                                      double* __restrict__ act_rec, const double* __restrict__ sgains,
+                                                                                      const FbBounds sb, const double* __restrict__ hidden, const int activation) {
+  AUV_KERNARG_DESC(d);
+#define STEP_MULTI_REC 1
+#define STEP_MULTI_FB 3
 #include "k_step_multi_body.inc"
 #undef STEP_MULTI_FB
 #undef STEP_MULTI_REC
@@ -1342,11 +1459,12 @@ void auv_launch_step_record(const AuvDev& d0, const void* actions, int dtype, fl
 
 // the closed-loop form: the record launch with the gain table, an optional ring and an optional action record; each of the three
 // output records may be missing (that output's every step then goes to obs / reward / done, and nothing is copied for it)
-// (sector_gains / sector_bounds: nullptr, or [N][2][16] fp64 and the table of 17 -- k_step_sector_feedback is launched instead)
+// (sector_gains / sector_bounds: nullptr, or [N][2][16] fp64 and the table of 17 -- k_step_sector_feedback is launched instead;
+// hidden: nullptr, or with those two the [N][16][28] fp64 block and `activation` -- k_step_hidden_feedback)
 void auv_launch_step_feedback(const AuvDev& d0, const double* gains, const void* actions, int dtype, float* obs, float* reward, uint8_t* done,
                               float* obs_rec, float* reward_rec, uint8_t* done_rec, double* act_rec, int n_steps, int first_slot, int n_slots,
                               unsigned long long seq0, int order, int lead, int lag, hipStream_t st, const double* sector_gains,
-                              const int32_t* sector_bounds) {
+                              const int32_t* sector_bounds, const double* hidden, int activation) {
   AuvDev d = d0;
   d.act_f64 = dtype == AUV_F64;
   d.ring_slots = 1;
@@ -1355,7 +1473,13 @@ void auv_launch_step_feedback(const AuvDev& d0, const double* gains, const void*
   const dim3 grid((unsigned)auv_multi_grid(g)), block(AUV_WAVE);
   const int D = auv_obs_cols(d.cfg, d.pool_ns);
   const unsigned long long n = (unsigned long long)d.n, obs_stride = obs_rec ? n * (unsigned long long)D : 0ull;
-  if (sector_gains) {
+  if (hidden) {
+    FbBounds sb;
+    for (int i = 0; i < 17; i++) sb.b[i] = sector_bounds[i];
+    hipLaunchKernelGGL(k_step_hidden_feedback, grid, block, lds, st, d, actions, obs_rec ? obs_rec : obs, reward_rec ? reward_rec : reward,
+                       done_rec ? done_rec : done, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic, obs_stride, reward_rec ? n : 0ull,
+                       done_rec ? n : 0ull, gains, act_rec, sector_gains, sb, hidden, activation);
+  } else if (sector_gains) {
     FbBounds sb;
     for (int i = 0; i < 17; i++) sb.b[i] = sector_bounds[i];
     hipLaunchKernelGGL(k_step_sector_feedback, grid, block, lds, st, d, actions, obs_rec ? obs_rec : obs, reward_rec ? reward_rec : reward,
@@ -1403,6 +1527,8 @@ hipError_t auv_step_fused_prepare(const AuvDev& d) {
   e = hipFuncSetAttribute((const void*)k_step_feedback, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void*)k_step_sector_feedback, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute((const void*)k_step_hidden_feedback, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)k_step_roles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
 }

@@ -7,6 +7,8 @@
 //                      parameters: gains ([N][2][8] fp64), act_rec ([T][N][2] fp64 or nullptr); `actions` may be nullptr (x_7 = 0).
 //   STEP_MULTI_FB 2    k_step_sector_feedback  the same with LiDAR sector inputs in the law (fb_sector_pair, fb_law_sectors): further
 //                      parameters sgains ([N][2][16] fp64) and sb (FbBounds by value, the sector bounds).
+//   STEP_MULTI_FB 3    k_step_hidden_feedback  the same with one hidden layer of 16 units over the law's 24 inputs (fb_hidden): further
+//                      parameters hidden ([N][16][28] fp64) and activation (0 relu, 1 hard tanh).
 // The includer has declared `d` (AUV_KERNARG_DESC) and the kernel's parameters: actions, obs_out, reward_out, done_out, n_steps,
 // first_slot, n_slots, seq0, lead_dyn, lag_fin, magic_c -- and, recording, obs_stride, reward_stride, done_stride (elements; 0: no
 // record of that output).  The record's offset is wave-uniform (the step is, the strides are kernel arguments): 64-bit scalar
@@ -80,7 +82,18 @@
 #if STEP_MULTI_FB
       // the arrays, behind the kernel boundary: the OBS64 row and the gains
       const double x = c < 6 ? d.obs64[(size_t)eg * (6 + d.cfg.n_sensors) + c] : 0.0;
-#if STEP_MULTI_FB == 2
+#if STEP_MULTI_FB == 3
+      double2 a = fb_law(c, x, gains[16 * (size_t)eg + c], gains[16 * (size_t)eg + 8 + c], act0, act1);
+      {
+        const double* hp = sgains + 32 * (size_t)eg + c;
+        const double2 h0 = make_double2(hp[0], hp[8]), h1 = make_double2(hp[16], hp[24]);
+        const double* wp = hidden + (size_t)(16 * FB_HIDDEN_ROW) * (size_t)eg + FB_HIDDEN_ROW * c;
+        const FbHiddenBatch w0 = fb_hidden_request<0>(wp);
+        const FbHiddenTail wt = fb_hidden_request_tail(wp);
+        const double2 z = fb_sector_pair<false>(d.obs64 + (size_t)eg * (6 + d.cfg.n_sensors) + 6, fb_ranges(sb, c));
+        a = fb_hidden(fb_law_sectors(a, z, h0, h1), x, act0, act1, z, w0, wt, wp, activation);
+      }
+#elif STEP_MULTI_FB == 2
       double2 a = fb_law(c, x, gains[16 * (size_t)eg + c], gains[16 * (size_t)eg + 8 + c], act0, act1);
       {
         const double* hp = sgains + 32 * (size_t)eg + c;
@@ -238,7 +251,10 @@
     const bool fst = fer < ne && lane % K1_GROUP == 0;
 #endif
     MSTAMP_IF(fst, d.e0 + fer, 13);
-#if STEP_MULTI_FB == 2
+#if STEP_MULTI_FB == 3
+    roles_finish_wave_multi<true, 3>(d, f, lane, obs_out, reward_out, done_out, step, step == n_steps - 1, tagmix, tagmix_prev MSTAMP_ARG, gains,
+                                     actions, (first_slot + step + 1) % n_slots, sgains, &sb, hidden, activation);
+#elif STEP_MULTI_FB == 2
     roles_finish_wave_multi<true, 2>(d, f, lane, obs_out, reward_out, done_out, step, step == n_steps - 1, tagmix, tagmix_prev MSTAMP_ARG, gains,
                                      actions, (first_slot + step + 1) % n_slots, sgains, &sb);
 #elif STEP_MULTI_FB

@@ -42,11 +42,36 @@ n_sectors <= 16; pooled, arange(n_sectors + 1): z_k is the pooled column itself.
     a_j = s_j + (u_j + w_j)
 
 fp64, no fused multiply-add, exactly this association.  `sector_action` is its host mirror.
+
+One hidden layer (auv_step_feedback_hidden / k_step_hidden_feedback, step_feedback(..., hidden=)).  Per environment 16 hidden units
+over 24 inputs, the same for both outputs:
+
+    v_0..5  = x_0..5 above                  v_6, v_7 = the two components of the ring's action for the step (0.0 without a ring)
+    v_8..23 = z_0..15 above (the same bounds table, the same maxima)
+
+Hidden unit h has weights w_h[0..23] and a bias b_h:
+
+    s = b_h;  for i = 0, 1, ..., 23 in this order:  s = s + (w_h[i] * v_i)        every product and every sum rounded once
+    y_h = s > 0.0 ? s : +0.0                               activation 0, "relu" (a NaN gives +0.0)
+    y_h = s > 1.0 ? 1.0 : (s < -1.0 ? -1.0 : s)            activation 1, "hardtanh" (a NaN passes on to the dynamics' NaN rule)
+
+and with output weights V[2][16], r_k = V[j][k] * y_k:
+
+    ha_j = ((r_0 + r_1) + (r_2 + r_3)) + ((r_4 + r_5) + (r_6 + r_7))       hb_j = the same association over r_8 ... r_15
+    a_j  = (s_j + (u_j + w_j)) + (ha_j + hb_j)
+
+The first bracket is the law with sector inputs, unchanged: the affine part stays as a skip connection, and V = 0 gives its values.
+Smaller nets are rows of zeros.  The parameters travel as one block [N][16][28] (`pack_hidden`): row h = (w_h[0..23], b_h, V[0][h],
+V[1][h], one pad word).  `hidden_action` is the host mirror.
 """
 import numpy as np
 
 N_INPUTS = 8
 N_SECTOR_INPUTS = 16
+N_HIDDEN = 16
+N_HIDDEN_INPUTS = 24
+HIDDEN_ROW = 28                                                 # doubles per hidden unit in the packed block: 24 weights, bias, V[0], V[1], pad
+ACTIVATIONS = {"relu": 0, "hardtanh": 1}
 COL_U, COL_V, COL_R, COL_LOOKAHEAD_ERR, COL_HEADING_ERR, COL_CROSS_TRACK, COL_BIAS, COL_RING = range(8)
 
 
@@ -150,6 +175,83 @@ def sector_action(obs64_rows, gains, sector_gains, bounds, ring_action=None) -> 
     return out
 
 
+def pack_hidden(W1, b1, V) -> np.ndarray:
+    """The parameter block [..., 16, 28] (fp64) of the hidden layer: row h = (W1[..., h, 0:24], b1[..., h], V[..., 0, h], V[..., 1, h],
+    0.0).  W1: [..., 16, 24], b1: [..., 16], V: [..., 2, 16] with the same leading dimensions."""
+    W1, b1, V = (np.asarray(a, dtype=np.float64) for a in (W1, b1, V))
+    lead = W1.shape[:-2]
+    if W1.shape[-2:] != (N_HIDDEN, N_HIDDEN_INPUTS) or b1.shape != lead + (N_HIDDEN,) or V.shape != lead + (2, N_HIDDEN):
+        raise ValueError("W1 must be [..., 16, 24], b1 [..., 16] and V [..., 2, 16] with the same leading dimensions, got %s, %s, %s"
+                         % (W1.shape, b1.shape, V.shape))
+    out = np.zeros(lead + (N_HIDDEN, HIDDEN_ROW), dtype=np.float64)
+    out[..., :N_HIDDEN_INPUTS] = W1
+    out[..., 24] = b1
+    out[..., 25] = V[..., 0, :]
+    out[..., 26] = V[..., 1, :]
+    return out
+
+
+def hidden_inputs(obs64_rows, bounds, ring_action=None) -> np.ndarray:
+    """v[N, 24] of the module docstring.  obs64_rows: [N, 6 + L] fp64; bounds: [K + 1]; ring_action: [N, 2] (converted to fp64 as
+    the kernels convert an action) or None (v_6 = v_7 = 0)."""
+    x = np.asarray(obs64_rows, dtype=np.float64)
+    z = sector_inputs(x, bounds)
+    n = x.shape[0]
+    v = np.zeros((n, N_HIDDEN_INPUTS), dtype=np.float64)
+    v[:, :6] = x[:, :6]
+    if ring_action is not None:
+        ring = np.asarray(ring_action).astype(np.float64)
+        if ring.shape != (n, 2):
+            raise ValueError("ring_action must be [%d, 2]" % n)
+        v[:, 6:8] = ring
+    v[:, 8:] = z
+    return v
+
+
+def _activation_code(activation) -> int:
+    if isinstance(activation, str) and activation in ACTIVATIONS:
+        return ACTIVATIONS[activation]
+    raise ValueError("activation must be \"relu\" or \"hardtanh\", got %r" % (activation,))
+
+
+def hidden_preactivations(obs64_rows, bounds, hidden, ring_action=None) -> np.ndarray:
+    """s[N, 16] of the module docstring: the hidden units' sums before the activation, in the law's order of operations."""
+    v = hidden_inputs(obs64_rows, bounds, ring_action)
+    n = v.shape[0]
+    p = np.asarray(hidden, dtype=np.float64)
+    if p.shape == (N_HIDDEN, HIDDEN_ROW):
+        p = np.broadcast_to(p, (n, N_HIDDEN, HIDDEN_ROW))
+    if p.shape != (n, N_HIDDEN, HIDDEN_ROW):
+        raise ValueError("hidden must be [%d, 16, 28] or [16, 28], got %s" % (n, p.shape))
+    s = p[:, :, 24].copy()
+    for i in range(N_HIDDEN_INPUTS):
+        s = s + p[:, :, i] * v[:, i, None]                     # one product and one sum per input, in the order of the inputs
+    return s
+
+
+def hidden_action(obs64_rows, gains, sector_gains, bounds, hidden, activation="relu", ring_action=None) -> np.ndarray:
+    """a[N, 2] of the law with the hidden layer: NumPy fp64, the same association, bit for bit the kernel's.  hidden: [N, 16, 28]
+    or [16, 28] (pack_hidden); activation: "relu" or "hardtanh"; the rest as sector_action's."""
+    code = _activation_code(activation)
+    x = np.asarray(obs64_rows, dtype=np.float64)
+    n = x.shape[0]
+    s = hidden_preactivations(x, bounds, hidden, ring_action)
+    p = np.broadcast_to(np.asarray(hidden, dtype=np.float64), (n, N_HIDDEN, HIDDEN_ROW))
+    with np.errstate(invalid="ignore"):
+        if code == 0:
+            y = np.where(s > 0.0, s, 0.0)
+        else:
+            y = np.where(s > 1.0, 1.0, np.where(s < -1.0, -1.0, s))
+        a = sector_action(x, gains, sector_gains, bounds, ring_action)
+        out = np.empty((n, 2), dtype=np.float64)
+        for j in range(2):
+            r = p[:, :, 25 + j] * y                                # sixteen products, each rounded once
+            ha = ((r[:, 0] + r[:, 1]) + (r[:, 2] + r[:, 3])) + ((r[:, 4] + r[:, 5]) + (r[:, 6] + r[:, 7]))
+            hb = ((r[:, 8] + r[:, 9]) + (r[:, 10] + r[:, 11])) + ((r[:, 12] + r[:, 13]) + (r[:, 14] + r[:, 15]))
+            out[:, j] = a[:, j] + (ha + hb)
+    return out
+
+
 def los_gains(thrust, k_heading, k_yaw_rate, k_cross_track=0.0) -> np.ndarray:
     """The line-of-sight autopilot as a [2, 8] gain row: constant thrust, rudder = -k_heading * e_psi - k_yaw_rate * r with the
     heading error e_psi = heading - direction to the look-ahead point.  Column 4 of the observation holds -e_psi (target - heading,
@@ -215,3 +317,20 @@ def check_sector_args(cfg, n_envs, device, sector_gains, sector_bounds=None):
         raise ValueError("sector_gains must have shape (%d, 2, 16) or (2, 16), got %s" % (n_envs, tuple(sector_gains.shape)))
     bounds = default_sector_bounds(cfg) if sector_bounds is None else check_sector_bounds(sector_bounds, _lidar_columns(cfg))
     return sector_gains.contiguous(), bounds
+
+
+def check_hidden_args(n_envs, device, hidden, activation="relu", sector_gains=True):
+    """What BatchedAuvEnv.step_feedback checks of its hidden-layer arguments before the C call (no GPU needed to evaluate it).
+    `sector_gains`: what the caller passed as sector gains (None: the hidden layer needs them).  Returns (the block as a contiguous
+    [N, 16, 28] fp64 tensor, the activation's code)."""
+    import torch
+    if sector_gains is None:
+        raise ValueError("hidden needs sector_gains (zeros switch the affine sector terms off)")
+    code = _activation_code(activation)
+    if not isinstance(hidden, torch.Tensor) or hidden.dtype != torch.float64 or hidden.device != device:
+        raise ValueError("hidden must be a float64 tensor on %s" % (device,))
+    if tuple(hidden.shape) == (N_HIDDEN, HIDDEN_ROW):
+        hidden = hidden.expand(n_envs, N_HIDDEN, HIDDEN_ROW)
+    if tuple(hidden.shape) != (n_envs, N_HIDDEN, HIDDEN_ROW):
+        raise ValueError("hidden must have shape (%d, 16, 28) or (16, 28), got %s" % (n_envs, tuple(hidden.shape)))
+    return hidden.contiguous(), code

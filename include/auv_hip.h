@@ -278,6 +278,35 @@ int auv_step_feedback_sectors(auv_handle_t* h, int32_t n_slices, const int32_t* 
                               float* obs_dev, float* reward_dev, uint8_t* done_dev, float* obs_rec, float* reward_rec, uint8_t* done_rec,
                               double* act_rec, const double* sector_gains_dev, const int32_t* sector_bounds_host, int32_t n_sectors);
 
+/* auv_step_feedback_sectors with ONE HIDDEN LAYER in the law: n_steps consecutive step() calls (environment.py:292-347) in one launch
+ * per slice, the action of every step formed inside the launch from the navigation columns, the ring's action and the sector inputs
+ * (Vessel.perceive's row, sensor.py:140-159; utils/sector_partitioning.py:4-9, sensor.py:197) through 16 hidden units per
+ * environment -- the smallest law that can say "steer away only when something is close on that side".  The hidden layer's inputs,
+ * the same for both outputs:
+ *     v_0..5  = x_0..5 of auv_step_feedback, with the same source rules at step 0 and after an auto-reset,
+ *     v_6, v_7 = the two components of the ring's action for the step, converted as every step converts its action (no ring: 0.0),
+ *     v_8..23 = z_0..15 of auv_step_feedback_sectors (the same bounds table, the same maxima).
+ * Hidden unit h has weights w_h[0..23] and a bias b_h:
+ *     s = b_h;  for i = 0, 1, ..., 23 in this order  s = s + (w_h[i] * v_i)      (every product and every sum rounded once),
+ *     activation 0 (relu):       y_h = s > 0.0 ? s : +0.0                         (a NaN gives +0.0),
+ *     activation 1 (hard tanh):  y_h = s > 1.0 ? 1.0 : (s < -1.0 ? -1.0 : s)      (a NaN passes on to the dynamics' NaN rule),
+ * and with output weights V[2][16], r_k = V[j][k] * y_k:
+ *     ha_j = ((r_0 + r_1) + (r_2 + r_3)) + ((r_4 + r_5) + (r_6 + r_7)),   hb_j = the same association over r_8 .. r_15,
+ *     a_j = (s_j + (u_j + w_j)) + (ha_j + hb_j),   the first bracket auv_step_feedback_sectors' result, unchanged,
+ * fp64, FMA contraction off, exactly this association.  The affine part stays as a skip connection: V = 0 gives the sector launch's
+ * values; smaller nets are rows of zeros.  hidden_dev is one fp64 block [N][16][28]: row h = (w_h[0..23], b_h, V[0][h], V[1][h], one
+ * pad word), 224 bytes.  Host mirror: gym_auv_amd/feedback.py, hidden_action (pack_hidden makes the block); the launch is bit for bit
+ * n_steps one-step calls fed by it (tests/test_gpu_feedback_hidden.py).  Lane c of a group of eight owns units c and 8 + c and takes
+ * the inputs from its group by DPP moves (csrc/k_step_fused.hip, fb_hidden, k_step_hidden_feedback); the hand-over of the action is
+ * auv_step_feedback's, and so is every other argument.
+ * Preconditions are auv_step_feedback_sectors' plus: a non-NULL, 16-byte aligned hidden_dev and activation 0 or 1; every refusal is
+ * AUV_EINVAL, before anything launches or any step number is spent.  Eager only.                                                */
+int auv_step_feedback_hidden(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const double* gains_dev,
+                             const void* actions_dev, int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps,
+                             float* obs_dev, float* reward_dev, uint8_t* done_dev, float* obs_rec, float* reward_rec, uint8_t* done_rec,
+                             double* act_rec, const double* sector_gains_dev, const int32_t* sector_bounds_host, int32_t n_sectors,
+                             const double* hidden_dev, int32_t activation);
+
 /* Workgroup order of auv_step_multi's launches (same results either way).  order 0: step-major (all of step t, role by role, then
  * step t + 1).  order 1 (default): cohort-pipelined -- cohorts of 64 environments; the sweeps of a cohort-step are dispatched `lead`
  * cohort positions behind its dynamics and its finish waves `lag` positions behind the sweeps, so a wave finds its inputs instead of

@@ -14,7 +14,15 @@ measures instead, in the same alternating passes, (b) against
     (d) feedback_sectors   step_feedback(los_gains(...), sector_gains=..., record="reward"): the same autopilot with the LiDAR's
                            sector inputs in the law (auv_step_feedback_sectors; the reference's 9 x 20 partition, every sector gain
                            non-zero: the rudder steers away from the side of the nearest return, the thrust drops with it)
-and writes the rows to feedback_sectors_bench.jsonl and the ranges and their ratio to feedback_sectors_bench.md under --out."""
+and writes the rows to feedback_sectors_bench.jsonl and the ranges and their ratio to feedback_sectors_bench.md under --out.
+    python tools/feedback_bench.py --hidden [--out profiles/feedback_hidden]
+measures, in the same alternating passes,
+    (d) feedback_sectors   as above: the yardstick
+    (e) feedback_hidden    step_feedback(los_gains(...), sector_gains=..., hidden=..., record="reward"): the same law with 16 relu
+                           units over its 24 inputs (auv_step_feedback_hidden; per-environment N(0, 0.3) weights, every entry non-zero)
+    (f) per_step_hidden    one step() per step with the same law as torch ops on env.obs (float32: a gather and a maximum for the
+                           sector inputs, two matrix products for the layer)
+and writes the rows to feedback_hidden_bench.jsonl and the ranges, b / a and the verdict to README.md under --out."""
 import argparse
 import hashlib
 import json
@@ -29,19 +37,20 @@ import torch  # noqa: E402
 from gym_auv_amd import _capi  # noqa: E402
 from gym_auv_amd.batched_env import BatchedAuvEnv  # noqa: E402
 from gym_auv_amd.config import effective_reference_config  # noqa: E402
-from gym_auv_amd.feedback import los_gains  # noqa: E402
+from gym_auv_amd.feedback import default_sector_bounds, los_gains, pack_hidden  # noqa: E402
 from gym_auv_amd.world import build_bank_parallel  # noqa: E402
 
 ap = argparse.ArgumentParser()
 ap.add_argument("--out", default=None)
 ap.add_argument("--sectors", action="store_true", help="measure the launch with sector inputs against the one without")
+ap.add_argument("--hidden", action="store_true", help="measure the launch with a hidden layer against the sector launch and per-step torch ops")
 ap.add_argument("--envs", type=int, default=4096)
 ap.add_argument("--steps", type=int, default=1920)
 ap.add_argument("--passes", type=int, default=5)
 ap.add_argument("--launch", type=int, default=64)
 args = ap.parse_args()
 if args.out is None:
-    args.out = "profiles/feedback_sectors" if args.sectors else "profiles/feedback"
+    args.out = "profiles/feedback_hidden" if args.hidden else ("profiles/feedback_sectors" if args.sectors else "profiles/feedback")
 dev = torch.device("cuda:0")
 n, T, steps = args.envs, args.launch, args.steps
 cfg = effective_reference_config(use_lidar=True)
@@ -81,6 +90,42 @@ def feedback_sectors(m):
         env.step_feedback(gains, T, record="reward", sector_gains=sector_gains)
 
 
+# (e): one block per environment (the parameter traffic of a population), every entry non-zero
+_rs = np.random.RandomState(7)
+W1_np, b1_np, V_np = _rs.normal(0, 0.3, (n, 16, 24)), _rs.normal(0, 0.3, (n, 16)), _rs.normal(0, 0.05, (n, 2, 16))
+hidden = torch.as_tensor(pack_hidden(W1_np, b1_np, V_np), device=dev) if args.hidden else None
+
+
+def feedback_hidden(m):
+    for i in range(0, m, T):
+        env.step_feedback(gains, T, record="reward", sector_gains=sector_gains, hidden=hidden)
+
+
+# (f): the same law in float32 on the float32 observation, what a caller writes in torch.  The sector maxima: one gather of the
+# closeness columns into [N, K, widest sector] (short sectors repeat their last beam) and a maximum
+if args.hidden:
+    sb = default_sector_bounds(cfg)
+    wide = int(np.diff(sb).max())
+    idx_np = np.stack([6 + np.minimum(sb[k] + np.arange(wide), sb[k + 1] - 1) for k in range(ns)])
+    sec_idx = torch.as_tensor(idx_np.reshape(-1), dtype=torch.long, device=dev)
+    W1_t = torch.as_tensor(W1_np, dtype=torch.float32, device=dev)                           # [N, 16, 24]
+    b1_t = torch.as_tensor(b1_np, dtype=torch.float32, device=dev)
+    V_t = torch.as_tensor(V_np, dtype=torch.float32, device=dev)                              # [N, 2, 16]
+    H_t = torch.as_tensor(h_np[:, :ns], dtype=torch.float32, device=dev).t().contiguous()     # [K, 2]
+    v_buf = torch.zeros((n, 24), dtype=torch.float32, device=dev)                             # v_6 = v_7 = 0 (no ring), padding sectors 0
+
+
+def per_step_hidden(m):
+    for i in range(m):
+        obs = env.obs
+        z = obs.index_select(1, sec_idx).view(n, ns, wide).amax(dim=2)
+        v_buf[:, :6] = obs[:, :6]
+        v_buf[:, 8:8 + ns] = z
+        y = torch.relu(torch.baddbmm(b1_t.unsqueeze(2), W1_t, v_buf.unsqueeze(2)))            # [N, 16, 1]
+        a = torch.addmm(b, obs[:, :6], W) + z @ H_t + torch.bmm(V_t, y).squeeze(2)
+        env.step(a)
+
+
 def per_step(m):
     for i in range(m):
         env.step(torch.addmm(b, env.obs[:, :6], W))
@@ -89,6 +134,8 @@ def per_step(m):
 FORMS = (("open_loop", open_loop), ("feedback", feedback), ("per_step", per_step))
 if args.sectors:
     FORMS = (("feedback", feedback), ("feedback_sectors", feedback_sectors))
+if args.hidden:
+    FORMS = (("feedback_sectors", feedback_sectors), ("feedback_hidden", feedback_hidden), ("per_step_hidden", per_step_hidden))
 sha = hashlib.sha256(open(_capi.LIB_PATH, "rb").read()).hexdigest()
 rows = []
 for p in range(args.passes):
@@ -99,7 +146,7 @@ for p in range(args.passes):
         run(steps)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        row = dict(form=name, pass_=p, envs=n, beams=env.n_sensors, steps=steps, steps_per_launch=1 if name == "per_step" else T,
+        row = dict(form=name, pass_=p, envs=n, beams=env.n_sensors, steps=steps, steps_per_launch=1 if name.startswith("per_step") else T,
                    rate_M=round(n * steps / dt / 1e6, 2), us_per_step=round(1e6 * dt / steps, 2), health=env.health(), lib_sha256=sha,
                    command=" ".join(sys.argv))
         rows.append(row)
@@ -107,6 +154,28 @@ for p in range(args.passes):
 env.close()
 
 os.makedirs(args.out, exist_ok=True)
+if args.hidden:
+    with open(os.path.join(args.out, "feedback_hidden_bench.jsonl"), "w") as f:
+        for r in rows:
+            f.write(json.dumps(r) + "\n")
+    ra, rb, rc = ([r["rate_M"] for r in rows if r["form"] == k] for k in ("feedback_sectors", "feedback_hidden", "per_step_hidden"))
+    POLICY_LAUNCH = (75.0, 81.0)                               # the separate fused policy launch in the loop (README.md)
+    with open(os.path.join(args.out, "README.md"), "w") as f:
+        f.write("# Closed-loop launches: a hidden layer in the feedback law\n\n`python %s` on one MI355X, one process: %d environments x %d "
+                "beams, 50 polygons, one chain, %d steps per launch, 9 x 20 sectors; %d alternating passes in one session, each form warmed by "
+                "half a pass and timed by the host clock over %d steps ended by a synchronise.  Library sha256 `%s`.\n\n"
+                "| form | M env-steps/s per pass | min | max |\n|---|---|---|---|\n" % (" ".join(sys.argv), n, env.n_sensors, T, args.passes, steps, sha))
+        f.write("| (a) `step_feedback(los_gains, sector_gains=..., record=\"reward\")`, the sector launch | %s | %.1f | %.1f |\n"
+                % (", ".join("%.1f" % x for x in ra), min(ra), max(ra)))
+        f.write("| (b) `step_feedback(..., sector_gains=..., hidden=..., record=\"reward\")`, 16 relu units per environment | %s | %.1f | %.1f |\n"
+                % (", ".join("%.1f" % x for x in rb), min(rb), max(rb)))
+        f.write("| (c) one `step()` per step, the same law as torch ops on `env.obs` | %s | %.1f | %.1f |\n"
+                % (", ".join("%.1f" % x for x in rc), min(rc), max(rc)))
+        f.write("\n(b) / (a), pass by pass: %s.\n\nEvery run of (b) above every run of (c): **%s** (min (b) %.1f, max (c) %.1f).  Every run of (b) "
+                "above the %.0f-%.0f M of the separate policy launch in the loop: **%s**.\n\nRaw rows: `feedback_hidden_bench.jsonl`.\n"
+                % (", ".join("%.3f" % (y / x) for x, y in zip(ra, rb)), "yes" if min(rb) > max(rc) else "NO", min(rb), max(rc),
+                   POLICY_LAUNCH[0], POLICY_LAUNCH[1], "yes" if min(rb) > POLICY_LAUNCH[1] else "NO"))
+    sys.exit(0)
 if args.sectors:
     with open(os.path.join(args.out, "feedback_sectors_bench.jsonl"), "w") as f:
         for r in rows:
