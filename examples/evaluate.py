@@ -6,6 +6,7 @@ are auto-reset into the next world of the bank, and the episode log says how the
 
     python examples/evaluate.py --envs 256 --episodes 4                    # a freshly initialised policy
     python examples/evaluate.py --ckpt policy.pt --task pathfollow          # a state_dict of examples/ppo.py's ActorCritic
+    python examples/evaluate.py --envs 64 --frames out/                     # and pictures of the first 16 environments
 """
 import argparse
 import json
@@ -14,6 +15,7 @@ import sys
 import time
 import warnings
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -37,9 +39,19 @@ def load_policy(ckpt, obs_dim, device, seed=0):
     return net.eval()
 
 
-def evaluate(env, fused, episodes, max_steps=100000):
+def save_frames(env, frames_dir, step, n_frames=16):
+    """Frames of the first `n_frames` environments, drawn on the device (BatchedAuvEnv.render): the stack as
+    frames_<step>.npy [B, H, W, 3] and, tiled into one picture, frames_<step>.ppm (a binary PPM: any viewer opens it)."""
+    from gym_auv_amd.render import tile_frames, write_ppm
+    frames = env.render(envs=list(range(min(env.n_envs, n_frames)))).cpu().numpy()
+    np.save(os.path.join(frames_dir, "frames_%06d.npy" % step), frames)
+    write_ppm(os.path.join(frames_dir, "frames_%06d.ppm" % step), tile_frames(frames))
+
+
+def evaluate(env, fused, episodes, max_steps=100000, frames_dir=None):
     """Step until every environment has finished `episodes` episodes (or max_steps): returns the episode-log rows [k, 8] (float64,
-    BatchedAuvEnv.EPISODE_LOG_COLUMNS) of the first `episodes` episodes of every environment, and the number of steps taken."""
+    BatchedAuvEnv.EPISODE_LOG_COLUMNS) of the first `episodes` episodes of every environment, and the number of steps taken.
+    frames_dir: a picture of the first environments every 50 steps (save_frames)."""
     env.episode_log()                                      # (drop whatever ended before)
     rows, steps = [], 0
     count = torch.zeros(env.n_envs, dtype=torch.int64, device=env.device)
@@ -48,6 +60,8 @@ def evaluate(env, fused, episodes, max_steps=100000):
             fused.predict()                                # -> fused.actions
             env.step(fused.actions)
         steps += 50
+        if frames_dir:
+            save_frames(env, frames_dir, steps)
         log = env.episode_log()
         if log.shape[0]:
             rows.append(log)
@@ -78,6 +92,7 @@ def main():
     ap.add_argument("--act-space", default="raw", choices=["raw", "normalized"])
     ap.add_argument("--max-steps", type=int, default=100000, help="stop after this many steps even if episodes are still open")
     ap.add_argument("--seed", type=int, default=0)
+    ap.add_argument("--frames", default=None, metavar="DIR", help="write frames of the first 16 environments every 50 steps: .npy stacks and .ppm pictures")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     colav = a.task == "colav"
@@ -98,7 +113,10 @@ def main():
     fused = FusedActorCritic(net, env, rollout=1, **kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    log, steps = evaluate(env, fused, a.episodes, a.max_steps)
+    if a.frames:
+        os.makedirs(a.frames, exist_ok=True)
+        save_frames(env, a.frames, 0)
+    log, steps = evaluate(env, fused, a.episodes, a.max_steps, frames_dir=a.frames)
     torch.cuda.synchronize()
     dt = time.perf_counter() - t0
     k = int(log.shape[0])

@@ -20,6 +20,7 @@ AUV_REWARD_COLAV, AUV_REWARD_PATHFOLLOW = 0, 1
 AUV_CULL_REFERENCE, AUV_CULL_EXACT = 0, 1
 AUV_F32, AUV_F64 = 0, 1
 AUV_RDV_EVENTS, AUV_RDV_DEVICE, AUV_RDV_CP = 0, 1, 2
+AUV_VIEW_HEADING_UP, AUV_VIEW_NORTH_UP = 0, 1
 
 FIELDS = dict(STATE=0, LIDAR_D=1, OBS64=2, REWARD64=3, INFO64=4, WORLD_IDX=5, COUNTERS=6,
               MOVER_STATE=7, NEARBY=8, EPISODE=9, CULL_LIMITS=10, NAV64=11, COLLISION=12, STAMPS=13, STEP_INFO=14, BROKEN=15, FW_STATE=16, FW_SERIAL=17,
@@ -262,6 +263,7 @@ def load_library(path: str = None) -> C.CDLL:
         "auv_ppo_attach_policy": (C.c_int, [vp, vp]),
         "auv_ppo_grad": (C.c_int, [vp, C.POINTER(AuvPpoBatch), vp, vp, vp]),
         "auv_ppo_adam": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(AuvPpoAdam), vp, vp]),
+        "auv_render": (C.c_int, [vp, vp, C.POINTER(i32), i32, i32, i32, C.c_double, i32, C.c_double, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
         "auv_abi_version": (i32, []),
         "auv_last_error": (C.c_char_p, []),
     }
@@ -275,6 +277,8 @@ def load_library(path: str = None) -> C.CDLL:
         raise AuvLibraryError("ABI mismatch: library %d, binding %d" % (lib.auv_abi_version(), ABI_VERSION))
     if hasattr(lib, "auv_test_hooks"):   # only the -DAUV_TEST_HOOKS build exports it
         lib.auv_test_hooks.restype, lib.auv_test_hooks.argtypes = C.c_int, [vp, i32, i32]
+    if hasattr(lib, "auv_render_diag"):  # only the -DAUV_RENDER_DIAG build exports it (tools/render_bench.py)
+        lib.auv_render_diag.restype, lib.auv_render_diag.argtypes = C.c_int, [vp, C.POINTER(C.c_uint64)]
     _lib = lib
     return lib
 
@@ -290,6 +294,7 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_snapshot_row_bytes", "auv_snapshot_layout", "auv_snapshot", "auv_restore", "auv_snapshot_skipped", "auv_plan_score",
                     "auv_plan_score_v", "auv_policy_eval",
                     "auv_ppo_param_floats", "auv_ppo_create", "auv_ppo_destroy", "auv_ppo_load", "auv_ppo_attach_policy", "auv_ppo_grad", "auv_ppo_adam",
+                    "auv_render",
                     "auv_abi_version", "auv_last_error"]
 
 # tables of a generated bank (auv_read_bank): id, dtype, trailing shape ('P' = AUV_GEN_POLY_CAP,

@@ -817,6 +817,53 @@ class BatchedAuvEnv:
         _check(_LIB.auv_snapshot_skipped(self._h, C.byref(out), self._stream()), "auv_snapshot_skipped")
         return int(out.value)
 
+    # ------------------------------------------------------------------------------ rendering
+    def render(self, envs=None, size=(600, 720), zoom: float = 1.5, view: str = "heading_up", trail=None, markers=None,
+               return_geometry: bool = False, line_px: float = 1.0, palette=None):
+        """rgb_array frames of the environments `envs` (default: the first min(n, 16); any indices, repeats allowed), drawn on the
+        device (auv_render: two launches on the caller's stream, ordered behind the sub-batch chains, no host synchronisation):
+        uint8 [B, H, W, 3], a vessel-centred top view at `zoom` pixels per metre, the heading or north pointing up.  trail:
+        [B, L, 2] positions joined by a line, a NaN row ends a frame's trail; markers: [B, M, 3] filled discs x, y, radius.  The
+        pixel rule is stated in include/auv_hip.h and restated by render.render_reference; with return_geometry the call also
+        returns what its geometry pass made of the state, dict(cam, dyn_seg, ray_seg, ray_q): the mirror's inputs."""
+        from .render import VIEWS, check_palette, check_render_args
+        idx = check_render_args(self.n_envs, envs, size, zoom, view, line_px)
+        pal = check_palette(palette)
+        B, H, W, S = len(idx), int(size[0]), int(size[1]), self.n_sensors
+
+        def dev(x, last, name):
+            if x is None:
+                return None, 0
+            t = torch.as_tensor(x).to(device=self.device, dtype=torch.float64).contiguous()
+            if t.dim() != 3 or t.shape[0] != B or t.shape[2] != last:
+                raise ValueError("render: %s must have shape (%d, *, %d), got %s" % (name, B, last, tuple(t.shape)))
+            return t, int(t.shape[1])
+
+        tr, L = dev(trail, 2, "trail")
+        mk, M = dev(markers, 3, "markers")
+        with torch.cuda.device(self.device):
+            frames = torch.empty((B, H, W, 3), dtype=torch.uint8, device=self.device)
+            geo = None
+            if return_geometry:
+                geo = dict(cam=torch.empty((B, 8), dtype=torch.float64, device=self.device),
+                           dyn_seg=torch.empty((B, 5 * self.m_max + 5, 4), dtype=torch.float64, device=self.device),
+                           ray_seg=torch.empty((B, max(S, 1), 4), dtype=torch.float64, device=self.device),
+                           ray_q=torch.empty((B, max(S, 1)), dtype=torch.uint8, device=self.device))
+        ptr = lambda t: None if t is None else C.c_void_p(t.data_ptr())   # noqa: E731
+        g = geo or {}
+        self._join_chains()
+        _check(_LIB.auv_render(self._h, self._stream(), idx.ctypes.data_as(C.POINTER(C.c_int32)), B, H, W, float(zoom), VIEWS[view],
+                               float(line_px), ptr(tr), L, ptr(mk), M, C.c_void_p(pal.ctypes.data), ptr(frames),
+                               ptr(g.get("cam")), ptr(g.get("dyn_seg")), ptr(g.get("ray_seg")), ptr(g.get("ray_q"))), "auv_render")
+        cur = torch.cuda.current_stream(self.device)
+        for t in (tr, mk):
+            if t is not None:
+                t.record_stream(cur)
+        if geo is not None:
+            geo["ray_seg"], geo["ray_q"] = geo["ray_seg"][:, :S], geo["ray_q"][:, :S]
+            return frames, geo
+        return frames
+
     # ------------------------------------------------------------------------------ field access
     def field_shape(self, name: str):
         n, S = self.n_envs, self.n_sensors

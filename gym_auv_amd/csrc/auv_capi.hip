@@ -16,6 +16,7 @@
 #include "auv_multi_geom.h"
 #include "auv_snapshot.h"
 #include "auv_ppo.h"
+#include "auv_render.h"
 
 void auv_launch_k1(const AuvDev& d, const void* actions, int dtype, hipStream_t st, hipEvent_t ev0 = nullptr,
                    hipEvent_t ev1 = nullptr);
@@ -131,6 +132,17 @@ struct auv_handle {
   int chain_steps = 1, graph_steps = 1;    // steps per replay of the captured chains / of the one graph
   unsigned long long multi_seq = 0;        // auv_step_multi: step numbers handed out so far (every mark of a step carries its number)
   int multi_order = 1, multi_lead = 16, multi_lag = 30;   // auv_set_multi_order: workgroup order of a launch of several steps
+  // auv_render: the geometry pass's outputs and the device copy of the index list, for `render_cap` frames
+  std::vector<void*> render_allocs;
+  int render_cap = 0;
+  // the index list travels through one of four pinned host slots (an event per slot: a slot is reused once the copy out of it is done)
+  int32_t* r_pin = nullptr;
+  hipEvent_t r_pin_ev[4] = {nullptr, nullptr, nullptr, nullptr};
+  unsigned r_seq = 0;
+#ifdef AUV_RENDER_DIAG
+  unsigned long long* r_diag = nullptr;
+#endif
+  int32_t* r_idx = nullptr; double* r_cam = nullptr; double4* r_dyn = nullptr; double4* r_ray = nullptr; uint8_t* r_q = nullptr; int32_t* r_tlen = nullptr;
   unsigned int* snap_skipped = nullptr;    // [1] device: pairs auv_snapshot / auv_restore skipped for an index out of range (restarts with every bank)
   // on-device generation (auv_generate_worlds): shape of the slot bank, 0 = packed upload
   int gen_worlds, gen_moving, gen_static, gen_grid;
@@ -288,6 +300,9 @@ static int finish_bank(auv_handle* h, bool alloc_env) {
   const size_t n = (size_t)d.n, S = (size_t)d.cfg.n_sensors;
   int rc = 0;
   h->bank_seen = true;
+  (void)hipDeviceSynchronize();    // (renders in flight read the scratch that goes next)
+  free_pool(h->render_allocs);     // (auv_render's scratch is sized by this bank's Mmax: the next call allocates it again)
+  h->render_cap = 0;
   if (alloc_env) {
   free_pool(h->env_allocs);
   auto& ep = h->env_allocs;
@@ -733,6 +748,12 @@ int auv_destroy(auv_handle_t* h) {
   for (auto& st : h->fork_streams) (void)hipStreamDestroy(st);
   free_pool(h->env_allocs);
   free_pool(h->bank_allocs);
+  free_pool(h->render_allocs);
+  if (h->r_pin) (void)hipHostFree(h->r_pin);
+  for (auto& ev : h->r_pin_ev) if (ev) (void)hipEventDestroy(ev);
+#ifdef AUV_RENDER_DIAG
+  if (h->r_diag) (void)hipFree(h->r_diag);
+#endif
   if (h->pair_error_host) (void)hipHostFree(h->pair_error_host);
   if (h->d.self) (void)hipFree((void*)h->d.self);
   delete h;
@@ -1776,6 +1797,20 @@ int auv_set_step_mode(auv_handle_t* h, int32_t mode) {
   return AUV_OK;
 }
 
+#ifdef AUV_RENDER_DIAG
+// Only in the diagnostic build (tools/build_variant.sh render_diag "-DAUV_RENDER_DIAG"; tools/render_bench.py): segments the
+// rasteriser's tiles were offered / kept after the tile cull since the last call (synchronises the device; resets the counts).
+int auv_render_diag(auv_handle_t* h, uint64_t* out2) {
+  if (!h || !out2) return fail(AUV_EINVAL, "auv_render_diag: null argument");
+  out2[0] = out2[1] = 0;
+  if (!h->r_diag) return AUV_OK;
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out2, h->r_diag, 2 * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemset(h->r_diag, 0, 2 * sizeof(uint64_t)));
+  return AUV_OK;
+}
+#endif
+
 #ifdef AUV_CUTS
 // Only in the diagnostic build (tools/build_variant.sh cuts "-DAUV_CUTS"; tools/valu_budget.py): switch off the
 // LiDAR role's phases from `cut_lidar` on and the navigation role's from `cut_nav` on (0 = run everything).
@@ -1911,6 +1946,80 @@ int auv_feasibility_pooling(auv_handle_t* h, const int32_t* sector_start_dev, in
   if (!sector_start_dev || n_sectors < 1 || n_sectors > h->d.cfg.n_sensors || !(width >= 0.0))
     return fail(AUV_EINVAL, "auv_feasibility_pooling: bad arguments");
   auv_launch_k4(h->d, sector_start_dev, n_sectors, width, out_dist_dev, out_closeness_dev, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+int auv_render(auv_handle_t* h, void* stream, const int32_t* env_idx_host, int32_t B, int32_t H, int32_t W, double zoom, int32_t view,
+               double line_px, const double* trail_dev, int32_t L, const double* markers_dev, int32_t M, const uint8_t* palette_host,
+               uint8_t* frames_dev, double* cam_out, double* dyn_seg_out, double* ray_seg_out, uint8_t* ray_q_out) {
+  if (!h) return fail(AUV_EINVAL, "auv_render: null handle");
+  if (!h->worlds_loaded) return fail(AUV_EINVAL, "auv_render: no world bank loaded");
+  if (B < 1 || H < 1 || W < 1) return fail(AUV_EINVAL, "auv_render: B = %d, H = %d, W = %d: each must be >= 1", B, H, W);
+  if (H > 4096 || W > 4096 || B > 65535) return fail(AUV_EINVAL, "auv_render: H = %d, W = %d (at most 4096), B = %d (at most 65535)", H, W, B);
+  if (!(std::isfinite(zoom) && zoom > 0.0)) return fail(AUV_EINVAL, "auv_render: zoom = %g must be finite and > 0", zoom);
+  if (!(std::isfinite(line_px) && line_px > 0.0)) return fail(AUV_EINVAL, "auv_render: line_px = %g must be finite and > 0", line_px);
+  if (view != AUV_VIEW_HEADING_UP && view != AUV_VIEW_NORTH_UP) return fail(AUV_EINVAL, "auv_render: unknown view %d", view);
+  if (!env_idx_host || !palette_host || !frames_dev) return fail(AUV_EINVAL, "auv_render: null index list, palette or frame buffer");
+  if (L < 0 || M < 0) return fail(AUV_EINVAL, "auv_render: L = %d, M = %d must not be negative", L, M);
+  for (int j = 0; j < B; j++)
+    if (env_idx_host[j] < 0 || env_idx_host[j] >= h->d.n)
+      return fail(AUV_EINVAL, "auv_render: env_idx[%d] = %d is outside the handle's %d environments", j, env_idx_host[j], h->d.n);
+  HIP_TRY(hipSetDevice(h->device));
+  const AuvDev& d = h->d;
+  const size_t S = (size_t)(d.cfg.n_sensors > 0 ? d.cfg.n_sensors : 1), nd = 5 * (size_t)d.m_max + 5;
+  hipStream_t st = (hipStream_t)stream;
+  if (B > h->render_cap) {
+    // grow: the old scratch may still be read by renders in flight, so the device is drained first (a host synchronisation, on
+    // the first call and on a call with more frames than any before it only)
+    HIP_TRY(hipDeviceSynchronize());
+    free_pool(h->render_allocs);
+    if (h->r_pin) (void)hipHostFree(h->r_pin);
+    h->r_pin = nullptr;
+    h->render_cap = 0;
+    int cap = 16;
+    while (cap < B) cap *= 2;
+    int rc = 0;
+    rc |= dev_alloc(h->render_allocs, &h->r_idx, (size_t)cap);
+    rc |= dev_alloc(h->render_allocs, &h->r_cam, (size_t)cap * 8);
+    rc |= dev_alloc(h->render_allocs, &h->r_dyn, (size_t)cap * nd);
+    rc |= dev_alloc(h->render_allocs, &h->r_ray, (size_t)cap * S);
+    rc |= dev_alloc(h->render_allocs, &h->r_q, (size_t)cap * S);
+    rc |= dev_alloc(h->render_allocs, &h->r_tlen, (size_t)cap);
+    if (rc) return AUV_EHIP;
+    HIP_TRY(hipHostMalloc((void**)&h->r_pin, 4 * (size_t)cap * sizeof(int32_t), hipHostMallocDefault));
+    for (int k = 0; k < 4; k++)
+      if (!h->r_pin_ev[k]) HIP_TRY(hipEventCreateWithFlags(&h->r_pin_ev[k], hipEventDisableTiming));
+    h->render_cap = cap;
+    h->r_seq = 0;
+  }
+  const unsigned slot = h->r_seq & 3;
+  if (h->r_seq >= 4) HIP_TRY(hipEventSynchronize(h->r_pin_ev[slot]));   // (returns at once unless four renders are still queued)
+  h->r_seq++;
+  int32_t* pin = h->r_pin + (size_t)slot * h->render_cap;
+  memcpy(pin, env_idx_host, (size_t)B * sizeof(int32_t));
+  HIP_TRY(hipMemcpyAsync(h->r_idx, pin, (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice, st));
+  HIP_TRY(hipEventRecord(h->r_pin_ev[slot], st));
+  AuvRenderArgs a;
+  memset(&a, 0, sizeof(a));
+  a.env_idx = h->r_idx, a.B = B, a.H = H, a.W = W, a.view = view, a.zoom = zoom, a.line_px = line_px;
+  a.trail = L > 0 ? trail_dev : nullptr, a.L = L;
+  a.markers = M > 0 ? markers_dev : nullptr, a.M = M;
+  memcpy(a.palette, palette_host, 27);
+  a.frames = frames_dev;
+  a.cam = cam_out ? cam_out : h->r_cam;
+  a.dyn_seg = dyn_seg_out ? (double4*)dyn_seg_out : h->r_dyn;
+  a.ray_seg = ray_seg_out ? (double4*)ray_seg_out : h->r_ray;
+  a.ray_q = ray_q_out ? ray_q_out : h->r_q;
+  a.trail_len = h->r_tlen;
+#ifdef AUV_RENDER_DIAG
+  if (!h->r_diag) {
+    HIP_TRY(hipMalloc((void**)&h->r_diag, 2 * sizeof(unsigned long long)));
+    HIP_TRY(hipMemset(h->r_diag, 0, 2 * sizeof(unsigned long long)));
+  }
+  a.diag = h->r_diag;
+#endif
+  auv_launch_render(d, a, st);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }

@@ -42,6 +42,7 @@
 // + 24*K (cull circles) + 16*K (meta) + 24 (pose) + 16*S (d + closeness out) + K (nearby) + 4*S
 // (float32 closeness).
 #include "auv_device.h"
+#include "auv_mover_segs.h"
 
 namespace {
 
@@ -72,26 +73,6 @@ __device__ __forceinline__ int wrap_ray(int i, int S) {   // Python list index f
   if (i >= S) i -= S;
   return i;
 }
-
-// The five boundary segments of a mover (obstacles.py:217-233) formed on demand from its pose, with
-// the arithmetic phase A used to form them: LDS keeps 40 bytes per mover instead of 160.
-struct MoverSegs {
-  double c, s, x, y, wd;    // snapped cos / sin of the heading, position, width
-  __device__ __forceinline__ void vertex(int k, double& vx, double& vy) const {
-    const double bx = (k <= 1) ? -wd / 2 : (k == 3 ? 3.0 / 2 * wd : wd / 2);
-    const double by = (k == 0 || k == 4) ? -wd / 2 : (k == 3 ? 0.0 : wd / 2);
-    const double x0 = 5.0 * wd / 18.0;
-    const double xo = x0 - x0 * c, yo = 0.0 - x0 * s;
-    vx = (c * bx + -s * by + xo) + x;
-    vy = (s * bx + c * by + yo) + y;
-  }
-  __device__ __forceinline__ double4 operator[](int i) const {
-    double ax, ay, bx, by;
-    vertex(i, ax, ay);
-    vertex(i == 4 ? 0 : i + 1, bx, by);
-    return make_double4(ax, ay, bx, by);
-  }
-};
 
 #ifndef K2_SEG_CAP
 #define K2_SEG_CAP 96    // the LARGEST stage: segments per wave and batch (180 beams, 50 obstacles: slice <= 10 KiB -> 16 waves per CU)
@@ -145,12 +126,6 @@ struct Slice {
   int* hits;      // k2_back: the returns' beam indices and weights, in regions that are idle by then (nullptr: they do not fit --
   double* hitw;   // every pass of k2_back then does everything)
 };
-
-__device__ __forceinline__ MoverSegs mover_segs(const double4 rot, const double wd) {
-  MoverSegs ms;
-  ms.c = rot.x, ms.s = rot.y, ms.x = rot.z, ms.y = rot.w, ms.wd = wd;
-  return ms;
-}
 
 // the slice without k2_back's lists (`hits` / `hitw` null: carve_hits places them)
 __device__ __forceinline__ Slice carve_base(unsigned char* p, int S, int k_max, int m_max, int cap) {

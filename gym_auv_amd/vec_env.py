@@ -183,11 +183,23 @@ class AuvVecEnv:
     def close(self):
         self.env.close()
 
-    def render(self, *args, **kwargs):
-        return None                                                          # rendering is out of scope
+    def get_images(self, **kwargs):
+        """VecEnv.get_images: one entry per environment -- an [H, W, 3] uint8 frame for each tracked environment (the first
+        environment when none is tracked), drawn on the device in one call (BatchedAuvEnv.render; keyword arguments go there), and
+        None for the others: thousands of environments are not drawn to look at a few."""
+        which = self._track or [0]
+        frames = self.env.render(envs=which, **kwargs).cpu().numpy()
+        out = [None] * self.num_envs
+        for k, e in enumerate(which):
+            out[e] = frames[k]
+        return out
 
-    def get_images(self):
-        return [None] * self.num_envs
+    def render(self, mode="rgb_array", **kwargs):
+        """VecEnv.render: the frames get_images() drew, tiled into one image; "human" (a window) returns None."""
+        if mode != "rgb_array":
+            return None
+        from .render import tile_frames
+        return tile_frames(np.stack([f for f in self.get_images(**kwargs) if f is not None]))
 
     # ------------------------------------------------------------------------------ attributes of the environments
     def _indices(self, indices) -> List[int]:

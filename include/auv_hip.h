@@ -800,6 +800,45 @@ int auv_ppo_grad(auv_ppo_t* p, const auv_ppo_batch_t* batch, float* grad, float*
 int auv_ppo_adam(auv_ppo_t* p, float* theta, float* m, float* v, const float* grad, const auv_ppo_adam_t* adam, float* norms_out,
                  void* stream);
 
+/* ---- rendering: rgb_array frames of B environments, drawn on the device (BaseEnvironment.render, environment.py:410-437; the
+ * reference draws ONE environment on the host with pygame: a vessel-centred top view, render2d/renderer.py:62-120) -------------
+ * frames_dev [B][H][W][3] uint8 <- a top view of environment env_idx_host[j] (any environments, repeats allowed), centred on
+ * the vessel, `zoom` pixels per metre, screen y downwards.  view: AUV_VIEW_HEADING_UP (the heading points up) or
+ * AUV_VIEW_NORTH_UP (world x to the right, world y up).  Two launches on `stream` (csrc/k10_render.hip): a geometry pass, one
+ * wave per frame, and the rasteriser, one workgroup per 16 x 16 tile.  The index list is copied into a pinned buffer of the
+ * handle before the call returns (the caller's list may go at once) and travels from there by an asynchronous copy.  The geometry
+ * lives in scratch of the handle (some 40 S + 160 Mmax bytes per frame), shared by all calls: renders of one handle must be
+ * ordered against each other -- one stream, or events between streams.  HOST SYNCHRONISATION: none in the steady state.  The first
+ * call, a call with more frames than any call before it, and loading a new bank drain the device and (re)allocate that scratch;
+ * and a call waits for the render four calls back if that one has not started yet.  Eager only (not inside a stream capture).
+ * THE PIXEL RULE -- the contract; gym_auv_amd/render.py (render_reference) restates it in NumPy bit for bit.  IEEE fp64, no
+ * contraction, no square root.  The centre of pixel (row i, column j) is the world point
+ *     p = (x, y) + M (j + 0.5 - W / 2, i + 0.5 - H / 2),   cam = x, y, M00, M01, M10, M11, zoom, view
+ * M in metres per pixel: heading up (s / zoom, -c / zoom; -c / zoom, -s / zoom) with (s, c) the device's sincos of psi, north up
+ * (1 / zoom, 0; 0, -1 / zoom).  Layers, later ones overwrite: background, path, trail, static obstacles, markers, movers,
+ * LiDAR beams, vessel.
+ *     line    (path, trail, beams)  e = b - a, t = clamp(((p - a) . e) / (e . e), 0, 1) with one division (t = 0 when e . e is
+ *             not > 0), lit when |(p - a) - t e|^2 <= h^2, h = 0.5 line_px / zoom
+ *     filled  (obstacles, movers, vessel; per shape)  lit when an odd number of its boundary segments (ax, ay, bx, by) have
+ *             (ay > py) != (by > py) and px < ax + (py - ay) * (bx - ax) / (by - ay).  Circles are their stored 64-gons.
+ *     disc    (markers: x, y, radius)  (px - x)^2 + (py - y)^2 <= radius^2
+ * Among several lit beams the highest index wins; a beam's channel is (lo * (255 - q) + hi * q + 127) / 255 in integers between
+ * palette rows 6 and 7, q = min(255, int(max(0, closeness) * 255 + 0.5)) (the beam's closeness column of the observation row; the
+ * linear rule 1 - clip(range / sensor_range, 0, 1) with pooled observations, which keep no such column).  With the LiDAR off nothing
+ * was measured: every beam has length 0 and lies under the vessel.
+ *   trail_dev    [B][L][2] fp64 or NULL: positions joined by line segments; the first row with a NaN ends a frame's trail.
+ *   markers_dev  [B][M][3] fp64 or NULL: x, y, radius.
+ *   palette_host [9][3] uint8: background, path, trail, obstacle, marker, mover, beam lo, beam hi, vessel.
+ *   cam_out [B][8], dyn_seg_out [B][5 Mmax + 5][4] (every mover's pentagon -- zeros for the slots past the world's movers -- then
+ *   the vessel's), ray_seg_out [B][S][4] (vessel -> end of beam), ray_q_out [B][S] uint8: fp64 device buffers or NULL; what the
+ *   geometry pass made of the state, i.e. everything the rasteriser reads besides the bank's tables.
+ * AUV_EINVAL: B, H or W < 1, H or W > 4096, B > 65535, an index outside [0, N), a zoom or line width that is not finite and > 0,
+ * an unknown view, a NULL palette or frame buffer, L or M < 0, a handle with no bank loaded.                                 */
+enum { AUV_VIEW_HEADING_UP = 0, AUV_VIEW_NORTH_UP = 1 };
+int auv_render(auv_handle_t* h, void* stream, const int32_t* env_idx_host, int32_t B, int32_t H, int32_t W, double zoom, int32_t view,
+               double line_px, const double* trail_dev, int32_t L, const double* markers_dev, int32_t M, const uint8_t* palette_host,
+               uint8_t* frames_dev, double* cam_out, double* dyn_seg_out, double* ray_seg_out, uint8_t* ray_q_out);
+
 int32_t auv_abi_version(void);
 const char* auv_last_error(void);
 
