@@ -650,6 +650,8 @@ class BatchedAuvEnv:
         nd = devgen.n_draws(spec.n_moving, spec.n_static)
         if tuple(draws.shape) != (spec.n_worlds, nd):
             raise ValueError("draws must have shape (%d, %d), got %s" % (spec.n_worlds, nd, tuple(draws.shape)))
+        if not seeded and not bool(((draws[:, :11] >= 0) & (draws[:, :11] < 1)).all()):
+            raise ValueError("draws[:, :11] (waypoint count, theta0, jitters, pose) must be uniform draws in [0, 1)")
         unit, nseg = devgen.ring_tables()
         unit = np.ascontiguousarray(unit, dtype=np.float64)
         nseg = np.ascontiguousarray(nseg, dtype=np.int32)

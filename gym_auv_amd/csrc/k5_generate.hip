@@ -17,6 +17,9 @@
 #include "auv_generate.h"
 
 #define GEN_EXTRA_CAND 56   // devgen.EXTRA_CAND
+// raw waypoints of a curve: 2 * (floor(4 u + 2) / 2) + 3 = 5 or 7 for u < 1 -- and 9 for the one draw u = 1 - 2^-53, where
+// 4 u + 2 rounds to 6 (path.py:96-120 and the host mirror build that curve too; it uses all six jitters of the row)
+#define GEN_WP_MAX 9
 
 namespace {
 
@@ -164,8 +167,8 @@ __global__ void __launch_bounds__(256) k5_generate(GenOut g, const double* __res
                                                    const int32_t* __restrict__ slots, const int32_t* __restrict__ count_dev) {
   __shared__ double s_part[256];
   __shared__ double s_ks[GEN_NK], s_wx[GEN_NK], s_wy[GEN_NK], s_dx[GEN_NK], s_dy[GEN_NK];   // 40 KB: knots, points, slopes of the pass in hand
-  __shared__ double s_wp[2][8];      // raw waypoints
-  __shared__ double s_s1[8], s_d1[2][8], s_c1[2][8][4];
+  __shared__ double s_wp[2][GEN_WP_MAX];      // raw waypoints
+  __shared__ double s_s1[GEN_WP_MAX], s_d1[2][GEN_WP_MAX], s_c1[2][GEN_WP_MAX][4];
   __shared__ double s_pose[3], s_goal[2], s_L;
   __shared__ int s_n1, s_P;
   const int tid = threadIdx.x, nt = blockDim.x;
@@ -184,7 +187,7 @@ __global__ void __launch_bounds__(256) k5_generate(GenOut g, const double* __res
       const double length = 800.0;
       const double theta0 = 2 * PI * (row[1] - 0.5);
       const double sx = 0.5 * length * cos(theta0), sy = 0.5 * length * sin(theta0);
-      const int half = nwp / 2;
+      const int half = min(max(nwp / 2, 1), (GEN_WP_MAX - 3) / 2);   // (1 .. 3 for any row[0] in [0, 1): the bounds guard rows that are not draws)
       const int n1 = 2 * half + 3;
       s_wp[0][0] = sx, s_wp[1][0] = sy;
       s_wp[0][n1 - 1] = -sx, s_wp[1][n1 - 1] = -sy;
@@ -196,7 +199,7 @@ __global__ void __launch_bounds__(256) k5_generate(GenOut g, const double* __res
         s_wp[0][n1 - 2 - k] = (half - k) * (-sx) / (half + 1) + j2;
         s_wp[1][n1 - 2 - k] = (half - k) * (-sy) / (half + 1) + j2;
       }
-      // pass 1 on the raw waypoints (serial: <= 7 points)
+      // pass 1 on the raw waypoints (serial: <= GEN_WP_MAX points)
       s_s1[0] = 0.0;
       for (int i = 0; i + 1 < n1; i++) {
         const double dx = s_wp[0][i + 1] - s_wp[0][i], dy = s_wp[1][i + 1] - s_wp[1][i];

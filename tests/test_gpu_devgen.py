@@ -15,6 +15,8 @@ from gym_auv_amd.config import effective_reference_config
 from gym_auv_amd.devgen import GeneratedWorlds
 from gym_auv_amd.world import build_world, pack_bank
 
+from devgen_rows import assert_world_tables, read_tables
+
 pytestmark = pytest.mark.gpu
 
 
@@ -39,43 +41,9 @@ def test_generated_tables_match_host_builder(nm, ns, seed):
     spec = GeneratedWorlds(6, nm, ns, seed)
     env = _env(cfg, spec, 6, auto_reset=False)
     host = _host_worlds(cfg, spec)
-    cnt = _np(env.read_bank("POLY_CNT"))
-    xy, cum = _np(env.read_bank("POLY_XY")), _np(env.read_bank("POLY_CUM"))
-    ks, kc = _np(env.read_bank("KNOT_S")), _np(env.read_bank("KNOT_COEF"))
-    sc = _np(env.read_bank("WORLD_SCALAR"))
-    meta, cull, seg = _np(env.read_bank("OBS_META")), _np(env.read_bank("OBS_CULL")), _np(env.read_bank("SEG"))
-    mp, mi, mv = _np(env.read_bank("MV_PARAM")), _np(env.read_bank("MV_INIT")), _np(env.read_bank("MV_VTAB"))
-    cb = _np(env.read_bank("CHUNK_BOUND"))
+    tables = read_tables(env)
     for w, hw in enumerate(host):
-        p = hw.path
-        P = len(p.points)
-        assert cnt[w] == P
-        np.testing.assert_allclose(ks[w], p.knot_s, rtol=0, atol=1e-9)
-        np.testing.assert_allclose(kc[w, :-1, 0:4], p.cx.T, rtol=1e-6, atol=1e-9)
-        np.testing.assert_allclose(kc[w, :-1, 4:8], p.cy.T, rtol=1e-6, atol=1e-9)
-        np.testing.assert_allclose(xy[w, :P], p.points, rtol=0, atol=1e-9)
-        np.testing.assert_allclose(cum[w, :P], p._cum, rtol=0, atol=1e-9)
-        np.testing.assert_allclose(sc[w], hw.scalar, rtol=0, atol=1e-9)
-        # every chunk circle really bounds its vertices
-        for c in range((P - 1 + 63) // 64):
-            v = p.points[c * 64:min(c * 64 + 64, P - 1) + 1]
-            assert np.all(np.hypot(v[:, 0] - cb[w, c, 0], v[:, 1] - cb[w, c, 1]) <= cb[w, c, 2])
-        K = nm + ns
-        if K:
-            hm = hw.obs_meta
-            np.testing.assert_array_equal(meta[w, :K, 0], hm[:, 0])
-            np.testing.assert_array_equal(meta[w, :K, 2], hm[:, 2])
-            # movers: index within the world; circles: -3 = simple clockwise ring (back-face flag set on the device)
-            np.testing.assert_array_equal(meta[w, :K, 3], np.where(hm[:, 0] == 0, -3, hm[:, 3]))
-            np.testing.assert_allclose(cull[w, :K], hw.obs_cull, rtol=0, atol=1e-9)
-            for k in range(ns):
-                so = meta[w, k, 1] - w * seg.shape[1]          # absolute slot offset -> world-relative
-                assert so == 64 * k
-                np.testing.assert_allclose(seg[w, so:so + hm[k, 2]], hw.seg[hm[k, 1]:hm[k, 1] + hm[k, 2]], rtol=0, atol=1e-9)
-        if nm:
-            np.testing.assert_allclose(mp[w], hw.mv_param, rtol=0, atol=1e-9)
-            np.testing.assert_allclose(mi[w], hw.mv_init, rtol=0, atol=1e-9)
-            np.testing.assert_allclose(mv[w], np.concatenate(hw.mv_vtab), rtol=0, atol=1e-9)
+        assert_world_tables(tables, w, hw, nm, ns)
     env.close()
 
 
