@@ -16,4 +16,8 @@ def __getattr__(name):
     if name == "FusedPPOUpdate":
         from .ppo_update import FusedPPOUpdate
         return FusedPPOUpdate
+    # PolicyPopulation: a policy per group of environments (population.py; its NumPy mirrors need no library)
+    if name == "PolicyPopulation":
+        from .population import PolicyPopulation
+        return PolicyPopulation
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

@@ -154,6 +154,17 @@ class AuvPolicyEval(C.Structure):
     ]
 
 
+class AuvPopulationIO(C.Structure):
+    """== auv_population_io_t (include/auv_hip.h): one launch of a population of policies (auv_population_act / _rollout)"""
+    _fields_ = [
+        ("members", C.c_void_p), ("X", C.c_void_p), ("mu", C.c_void_p), ("action", C.c_void_p),
+        ("reward_in", C.c_void_p), ("done_in", C.c_void_p), ("fit", C.c_void_p), ("ends", C.c_void_p),
+        ("stride", C.c_int64), ("ldx", C.c_int64), ("G", C.c_int32), ("M", C.c_int32), ("obs_dim", C.c_int32), ("action_ld", C.c_int32),
+        ("accumulate", C.c_int32), ("act", C.c_int32),
+        ("act_mid", C.c_float * 2), ("act_half", C.c_float * 2), ("clip_lo", C.c_float * 2), ("clip_hi", C.c_float * 2),
+    ]
+
+
 class AuvPpoBatch(C.Structure):
     """== auv_ppo_batch_t (include/auv_hip.h): the rows of one PPO minibatch step"""
     _fields_ = [
@@ -256,6 +267,11 @@ def load_library(path: str = None) -> C.CDLL:
         "auv_plan_score": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp]),
         "auv_plan_score_v": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, vp]),
         "auv_policy_eval": (C.c_int, [i32, C.POINTER(AuvPolicyEval), vp]),
+        "auv_population_member_floats": (sz, [i32]),
+        "auv_population_act": (C.c_int, [i32, C.POINTER(AuvPopulationIO), vp]),
+        "auv_population_rollout": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(AuvPopulationIO), vp, vp, vp, i32, i32]),
+        "auv_population_perturb": (C.c_int, [i32, vp, vp, C.c_int64, i32, i32, C.c_float, C.c_uint64, C.c_int64, vp]),
+        "auv_population_update": (C.c_int, [i32, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, C.c_int64, vp]),
         "auv_ppo_param_floats": (sz, [i32]),
         "auv_ppo_create": (C.c_int, [i32, i32, i32, C.POINTER(vp)]),
         "auv_ppo_destroy": (None, [vp]),
@@ -293,6 +309,7 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_fresh_worlds_create", "auv_fresh_worlds_refill", "auv_fresh_worlds_stats", "auv_fresh_worlds_draws", "auv_fresh_worlds_set_stream",
                     "auv_snapshot_row_bytes", "auv_snapshot_layout", "auv_snapshot", "auv_restore", "auv_snapshot_skipped", "auv_plan_score",
                     "auv_plan_score_v", "auv_policy_eval",
+                    "auv_population_member_floats", "auv_population_act", "auv_population_rollout", "auv_population_perturb", "auv_population_update",
                     "auv_ppo_param_floats", "auv_ppo_create", "auv_ppo_destroy", "auv_ppo_load", "auv_ppo_attach_policy", "auv_ppo_grad", "auv_ppo_adam",
                     "auv_render",
                     "auv_abi_version", "auv_last_error"]

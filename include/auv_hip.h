@@ -693,6 +693,72 @@ typedef struct auv_policy_eval {
 } auv_policy_eval_t;
 int auv_policy_eval(int32_t device, const auv_policy_eval_t* ev, void* stream);
 
+/* ---- a population of policies: one weight block per group of rows (csrc/k11_population.hip) ---------------------------------------
+ * A MEMBER is the packed policy net of auv_policy_io::params -- W1 b1 W2 b2 W3 b3 W4 b4 in MFMA fragment order, what the first
+ * net of that buffer holds -- auv_population_member_floats(obs_dim) floats (the net rounded up to a multiple of 4 floats).  Members
+ * lie `stride` floats apart.  Row j of a launch belongs to member j / G and is evaluated with the block members + (j / G) * stride; G
+ * (rows per member) is a multiple of 16, so a 16-row tile -- one workgroup -- never straddles two members.  The matrix chains are
+ * those of auv_policy_eval: for the same row and the same block the mean has the same bits.  Deterministic: no value net, no
+ * sampling, no rollout stores.
+ *   outputs     each nullable, written for rows < M only:  mu[j][2];  action[j * action_ld + c] = act_mid[c] + act_half[c] *
+ *               clip(mu[c], clip_lo[c], clip_hi[c]) (auv_policy_eval's expression).
+ *   accumulate  != 0: before the matrix work the launch reads reward_in[j] and done_in[j] -- the step row j's environment has just
+ *               completed -- and at its end stores fit[j] = fit[j] + reward_in[j] (one rounded float32 add per launch) and ends[j] =
+ *               ends[j] + (done_in[j] != 0).  Needs all four buffers.
+ *   act         != 0: the nets are evaluated and the outputs written; 0: the launch only accumulates (the flush behind a
+ *               window's last step) and X, mu and action are not touched.
+ * AUV_EINVAL, before anything is enqueued: G not a positive multiple of 16; members NULL or not 16-byte aligned; stride smaller than
+ * auv_population_member_floats(obs_dim) or not a multiple of 4; obs_dim < 1 or too wide for the kernel's LDS tile (auv_policy_eval's
+ * rule); with act: X NULL, ldx < obs_dim, action with action_ld < 2, neither output and no accumulation; without act: no
+ * accumulation; accumulate with one of its buffers NULL; M < 0; a buffer that is not 4-byte aligned.  M == 0 succeeds and launches
+ * nothing.  Enqueued on `stream`; no synchronisation, no allocation.  All pointers except `io` are device pointers.                  */
+typedef struct auv_population_io {
+  const float* members;      /* [P][stride], P >= ceil(M / G) members                                            */
+  const float* X;            /* observation rows, row stride ldx floats                                          */
+  float* mu;                 /* [M][2]         (nullable)                                                        */
+  float* action;             /* [M][action_ld] (nullable)                                                        */
+  const float* reward_in;    /* [M]  accumulation: the environment's reward buffer                               */
+  const uint8_t* done_in;    /* [M]  accumulation: the environment's done buffer                                 */
+  float* fit;                /* [M]  accumulation: running sum of rewards                                        */
+  int32_t* ends;             /* [M]  accumulation: running count of dones                                        */
+  int64_t stride, ldx;       /* floats                                                                           */
+  int32_t G, M, obs_dim, action_ld;
+  int32_t accumulate, act;
+  float act_mid[2], act_half[2], clip_lo[2], clip_hi[2];   /* action = mid + half * clip(mu, lo, hi)          */
+} auv_population_io_t;
+size_t auv_population_member_floats(int32_t obs_dim);
+int auv_population_act(int32_t device, const auv_population_io_t* io, void* stream);
+/* n_steps steps of every slice with ONE call: per step and slice the population launch and the environment's step of that slice, back
+ * to back on streams[i] (auv_policy_rollout's loop).  ios[i] is written in WHOLE-BATCH rows -- row j is environment j, M = N, action
+ * the environment's [N][action_ld] float32 action buffer (8-byte aligned), fit / ends [N] -- and the call itself takes the slice's
+ * rows of it; X, ldx, reward_in, done_in, accumulate and act of ios[i] are not read: rows come from obs_dev, rewards and dones from
+ * reward_dev / done_dev.  The first launch of a call does not accumulate, every later one adds the step before it; `flush` != 0: a
+ * final accumulate-only launch per slice adds the last step.  Slice bounds must be multiples of ios[i].G (AUV_EINVAL).  The chains are
+ * not ordered against each other or the caller's stream.                                                                         */
+int auv_population_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
+                           const auv_population_io_t* ios, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps,
+                           int32_t flush);
+/* Members from a base block, on the device (mirrored sampling): member p of generation g is
+ *   members[p * stride + i] = theta[i] + s_p * (sigma * eps(seed, g, p / 2, i)),   s_p = +1 for even p, -1 for odd p,
+ * two rounded float32 operations in that association.  eps is counter-based and free of transcendental functions, so that a host
+ * mirror reproduces it bit for bit (gym_auv_amd/population.py: es_noise):
+ *   h = mix(mix(mix(seed ^ g * 0xd1342543de82ef95) ^ pair) ^ i)   (mix: the splitmix64 finaliser, 64-bit wrap-around arithmetic)
+ *   S = the sum of the four 16-bit fields of h;   eps = float32(S - 131070) * c,   c = float32(1 / sqrt(4 (65536^2 - 1) / 12))
+ * -- symmetric, unit variance, |eps| <= 131070 c ~ 3.464.  PADDING elements of the block -- the columns of W1 beyond obs_dim, rows
+ * 2..15 of W4, entries 2..15 of b4 -- get no noise: they keep theta's value (zero); the tail [member_floats, stride) is set to zero.
+ * theta: auv_population_member_floats(obs_dim) floats; theta and members 16-byte aligned, stride a multiple of 4 and >= the block;
+ * P >= 1 (an odd P leaves the last pair half used); sigma finite.                                                                  */
+int auv_population_perturb(int32_t device, const float* theta, float* members, int64_t stride, int32_t P, int32_t obs_dim, float sigma,
+                           uint64_t seed, int64_t generation, void* stream);
+/* The ES gradient estimate with eps regenerated from the counters (nothing of the noise is stored):
+ *   grad[i] = (1 / (P sigma)) * sum over pair = 0 .. P / 2 - 1 of (w[2 pair] - w[2 pair + 1]) * eps(seed, g, pair, i)
+ * one float32 accumulator per element, pairs in increasing order, per pair one rounded difference, one rounded product and one rounded
+ * add; the factor last, as acc * float32(1 / (P sigma)) (the quotient formed in double).  Padding elements get exactly 0.  lr != 0:
+ * also theta[i] = theta[i] + lr * grad[i] (ascent; two rounded operations; padding untouched).  w: [P] float32 device, the shaped
+ * fitness; P even and >= 2; sigma finite and > 0; theta (needed with lr != 0) and grad: one member block each, 16-byte aligned.     */
+int auv_population_update(int32_t device, float* theta, const float* w, float* grad, int32_t P, int32_t obs_dim, float sigma, float lr,
+                          uint64_t seed, int64_t generation, void* stream);
+
 /* Generalised advantage estimation over a rollout of T steps x N environments (row-major [T][N] device buffers; V and
  * last_v in the same units as R): adv and ret = adv + V, one launch on `stream`.                                       */
 int auv_gae(auv_handle_t* h, const float* R, const float* V, const float* Dn, const float* last_v, float gamma, float lam,
