@@ -256,6 +256,7 @@ def load_library(path: str = None) -> C.CDLL:
         "auv_fresh_worlds_refill": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), i32]),
         "auv_fresh_worlds_stats": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "auv_fresh_worlds_set_stream": (C.c_int, [vp, vp]),
+        "auv_fresh_worlds_multi": (C.c_int, [vp, i32]),
         "auv_fresh_worlds_draws": (C.c_int, [vp, C.POINTER(i32), C.POINTER(i32), i32, vp, vp]),
         "auv_bank_bytes": (sz, [vp, i32]),
         "auv_read_bank": (C.c_int, [vp, i32, vp, sz, vp]),
@@ -306,7 +307,7 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_field_bytes", "auv_graph_capture", "auv_graph_launch", "auv_graph_capture_steps", "auv_step_timed",
                     "auv_set_action_ring", "auv_set_step_mode", "auv_set_obs_pooling", "auv_feasibility_pooling",
                     "auv_generate_worlds", "auv_bank_bytes", "auv_read_bank",
-                    "auv_fresh_worlds_create", "auv_fresh_worlds_refill", "auv_fresh_worlds_stats", "auv_fresh_worlds_draws", "auv_fresh_worlds_set_stream",
+                    "auv_fresh_worlds_create", "auv_fresh_worlds_refill", "auv_fresh_worlds_stats", "auv_fresh_worlds_draws", "auv_fresh_worlds_set_stream", "auv_fresh_worlds_multi",
                     "auv_snapshot_row_bytes", "auv_snapshot_layout", "auv_snapshot", "auv_restore", "auv_snapshot_skipped", "auv_plan_score",
                     "auv_plan_score_v", "auv_policy_eval",
                     "auv_population_member_floats", "auv_population_act", "auv_population_rollout", "auv_population_perturb", "auv_population_update",

@@ -314,7 +314,11 @@ class BatchedAuvEnv:
             (obs_or_None, reward, done)   the caller's tensors of those shapes and dtypes, contiguous, on this device -- e.g. a
                        slice buf[t0:t0 + T] of a rollout buffer; returned as passed
         `self.obs / reward / done` hold the last step's values either way.  Action repeat needs nothing else: a ring of ONE slot
-        repeats its action for n_steps steps ((first_slot + k) % 1 == 0); sum the reward record up to the first done."""
+        repeats its action for n_steps steps ((first_slot + k) % 1 == 0); sum the reward record up to the first done.
+
+        With worlds=FreshWorlds(...) only when built with multi_step=True (RuntimeError otherwise): an environment that resets
+        inside the launch moves to its next slot if that slot was published before the call began, else it restarts in the world
+        it has just left and `fresh_stats()["reused"]` counts it."""
         if self._slices is None:
             self.set_sub_batches(1)
         if ring.dim() != 3 or tuple(ring.shape[1:]) != (self.n_envs, 2) or ring.device != self.device or not ring.is_contiguous() \
@@ -671,7 +675,8 @@ class BatchedAuvEnv:
 
     def fresh_worlds(self, spec: "FreshWorlds"):
         """Switch to a fresh world on every reset (auv_fresh_worlds_create): builds the bank of depth * n_envs slots on the
-        device from the counter-based draws of (seed, global environment index, serial) and resets every environment."""
+        device from the counter-based draws of (seed, global environment index, serial) and resets every environment.
+        `spec.multi_step` also allows `step_multi` on the handle (see devgen.FreshWorlds for what is guaranteed there)."""
         from . import devgen
         if not self._cfg_struct.auto_reset:
             raise ValueError("FreshWorlds needs auto_reset=True")
@@ -683,6 +688,8 @@ class BatchedAuvEnv:
                                             int(spec.env_index_base), int(spec.batch_cap), int(spec.period),
                                             unit.ctypes.data_as(C.c_void_p), nseg.ctypes.data_as(C.c_void_p), len(nseg)),
                "auv_fresh_worlds_create")
+        if spec.multi_step:
+            _check(_LIB.auv_fresh_worlds_multi(self._h, 1), "auv_fresh_worlds_multi")
         self._fresh = spec
         self._worlds_arg = None
         # the passes' stream: one that runs side by side with the caller's current stream (set_sub_batches picks again for chains)

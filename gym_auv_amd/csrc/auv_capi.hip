@@ -44,9 +44,10 @@ void auv_launch_step_roles(const AuvDev& d, const void* actions, int dtype, floa
                            hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
 void auv_launch_k31(const AuvDev& d, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, hipStream_t st);
 void auv_launch_step_multi(const AuvDev& d, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, int n_steps, int first_slot,
-                           int n_slots, unsigned long long seq0, int order, int lead, int lag, hipStream_t st);
+                           int n_slots, unsigned long long seq0, int order, int lead, int lag, hipStream_t st, unsigned int fw_call = 0u);
 void auv_launch_step_record(const AuvDev& d, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, float* obs_rec, float* reward_rec,
-                            uint8_t* done_rec, int n_steps, int first_slot, int n_slots, unsigned long long seq0, int order, int lead, int lag, hipStream_t st);
+                            uint8_t* done_rec, int n_steps, int first_slot, int n_slots, unsigned long long seq0, int order, int lead, int lag, hipStream_t st,
+                            unsigned int fw_call = 0u);
 void auv_launch_step_feedback(const AuvDev& d, const double* gains, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, float* obs_rec,
                               float* reward_rec, uint8_t* done_rec, double* act_rec, int n_steps, int first_slot, int n_slots, unsigned long long seq0,
                               int order, int lead, int lag, hipStream_t st, const double* sector_gains, const int32_t* sector_bounds,
@@ -170,7 +171,9 @@ struct auv_handle {
     int32_t* env_next_serial = nullptr;       // [N]
     static const int NEV = 64;                // pacing events (ring): a pass starts when chain 0 has reached the step it was enqueued behind
     hipEvent_t pace[NEV];
-    unsigned long long issued = 0, calls = 0;
+    unsigned long long issued = 0, calls = 0, paced = 0;   // passes enqueued, step calls counted, pacing events handed out
+    bool multi = false;                       // auv_fresh_worlds_multi: launches of several steps allowed (k_fresh_multi / k_fresh_record)
+    unsigned int multi_call = 0;              // multi-step calls so far: the number the next one's launches carry is this + 1
     hipGraphExec_t pass_exec = nullptr;       // the pass as ONE graph launch (captured at create)
     hipGraph_t pass_graph = nullptr;
   } fw;
@@ -385,7 +388,7 @@ static int finish_bank(auv_handle* h, bool alloc_env) {
       HIP_TRY(hipHostGetDevicePointer((void**)&d.pair_error, h->pair_error_host, 0));
     }
     *h->pair_error_host = 0;   // (a new bank starts with a clean slate; see PAIR_CHECK)
-    HIP_TRY(hipMemset(d.abort_flag, 0, sizeof(int32_t)));
+    HIP_TRY(hipMemset(d.abort_flag, 0, 4 * sizeof(int32_t)));   // ([1], [2]: "a report is out" -- a time-out pending across a reload must not mute the next)
     HIP_TRY(hipMemset(d.broken, 0, n));
     HIP_TRY(hipMemset(d.k1_pkt, 0, 8 * n * sizeof(unsigned long long)));
     HIP_TRY(hipMemset(d.nav_hand, 0, 8 * n * sizeof(unsigned long long)));
@@ -627,7 +630,8 @@ static void fw_disable(auv_handle* h) {
   f.side = nullptr, f.side_owned = false;
   free_pool(f.allocs);
   f.on = false;
-  f.issued = f.calls = 0;
+  f.issued = f.calls = f.paced = 0;
+  f.multi = false, f.multi_call = 0;
   h->d.fw_state = nullptr, h->d.fw_serial = nullptr, h->d.fw_queue = nullptr, h->d.fw_ctl = nullptr, h->d.fw_cap = 0;
 }
 
@@ -643,18 +647,22 @@ static void fw_pass_kernels(auv_handle* h, hipStream_t st) {
   auv_launch_k2_fresh(f.shadow, st);
   auv_launch_k3_fresh(f.shadow, nullptr, st);
   auv_launch_harvest(f.shadow, f.cap, st, f.batch.count);
-  auv_launch_fw_ready(f.batch, d.fw_state, d.fw_serial, d.fw_ctl, f.cap, st);
+  auv_launch_fw_ready(f.batch, d.fw_state, d.fw_serial, d.fw_ctl, d.n_worlds, f.cap, st);
 }
 
 // One refill pass on the side stream.  `behind` (nullable): the pass starts when THAT stream has reached this point -- the
 // host may run thousands of launches ahead of the GPU (open-loop chains, a whole rollout enqueued by one call), and a pass
 // that ran at enqueue time would find an empty queue long before the episodes it is meant for have ended.
-static int fw_enqueue_pass(auv_handle* h, hipStream_t behind, bool paced) {
+// `more` / `n_more`: further streams the pass starts behind (a multi-step call: EVERY chain -- the pass enqueued by call c then finds
+// all the slots call c has left in the queue, whichever chain finished last).
+static int fw_enqueue_pass(auv_handle* h, hipStream_t behind, bool paced, void* const* more = nullptr, int n_more = 0) {
   auv_handle::Fresh& f = h->fw;
   if (paced) {
-    hipEvent_t ev = f.pace[f.issued % auv_handle::Fresh::NEV];
-    HIP_TRY(hipEventRecord(ev, behind));
-    HIP_TRY(hipStreamWaitEvent(f.side, ev, 0));
+    for (int i = -1; i < n_more; i++) {
+      hipEvent_t ev = f.pace[f.paced++ % auv_handle::Fresh::NEV];
+      HIP_TRY(hipEventRecord(ev, i < 0 ? behind : (hipStream_t)more[i]));
+      HIP_TRY(hipStreamWaitEvent(f.side, ev, 0));
+    }
   }
   if (f.pass_exec) HIP_TRY(hipGraphLaunch(f.pass_exec, f.side));
   else {
@@ -667,7 +675,8 @@ static int fw_enqueue_pass(auv_handle* h, hipStream_t behind, bool paced) {
 
 // once per step call of the whole batch (the callers name the chains' streams): every `period`-th call a pass is enqueued,
 // paced behind the first chain.  Never waits; skipped while a stream is being captured.
-static int fw_tick(auv_handle* h, int n_slices, const int32_t* bounds, void* const* streams, int n_steps = 1) {
+// `all_chains`: the pass is paced behind every chain, not only the first (multi-step calls, which tick BEHIND their launches).
+static int fw_tick(auv_handle* h, int n_slices, const int32_t* bounds, void* const* streams, int n_steps = 1, bool all_chains = false) {
   auv_handle::Fresh& f = h->fw;
   if (!f.on) return AUV_OK;
   (void)bounds;
@@ -675,7 +684,8 @@ static int fw_tick(auv_handle* h, int n_slices, const int32_t* bounds, void* con
     if (stream_capturing((hipStream_t)streams[s])) return AUV_OK;
   const unsigned long long before = f.calls / (unsigned long long)f.period;
   f.calls += (unsigned long long)n_steps;
-  if (f.calls / (unsigned long long)f.period != before) return fw_enqueue_pass(h, (hipStream_t)streams[0], true);
+  if (f.calls / (unsigned long long)f.period != before)
+    return fw_enqueue_pass(h, (hipStream_t)streams[0], true, all_chains ? streams + 1 : nullptr, all_chains ? n_slices - 1 : 0);
   return AUV_OK;
 }
 
@@ -1029,7 +1039,7 @@ int auv_fresh_worlds_create(auv_handle_t* h, int32_t depth, int32_t n_moving, in
   f.depth = depth, f.cap = batch_cap, f.period = period, f.n_draws = nd, f.seed = seed, f.env_base = env_index_base;
   auto& ap = f.allocs;
   int rc = 0;
-  rc |= dev_alloc(ap, &d.fw_state, (size_t)W);
+  rc |= dev_alloc(ap, &d.fw_state, 2 * (size_t)W);   // states, then stamps (zero: published before any multi-step call)
   rc |= dev_alloc(ap, &d.fw_serial, (size_t)W);
   rc |= dev_alloc(ap, &d.fw_queue, (size_t)W);
   rc |= dev_alloc(ap, &d.fw_ctl, 8);
@@ -1084,7 +1094,8 @@ int auv_fresh_worlds_create(auv_handle_t* h, int32_t depth, int32_t n_moving, in
   HIP_TRY(hipStreamCreateWithFlags(&f.side, hipStreamNonBlocking));
   f.side_owned = true;
   for (int b = 0; b < auv_handle::Fresh::NEV; b++) HIP_TRY(hipEventCreateWithFlags(&f.pace[b], hipEventDisableTiming));
-  f.issued = f.calls = 0;
+  f.issued = f.calls = f.paced = 0;
+  f.multi = false, f.multi_call = 0;
   {
     // the eight kernels of a pass as ONE graph: a pass costs the host one launch, not eight (every argument is a fixed
     // device buffer of this mode; what a pass works on it learns on the device)
@@ -1138,6 +1149,16 @@ int auv_fresh_worlds_set_stream(auv_handle_t* h, void* stream) {
   HIP_TRY(hipStreamSynchronize(f.side));
   if (f.side_owned) HIP_TRY(hipStreamDestroy(f.side));
   f.side = (hipStream_t)stream, f.side_owned = false;
+  return AUV_OK;
+}
+
+int auv_fresh_worlds_multi(auv_handle_t* h, int32_t on) {
+  REQUIRE_READY(h);
+  auv_handle::Fresh& f = h->fw;
+  if (!f.on) return fail(AUV_ESTATE, "auv_fresh_worlds_multi: auv_fresh_worlds_create first");
+  if (on && f.depth < 3)
+    return fail(AUV_EINVAL, "auv_fresh_worlds_multi: depth >= 3 (with %d slots an environment could not reset twice without re-use in a launch that has used its spare)", f.depth);
+  f.multi = on != 0;
   return AUV_OK;
 }
 
@@ -1323,18 +1344,32 @@ int auv_step_pipelined(auv_handle_t* h, int32_t n_slices, const int32_t* bounds,
   return AUV_OK;
 }
 
+// A multi-step call in fresh-world mode (auv_fresh_worlds_multi): its number, handed to every chain's launch; fw_multi_begin puts the
+// one-wave kernel that announces the call directly in front of a chain's launch (auv_device.h: auv_next_world_multi has the argument).
+static unsigned int fw_multi_call(auv_handle* h) { return h->fw.on ? ++h->fw.multi_call : 0u; }
+static void fw_multi_begin(auv_handle* h, unsigned int call, hipStream_t st) {
+  if (call) auv_launch_fw_call(h->d.fw_ctl, call, st);
+}
+
 // what auv_step_multi, auv_step_multi_record and auv_step_feedback refuse, before anything launches and before any step number is spent
 // `ring_optional`: a NULL ring is allowed (auv_step_feedback: x_7 = 0); `state_rc`: the code of the refusals that hang on the handle's
 // configuration (auv_step_feedback reports every refusal as AUV_EINVAL)
 static int check_multi(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const void* actions_dev, int32_t action_dtype,
-                       int32_t n_slots, int32_t first_slot, int32_t n_steps, const char* who, bool ring_optional = false, int state_rc = AUV_ESTATE) {
+                       int32_t n_slots, int32_t first_slot, int32_t n_steps, const char* who, bool ring_optional = false, int state_rc = AUV_ESTATE,
+                       bool fresh_kernels = false) {
   int rc = (ring_optional && !actions_dev) ? AUV_OK : check_actions(actions_dev, action_dtype, who);
   if (rc) return rc;
   rc = check_slices(h, n_slices, bounds, streams, who);
   if (rc) return rc;
   if (n_slots < 1 || first_slot < 0 || first_slot >= n_slots || n_steps < 1 || n_steps > 1024)
     return fail(AUV_EINVAL, "%s: n_slots >= 1, 0 <= first_slot < n_slots, 1 <= n_steps <= 1024", who);
-  if (h->fw.on) return fail(state_rc, "%s: not with a fresh world per reset (a slot's tables may be rebuilt beside the launch)", who);
+  // (`fresh_kernels`: the entry has kernels that bind only slots published before the call began -- used once the handle has opted in)
+  if (h->fw.on && !(fresh_kernels && h->fw.multi))
+    return fail(state_rc, "%s: not with a fresh world per reset (a slot's tables may be rebuilt beside the launch)", who);
+  if (h->fw.on)
+    for (int s = 0; s < n_slices; s++)
+      if (stream_capturing((hipStream_t)streams[s]))
+        return fail(state_rc, "%s: with a fresh world per reset not on a stream that is being captured (the call's number is a launch argument)", who);
   if (h->d.k_max > AUV_WAVE) return fail(state_rc, "%s: more than 64 obstacles per world", who);
   for (int i = 0; i < n_slices; i++) {
     const int ne = bounds[i + 1] - bounds[i];
@@ -1351,26 +1386,28 @@ static int check_multi(auv_handle_t* h, int32_t n_slices, const int32_t* bounds,
 int auv_step_multi(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const void* actions_dev, int32_t action_dtype,
                    int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev, float* reward_dev, uint8_t* done_dev) {
   REQUIRE_READY(h);
-  const int rc = check_multi(h, n_slices, bounds, streams, actions_dev, action_dtype, n_slots, first_slot, n_steps, "auv_step_multi");
+  const int rc = check_multi(h, n_slices, bounds, streams, actions_dev, action_dtype, n_slots, first_slot, n_steps, "auv_step_multi", false, AUV_ESTATE, true);
   if (rc) return rc;
   PAIR_CHECK(h, obs_dev);
   const unsigned long long seq0 = h->multi_seq;
   h->multi_seq += (unsigned long long)n_steps;
+  const unsigned int call = fw_multi_call(h);
   for (int i = 0; i < n_slices; i++) {
     AuvDev d = h->d;
     d.e0 = bounds[i], d.ne = bounds[i + 1] - bounds[i];
+    fw_multi_begin(h, call, (hipStream_t)streams[i]);
     auv_launch_step_multi(d, actions_dev, action_dtype, obs_dev, reward_dev, done_dev, n_steps, first_slot, n_slots, seq0, h->multi_order, h->multi_lead,
-                          h->multi_lag, (hipStream_t)streams[i]);
+                          h->multi_lag, (hipStream_t)streams[i], call);
   }
   HIP_TRY(hipGetLastError());
-  return AUV_OK;
+  return fw_tick(h, n_slices, bounds, streams, n_steps, true);   // (behind the launches: the pass finds what this call has left)
 }
 
 int auv_step_multi_record(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const void* actions_dev,
                           int32_t action_dtype, int32_t n_slots, int32_t first_slot, int32_t n_steps, float* obs_dev, float* reward_dev,
                           uint8_t* done_dev, float* obs_rec, float* reward_rec, uint8_t* done_rec) {
   REQUIRE_READY(h);
-  const int rc = check_multi(h, n_slices, bounds, streams, actions_dev, action_dtype, n_slots, first_slot, n_steps, "auv_step_multi_record");
+  const int rc = check_multi(h, n_slices, bounds, streams, actions_dev, action_dtype, n_slots, first_slot, n_steps, "auv_step_multi_record", false, AUV_ESTATE, true);
   if (rc) return rc;
   if (!reward_rec || !done_rec) return fail(AUV_EINVAL, "auv_step_multi_record: reward_rec and done_rec are required (only obs_rec may be NULL)");
   if (!obs_dev || !reward_dev || !done_dev) return fail(AUV_EINVAL, "auv_step_multi_record: null obs / reward / done buffer");
@@ -1383,14 +1420,16 @@ int auv_step_multi_record(auv_handle_t* h, int32_t n_slices, const int32_t* boun
   PAIR_CHECK(h, obs_dev);
   const unsigned long long seq0 = h->multi_seq;
   h->multi_seq += (unsigned long long)n_steps;
+  const unsigned int call = fw_multi_call(h);
   for (int i = 0; i < n_slices; i++) {
     AuvDev d = h->d;
     d.e0 = bounds[i], d.ne = bounds[i + 1] - bounds[i];
+    fw_multi_begin(h, call, (hipStream_t)streams[i]);
     auv_launch_step_record(d, actions_dev, action_dtype, obs_dev, reward_dev, done_dev, obs_rec, reward_rec, done_rec, n_steps, first_slot, n_slots, seq0,
-                           h->multi_order, h->multi_lead, h->multi_lag, (hipStream_t)streams[i]);
+                           h->multi_order, h->multi_lead, h->multi_lag, (hipStream_t)streams[i], call);
   }
   HIP_TRY(hipGetLastError());
-  return AUV_OK;
+  return fw_tick(h, n_slices, bounds, streams, n_steps, true);   // (as auv_step_multi)
 }
 
 // auv_step_feedback (`sectors` false) and auv_step_feedback_sectors: the same checks and the same launch, the second with the sector

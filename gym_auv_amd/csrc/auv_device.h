@@ -123,15 +123,22 @@ struct AuvDev {
   // ---- a fresh world on every reset (auv_fresh_worlds_create; SURVEY 8(f) F1: generation joined to auto-reset) ----
   // The bank is D slots per environment (slot e + j N belongs to environment e); an environment whose episode ends moves
   // to its next slot IF that slot holds a world nobody has seen (READY), marks the slot it leaves STALE and queues it; a
-  // refill pass on a side stream (auv_capi.hip: fw_refill) pops the queue, rebuilds exactly those slots -- tables
-  // (k5_generate) and reset rows (the step's own kernels on a few shadow environments) -- and a publish kernel ON THE
-  // ENVIRONMENT'S OWN STREAM, enqueued after the host has seen the pass complete, flips them to READY: every step launch that
-  // can bind a regenerated slot started after the slot's tables were complete (kernel-boundary visibility, no fences).
-  int32_t* fw_state;     // [W] AUV_FW_READY / _IN_USE / _STALE, or nullptr: the bank cycles (w + N) % W as before
+  // refill pass on a side stream (auv_capi.hip: fw_pass_kernels, fw_enqueue_pass) pops the queue, rebuilds exactly those slots
+  // -- tables (k5_generate) and reset rows (the step's own kernels on a few shadow environments) -- and ITS OWN last kernel
+  // (k5_generate.hip: k_fw_ready), on the side stream, flips them to READY with agent-scope stores.  No host round trip and no
+  // kernel boundary between a pass and the launch that binds what it rebuilt: a ONE-step launch that reads READY reads the
+  // slot's reset rows and tables with agent-scope (sc1) loads (restore_env<COH>); every later launch starts behind a kernel
+  // boundary and reads them the plain way.  A launch of SEVERAL steps (k_fresh_multi / k_fresh_record) goes on reading a bound
+  // slot's tables with plain loads in the same launch, so it binds only slots that were published before any kernel of its call
+  // began: k_fw_ready stamps every slot with the number of the latest multi-step call that had started when the slot's tables
+  // were complete, and a launch of call c takes a slot only if its stamp is below c (auv_next_world_multi).
+  int32_t* fw_state;     // [2 W] [w]: AUV_FW_READY / _IN_USE / _STALE; [W + w]: the slot's stamp (see above); nullptr: the bank cycles (w + N) % W
   int32_t* fw_serial;    // [W] which world of its environment the slot holds: the world of (seed, environment, serial)
   int32_t* fw_queue;     // [fw_cap] ring of stale slots (-1: empty entry); a slot is in it at most once
   unsigned int* fw_ctl;  // [8] [0] tail (producers: finish waves of any chain), [1] head (the refill pass), [2] episodes that had to
-                         //     start in the world they had just finished because the next slot was not READY yet (stale re-use)
+                         //     start in the world they had just finished because the next slot was not READY yet (stale re-use),
+                         //     [3] the number of the latest multi-step call that has started (k_fw_call raises it, k_fw_ready reads it),
+                         //     [4..5] worlds rebuilt, [6..7] passes completed (64-bit each)
   int32_t fw_cap;
   // ---- feasibility-pooled observations (auv_set_obs_pooling): the observation row carries one closeness per
   //      sector -- of the sector's feasible distance (LidarPreprocessor._feasibility_pooling, sensor.py:251-296) -- instead of one
@@ -197,6 +204,41 @@ __device__ __forceinline__ int auv_next_world(const AuvDev& d, const int w) {
   if (!d.fw_state) return w2;
   if (w2 == w) return w;
   if (__hip_atomic_load(d.fw_state + w2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != AUV_FW_READY) {
+    __hip_atomic_fetch_add(d.fw_ctl + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    return w;
+  }
+  __hip_atomic_store(d.fw_state + w2, AUV_FW_IN_USE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(d.fw_state + w, AUV_FW_STALE, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  const unsigned int at = __hip_atomic_fetch_add(d.fw_ctl, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  __hip_atomic_store(d.fw_queue + (at % (unsigned int)d.fw_cap), w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  return w2;
+}
+// The same for a launch of SEVERAL steps of call number `call` (k_fresh_multi / k_fresh_record; one lane calls this).  Steps
+// t + 1 .. T - 1 of the launch read the tables of a slot bound in step t with PLAIN loads and no kernel boundary in between, so
+// the launch may bind only slots whose tables were complete before any of its waves -- of any chain of the call -- existed:
+//   * k_fw_call, one wave directly in front of every chain's launch on that chain's stream, raises fw_ctl[3] to `call`
+//     (agent-scope atomic max): fw_ctl[3] >= c from the moment the first chain's launch of call c MAY begin;
+//   * k_fw_ready, the pass's last kernel, starts when the pass's table and reset-row kernels have ended (stream order: their
+//     stores are complete in memory), reads fw_ctl[3] (agent-scope load) and stores what it read as the slot's stamp, then the
+//     serial, and -- when those two stores have been acknowledged -- READY;
+//   * here: READY (agent-scope load), then -- behind the wait for that load -- the stamp.  stamp < call: when the tables were
+//     complete no k_fw_call of this call had run, hence no launch of this call had begun; the kernel boundary in front of this
+//     launch (acquire: L2 / L1 lines of the slot's previous world are gone) does the rest, as for any later launch.
+//     stamp >= call: the slot may have been rebuilt beside this launch -- it stays READY for the next call, and the environment
+//     starts over in the world it has just finished, counted in fw_ctl[2] like every re-use.
+// The state is read before the stamp and the stamp is written before the state: a READY seen here is never paired with the
+// stamp of the slot's previous publication.  The reset rows are read coherently anyway (restore_env<true>); the queue entry and
+// the two state words go out exactly as in auv_next_world.  The slot left behind may be rebuilt beside this launch: nobody reads
+// it again before it is bound again, which takes a stamp below a LATER call's number.
+__device__ __forceinline__ int auv_next_world_multi(const AuvDev& d, const int w, const unsigned int call) {
+  const int w2 = (int)(((long long)w + d.n) % d.n_worlds);
+  if (w2 == w) return w;
+  bool take = __hip_atomic_load(d.fw_state + w2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) == AUV_FW_READY;
+  if (take) {
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");        // (the state has arrived before the stamp is requested)
+    take = (unsigned int)__hip_atomic_load(d.fw_state + d.n_worlds + w2, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) < call;
+  }
+  if (!take) {
     __hip_atomic_fetch_add(d.fw_ctl + 2, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     return w;
   }

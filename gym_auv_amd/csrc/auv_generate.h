@@ -42,4 +42,5 @@ void auv_launch_draws(double* draws, int n_draws, int n_moving, int n_static, un
                       const int32_t* serials, int n_rows, const int32_t* count_dev, int grid, hipStream_t st);
 void auv_launch_fw_bind(const FwBatch& b, int32_t* queue, unsigned int* ctl, int q_cap, int n_envs, int cap, int32_t* env_next_serial,
                         int32_t* shadow_world_idx, int32_t* shadow_fresh_count, hipStream_t st);
-void auv_launch_fw_ready(const FwBatch& b, int32_t* state, int32_t* serial, unsigned int* ctl, int cap, hipStream_t st);
+void auv_launch_fw_ready(const FwBatch& b, int32_t* state, int32_t* serial, unsigned int* ctl, int n_worlds, int cap, hipStream_t st);
+void auv_launch_fw_call(unsigned int* ctl, unsigned int call, hipStream_t st);

@@ -736,9 +736,11 @@ struct RewardIn {
 // `D`: AuvDev or StepTabs (see there)
 template <class D>
 // `carry_out` (nullable): [0] the cumulative reward, [1] the sum of |cross-track error| after this step (k_step_multi)
+// `w_known` (>= 0): the environment's world where the caller holds it (k_fresh_multi: from the carry record -- WORLD_IDX[e] may have
+// been written by another wave of the same launch); else WORLD_IDX[e] is read
 __device__ __forceinline__ int reward_apply(const D& d, const int e, const int collision, int4& cnt, const RewardIn in,
                                             float* __restrict__ reward_out, uint8_t* __restrict__ done_out,
-                                            const bool advance_ring, double* carry_out = nullptr) {
+                                            const bool advance_ring, double* carry_out = nullptr, const int w_known = -1) {
   double* inf = d.info64 + 8 * (size_t)e;
   const bool colav = d.cfg.rewarder == AUV_REWARD_COLAV;
   const double lambda = 0.5, eta = 0.0, penalty_yawrate = 10.0, neutral_speed = 0.05, max_speed = 2.0;
@@ -794,7 +796,7 @@ __device__ __forceinline__ int reward_apply(const D& d, const int e, const int c
     // the world column: the bank's index -- with a fresh world per reset the index the world WOULD have in a bank that never
     // repeats: environment + N * serial (serial: the how-manieth world of this environment), so that no two episodes of a run
     // may ever log the same number
-    const int wl = d.world_idx[e];
+    const int wl = w_known >= 0 ? w_known : d.world_idx[e];
     row[3] = make_double2(cte_sum / (double)(t_step + 1), d.fw_serial ? (double)e + (double)d.n * (double)d.fw_serial[wl] : (double)wl);
   }
   const int do_reset = done && d.cfg.auto_reset;

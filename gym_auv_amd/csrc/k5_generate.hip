@@ -455,21 +455,32 @@ __global__ void k_fw_bind(FwBatch b, int32_t* __restrict__ queue, unsigned int* 
 }
 
 // The pass's LAST kernel: the slots it has rebuilt become READY.  Every kernel of the pass before this one has ended (stream
-// order), i.e. the slots' tables and reset rows are complete in memory; the serial and the state go out as agent-scope stores,
-// the state last.  A finish wave that reads READY (agent-scope load) reads the slot's tables with agent-scope loads in the
-// same launch (restore_env<true>) and the plain way, behind a kernel boundary, ever after.
-__global__ void k_fw_ready(FwBatch b, int32_t* __restrict__ state, int32_t* __restrict__ serial, unsigned int* __restrict__ ctl) {
+// order), i.e. the slots' tables and reset rows are complete in memory; the stamp, the serial and the state go out as agent-scope
+// stores, the state last.  A finish wave of a one-step launch that reads READY (agent-scope load) reads the slot's tables with
+// agent-scope loads in the same launch (restore_env<true>) and the plain way, behind a kernel boundary, ever after.
+// The stamp ([W + s] of `state`): ctl[3] as this kernel finds it -- the number of the latest multi-step call of which a chain's
+// launch may have begun (k_fw_call).  A launch of several steps binds the slot only if its own call's number is larger
+// (auv_device.h: auv_next_world_multi): then it began after the tables were complete.
+__global__ void k_fw_ready(FwBatch b, int32_t* __restrict__ state, int32_t* __restrict__ serial, unsigned int* __restrict__ ctl, int n_worlds) {
   const int count = *b.count;
+  const unsigned int started = __hip_atomic_load(ctl + 3, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   for (int i = blockIdx.x * blockDim.x + threadIdx.x; i < count; i += gridDim.x * blockDim.x) {
     const int s = b.slot[i];
+    __hip_atomic_store(state + n_worlds + s, (int32_t)started, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     __hip_atomic_store(serial + s, b.serial[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    __builtin_amdgcn_s_waitcnt(0x0F70);                       // (vmcnt(0): the serial is out before the state)
+    __builtin_amdgcn_s_waitcnt(0x0F70);                       // (vmcnt(0): the stamp and the serial are out before the state)
     __hip_atomic_store(state + s, AUV_FW_READY, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
   }
   if (blockIdx.x == 0 && threadIdx.x == 0) {
     __hip_atomic_fetch_add((unsigned long long*)(ctl + 4), (unsigned long long)count, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);   // worlds rebuilt so far
     __hip_atomic_fetch_add((unsigned long long*)(ctl + 6), 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);                        // passes completed
   }
+}
+
+// One wave directly in front of a chain's launch of several steps, on that chain's stream: "a launch of call `call` may begin now".
+// The launch behind it starts when this kernel has ended, i.e. with ctl[3] >= call visible to every k_fw_ready from then on.
+__global__ void k_fw_call(unsigned int* __restrict__ ctl, unsigned int call) {
+  if (threadIdx.x == 0 && blockIdx.x == 0) __hip_atomic_fetch_max(ctl + 3, call, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
 }
 
 }  // namespace
@@ -491,6 +502,8 @@ void auv_launch_fw_bind(const FwBatch& b, int32_t* queue, unsigned int* ctl, int
   hipLaunchKernelGGL(k_fw_bind, dim3(1), dim3(AUV_WAVE), 0, st, b, queue, ctl, q_cap, n_envs, cap, env_next_serial, shadow_world_idx, shadow_fresh_count);
 }
 
-void auv_launch_fw_ready(const FwBatch& b, int32_t* state, int32_t* serial, unsigned int* ctl, int cap, hipStream_t st) {
-  hipLaunchKernelGGL(k_fw_ready, dim3((cap + 255) / 256), dim3(256), 0, st, b, state, serial, ctl);
+void auv_launch_fw_ready(const FwBatch& b, int32_t* state, int32_t* serial, unsigned int* ctl, int n_worlds, int cap, hipStream_t st) {
+  hipLaunchKernelGGL(k_fw_ready, dim3((cap + 255) / 256), dim3(256), 0, st, b, state, serial, ctl, n_worlds);
 }
+
+void auv_launch_fw_call(unsigned int* ctl, unsigned int call, hipStream_t st) { hipLaunchKernelGGL(k_fw_call, dim3(1), dim3(AUV_WAVE), 0, st, ctl, call); }

@@ -619,8 +619,10 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_roles(AuvD
 //     chunk, where a stale value costs nothing but a wider first bound).
 //   * every mark of a step is mixed with the step's number (roles_tagmix), so a packet of step t still up cannot pass for
 //     step t + 1's.
-// Bitwise the same as T launches of k_step_roles (tests/test_gpu_multi.py).  Not with a fresh world per reset: there a slot's
-// tables may be rebuilt beside the launch, and only the binding launch reads them coherently.
+// Bitwise the same as T launches of k_step_roles (tests/test_gpu_multi.py).  With a fresh world per reset a slot's tables may be
+// rebuilt beside the launch, and only the binding STEP reads them coherently: these kernels are refused there, and k_fresh_multi /
+// k_fresh_record (the same body, STEP_MULTI_FW) bind only slots published before their call began (auv_device.h:
+// auv_next_world_multi).
 #define CARRY_WORDS 24
 
 // Diagnostic build only (-DAUV_STAMPS_MULTI, tools/multi_stamps.py): wall-clock stamps of the waves of ONE step in the middle of a
@@ -887,14 +889,18 @@ __device__ __forceinline__ double2 fb_hidden(const double2 a, const double x, co
 // step's action by the feedback law and hands it over in words 21..23 of the carry record (fb_gains: [N][2][8]; fb_actions / fb_slot:
 // the ring and the next step's slot, or nullptr; FB >= 2: fb_sgains, [N][2][16], and fb_sb, the sector bounds; FB 3: fb_hidden,
 // [N][16][28], and fb_activation)
-template <bool MULTI, int FB = 0>
+// FW (k_fresh_multi / k_fresh_record): a fresh world per reset.  The reset takes the environment's next slot only if it was published
+// before this call began (auv_next_world_multi with `fw_call`, else the world just left, counted), binds it through the coherent
+// restore_env and hands the descriptor of the slot it actually took on in the carry record; the episode log's world column is
+// environment + N * serial of the world the carry record names.
+template <bool MULTI, int FB = 0, int FW = 0>
 __device__ __forceinline__ void roles_finish_wave_multi(const AuvDev& dk, const int f, const int lane, float* __restrict__ obs_out,
                                                         float* __restrict__ reward_out, uint8_t* __restrict__ done_out, const int step,
                                                         const bool last_step, const unsigned long long tagmix, const unsigned long long tagmix_prev MSTAMP_PARAM,
                                                         const double* __restrict__ fb_gains = nullptr, const void* __restrict__ fb_actions = nullptr,
                                                         const int fb_slot = 0, const double* __restrict__ fb_sgains = nullptr,
                                                         const FbBounds* fb_sb = nullptr, const double* __restrict__ fb_hidden_tab = nullptr,
-                                                        const int fb_activation = 0) {
+                                                        const int fb_activation = 0, const unsigned int fw_call = 0u) {
   // (roles_finish_wave with the previous step's outcome from the carry record instead of the arrays, and its own outcome into
   // the record at the end; the arithmetic in between is the very same code)
   const __attribute__((address_space(4))) AuvDev* dc = (const __attribute__((address_space(4))) AuvDev*)dk.self;
@@ -910,6 +916,7 @@ __device__ __forceinline__ void roles_finish_wave_multi(const AuvDev& dk, const 
   st.step_info = dc->step_info, st.episode = dc->episode, st.ep_log = dc->ep_log, st.ep_log_count = dc->ep_log_count;
   st.ep_log_cap = dc->ep_log_cap, st.world_idx = dc->world_idx, st.counters = dc->counters;
   st.fw_serial = nullptr, st.n = dc->n;
+  if constexpr (FW) st.fw_serial = dc->fw_serial;
   st.ring_slots = 1, st.ring_slot_host = 0, st.ring_pos = nullptr;
   unsigned long long* const pair_word = dc->pair_word;
   unsigned long long* const k1_pkt = dc->k1_pkt;
@@ -1036,10 +1043,12 @@ __device__ __forceinline__ void roles_finish_wave_multi(const AuvDev& dk, const 
     in.cum = cum_in;
     in.cte100 = no.cte100, in.cte_sum = cte_sum_in;
     st.info64[8 * (size_t)e] = collision;
-    do_reset = reward_apply(st, e, collision, cnt, in, reward_out, done_out, false, co);
+    if constexpr (FW) do_reset = reward_apply(st, e, collision, cnt, in, reward_out, done_out, false, co, w);
+    else do_reset = reward_apply(st, e, collision, cnt, in, reward_out, done_out, false, co);
   }
   unsigned long long m = __ballot(do_reset);
   const unsigned long long m_reset = m;
+  int w_next = w;                                          // (FW: the slot this group's environment was restored into)
   while (m) {
     const int src = __ffsll((long long)m) - 1;
     m &= m - 1;
@@ -1048,7 +1057,15 @@ __device__ __forceinline__ void roles_finish_wave_multi(const AuvDev& dk, const 
     const AuvDev* dp = dk.self;
     asm volatile("" : "+s"(dp));
     const AuvDev& dr = *(const AuvDev*)(const __attribute__((address_space(4))) AuvDev*)dp;
-    restore_env<false, true>(dr, er2, (int)(((long long)wr + dr.n) % dr.n_worlds), lane, ep, obs_out);
+    if constexpr (FW) {
+      int w2 = 0;
+      if (lane == 0) w2 = auv_next_world_multi(dr, wr, fw_call);
+      w2 = auv_uniform(w2);
+      w_next = lane / K1_GROUP == src / K1_GROUP ? w2 : w_next;
+      restore_env<true, true>(dr, er2, w2, lane, ep, obs_out);
+    } else {
+      restore_env<false, true>(dr, er2, (int)(((long long)wr + dr.n) % dr.n_worlds), lane, ep, obs_out);
+    }
   }
   if (last_step) return;                                   // (the launch that follows reads the arrays, behind a kernel boundary)
   // ---- this step's outcome into the carry record ----
@@ -1070,7 +1087,7 @@ __device__ __forceinline__ void roles_finish_wave_multi(const AuvDev& dk, const 
     // this group's environment was restored: what the restore has just written (this wave's own stores, complete: read past L1)
     const size_t n = (size_t)n_envs;
     const int4 rc = make_int4(0, 0, __shfl(cnt.z, 0, K1_GROUP), 0);
-    const EnvDesc ne_ = auv_make_desc<true>(d, (int)(((long long)w + d.n) % d.n_worlds));
+    const EnvDesc ne_ = auv_make_desc<true>(d, FW ? w_next : (int)(((long long)w + d.n) % d.n_worlds));
     const double sv = c < 6 ? __hip_atomic_load(state + (size_t)c * n + e, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
     const double iv = (c >= 1 && c <= 3) ? __hip_atomic_load(st.info64 + 8 * (size_t)e + (c == 1 ? 4 : (c == 2 ? 5 : 7)), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : 0.0;
     w0 = c < 6 ? (unsigned long long)__double_as_longlong(sv) : 0ull;          // counters x = y = 0
@@ -1164,6 +1181,40 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_record(Auv
 #define STEP_MULTI_REC 1
 #define STEP_MULTI_FB 0
 #include "k_step_multi_body.inc"
+#undef STEP_MULTI_FB
+#undef STEP_MULTI_REC
+}
+
+// A fresh world on every reset in launches of several steps (auv_fresh_worlds_multi): k_step_multi and k_step_record whose finish
+// wave resets through the gated slot choice (STEP_MULTI_FW; roles_finish_wave_multi<.., FW>).  fw_call: the number of the call this
+// launch belongs to.  Two further inclusions of the body: the other six keep their argument lists and their code.
+__global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_fresh_multi(AuvDev dk, const void* __restrict__ actions, float* __restrict__ obs_out,
+                                                                            float* __restrict__ reward_out, uint8_t* __restrict__ done_out,
+                                                                            const int n_steps, const int first_slot, const int n_slots,
+                                                                            const unsigned long long seq0, const int lead_dyn, const int lag_fin, const unsigned magic_c,
+                                                                            const unsigned int fw_call) {
+  AUV_KERNARG_DESC(d);
+#define STEP_MULTI_REC 0
+#define STEP_MULTI_FB 0
+#define STEP_MULTI_FW 1
+#include "k_step_multi_body.inc"
+#undef STEP_MULTI_FW
+#undef STEP_MULTI_FB
+#undef STEP_MULTI_REC
+}
+
+__global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_fresh_record(AuvDev dk, const void* __restrict__ actions, float* __restrict__ obs_out,
+                                                                             float* __restrict__ reward_out, uint8_t* __restrict__ done_out,
+                                                                             const int n_steps, const int first_slot, const int n_slots,
+                                                                             const unsigned long long seq0, const int lead_dyn, const int lag_fin, const unsigned magic_c,
+                                                                             const unsigned long long obs_stride, const unsigned long long reward_stride,
+                                                                             const unsigned long long done_stride, const unsigned int fw_call) {
+  AUV_KERNARG_DESC(d);
+#define STEP_MULTI_REC 1
+#define STEP_MULTI_FB 0
+#define STEP_MULTI_FW 1
+#include "k_step_multi_body.inc"
+#undef STEP_MULTI_FW
 #undef STEP_MULTI_FB
 #undef STEP_MULTI_REC
 }
@@ -1427,21 +1478,25 @@ void auv_launch_step_roles(const AuvDev& d0, const void* actions, int dtype, flo
 
 // order: 0 step-major; 1 cohort-pipelined where the slice has whole cohorts for it (lead / lag clamped: auv_multi_geom.h)
 void auv_launch_step_multi(const AuvDev& d0, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, int n_steps,
-                           int first_slot, int n_slots, unsigned long long seq0, int order, int lead, int lag, hipStream_t st) {
+                           int first_slot, int n_slots, unsigned long long seq0, int order, int lead, int lag, hipStream_t st, unsigned int fw_call) {
   AuvDev d = d0;
   d.act_f64 = dtype == AUV_F64;
   d.ring_slots = 1;
   const uint32_t lds = (uint32_t)k2_slice_bytes(d);
   const AuvMultiGeom g = auv_multi_geom(d.ne, n_steps, order, lead, lag);      // (the host has checked that the grid fits)
   const dim3 grid((unsigned)auv_multi_grid(g)), block(AUV_WAVE);
-  hipLaunchKernelGGL(k_step_multi, grid, block, lds, st, d, actions, obs, reward, done, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic);
+  // fw_call != 0: a fresh world per reset, this launch belongs to multi-step call number fw_call
+  if (fw_call)
+    hipLaunchKernelGGL(k_fresh_multi, grid, block, lds, st, d, actions, obs, reward, done, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic, fw_call);
+  else
+    hipLaunchKernelGGL(k_step_multi, grid, block, lds, st, d, actions, obs, reward, done, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic);
 }
 
 // the recording form: step k's rows at obs_rec + k N D, reward_rec + k N, done_rec + k N (obs_rec == nullptr: no observation record,
 // every step writes `obs`); then the last row into obs / reward / done
 void auv_launch_step_record(const AuvDev& d0, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, float* obs_rec,
                             float* reward_rec, uint8_t* done_rec, int n_steps, int first_slot, int n_slots, unsigned long long seq0, int order,
-                            int lead, int lag, hipStream_t st) {
+                            int lead, int lag, hipStream_t st, unsigned int fw_call) {
   AuvDev d = d0;
   d.act_f64 = dtype == AUV_F64;
   d.ring_slots = 1;
@@ -1450,8 +1505,12 @@ void auv_launch_step_record(const AuvDev& d0, const void* actions, int dtype, fl
   const dim3 grid((unsigned)auv_multi_grid(g)), block(AUV_WAVE);
   const int D = auv_obs_cols(d.cfg, d.pool_ns);
   const unsigned long long n = (unsigned long long)d.n, obs_stride = obs_rec ? n * (unsigned long long)D : 0ull;
-  hipLaunchKernelGGL(k_step_record, grid, block, lds, st, d, actions, obs_rec ? obs_rec : obs, reward_rec, done_rec, n_steps, first_slot, n_slots, seq0,
-                     g.lead, g.lag, g.magic, obs_stride, n, n);
+  if (fw_call)                                                                   // (as auv_launch_step_multi)
+    hipLaunchKernelGGL(k_fresh_record, grid, block, lds, st, d, actions, obs_rec ? obs_rec : obs, reward_rec, done_rec, n_steps, first_slot, n_slots, seq0,
+                       g.lead, g.lag, g.magic, obs_stride, n, n, fw_call);
+  else
+    hipLaunchKernelGGL(k_step_record, grid, block, lds, st, d, actions, obs_rec ? obs_rec : obs, reward_rec, done_rec, n_steps, first_slot, n_slots, seq0,
+                       g.lead, g.lag, g.magic, obs_stride, n, n);
   const size_t last = (size_t)(n_steps - 1), items = (size_t)d.ne * (size_t)(obs_rec ? D : 1);
   hipLaunchKernelGGL(k_record_last, dim3((unsigned)((items + 255) / 256)), dim3(256), 0, st, obs_rec ? obs_rec + last * obs_stride : nullptr,
                      reward_rec + last * n, done_rec + last * n, obs, reward, done, d.e0, d.ne, D, d.abort_flag);
@@ -1523,6 +1582,10 @@ hipError_t auv_step_fused_prepare(const AuvDev& d) {
   e = hipFuncSetAttribute((const void*)k_step_multi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void*)k_step_record, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute((const void*)k_fresh_multi, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute((const void*)k_fresh_record, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void*)k_step_feedback, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
   if (e != hipSuccess) return e;

@@ -9,6 +9,9 @@
 //                      parameters sgains ([N][2][16] fp64) and sb (FbBounds by value, the sector bounds).
 //   STEP_MULTI_FB 3    k_step_hidden_feedback  the same with one hidden layer of 16 units over the law's 24 inputs (fb_hidden): further
 //                      parameters hidden ([N][16][28] fp64) and activation (0 relu, 1 hard tanh).
+//   STEP_MULTI_FW 1    k_fresh_multi / k_fresh_record (REC 0 / 1, FB 0)  a fresh world per reset: the finish wave's reset binds the
+//                      environment's next slot only if it was published before this call began (auv_next_world_multi).  Further
+//                      parameter: fw_call, the call's number.  (Not defined by the other inclusions: `#if` reads it as 0.)
 // The includer has declared `d` (AUV_KERNARG_DESC) and the kernel's parameters: actions, obs_out, reward_out, done_out, n_steps,
 // first_slot, n_slots, seq0, lead_dyn, lag_fin, magic_c -- and, recording, obs_stride, reward_stride, done_stride (elements; 0: no
 // record of that output).  The record's offset is wave-uniform (the step is, the strides are kernel arguments): 64-bit scalar
@@ -260,6 +263,9 @@
 #elif STEP_MULTI_FB
     roles_finish_wave_multi<true, true>(d, f, lane, obs_out, reward_out, done_out, step, step == n_steps - 1, tagmix, tagmix_prev MSTAMP_ARG, gains,
                                         actions, (first_slot + step + 1) % n_slots);
+#elif STEP_MULTI_FW
+    roles_finish_wave_multi<true, 0, 1>(d, f, lane, obs_out, reward_out, done_out, step, step == n_steps - 1, tagmix, tagmix_prev MSTAMP_ARG, nullptr,
+                                        nullptr, 0, nullptr, nullptr, nullptr, 0, fw_call);
 #else
     roles_finish_wave_multi<true>(d, f, lane, obs_out, reward_out, done_out, step, step == n_steps - 1, tagmix, tagmix_prev MSTAMP_ARG);
 #endif

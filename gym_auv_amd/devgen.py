@@ -51,7 +51,19 @@ class FreshWorlds:
     environment (>= 2); the world of environment e's k-th episode is the world of (seed, env_index_base + e, k) whatever the
     timing, the sub-batch chains or the sharding over GPUs.  A refill pass of up to `batch_cap` worlds is enqueued on a side
     stream every `period` step calls; `BatchedAuvEnv.fresh_stats()["reused"]` counts episodes that had to start in the world
-    they had just finished because the pass fell behind (0 when depth / period / batch_cap fit the turn-over rate)."""
+    they had just finished because the pass fell behind (0 when depth / period / batch_cap fit the turn-over rate).
+
+    `multi_step=True` (auv_fresh_worlds_multi; needs depth >= 3, else ValueError) also allows `step_multi` -- several steps per
+    launch, with or without a record; the closed-loop `step_feedback` stays refused.  Guaranteed there: a launch binds only slots
+    that were rebuilt AND published before any kernel of its call began (its later steps read the tables with plain loads), the
+    world of an environment's k-th episode is still the world of (seed, global index, k), and an environment whose next slot
+    does not qualify starts over in the world it has just left, counted in `reused` -- never silently.  Every call counts its
+    n_steps towards `period` and enqueues its pass behind its own launches, so a slot left in call c is bindable from call
+    c + 2 on (c + 1 where the caller synchronises between calls; at once after `refill(flush=True)`).  Rule of thumb: depth 3
+    sustains one reset per environment per launch and a burst of two; shorter episodes than that need more depth or shorter
+    launches.  Step such a handle on ONE chain: sub-batch chains drift apart by whole calls and a slot's stamp follows the
+    fastest (moving28, random actions, depth 3: 1 % of the episodes re-used on one chain, 24 % on three;
+    profiles/multi_fresh/README.md)."""
     depth: int = 3           # (measured on moving28 with i.i.d. random actions, where a quarter of the episodes end within a few
     n_moving: int = 17       #  dozen steps of their reset: depth 2 re-used 25-80 of 11 800 worlds, depth 3 none -- profiles/r05)
     n_static: int = 11
@@ -59,6 +71,12 @@ class FreshWorlds:
     env_index_base: int = 0
     batch_cap: int = 64
     period: int = 16         # (a pass takes ~0.3 ms whatever it holds: fewer, fuller passes cost the chains less)
+    multi_step: bool = False
+
+    def __post_init__(self):
+        if self.multi_step and self.depth < 3:
+            raise ValueError("FreshWorlds(multi_step=True) needs depth >= 3, got %d: with two slots an environment could never "
+                             "reset without re-use inside a launch that has already used its spare" % self.depth)
 
 
 def n_draws(n_moving: int, n_static: int) -> int:

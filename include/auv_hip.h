@@ -600,6 +600,22 @@ int auv_fresh_worlds_refill(auv_handle_t* h, int32_t n_slices, const int32_t* bo
  * side with all three (auv_streams_overlap) -- what BatchedAuvEnv.set_sub_batches does in this mode.  The stream stays the
  * caller's; it must outlive the mode.                                                                              */
 int auv_fresh_worlds_set_stream(auv_handle_t* h, void* stream);
+/* Launches of SEVERAL steps with a fresh world on every reset.  auv_step_multi / auv_step_multi_record refuse this mode ("not with a
+ * fresh world per reset") until the handle opts in here; the closed-loop entries (auv_step_feedback*) refuse it either way.
+ * on != 0 needs depth >= 3 (AUV_EINVAL) and the mode itself (AUV_ESTATE); auv_fresh_worlds_create switches it off again.
+ * What an opted-in handle does in those two calls:
+ *   - the steps of a launch read a bound slot's tables with plain loads and no kernel boundary in between, so a launch binds ONLY
+ *     slots that were published before any kernel of its call began: every call has a number, a one-wave kernel in front of each
+ *     chain's launch announces it on the device, the pass's last kernel stamps every slot it publishes with the latest number
+ *     announced, and a launch of call c takes a slot only if its stamp is below c.  An environment whose next slot does not
+ *     qualify starts over in the world it has just finished, COUNTED in auv_fresh_worlds_stats [2] like every re-use;
+ *   - every call counts n_steps towards `period` and enqueues its pass BEHIND its launches, paced behind every chain: a slot left
+ *     in call c is rebuilt beside call c + 1 and bindable from call c + 2 on (from c + 1 on where the caller synchronises in
+ *     between).  depth 3 therefore sustains one reset per environment per launch and a burst of two;
+ *   - auv_fresh_worlds_refill(flush) leaves every slot left so far bindable by the next call;
+ *   - not on a stream that is being captured (the call's number is a launch argument).
+ * One-step calls on the handle behave as before.                                                                        */
+int auv_fresh_worlds_multi(auv_handle_t* h, int32_t on);
 int auv_fresh_worlds_stats(auv_handle_t* h, int64_t* out8);
 int auv_fresh_worlds_draws(auv_handle_t* h, const int32_t* envs_host, const int32_t* serials_host, int32_t n_rows, double* dst_dev,
                            void* stream);
