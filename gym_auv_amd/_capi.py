@@ -173,6 +173,14 @@ class AuvPpoBatch(C.Structure):
     ]
 
 
+class AuvPpoCloneBatch(C.Structure):
+    """== auv_ppo_clone_batch_t: the rows of one supervised (clone) step -- target actions, value targets, row weights"""
+    _fields_ = [
+        ("O", C.c_void_p), ("A", C.c_void_p), ("RET", C.c_void_p), ("W", C.c_void_p), ("idx", C.c_void_p),
+        ("B", C.c_int32), ("n_rows", C.c_int32), ("kind", C.c_int32), ("vf_coef", C.c_float), ("ent_coef", C.c_float),
+    ]
+
+
 class AuvPpoAdam(C.Structure):
     """== auv_ppo_adam_t: Adam's hyper-parameters and the bias corrections of this step"""
     _fields_ = [
@@ -280,6 +288,7 @@ def load_library(path: str = None) -> C.CDLL:
         "auv_ppo_attach_policy": (C.c_int, [vp, vp]),
         "auv_ppo_grad": (C.c_int, [vp, C.POINTER(AuvPpoBatch), vp, vp, vp]),
         "auv_ppo_adam": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(AuvPpoAdam), vp, vp]),
+        "auv_ppo_grad_clone": (C.c_int, [vp, C.POINTER(AuvPpoCloneBatch), vp, vp, vp]),
         "auv_render": (C.c_int, [vp, vp, C.POINTER(i32), i32, i32, i32, C.c_double, i32, C.c_double, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
         "auv_abi_version": (i32, []),
         "auv_last_error": (C.c_char_p, []),
@@ -312,6 +321,7 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_plan_score_v", "auv_policy_eval",
                     "auv_population_member_floats", "auv_population_act", "auv_population_rollout", "auv_population_perturb", "auv_population_update",
                     "auv_ppo_param_floats", "auv_ppo_create", "auv_ppo_destroy", "auv_ppo_load", "auv_ppo_attach_policy", "auv_ppo_grad", "auv_ppo_adam",
+                    "auv_ppo_grad_clone",
                     "auv_render",
                     "auv_abi_version", "auv_last_error"]
 

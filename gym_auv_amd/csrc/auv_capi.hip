@@ -2612,6 +2612,20 @@ int auv_ppo_grad(auv_ppo_t* p, const auv_ppo_batch_t* b, float* grad, float* sta
   return AUV_OK;
 }
 
+int auv_ppo_grad_clone(auv_ppo_t* p, const auv_ppo_clone_batch_t* b, float* grad, float* stats, void* stream) {
+  if (!p || !b || !grad || !stats) return fail(AUV_EINVAL, "auv_ppo_grad_clone: null argument");
+  if (!b->O || !b->A || !b->RET) return fail(AUV_EINVAL, "auv_ppo_grad_clone: null batch buffer (O, A and RET are required)");
+  if (b->kind != 0 && b->kind != 1) return fail(AUV_EINVAL, "auv_ppo_grad_clone: kind = %d (0: Gaussian NLL, 1: MSE on the mean)", b->kind);
+  if (b->B < 1) return fail(AUV_EINVAL, "auv_ppo_grad_clone: B = %d < 1", b->B);
+  if (b->n_rows < 1 || (!b->idx && b->B > b->n_rows)) return fail(AUV_EINVAL, "auv_ppo_grad_clone: B = %d rows of n_rows = %d", b->B, b->n_rows);
+  if (b->B > p->d.max_batch) return fail(AUV_EINVAL, "auv_ppo_grad_clone: B = %d above max_batch = %d", b->B, p->d.max_batch);
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(auv_ppo_prepare(p->d.obs_dim, true));
+  auv_launch_ppo_grad_clone(p->d, *b, grad, stats, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
 int auv_ppo_adam(auv_ppo_t* p, float* theta, float* m, float* v, const float* grad, const auv_ppo_adam_t* a, float* norms_out, void* stream) {
   if (!p || !theta || !m || !v || !grad || !a || !norms_out) return fail(AUV_EINVAL, "auv_ppo_adam: null argument");
   if (!(a->bc1 > 0.0) || !(a->bc2 > 0.0)) return fail(AUV_EINVAL, "auv_ppo_adam: bias corrections must be > 0 (step >= 1)");

@@ -22,6 +22,7 @@ struct AuvPpoDev {
   float* dZ[2][4];     // per net: dZ1 [rt][16][256], dZ2 [rt][8][256], dZ3 [rt][4][256], dZ4 [rt][1][256]
   float* part;         // [AUV_PPO_MAX_SPLIT][2][net floats]: split-K partials of dW (row-major, padded like the forward copy) and db
   float* tstat;        // [rt][8]: per row tile sum pg, sum vf, max |adv|, max ratio, non-finite inputs, clipped rows, d log_std[2]
+                       // (k8_clone: sum bc, sum vf, max |a - mu|, sum w, non-finite inputs, 0, d log_std[2])
   double* sqpart;      // [AUV_PPO_NORM_BLOCKS][2]: partial sums of squares of the policy and the value group
   float* pol;          // attached auv_policy_io::params buffer (nullable)
 };
@@ -35,9 +36,10 @@ size_t auv_ppo_param_floats_impl(int obs_dim);
 size_t auv_ppo_fwd_floats(int obs_dim);
 size_t auv_ppo_tr_floats();
 size_t auv_ppo_lds_bytes(int obs_dim);
-hipError_t auv_ppo_prepare(int obs_dim);
+hipError_t auv_ppo_prepare(int obs_dim, bool clone = false);    // clone: for k8_clone, the row pass of auv_ppo_grad_clone
 void auv_launch_ppo_load(const AuvPpoDev& d, const float* theta, hipStream_t st);
 void auv_launch_ppo_grad(const AuvPpoDev& d, const auv_ppo_batch_t& b, float* grad, float* stats, hipStream_t st);
+void auv_launch_ppo_grad_clone(const AuvPpoDev& d, const auv_ppo_clone_batch_t& b, float* grad, float* stats, hipStream_t st);
 void auv_launch_ppo_adam(const AuvPpoDev& d, float* theta, float* m, float* v, const float* grad, const AuvPpoAdamDev& a, float* norms_out,
                          hipStream_t st);
 #endif /* AUV_PPO_H */

@@ -16,6 +16,7 @@
 //   k8_wgrad   dW_l = dZ_l^T Y_{l-1}, db_l = column sums of dZ_l: split-K over the batch, one workgroup = up to four 16 x 16
 //              output tiles of one row of tiles, four waves on four row ranges, summed in a fixed order.
 //   k8_reduce  sums the split partials in a fixed order into the flat gradient (torch layout), and the tile statistics.
+// auv_ppo_grad_clone: the same three with k8_clone in place of k8_rows -- the same row pass with a supervised head (ppo_head).
 // Launches of auv_ppo_adam: k8_norm (partial sums of squares per group), k8_adam (clip, Adam, and the scatter of every updated
 // weight into the forward copy, the transposed copy and an attached auv_policy_io::params buffer).
 // No floating-point atomics anywhere: every sum crosses workgroups through memory and a kernel boundary, in an order that depends
@@ -87,9 +88,10 @@ __device__ inline PpoWhere ppo_where(long long p, const int D, const int K0p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- row pass
+template <class Batch>                                             // auv_ppo_batch_t: k8_rows; auv_ppo_clone_batch_t: k8_clone
 struct RowArgs {
   AuvPpoDev d;
-  auv_ppo_batch_t b;
+  Batch b;
 };
 
 __device__ __forceinline__ int ppo_bad(const float x) { return !(fabsf(x) <= 3.402823466e38f); }   // NaN or +-inf
@@ -131,13 +133,152 @@ __device__ __forceinline__ void ppo_back_store(f32x4 (*o)[POL_MT], const float* 
   }
 }
 
-// grid (ceil(B / 16), 2): blockIdx.y = 0 the policy net, 1 the value net
-__global__ void __launch_bounds__(POL_THREADS, 4) k8_rows(RowArgs ra) {
+// The head of k8_rows (wave 0, between the forward and the backward pass): o = this lane's four rows 4 g + i of output column n of
+// the net (the policy's mean, the value), srow the tile's source rows (-1: padding).  Returns d loss / d o and writes the tile's
+// statistics; the overload on the batch's type is the supervised head of k8_clone.
+__device__ __forceinline__ f32x4 ppo_head(const AuvPpoDev& d, const auv_ppo_batch_t& b, const int net, const int rt, const int lane, const f32x4 o,
+                                          const long long* __restrict__ srow, const int* __restrict__ nbad) {
+  const size_t netf = pol_net_floats(d.obs_dim);
+  const int B = b.B;
+  const int n = lane & 15, g = lane >> 4;
+  const float invB = 1.0f / (float)B;
+  f32x4 d4 = {0.0f, 0.0f, 0.0f, 0.0f};
+  float* ts = d.tstat + 8 * (size_t)rt;
+  if (net == 0) {
+    const int nc = n < 2 ? n : 0;
+    const float ls = (d.fwd + 2 * netf)[nc];
+    const float sigma = expf(ls);
+    const float lo = 1.0f - b.clip, hi = 1.0f + b.clip;
+    float s_pg = 0.0f, s_clip = 0.0f, s_dls = 0.0f, mx_adv = 0.0f, mx_ratio = 0.0f;
+    int bad = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const long long s = srow[4 * g + i];
+      const bool valid = s >= 0;
+      const size_t sr = valid ? (size_t)s : 0;
+      const float a = valid ? b.A[2 * sr + nc] : 0.0f, lpo = valid ? b.LP[sr] : 0.0f, adv = valid ? b.ADV[sr] : 0.0f;
+      const float ret = valid ? b.RET[sr] : 0.0f;
+      const float mu = o[i];
+      const float z = (a - mu) / sigma;
+      float lp = -0.5f * (z * z) - ls - POL_LOG_SQRT_2PI;
+      lp += __shfl_xor(lp, 1, AUV_WAVE);                         // the two components sit on neighbouring lanes
+      const float ratio = expf(lp - lpo);
+      const float pgi = -fminf(ratio * adv, fminf(fmaxf(ratio, lo), hi) * adv);
+      const bool clipped = (adv > 0.0f && ratio > hi) || (adv < 0.0f && ratio < lo);
+      const float glp = clipped ? 0.0f : -adv * ratio * invB;
+      if (valid && n < 2) {
+        d4[i] = glp * ((a - mu) / (sigma * sigma));
+        s_dls += glp * (z * z - 1.0f);
+        bad += ppo_bad(a);
+      }
+      if (valid && n == 0) {
+        s_pg += pgi, s_clip += clipped ? 1.0f : 0.0f;
+        mx_adv = fmaxf(mx_adv, fabsf(adv)), mx_ratio = fmaxf(mx_ratio, ratio);
+        bad += ppo_bad(lpo) + ppo_bad(adv) + ppo_bad(ret);
+      }
+    }
+    // the four row groups of a column: a butterfly over lanes n, n + 16, n + 32, n + 48 (the same order on every call)
+#pragma unroll
+    for (int sh = 16; sh <= 32; sh <<= 1) {
+      s_pg += __shfl_xor(s_pg, sh, AUV_WAVE), s_clip += __shfl_xor(s_clip, sh, AUV_WAVE), s_dls += __shfl_xor(s_dls, sh, AUV_WAVE);
+      mx_adv = fmaxf(mx_adv, __shfl_xor(mx_adv, sh, AUV_WAVE)), mx_ratio = fmaxf(mx_ratio, __shfl_xor(mx_ratio, sh, AUV_WAVE));
+      bad += __shfl_xor(bad, sh, AUV_WAVE);
+    }
+    bad += __shfl_xor(bad, 1, AUV_WAVE);                         // (lane 1 counted the second action component)
+    if (lane == 0) ts[0] = s_pg, ts[2] = mx_adv, ts[3] = mx_ratio, ts[4] = (float)(bad + *nbad), ts[5] = s_clip, ts[6] = s_dls;
+    if (lane == 1) ts[7] = s_dls;
+  } else {
+    float s_vf = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const long long s = srow[4 * g + i];
+      const bool valid = s >= 0 && n == 0;
+      const float ret = valid ? b.RET[(size_t)s] : 0.0f;
+      const float e = o[i] - ret;
+      if (valid) d4[i] = b.vf_coef * e * invB, s_vf += 0.5f * (e * e);
+    }
+    s_vf += __shfl_xor(s_vf, 16, AUV_WAVE);
+    s_vf += __shfl_xor(s_vf, 32, AUV_WAVE);
+    if (lane == 0) ts[1] = s_vf;
+  }
+  return d4;
+}
+
+// The supervised head of k8_clone (include/auv_hip.h, auv_ppo_grad_clone): the policy towards the target actions A (kind 0: the
+// Gaussian negative log-likelihood, 1: the squared error of the mean), the value net towards RET, every row times its weight.
+//   kind 0: d bc / d mu_ik = -w_i (a_ik - mu_ik) / sigma_k^2 / B, d bc / d log_std_k = sum_i w_i (1 - z_ik^2) / B
+//   kind 1: d bc / d mu_ik = -w_i (a_ik - mu_ik) / B, nothing for log_std;   d loss / d v_i = vf_coef w_i (v_i - ret_i) / B
+// Laid out as the head above: components on neighbouring lanes, the same butterfly, the same non-finite count.  tstat: sum bc, sum vf,
+// max |a - mu| over rows of weight > 0, sum w, non-finite inputs, 0, d log_std[2] -- what k8_reduce (clone) turns into stats[8].
+__device__ __forceinline__ f32x4 ppo_head(const AuvPpoDev& d, const auv_ppo_clone_batch_t& b, const int net, const int rt, const int lane,
+                                          const f32x4 o, const long long* __restrict__ srow, const int* __restrict__ nbad) {
+  const int n = lane & 15, g = lane >> 4;
+  const float invB = 1.0f / (float)b.B;
+  f32x4 d4 = {0.0f, 0.0f, 0.0f, 0.0f};
+  float* ts = d.tstat + 8 * (size_t)rt;
+  if (net == 0) {
+    const int nc = n < 2 ? n : 0;
+    const float ls = (d.fwd + 2 * pol_net_floats(d.obs_dim))[nc];
+    const float sigma = expf(ls);
+    const bool nll = b.kind == 0;
+    float s_bc = 0.0f, s_w = 0.0f, s_dls = 0.0f, mx_err = 0.0f;
+    int bad = 0;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const long long s = srow[4 * g + i];
+      const bool valid = s >= 0;
+      const size_t sr = valid ? (size_t)s : 0;
+      const float a = valid ? b.A[2 * sr + nc] : 0.0f, ret = valid ? b.RET[sr] : 0.0f;
+      const float w = valid ? (b.W ? b.W[sr] : 1.0f) : 0.0f;
+      const float e = a - o[i];
+      const float z = e / sigma;
+      float bc = w * (nll ? 0.5f * (z * z) + ls + POL_LOG_SQRT_2PI : 0.5f * (e * e));
+      bc += __shfl_xor(bc, 1, AUV_WAVE);                         // the two components sit on neighbouring lanes
+      if (valid && n < 2) {
+        d4[i] = nll ? -w * (e / (sigma * sigma)) * invB : -w * e * invB;
+        if (nll) s_dls += w * (1.0f - z * z) * invB;
+        if (w > 0.0f) mx_err = fmaxf(mx_err, fabsf(e));
+        bad += ppo_bad(a);
+      }
+      if (valid && n == 0) {
+        s_bc += bc, s_w += w;
+        bad += ppo_bad(ret) + (b.W ? ppo_bad(w) : 0);
+      }
+    }
+#pragma unroll
+    for (int sh = 16; sh <= 32; sh <<= 1) {
+      s_bc += __shfl_xor(s_bc, sh, AUV_WAVE), s_w += __shfl_xor(s_w, sh, AUV_WAVE), s_dls += __shfl_xor(s_dls, sh, AUV_WAVE);
+      mx_err = fmaxf(mx_err, __shfl_xor(mx_err, sh, AUV_WAVE));
+      bad += __shfl_xor(bad, sh, AUV_WAVE);
+    }
+    bad += __shfl_xor(bad, 1, AUV_WAVE);
+    mx_err = fmaxf(mx_err, __shfl_xor(mx_err, 1, AUV_WAVE));
+    if (lane == 0) ts[0] = s_bc, ts[2] = mx_err, ts[3] = s_w, ts[4] = (float)(bad + *nbad), ts[5] = 0.0f, ts[6] = s_dls;
+    if (lane == 1) ts[7] = s_dls;
+  } else {
+    float s_vf = 0.0f;
+#pragma unroll
+    for (int i = 0; i < 4; i++) {
+      const long long s = srow[4 * g + i];
+      const bool valid = s >= 0 && n == 0;
+      const float ret = valid ? b.RET[(size_t)s] : 0.0f;
+      const float w = valid ? (b.W ? b.W[(size_t)s] : 1.0f) : 0.0f;
+      const float e = o[i] - ret;
+      if (valid) d4[i] = b.vf_coef * (w * e) * invB, s_vf += w * (0.5f * (e * e));
+    }
+    s_vf += __shfl_xor(s_vf, 16, AUV_WAVE);
+    s_vf += __shfl_xor(s_vf, 32, AUV_WAVE);
+    if (lane == 0) ts[1] = s_vf;
+  }
+  return d4;
+}
+
+// The row pass of one workgroup, 16 rows of net `net` (row tile rt): gather, forward, ppo_head of the batch's type, backward
+template <class Batch>
+__device__ __forceinline__ void ppo_row_pass(const AuvPpoDev& d, const Batch& b, const int net, const int rt) {
   extern __shared__ __align__(16) unsigned char smem[];
-  const AuvPpoDev& d = ra.d;
-  const auv_ppo_batch_t& b = ra.b;
   const int tid = threadIdx.x, wave = tid / AUV_WAVE, lane = tid % AUV_WAVE;
-  const int net = blockIdx.y, rt = blockIdx.x, r0 = rt * 16;
+  const int r0 = rt * 16;
   const int K0 = d.obs_dim, K0p = d.k0p, B = b.B;
   const int ldx = K0p + 8, ld1 = POL_H1 + 8, ld2 = POL_H2 + 8, ld3 = POL_H3 + 8, ld4 = 72;
   float* X = (float*)smem;
@@ -201,67 +342,8 @@ __global__ void __launch_bounds__(POL_THREADS, 4) k8_rows(RowArgs ra) {
   if (wave == 0) {
     f32x4 o[1][POL_MT];
     pol_layer<1, 2, true, false>(Y3, ld3, w4, b4, POL_H3, 0, lane, nullptr, 0, o);
+    const f32x4 d4 = ppo_head(d, b, net, rt, lane, o[0][0], srow, nbad);
     const int n = lane & 15, g = lane >> 4;
-    const float invB = 1.0f / (float)B;
-    f32x4 d4 = {0.0f, 0.0f, 0.0f, 0.0f};
-    float* ts = d.tstat + 8 * (size_t)rt;
-    if (net == 0) {
-      const int nc = n < 2 ? n : 0;
-      const float ls = (d.fwd + 2 * netf)[nc];
-      const float sigma = expf(ls);
-      const float lo = 1.0f - b.clip, hi = 1.0f + b.clip;
-      float s_pg = 0.0f, s_clip = 0.0f, s_dls = 0.0f, mx_adv = 0.0f, mx_ratio = 0.0f;
-      int bad = 0;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const long long s = srow[4 * g + i];
-        const bool valid = s >= 0;
-        const size_t sr = valid ? (size_t)s : 0;
-        const float a = valid ? b.A[2 * sr + nc] : 0.0f, lpo = valid ? b.LP[sr] : 0.0f, adv = valid ? b.ADV[sr] : 0.0f;
-        const float ret = valid ? b.RET[sr] : 0.0f;
-        const float mu = o[0][0][i];
-        const float z = (a - mu) / sigma;
-        float lp = -0.5f * (z * z) - ls - POL_LOG_SQRT_2PI;
-        lp += __shfl_xor(lp, 1, AUV_WAVE);                       // the two components sit on neighbouring lanes
-        const float ratio = expf(lp - lpo);
-        const float pgi = -fminf(ratio * adv, fminf(fmaxf(ratio, lo), hi) * adv);
-        const bool clipped = (adv > 0.0f && ratio > hi) || (adv < 0.0f && ratio < lo);
-        const float glp = clipped ? 0.0f : -adv * ratio * invB;
-        if (valid && n < 2) {
-          d4[i] = glp * ((a - mu) / (sigma * sigma));
-          s_dls += glp * (z * z - 1.0f);
-          bad += ppo_bad(a);
-        }
-        if (valid && n == 0) {
-          s_pg += pgi, s_clip += clipped ? 1.0f : 0.0f;
-          mx_adv = fmaxf(mx_adv, fabsf(adv)), mx_ratio = fmaxf(mx_ratio, ratio);
-          bad += ppo_bad(lpo) + ppo_bad(adv) + ppo_bad(ret);
-        }
-      }
-      // the four row groups of a column: a butterfly over lanes n, n + 16, n + 32, n + 48 (the same order on every call)
-#pragma unroll
-      for (int sh = 16; sh <= 32; sh <<= 1) {
-        s_pg += __shfl_xor(s_pg, sh, AUV_WAVE), s_clip += __shfl_xor(s_clip, sh, AUV_WAVE), s_dls += __shfl_xor(s_dls, sh, AUV_WAVE);
-        mx_adv = fmaxf(mx_adv, __shfl_xor(mx_adv, sh, AUV_WAVE)), mx_ratio = fmaxf(mx_ratio, __shfl_xor(mx_ratio, sh, AUV_WAVE));
-        bad += __shfl_xor(bad, sh, AUV_WAVE);
-      }
-      bad += __shfl_xor(bad, 1, AUV_WAVE);                       // (lane 1 counted the second action component)
-      if (lane == 0) ts[0] = s_pg, ts[2] = mx_adv, ts[3] = mx_ratio, ts[4] = (float)(bad + *nbad), ts[5] = s_clip, ts[6] = s_dls;
-      if (lane == 1) ts[7] = s_dls;
-    } else {
-      float s_vf = 0.0f;
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const long long s = srow[4 * g + i];
-        const bool valid = s >= 0 && n == 0;
-        const float ret = valid ? b.RET[(size_t)s] : 0.0f;
-        const float e = o[0][0][i] - ret;
-        if (valid) d4[i] = b.vf_coef * e * invB, s_vf += 0.5f * (e * e);
-      }
-      s_vf += __shfl_xor(s_vf, 16, AUV_WAVE);
-      s_vf += __shfl_xor(s_vf, 32, AUV_WAVE);
-      if (lane == 0) ts[1] = s_vf;
-    }
 #pragma unroll
     for (int i = 0; i < 4; i++) D4[(4 * g + i) * ld4 + n] = d4[i], D4[(4 * g + i) * ld4 + 16 + n] = 0.0f;
     *(float4*)(d.dZ[net][3] + (size_t)rt * 256 + 4 * lane) = make_float4(d4[0], d4[1], d4[2], d4[3]);
@@ -287,6 +369,12 @@ __global__ void __launch_bounds__(POL_THREADS, 4) k8_rows(RowArgs ra) {
   ppo_store_blocks(Y2, ld2, POL_H2 / 16, d.Y[net][1], rt, tid);
   ppo_store_blocks(Y3, ld3, POL_H3 / 16, d.Y[net][2], rt, tid);
 }
+
+// grid (ceil(B / 16), 2): blockIdx.y = 0 the policy net, 1 the value net
+__global__ void __launch_bounds__(POL_THREADS, 4) k8_rows(RowArgs<auv_ppo_batch_t> ra) { ppo_row_pass(ra.d, ra.b, blockIdx.y, blockIdx.x); }
+
+// the same grid with the supervised head: the row pass of auv_ppo_grad_clone
+__global__ void __launch_bounds__(POL_THREADS, 4) k8_clone(RowArgs<auv_ppo_clone_batch_t> ra) { ppo_row_pass(ra.d, ra.b, blockIdx.y, blockIdx.x); }
 
 // ------------------------------------------------------------------------------------------------------ weight-gradient pass
 #define WG_WAVES 4
@@ -383,6 +471,7 @@ struct RedArgs {
   float* stats;
   long long P;
   int32_t nsplit, rt, B;
+  int32_t clone;                   // the tiles are k8_clone's: slot 3 is a sum (of the weights), not a maximum
   float vf_coef, ent_coef;
 };
 
@@ -406,7 +495,7 @@ __global__ void __launch_bounds__(256) k8_reduce(RedArgs a) {
   for (int t = tid; t < a.rt; t += 256) {
     const float* ts = d.tstat + 8 * (size_t)t;
 #pragma unroll
-    for (int j = 0; j < 8; j++) v[j] = (j == 2 || j == 3) ? fmaxf(v[j], ts[j]) : v[j] + ts[j];
+    for (int j = 0; j < 8; j++) v[j] = (j == 2 || (j == 3 && !a.clone)) ? fmaxf(v[j], ts[j]) : v[j] + ts[j];
   }
 #pragma unroll
   for (int j = 0; j < 8; j++) red[j][tid] = v[j];
@@ -414,7 +503,8 @@ __global__ void __launch_bounds__(256) k8_reduce(RedArgs a) {
   for (int h = 128; h >= 1; h >>= 1) {
     if (tid < h) {
 #pragma unroll
-      for (int j = 0; j < 8; j++) red[j][tid] = (j == 2 || j == 3) ? fmaxf(red[j][tid], red[j][tid + h]) : red[j][tid] + red[j][tid + h];
+      for (int j = 0; j < 8; j++)
+        red[j][tid] = (j == 2 || (j == 3 && !a.clone)) ? fmaxf(red[j][tid], red[j][tid + h]) : red[j][tid] + red[j][tid + h];
     }
     __syncthreads();
   }
@@ -511,12 +601,12 @@ size_t auv_ppo_fwd_floats(int obs_dim) { return 2 * pol_net_floats(obs_dim) + 4;
 size_t auv_ppo_tr_floats() { return 2 * (size_t)PPO_TR_FLOATS; }
 size_t auv_ppo_lds_bytes(int obs_dim) { return sizeof(float) * ppo_lds_floats(obs_dim); }
 
-// The dynamic LDS k8_rows may ask for is an attribute of the KERNEL, not of an updater: auv_ppo_grad sets it in front of every launch
+// The dynamic LDS k8_rows (k8_clone) may ask for is an attribute of the KERNEL, not of an updater: auv_ppo_grad sets it in front of every launch
 // that needs more than the 64 KiB a kernel gets unasked, so updaters of different widths can live side by side.
-hipError_t auv_ppo_prepare(int obs_dim) {
+hipError_t auv_ppo_prepare(int obs_dim, bool clone) {
   const size_t b = auv_ppo_lds_bytes(obs_dim);
   if (b <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute((const void*)k8_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  return hipFuncSetAttribute(clone ? (const void*)k8_clone : (const void*)k8_rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
 }
 
 // The split-K factor, a function of B and obs_dim alone (so the summation order is): about 16 row tiles per wave for large batches;
@@ -535,18 +625,30 @@ void auv_launch_ppo_load(const AuvPpoDev& d, const float* theta, hipStream_t st)
   hipLaunchKernelGGL(k8_adam<true>, dim3((unsigned)((a.P + 255) / 256)), dim3(256), 0, st, a);
 }
 
-void auv_launch_ppo_grad(const AuvPpoDev& d, const auv_ppo_batch_t& b, float* grad, float* stats, hipStream_t st) {
-  const int rt = (b.B + 15) / 16, nsplit = ppo_nsplit(rt, d.k0p);
-  RowArgs ra;
-  ra.d = d, ra.b = b;
-  hipLaunchKernelGGL(k8_rows, dim3(rt, 2), dim3(POL_THREADS), auv_ppo_lds_bytes(d.obs_dim), st, ra);
+// the launches behind a row pass: weight gradients, then the flat gradient and the statistics
+static void ppo_launch_after_rows(const AuvPpoDev& d, int B, bool clone, float vf_coef, float ent_coef, float* grad, float* stats, hipStream_t st) {
+  const int rt = (B + 15) / 16, nsplit = ppo_nsplit(rt, d.k0p);
   WgArgs wa;
   wa.d = d, wa.rt = rt, wa.nsplit = nsplit;
   hipLaunchKernelGGL(k8_wgrad, dim3(2 * ppo_wg_units(d.k0p), nsplit), dim3(64 * WG_WAVES), 0, st, wa);
   RedArgs re;
   re.d = d, re.grad = grad, re.stats = stats, re.P = (long long)ppo_params(d.obs_dim);
-  re.nsplit = nsplit, re.rt = rt, re.B = b.B, re.vf_coef = b.vf_coef, re.ent_coef = b.ent_coef;
+  re.nsplit = nsplit, re.rt = rt, re.B = B, re.clone = clone, re.vf_coef = vf_coef, re.ent_coef = ent_coef;
   hipLaunchKernelGGL(k8_reduce, dim3((unsigned)((re.P + 255) / 256) + 1), dim3(256), 0, st, re);
+}
+
+void auv_launch_ppo_grad(const AuvPpoDev& d, const auv_ppo_batch_t& b, float* grad, float* stats, hipStream_t st) {
+  RowArgs<auv_ppo_batch_t> ra;
+  ra.d = d, ra.b = b;
+  hipLaunchKernelGGL(k8_rows, dim3((b.B + 15) / 16, 2), dim3(POL_THREADS), auv_ppo_lds_bytes(d.obs_dim), st, ra);
+  ppo_launch_after_rows(d, b.B, false, b.vf_coef, b.ent_coef, grad, stats, st);
+}
+
+void auv_launch_ppo_grad_clone(const AuvPpoDev& d, const auv_ppo_clone_batch_t& b, float* grad, float* stats, hipStream_t st) {
+  RowArgs<auv_ppo_clone_batch_t> ra;
+  ra.d = d, ra.b = b;
+  hipLaunchKernelGGL(k8_clone, dim3((b.B + 15) / 16, 2), dim3(POL_THREADS), auv_ppo_lds_bytes(d.obs_dim), st, ra);
+  ppo_launch_after_rows(d, b.B, true, b.vf_coef, b.ent_coef, grad, stats, st);
 }
 
 void auv_launch_ppo_adam(const AuvPpoDev& d, float* theta, float* m, float* v, const float* grad, const AuvPpoAdamDev& h, float* norms_out,

@@ -260,3 +260,70 @@ class ShootingPlanner:
 
     def close(self):
         self.sim.close()
+
+
+class DistillBuffer:
+    """A ring of supervised targets on the device: O [capacity, obs_dim], A [capacity, 2] (target actions in the POLICY's own space),
+    RET [capacity] (value targets), W [capacity] (row weights) -- the stored rows FusedPPOUpdate.clone_step gathers from.
+
+        buf = DistillBuffer(65536, env.obs_dim, env.device)
+        a, _, predicted = planner.plan()
+        buf.add(env.obs, *DistillBuffer.targets_from_plan(planner, a, predicted))
+        upd.clone_step(buf.O, buf.A, buf.RET, buf.W, buf.sample(256, gen))
+
+    add() writes with index_copy_ at positions that follow from the batch's size alone: nothing synchronises with the host."""
+
+    def __init__(self, capacity: int, obs_dim: int, device):
+        if int(capacity) < 1 or int(obs_dim) < 1:
+            raise ValueError("DistillBuffer: capacity and obs_dim must be >= 1")
+        self.capacity, self.obs_dim, self.device = int(capacity), int(obs_dim), torch.device(device)
+        z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)   # noqa: E731
+        self.O, self.A, self.RET, self.W = z(self.capacity, self.obs_dim), z(self.capacity, 2), z(self.capacity), z(self.capacity)
+        self.head = 0                                             # the next row to write
+        self.size = 0                                             # filled rows: 0 .. capacity
+
+    def add(self, obs: torch.Tensor, actions: torch.Tensor, ret: torch.Tensor, w: Optional[torch.Tensor] = None):
+        """Append n rows (the oldest are overwritten once the ring is full; of a batch longer than the ring the last `capacity` rows
+        stay).  obs [n, obs_dim], actions [n, 2], ret [n], w [n] or None (all one)."""
+        n = int(obs.shape[0])
+        if tuple(obs.shape) != (n, self.obs_dim) or tuple(actions.shape) != (n, 2) or tuple(ret.shape) != (n,) \
+                or (w is not None and tuple(w.shape) != (n,)):
+            raise ValueError("DistillBuffer.add: expected obs [n, %d], actions [n, 2], ret [n] and w [n] or None" % self.obs_dim)
+        if n == 0:
+            return
+        if w is None:
+            w = torch.ones((n,), dtype=torch.float32, device=self.device)
+        cols = [x.detach().to(device=self.device, dtype=torch.float32) for x in (obs, actions, ret, w)]
+        if n > self.capacity:
+            self.head = (self.head + n - self.capacity) % self.capacity
+            cols, n = [x[-self.capacity:] for x in cols], self.capacity
+        pos = (torch.arange(n, dtype=torch.int64, device=self.device) + self.head) % self.capacity
+        for dst, src in zip((self.O, self.A, self.RET, self.W), cols):
+            dst.index_copy_(0, pos, src)
+        self.head = (self.head + n) % self.capacity
+        self.size = min(self.capacity, self.size + n)
+
+    def sample(self, B: int, generator: Optional[torch.Generator] = None) -> torch.Tensor:
+        """[B] int64 on the device: rows drawn uniformly, with replacement, from the filled part."""
+        if self.size < 1:
+            raise ValueError("DistillBuffer.sample: the buffer is empty")
+        return torch.randint(0, self.size, (int(B),), generator=generator, device=self.device, dtype=torch.int64)
+
+    @staticmethod
+    def targets_from_plan(planner, first_actions: torch.Tensor, predicted: torch.Tensor):
+        """A plan's outputs as the policy's targets: (mu* [B, 2], ret [B]).  The planner decides in ENVIRONMENT actions; the policy's
+        mean reaches the environment through the prior's affine map action = mid + half * clip(mu), so mu* = (a - mid) / half.  The
+        predicted scores are in the planner's reward units, value * value_scale + value_shift: ret = (predicted - shift) / scale."""
+        prior = planner.prior
+        mid, half = (0.0, 0.0), (1.0, 1.0)
+        if prior is not None and getattr(prior, "action_map", None) is not None:
+            mid, half = prior.action_map[0], prior.action_map[1]
+        if any(float(h) == 0.0 for h in half):
+            raise ValueError("DistillBuffer.targets_from_plan: the action map's half-range %s has a zero: it cannot be inverted" % (tuple(half),))
+        if planner.value_scale == 0.0:
+            raise ValueError("DistillBuffer.targets_from_plan: value_scale is 0: the scores cannot be mapped back")
+        mid_t = torch.as_tensor(mid, dtype=first_actions.dtype, device=first_actions.device)
+        half_t = torch.as_tensor(half, dtype=first_actions.dtype, device=first_actions.device)
+        mu = (first_actions - mid_t) / half_t
+        ret = predicted if planner.value_scale == 1.0 and planner.value_shift == 0.0 else (predicted - planner.value_shift) / planner.value_scale
+        return mu.contiguous(), ret.contiguous()

@@ -14,10 +14,18 @@ weight into the packed buffer of an attached FusedActorCritic (so `refresh()` is
     g, stats = upd.grad(O, A, LP, ADV, RET, idx)   # or in two halves, e.g. around an all-reduce of g
     upd.apply(g)
 
+The same updater also takes supervised steps (k8_clone: the same row pass with another head): the policy towards target actions, the
+value net towards target values -- a planner's decisions (planning.DistillBuffer), an autopilot's, a warm start for PPO:
+
+    stats = upd.clone_step(O, A, RET, W, idx, kind="nll")   # [10]: loss, bc, vf, max |a - mu|, sum of weights, non-finite inputs, 0, 0,
+                                                            #       |g_pi|, |g_v|;  kind "mse": squared error of the mean instead
+    g, stats = upd.clone_grad(O, A, RET)                    # the two halves, as above
+
 The module's parameters become views of ONE flat tensor (`upd.theta`, torch layout: pi W1 b1 .. W4 b4, v W1 .. b4, log_std); the torch
 modules stay usable and stay the owners -- `net.v(obs)` sees every step.  Deterministic: the same inputs give the same bits.
 """
 import ctypes as C
+import math
 from typing import Optional, Tuple
 
 import torch
@@ -26,12 +34,35 @@ import torch.nn as nn
 from . import _capi
 
 HIDDEN = (256, 128, 64)
+CLONE_KINDS = {"nll": 0, "mse": 1}
 _LIB = _capi.load_library()
 
 
 def _check(rc: int, what: str):
     if rc != 0:
         raise RuntimeError("%s failed (%d): %s" % (what, rc, _LIB.auv_last_error().decode()))
+
+
+def clone_loss_terms(net, o, a, ret, w=None, kind="nll", vf_coef=0.5, ent_coef=0.0):
+    """The loss of auv_ppo_grad_clone in stock tensor operations, on any device and dtype: (loss, bc, vf).  `net`: pi, v, log_std as
+    examples/ppo.ActorCritic holds them; o [B, D], a [B, 2] target actions in the policy's own space, ret [B], w [B] >= 0 or None.
+        nll: bc = mean_i w_i sum_k (0.5 z_ik^2 + log_std_k + log sqrt(2 pi)), z = (a - mu) / exp(log_std);  mse: mean_i w_i sum_k 0.5 (a - mu)^2
+        vf = mean_i w_i 0.5 (v_i - ret_i)^2;  loss = bc + vf_coef vf - ent_coef sum_k (0.5 + log sqrt(2 pi) + log_std_k)
+    The means are over all B rows, whatever their weights."""
+    if kind not in CLONE_KINDS:
+        raise ValueError("kind must be one of %s, got %r" % (sorted(CLONE_KINDS), kind))
+    w = torch.ones_like(ret) if w is None else w
+    mu, log_std = net.pi(o), net.log_std
+    c = 0.5 * math.log(2.0 * math.pi)
+    if kind == "nll":
+        z = (a - mu) / log_std.exp()
+        per_row = (0.5 * z * z + log_std + c).sum(-1)
+    else:
+        per_row = (0.5 * (a - mu) ** 2).sum(-1)
+    bc = (w * per_row).mean()
+    vf = (w * 0.5 * (net.v(o).squeeze(-1) - ret) ** 2).mean()
+    loss = bc + vf_coef * vf - ent_coef * (0.5 + c + log_std).sum()
+    return loss, bc, vf
 
 
 class FusedPPOUpdate:
@@ -115,11 +146,11 @@ class FusedPPOUpdate:
     def _row(self):
         return self.log[self.n_steps % self.LOG_ROWS]
 
-    def grad(self, O, A, LP, ADV, RET, idx: Optional[torch.Tensor] = None, B: Optional[int] = None):
-        """The flat gradient of minibatch_step's loss over rows `idx` (int64; None: rows 0 .. B - 1, B default: all rows) of the stored
-        transitions, and the statistics row.  Returns (grad, stats): the updater's own buffers, overwritten by the next call."""
-        n_rows = int(O.shape[0])
-        for x, shape in ((O, (n_rows, self.obs_dim)), (A, (n_rows, 2)), (LP, (n_rows,)), (ADV, (n_rows,)), (RET, (n_rows,))):
+    def _rows(self, tensors, idx, B):
+        """The argument checks of grad() and clone_grad(): `tensors` = (tensor, trailing shape) per stored column.  Returns (n_rows, B)."""
+        n_rows = int(tensors[0][0].shape[0])
+        for x, tail in tensors:
+            shape = (n_rows,) + tail
             if tuple(x.shape) != shape or x.dtype != torch.float32 or not x.is_contiguous() or x.device != self.device:
                 raise ValueError("FusedPPOUpdate: expected a contiguous float32 tensor of shape %s on %s, got %s %s"
                                  % (shape, self.device, tuple(x.shape), x.dtype))
@@ -129,6 +160,12 @@ class FusedPPOUpdate:
             B = int(idx.numel())
         elif B is None:
             B = n_rows
+        return n_rows, int(B)
+
+    def grad(self, O, A, LP, ADV, RET, idx: Optional[torch.Tensor] = None, B: Optional[int] = None):
+        """The flat gradient of minibatch_step's loss over rows `idx` (int64; None: rows 0 .. B - 1, B default: all rows) of the stored
+        transitions, and the statistics row.  Returns (grad, stats): the updater's own buffers, overwritten by the next call."""
+        n_rows, B = self._rows(((O, (self.obs_dim,)), (A, (2,)), (LP, ()), (ADV, ()), (RET, ())), idx, B)
         b = _capi.AuvPpoBatch(O.data_ptr(), A.data_ptr(), LP.data_ptr(), ADV.data_ptr(), RET.data_ptr(),
                               idx.data_ptr() if idx is not None else None, int(B), n_rows, self.clip, self.vf_coef, self.ent_coef)
         row = self._row()
@@ -153,5 +190,31 @@ class FusedPPOUpdate:
         """grad then apply on the current stream.  Returns the step's record [10] (see the module's docstring)."""
         row = self._row()
         self.grad(O, A, LP, ADV, RET, idx)
+        self.apply()
+        return row
+
+    def clone_grad(self, O, A, RET, W: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None, B: Optional[int] = None,
+                   kind: str = "nll", vf_coef: Optional[float] = None, ent_coef: Optional[float] = None):
+        """The flat gradient of clone_loss_terms over rows `idx` of the stored rows (as grad(): int64; None: rows 0 .. B - 1, B default:
+        all rows), and the statistics row: loss, bc, vf, max |a - mu| over rows of weight > 0, the sum of the weights, non-finite
+        inputs, 0, 0.  A: target actions in the policy's own space; W: row weights >= 0 (None: all one); vf_coef / ent_coef default to the
+        updater's.  Returns (grad, stats): the updater's own buffers, overwritten by the next call."""
+        if kind not in CLONE_KINDS:
+            raise ValueError("FusedPPOUpdate.clone_grad: kind must be one of %s, got %r" % (sorted(CLONE_KINDS), kind))
+        cols = ((O, (self.obs_dim,)), (A, (2,)), (RET, ())) + (((W, ()),) if W is not None else ())
+        n_rows, B = self._rows(cols, idx, B)
+        b = _capi.AuvPpoCloneBatch(O.data_ptr(), A.data_ptr(), RET.data_ptr(), W.data_ptr() if W is not None else None,
+                                   idx.data_ptr() if idx is not None else None, B, n_rows, CLONE_KINDS[kind],
+                                   self.vf_coef if vf_coef is None else float(vf_coef), self.ent_coef if ent_coef is None else float(ent_coef))
+        row = self._row()
+        _check(_LIB.auv_ppo_grad_clone(self._h, C.byref(b), C.c_void_p(self.g.data_ptr()), C.c_void_p(row.data_ptr()), self._stream()),
+               "auv_ppo_grad_clone")
+        return self.g, row[:8]
+
+    def clone_step(self, O, A, RET, W: Optional[torch.Tensor] = None, idx: Optional[torch.Tensor] = None, B: Optional[int] = None,
+                   kind: str = "nll", vf_coef: Optional[float] = None, ent_coef: Optional[float] = None):
+        """clone_grad then apply on the current stream.  Returns the step's record [10]: clone_grad's statistics and the two norms."""
+        row = self._row()
+        self.clone_grad(O, A, RET, W, idx, B, kind, vf_coef, ent_coef)
         self.apply()
         return row

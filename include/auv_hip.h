@@ -882,6 +882,31 @@ int auv_ppo_grad(auv_ppo_t* p, const auv_ppo_batch_t* batch, float* grad, float*
 int auv_ppo_adam(auv_ppo_t* p, float* theta, float* m, float* v, const float* grad, const auv_ppo_adam_t* adam, float* norms_out,
                  void* stream);
 
+/* ---- the supervised (clone) row pass of the same updater: the policy trained towards given target actions, the value net towards
+ * given targets -- distilling a planner's decisions (gym_auv_amd/planning.py, DistillBuffer), cloning an autopilot, warm-starting PPO.
+ *   auv_ppo_grad_clone   auv_ppo_grad's contract (flat torch-layout gradient over the B rows idx[0 .. B) of n_rows stored rows,
+ *                    indices unchecked, everything enqueued on `stream`, deterministic) with another head.  With w_i the row's weight
+ *                    (1 without W), sigma_k = exp(log_std_k), z_ik = (a_ik - mu_ik) / sigma_k:
+ *                      kind 0   bc = (1/B) sum_i w_i sum_k (0.5 z_ik^2 + log_std_k + log sqrt(2 pi))      the Gaussian NLL of A
+ *                      kind 1   bc = (1/B) sum_i w_i sum_k 0.5 (a_ik - mu_ik)^2                            log_std gets no bc gradient
+ *                      vf = (1/B) sum_i w_i 0.5 (v_i - ret_i)^2;  loss = bc + vf_coef vf - ent_coef sum_k (0.5 + log sqrt(2 pi) + log_std_k)
+ *                    A is in the policy's own space: the mean BEFORE the affine action map and its clip.  A row of weight 0 adds
+ *                    exactly nothing.  stats[8]: loss, bc, vf, max |a - mu| over the rows of weight > 0, the sum of the weights, the
+ *                    number of non-finite values among the gathered rows of O, A, RET and W, 0, 0.
+ *                    AUV_EINVAL: B < 1, B > max_batch, a kind other than 0 / 1, a null O, A or RET.
+ * auv_ppo_adam applies the gradient as it applies auv_ppo_grad's: the packed copies and the attached policy buffer follow every
+ * clone step too, and clone and PPO steps may alternate on one updater.                                                          */
+typedef struct auv_ppo_clone_batch {
+  const float* O;            /* [n_rows][obs_dim]                                                            */
+  const float* A;            /* [n_rows][2]  target actions, in the policy's own (pre-action-map) space      */
+  const float* RET;          /* [n_rows]     value targets                                                   */
+  const float* W;            /* [n_rows]     row weights >= 0; NULL: all one                                 */
+  const int64_t* idx;        /* [B]; NULL: rows 0 .. B - 1                                                   */
+  int32_t B, n_rows, kind;   /* kind 0: Gaussian NLL, 1: MSE on the mean                                     */
+  float vf_coef, ent_coef;
+} auv_ppo_clone_batch_t;
+int auv_ppo_grad_clone(auv_ppo_t* p, const auv_ppo_clone_batch_t* batch, float* grad, float* stats, void* stream);
+
 /* ---- rendering: rgb_array frames of B environments, drawn on the device (BaseEnvironment.render, environment.py:410-437; the
  * reference draws ONE environment on the host with pygame: a vessel-centred top view, render2d/renderer.py:62-120) -------------
  * frames_dev [B][H][W][3] uint8 <- a top view of environment env_idx_host[j] (any environments, repeats allowed), centred on
