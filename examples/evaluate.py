@@ -7,6 +7,7 @@ are auto-reset into the next world of the bank, and the episode log says how the
     python examples/evaluate.py --envs 256 --episodes 4                    # a freshly initialised policy
     python examples/evaluate.py --ckpt policy.pt --task pathfollow          # a state_dict of examples/ppo.py's ActorCritic
     python examples/evaluate.py --envs 64 --frames out/                     # and pictures of the first 16 environments
+    python examples/evaluate.py --ckpt policy.pt --frame-stack 4            # a policy trained with examples/ppo.py --frames 4
 """
 import argparse
 import json
@@ -57,7 +58,10 @@ def evaluate(env, fused, episodes, max_steps=100000, frames_dir=None):
     count = torch.zeros(env.n_envs, dtype=torch.int64, device=env.device)
     while steps < max_steps:
         for _ in range(50):                                # one read-back every 50 steps
-            fused.predict()                                # -> fused.actions
+            if fused.frames > 1:                           # frame stacking: the history moves on with every step (FrameStack.push)
+                fused.predict(fused.stack.push(env.obs, env.done))
+            else:
+                fused.predict()                            # -> fused.actions
             env.step(fused.actions)
         steps += 50
         if frames_dir:
@@ -93,6 +97,8 @@ def main():
     ap.add_argument("--max-steps", type=int, default=100000, help="stop after this many steps even if episodes are still open")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--frames", default=None, metavar="DIR", help="write frames of the first 16 environments every 50 steps: .npy stacks and .ppm pictures")
+    ap.add_argument("--frame-stack", type=int, default=1, metavar="K",
+                    help="the policy sees the last K observations as one row (examples/ppo.py --frames K; here --frames is the picture directory)")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     colav = a.task == "colav"
@@ -105,12 +111,12 @@ def main():
         warnings.simplefilter("ignore")
         env = BatchedAuvEnv(cfg, bank, a.envs, device=a.device, rewarder="colav" if colav else "pathfollow", auto_reset=True)
     env.reset()
-    net = load_policy(a.ckpt, env.obs_dim, a.device, a.seed)
+    net = load_policy(a.ckpt, a.frame_stack * env.obs_dim, a.device, a.seed)
     kw = {}
     if a.act_space == "normalized":                        # the policy speaks [-1, 1]^2; the map stretches it onto the action space
         lo, hi = env.action_space.low, env.action_space.high
         kw = dict(act_mid=((lo + hi) / 2).tolist(), act_half=((hi - lo) / 2).tolist(), clip_lo=[-1.0, -1.0], clip_hi=[1.0, 1.0])
-    fused = FusedActorCritic(net, env, rollout=1, **kw)
+    fused = FusedActorCritic(net, env, rollout=1, frames=a.frame_stack, **kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if a.frames:

@@ -152,7 +152,7 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
           task="colav", step_mode=None, graph_rollout=False, sub_batches=4, minibatches=32,
           reward_scale=0.01, reward_clip=0.0, min_cumulative_reward=None, act_space="raw", ret_norm=False, orthogonal=False, ent_coef=0.01, log_std=-0.5, lr=2e-4,
           fused_policy=True, graph_update=False, policy_bf16=False, feasibility_pooling=False, fused_update=False,
-          fused_bootstrap=False):
+          fused_bootstrap=False, frames=1):
     from gym_auv_amd import distributed as D
     from gym_auv_amd.batched_env import BatchedAuvEnv
     from gym_auv_amd.config import effective_reference_config
@@ -195,7 +195,12 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
     else:                             # raw units, clipped to the action space (what stable-baselines does with a Box)
         a_mid, a_half = torch.zeros_like(low), torch.ones_like(high)
         c_lo, c_hi = low, high
-    net = ActorCritic(env.obs_dim, log_std=log_std, orthogonal=orthogonal).to(device)
+    # --frames k: the policy sees the last k observations of an environment as one row (gym_auv_amd/framestack.py; what stable-baselines
+    # ships as VecFrameStack): the nets are k * obs_dim wide, the fused policy launch forms the rows, everything behind it is unchanged
+    frames = int(frames)
+    if frames > 1 and not fused_policy:
+        raise ValueError("--frames %d needs --fused-policy 1: the stacked rows are formed by the fused policy launch" % frames)
+    net = ActorCritic(frames * env.obs_dim, log_std=log_std, orthogonal=orthogonal).to(device)
     params = list(net.parameters())
     pi_params, v_params = list(net.pi.parameters()) + [net.log_std], list(net.v.parameters())
     if world > 1:   # data parallel over GPUs: same initial weights, gradients averaged over RCCL
@@ -213,7 +218,7 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
     upd_graph, upd_in, upd_loss = None, None, None
     gamma, lam, clip, epochs, n_mb = 0.999, 0.98, 0.2, 4, int(minibatches)
     ret_mean, ret_std = torch.zeros((), device=device), torch.ones((), device=device)
-    T, Dobs = int(rollout), env.obs_dim
+    T, Dobs = int(rollout), frames * env.obs_dim
     env.reset()
     act_buf = torch.zeros((envs, 2), device=device)
     # per-chain rollout storage, written inside the chain's step at a device-side position
@@ -254,7 +259,7 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
         from gym_auv_amd.policy import FusedActorCritic
         fused = FusedActorCritic(net, env, rollout=T, reward_scale=reward_scale, reward_clip=reward_clip, act_mid=a_mid.tolist(),
                                  act_half=a_half.tolist(), clip_lo=c_lo.tolist(), clip_hi=c_hi.tolist(), seed=1000 * seed + rank,
-                                 bf16=policy_bf16)
+                                 bf16=policy_bf16, frames=frames)
         graph_rollout = False
     graphs = None
     if graph_rollout:
@@ -295,6 +300,8 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
             # fresh scenarios for every environment, built on the device; all envs restart
             env.generate(GeneratedWorlds(2 * envs, nm, ns, seed=1000 * seed + rank + 7919 * upd))
             env.reset()
+            if fused is not None:
+                fused.reset_frames()
         t0 = time.time()
         cur = torch.cuda.current_stream(device)
         if fused is not None:
@@ -336,7 +343,7 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
                 V = torch.cat([b["V"] for b in buf], 1) * ret_std + ret_mean        # value head predicts normalised returns
                 R = torch.cat([b["R"] for b in buf], 1)
                 Dn = torch.cat([b["Dn"] for b in buf], 1)
-            if fused_bootstrap and fused is not None:
+            if (fused_bootstrap or frames > 1) and fused is not None:      # (frames > 1: the bootstrap row is a stacked row, peeked)
                 # the bootstrap value through the fused critic (one launch, FusedActorCritic.value): the weights the rollout used
                 last_v = fused.value() * ret_std + ret_mean
             else:
@@ -553,6 +560,8 @@ if __name__ == "__main__":
     ap.add_argument("--fused-bootstrap", type=int, default=0, choices=[0, 1],
                     help="1: the GAE bootstrap value of the last observation comes from the fused critic (FusedActorCritic.value, one launch); "
                          "0 (default): the torch module")
+    ap.add_argument("--frames", type=int, default=1,
+                    help="k > 1: the policy sees the last k observations as one row of k * obs_dim columns (frame stacking; needs --fused-policy 1)")
     ap.add_argument("--step-mode", default=None, help="launch shape of a step (BatchedAuvEnv.STEP_MODES); default: the library's")
     ap.add_argument("--act-space", default="raw", choices=["raw", "normalized"])
     ap.add_argument("--ret-norm", type=int, default=0)
@@ -571,4 +580,4 @@ if __name__ == "__main__":
           sub_batches=a.sub_batches, minibatches=a.minibatches, act_space=a.act_space, ret_norm=bool(a.ret_norm),
           orthogonal=bool(a.orthogonal), ent_coef=a.ent_coef, log_std=a.log_std, lr=a.lr, reward_clip=a.reward_clip,
           min_cumulative_reward=a.min_cumulative_reward, feasibility_pooling=bool(a.feasibility_pooling), fused_update=bool(a.fused_update),
-          fused_bootstrap=bool(a.fused_bootstrap))
+          fused_bootstrap=bool(a.fused_bootstrap), frames=a.frames)

@@ -144,6 +144,14 @@ class AuvPolicyIO(C.Structure):
     ]
 
 
+class AuvPolicyStack(C.Structure):
+    """== auv_policy_stack_t (include/auv_hip.h): a policy launch on frame-stacked rows (auv_policy_act_stacked / _rollout_stacked)"""
+    _fields_ = [("io", AuvPolicyIO), ("hist", C.c_void_p), ("stk", C.c_void_p), ("frames", C.c_int32), ("reserved", C.c_int32)]
+
+
+MAX_FRAMES = 8
+
+
 class AuvPolicyEval(C.Structure):
     """== auv_policy_eval_t (include/auv_hip.h): one evaluation of M observation rows (auv_policy_eval)"""
     _fields_ = [
@@ -239,6 +247,10 @@ def load_library(path: str = None) -> C.CDLL:
         "auv_gae": (C.c_int, [vp, vp, vp, vp, vp, C.c_float, C.c_float, vp, vp, i32, i32, vp]),
         "auv_policy_rollout": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(AuvPolicyIO), vp, vp, vp, i32, i32,
                                          C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "auv_policy_act_stacked": (C.c_int, [vp, i32, i32, C.POINTER(AuvPolicyStack), vp]),
+        "auv_policy_rollout_stacked": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(AuvPolicyStack), vp, vp, vp, i32, i32,
+                                                 C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "auv_stack_frames": (C.c_int, [i32, vp, vp, vp, vp, vp, C.c_int64, i32, i32, i32, i32, i32, vp]),
         "auv_step_pipelined_timed": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), vp, i32, vp, vp, vp, C.POINTER(C.c_float)]),
         "auv_streams_overlap": (C.c_int, [vp, vp, vp, C.POINTER(C.c_float)]),
         "auv_episode_log": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
@@ -319,6 +331,7 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_fresh_worlds_create", "auv_fresh_worlds_refill", "auv_fresh_worlds_stats", "auv_fresh_worlds_draws", "auv_fresh_worlds_set_stream", "auv_fresh_worlds_multi",
                     "auv_snapshot_row_bytes", "auv_snapshot_layout", "auv_snapshot", "auv_restore", "auv_snapshot_skipped", "auv_plan_score",
                     "auv_plan_score_v", "auv_policy_eval",
+                    "auv_policy_act_stacked", "auv_policy_rollout_stacked", "auv_stack_frames",
                     "auv_population_member_floats", "auv_population_act", "auv_population_rollout", "auv_population_perturb", "auv_population_update",
                     "auv_ppo_param_floats", "auv_ppo_create", "auv_ppo_destroy", "auv_ppo_load", "auv_ppo_attach_policy", "auv_ppo_grad", "auv_ppo_adam",
                     "auv_ppo_grad_clone",

@@ -77,6 +77,12 @@ void auv_launch_plan_score_v(const float* reward, const uint8_t* done, const flo
 size_t auv_population_member_floats_impl(int obs_dim);
 hipError_t auv_population_prepare(int obs_dim);
 void auv_launch_population_act(const auv_population_io_t& io, hipStream_t st);
+// k12_policy_stacked.hip
+size_t auv_policy_stacked_lds_bytes(int width);
+hipError_t auv_policy_stacked_prepare(int width);
+void auv_launch_policy_stacked(const auv_policy_stack_t& s, int e0, int ne, hipStream_t st, long long t_host = -1, long long gstep_host = -1);
+void auv_launch_stack_frames(const float* obs, const uint8_t* done, float* hist, int32_t* stk, float* out, long long ldx, int e0, int ne,
+                             int obs_dim, int frames, int advance, hipStream_t st);
 void auv_launch_population_perturb(const float* theta, float* members, long long stride, int P, int obs_dim, float sigma, unsigned long long seed,
                                    unsigned long long generation, hipStream_t st);
 void auv_launch_population_update(float* theta, const float* w, float* grad, int P, int obs_dim, float sigma, float lr, unsigned long long seed,
@@ -2283,6 +2289,87 @@ int auv_policy_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds,
     for (int i = 0; i < n_slices; i++)
       auv_launch_policy(ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], t0 ? t0[i] + n_steps : -1,
                         t0 ? gstep0[i] + n_steps : -1);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+// ---- frame-stacked observations in the policy launch (include/auv_hip.h, auv_policy_stack; kernels: k12_policy_stacked.hip) ----
+static int check_policy_stack(const auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* s, const char* who) {
+  if (!s) return fail(AUV_EINVAL, "%s: null io", who);
+  if (s->frames < 1 || s->frames > AUV_MAX_FRAMES) return fail(AUV_EINVAL, "%s: frames = %d outside [1, %d]", who, s->frames, AUV_MAX_FRAMES);
+  int rc = check_policy_io(h, e0, ne, &s->io, who);
+  if (rc) return rc;
+  if (s->io.params_bf16) return fail(AUV_EINVAL, "%s: stacked rows are evaluated in exact f32 only (params_bf16 must be NULL)", who);
+  const int64_t width = (int64_t)s->frames * s->io.obs_dim;
+  if (width > 16384 || auv_policy_stacked_lds_bytes((int)width) > 160 * 1024)
+    return fail(AUV_EINVAL, "%s: %d frames of %d columns are too wide for the policy kernel's LDS tile", who, s->frames, s->io.obs_dim);
+  if (s->frames > 1) {
+    if (!s->hist || !s->stk) return fail(AUV_EINVAL, "%s: null hist or stk", who);
+    if (((uintptr_t)s->hist & 15) || ((uintptr_t)s->stk & 7)) return fail(AUV_EINVAL, "%s: hist must be 16-byte, stk 8-byte aligned", who);
+  }
+  return AUV_OK;
+}
+
+int auv_policy_act_stacked(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* io, void* stream) {
+  REQUIRE_READY(h);
+  int rc = check_policy_stack(h, e0, ne, io, "auv_policy_act_stacked");
+  if (rc) return rc;
+  HIP_TRY(auv_policy_stacked_prepare(io->frames * io->io.obs_dim));
+  auv_launch_policy_stacked(*io, e0, ne, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+// auv_policy_rollout's loop with the stacked launch: the same t0 / gstep0 contract, the same slices on their own streams
+int auv_policy_rollout_stacked(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_stack_t* ios,
+                               float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
+                               const int64_t* gstep0) {
+  REQUIRE_READY(h);
+  int rc = check_slices(h, n_slices, bounds, streams, "auv_policy_rollout_stacked");
+  if (rc) return rc;
+  if (!ios || n_steps < 0 || (!t0) != (!gstep0)) return fail(AUV_EINVAL, "auv_policy_rollout_stacked: bad arguments");
+  for (int i = 0; i < n_slices; i++) {
+    rc = check_policy_stack(h, bounds[i], bounds[i + 1] - bounds[i], ios + i, "auv_policy_rollout_stacked");
+    if (rc) return rc;
+    rc = check_actions(ios[i].io.actions_out, AUV_F32, "auv_policy_rollout_stacked");
+    if (rc) return rc;
+    if (ios[i].frames != ios[0].frames) return fail(AUV_EINVAL, "auv_policy_rollout_stacked: slice %d has %d frames, slice 0 has %d", i, ios[i].frames, ios[0].frames);
+    if (t0 && (t0[i] < 0 || gstep0[i] < 0)) return fail(AUV_EINVAL, "auv_policy_rollout_stacked: negative counter for slice %d", i);
+  }
+  PAIR_CHECK(h, obs_dev);
+  HIP_TRY(auv_policy_stacked_prepare(ios[0].frames * ios[0].io.obs_dim));
+  for (int32_t k = 0; k < n_steps; k++) {
+    if (rc == AUV_OK) rc = fw_tick(h, n_slices, bounds, streams);
+    for (int i = 0; i < n_slices && rc == AUV_OK; i++) {
+      const int ne = bounds[i + 1] - bounds[i];
+      auv_launch_policy_stacked(ios[i], bounds[i], ne, (hipStream_t)streams[i], t0 ? t0[i] + k : -1, t0 ? gstep0[i] + k : -1);
+      rc = enqueue_step(h, effective_mode(h, ne), bounds[i], ne, ios[i].io.actions_out, AUV_F32, obs_dev, reward_dev, done_dev,
+                        (hipStream_t)streams[i], false);
+    }
+  }
+  if (rc) return rc;
+  if (flush)
+    for (int i = 0; i < n_slices; i++)
+      auv_launch_policy_stacked(ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], t0 ? t0[i] + n_steps : -1,
+                                t0 ? gstep0[i] + n_steps : -1);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+int auv_stack_frames(int32_t device, const float* obs, const uint8_t* done, float* hist, int32_t* stk, float* out, int64_t ldx, int32_t e0,
+                     int32_t ne, int32_t obs_dim, int32_t frames, int32_t advance, void* stream) {
+  if (device < 0) return fail(AUV_EINVAL, "auv_stack_frames: device %d", device);
+  if (obs_dim < 1 || obs_dim > 16384) return fail(AUV_EINVAL, "auv_stack_frames: obs_dim %d outside [1, 16384]", obs_dim);
+  if (frames < 1 || frames > AUV_MAX_FRAMES) return fail(AUV_EINVAL, "auv_stack_frames: frames = %d outside [1, %d]", frames, AUV_MAX_FRAMES);
+  if (e0 < 0 || ne < 0 || (int64_t)e0 + ne > INT32_MAX) return fail(AUV_EINVAL, "auv_stack_frames: rows [%d, %d + %d)", e0, e0, ne);
+  if (!obs || !out) return fail(AUV_EINVAL, "auv_stack_frames: null %s", !obs ? "obs" : "out");
+  if (ldx < (int64_t)frames * obs_dim) return fail(AUV_EINVAL, "auv_stack_frames: ldx %lld < frames * obs_dim = %d", (long long)ldx, frames * obs_dim);
+  if (frames > 1 && (!hist || !stk)) return fail(AUV_EINVAL, "auv_stack_frames: null hist or stk");
+  if (((uintptr_t)obs & 3) || ((uintptr_t)out & 3) || ((uintptr_t)hist & 3) || ((uintptr_t)stk & 7))
+    return fail(AUV_EINVAL, "auv_stack_frames: obs, out and hist must be 4-byte, stk 8-byte aligned");
+  if (ne == 0) return AUV_OK;
+  HIP_TRY(hipSetDevice(device));
+  auv_launch_stack_frames(obs, done, hist, stk, out, ldx, e0, ne, obs_dim, frames, advance != 0, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }

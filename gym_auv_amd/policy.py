@@ -13,6 +13,13 @@ and value into the rollout buffers; reward / done of the previous step are store
     fused.begin_rollout()                          # t = 0 on every chain
     fused.rollout(T)                               # T steps of every sub-batch chain, policy + env.step, one C call
     O, A, LP, V, R, Dn = fused.buffers()           # [T, N, ...] views for the update
+
+Frame stacking (what stable-baselines ships as VecFrameStack; csrc/k12_policy_stacked.hip): `FusedActorCritic(net, env, T, frames=k)` with a
+net whose first layers take k * obs_dim columns evaluates every environment on its last k observations, NEWEST FIRST (columns [j * obs_dim,
+(j + 1) * obs_dim) = the observation of j steps ago; a column permutation of stable-baselines' newest-last order), zeros where the episode
+is younger than j steps.  The history lives on the device (`fused.stack`: gym_auv_amd/framestack.py) and is moved on by the policy launch
+itself; O is then [T, N, k * obs_dim] and everything behind the first layer -- FusedPPOUpdate, policy_eval, the planner -- takes those rows
+as they are.  Call `fused.reset_frames()` behind an `env.reset()`.
 """
 import ctypes as C
 from typing import Dict, List, Optional, Sequence
@@ -175,20 +182,30 @@ def policy_eval(params: torch.Tensor, obs_dim: int, X: torch.Tensor, idx: Option
 class FusedActorCritic:
     def __init__(self, net: nn.Module, env: BatchedAuvEnv, rollout: int, reward_scale: float = 1.0, reward_clip: float = 0.0,
                  act_mid=None, act_half=None, clip_lo=None, clip_hi=None, seed: int = 0, store_obs: bool = True, debug: bool = False,
-                 bf16: bool = False):
+                 bf16: bool = False, frames: int = 1):
         self.net, self.env, self.T = net, env, int(rollout)
         self.device = env.device
+        # frames > 1: every environment is evaluated on its last `frames` observations (module docstring); 1: the plain launch
+        self.frames = int(frames)
+        if self.frames < 1 or self.frames > _capi.MAX_FRAMES:
+            raise ValueError("FusedActorCritic: frames = %d outside [1, %d]" % (self.frames, _capi.MAX_FRAMES))
+        if self.frames > 1 and bf16:
+            raise ValueError("FusedActorCritic: frames = %d with bf16 = True -- stacked rows are evaluated in exact f32 only" % self.frames)
+        self.in_dim = self.frames * env.obs_dim                                        # the nets' input width
         self._lin = []
         for seq, out in ((net.pi, 2), (net.v, 1)):
             lin = [m for m in seq if isinstance(m, nn.Linear)]
             act = [m for m in seq if not isinstance(m, nn.Linear)]
             dims = tuple(l.out_features for l in lin[:-1])
-            if dims != HIDDEN or lin[-1].out_features != out or lin[0].in_features != env.obs_dim or not all(isinstance(a, nn.Tanh) for a in act):
+            if lin and lin[0].in_features != self.in_dim:                              # the width, with both numbers (one frame or several)
+                raise ValueError("FusedActorCritic: frames = %d of %d columns need a first Linear with in_features == %d, got %d"
+                                 % (self.frames, env.obs_dim, self.in_dim, lin[0].in_features))
+            if dims != HIDDEN or lin[-1].out_features != out or not all(isinstance(a, nn.Tanh) for a in act):
                 raise ValueError("FusedActorCritic evaluates the reference's architecture: obs -> %s tanh -> %d (scripts/run.py:332-357); "
                                  "got %s -> %d" % (list(HIDDEN), out, list(dims), lin[-1].out_features))
             self._lin.append(lin)
-        self.k0p = _pad16(env.obs_dim)
-        n_float = int(_LIB.auv_policy_param_floats(env.obs_dim))
+        self.k0p = _pad16(self.in_dim)
+        n_float = int(_LIB.auv_policy_param_floats(self.in_dim))
         self.params = torch.zeros(n_float, dtype=torch.float32, device=self.device)
         assert self.params.data_ptr() % 16 == 0
         # bf16 = True: the weights also as bf16 fragments, and the launch multiplies on v_mfma_f32_16x16x32_bf16 (one MFMA where
@@ -213,7 +230,7 @@ class FusedActorCritic:
         z = lambda *shape: torch.zeros(shape, dtype=torch.float32, device=self.device)   # noqa: E731
         # ONE set of rollout buffers [T, N, ...] for the whole batch: every chain writes its own columns, nothing is
         # concatenated afterwards
-        self.O = z(self.T, N, D) if store_obs else None
+        self.O = z(self.T, N, self.in_dim) if store_obs else None
         self.A, self.LP, self.V, self.R, self.Dn = z(self.T, N, 2), z(self.T, N), z(self.T, N), z(self.T, N), z(self.T, N)
         self.mu = z(N, 2) if debug else None
         self.eps = z(N, 2) if debug else None
@@ -239,6 +256,17 @@ class FusedActorCritic:
         # rollout() names them to the launches, which then need no count-off
         self._t = [0] * len(self.slices)
         self._g = [0] * len(self.slices)
+        self.stack = None
+        if self.frames > 1:
+            # the history of every environment (indexed by global environment: the chains advance their own rows) and the launches'
+            # io blocks: the plain ones with hist, stk and frames behind them
+            from .framestack import FrameStack
+            self.stack = FrameStack(env, self.frames)
+            self._sios = (_capi.AuvPolicyStack * len(self.slices))()
+            for i in range(len(self.slices)):
+                s = self._sios[i]
+                s.io = self._ios[i]
+                s.hist, s.stk, s.frames = self.stack.hist.data_ptr(), self.stack.stk.data_ptr(), self.frames
         self.refresh()
 
     # ------------------------------------------------------------------------------ weights
@@ -276,7 +304,10 @@ class FusedActorCritic:
         slice's rows of `self.actions` and the transition at the chain's position t, then moves t on."""
         lo, cnt = self.slices[i]
         st = self.env._sub_streams[i] if stream is None else stream
-        _check(_LIB.auv_policy_act(self.env._h, lo, cnt, C.byref(self._ios[i]), C.c_void_p(st.cuda_stream)), "auv_policy_act")
+        if self.frames > 1:
+            _check(_LIB.auv_policy_act_stacked(self.env._h, lo, cnt, C.byref(self._sios[i]), C.c_void_p(st.cuda_stream)), "auv_policy_act_stacked")
+        else:
+            _check(_LIB.auv_policy_act(self.env._h, lo, cnt, C.byref(self._ios[i]), C.c_void_p(st.cuda_stream)), "auv_policy_act")
         self._t[i] = min(self._t[i] + 1, self.T + 1)
         self._g[i] += 1
 
@@ -288,16 +319,23 @@ class FusedActorCritic:
         env = self.env
         k = len(self.slices)
         t0, g0 = (C.c_int64 * k)(*self._t), (C.c_int64 * k)(*self._g)
-        _check(_LIB.auv_policy_rollout(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._ios,
-                                       C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()),
-                                       C.c_void_p(env.done.data_ptr()), int(n_steps), int(bool(flush)), t0, g0), "auv_policy_rollout")
+        if self.frames > 1:
+            _check(_LIB.auv_policy_rollout_stacked(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._sios,
+                                                   C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()),
+                                                   C.c_void_p(env.done.data_ptr()), int(n_steps), int(bool(flush)), t0, g0),
+                   "auv_policy_rollout_stacked")
+        else:
+            _check(_LIB.auv_policy_rollout(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._ios,
+                                           C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()),
+                                           C.c_void_p(env.done.data_ptr()), int(n_steps), int(bool(flush)), t0, g0), "auv_policy_rollout")
         n_launch = int(n_steps) + int(bool(flush))
         for i in range(k):
             self._t[i] = min(self._t[i] + n_launch, self.T + 1)
             self._g[i] += n_launch
 
     def buffers(self):
-        """(O, A, LP, V, R, Dn) of the whole batch, [T, N, ...] (written in place by the chains: no copy)."""
+        """(O, A, LP, V, R, Dn) of the whole batch, [T, N, ...] (written in place by the chains: no copy).  With frames > 1 O holds the
+        stacked rows, [T, N, frames * obs_dim]."""
         return self.O, self.A, self.LP, self.V, self.R, self.Dn
 
     def gae(self, V: torch.Tensor, last_v: torch.Tensor, gamma: float, lam: float):
@@ -313,13 +351,23 @@ class FusedActorCritic:
 
     # ------------------------------------------------------------------------------ evaluation outside a rollout
     def _rows(self, obs):
+        if obs is None and self.frames > 1:
+            # the row the next policy launch would form: a peek, the history is not moved on
+            return self.stack.peek(self.env.obs, self.env.done)
         return self.env.obs if obs is None else obs
+
+    def reset_frames(self, envs: Optional[torch.Tensor] = None):
+        """Empty the history of the environments `envs` (indices or a boolean mask; None: all) on the current stream: their next row
+        holds the current observation and zeros.  Call it behind env.reset() -- an episode that ends inside a rollout resets its history
+        itself, through the done flag.  Nothing to do with frames == 1."""
+        if self.stack is not None:
+            self.stack.reset(envs)
 
     def predict(self, obs: Optional[torch.Tensor] = None, deterministic: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The deterministic action of the policy -- the reference's agent.predict(obs, deterministic=True) of its enjoy / play /
         test modes (scripts/run.py:175, 273, 567): act_mid + act_half * clip(mu(obs)), one launch (auv_policy_eval) on the caller's
         current stream, written into `out` (default: `self.actions`, which env.step takes as is).  obs = None: the environment's
-        observation buffer.  Reads `self.params`: refresh() after optimiser steps, as for rollouts.  Touches no rollout buffer and
+        observation buffer (with frames > 1: the stacked row of it, peeked; rows passed in are stacked rows already).  Reads `self.params`: refresh() after optimiser steps, as for rollouts.  Touches no rollout buffer and
         no counter."""
         if not deterministic:
             raise ValueError("predict(deterministic=False): sampling lives where its counters are -- use act(i) / rollout()")
@@ -328,14 +376,14 @@ class FusedActorCritic:
             if X.dim() != 2 or X.shape[0] != self.env.n_envs:
                 raise ValueError("predict: %s rows do not fit self.actions [%d, 2]; pass out=" % (tuple(X.shape[:1]), self.env.n_envs))
             out = self.actions
-        return policy_eval(self.params, self.env.obs_dim, X, want=("action",), action_map=self.action_map, out={"action": out})["action"]
+        return policy_eval(self.params, self.in_dim, X, want=("action",), action_map=self.action_map, out={"action": out})["action"]
 
     def value(self, obs: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The critic's value of every row of `obs` (None: the environment's observation buffer), [M] float32 in the units the
         critic was trained in (scaled rewards): one launch of the value net alone, on the caller's current stream."""
-        return policy_eval(self.params, self.env.obs_dim, self._rows(obs), want=("value",))["value"]
+        return policy_eval(self.params, self.in_dim, self._rows(obs), want=("value",))["value"]
 
     def evaluate(self, obs: torch.Tensor, actions: torch.Tensor):
         """(log pi(actions | obs) [M], value [M], mu [M, 2]) in one launch on the caller's current stream."""
-        r = policy_eval(self.params, self.env.obs_dim, obs, actions=actions, want=("logp", "value", "mu"))
+        r = policy_eval(self.params, self.in_dim, obs, actions=actions, want=("logp", "value", "mu"))
         return r["logp"], r["value"], r["mu"]

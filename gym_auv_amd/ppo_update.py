@@ -137,7 +137,7 @@ class FusedPPOUpdate:
             return
         if fused.bf16:
             raise ValueError("FusedPPOUpdate.attach: the bf16 policy keeps a second copy of the weights that only refresh() packs")
-        if fused.env.obs_dim != self.obs_dim or fused.params.device != self.device:
+        if getattr(fused, "in_dim", fused.env.obs_dim) != self.obs_dim or fused.params.device != self.device:   # (in_dim: frames * obs_dim)
             raise ValueError("FusedPPOUpdate.attach: the policy has another observation width or device")
         _check(_LIB.auv_ppo_attach_policy(self._h, C.c_void_p(fused.params.data_ptr())), "auv_ppo_attach_policy")
         self._fused = fused                                         # (keeps the buffer alive)

@@ -679,6 +679,53 @@ int auv_policy_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds,
                        const auv_policy_io_t* ios, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps,
                        int32_t flush, const int64_t* t0, const int64_t* gstep0);
 
+/* ---- frame-stacked observations in the policy launch (what stable-baselines ships as VecFrameStack; csrc/k12_policy_stacked.hip) ----
+ * auv_policy_act_stacked is auv_policy_act's exact-f32 launch on input rows of frames * obs_dim columns: columns [j * obs_dim,
+ * (j + 1) * obs_dim) hold the observation of j steps ago -- j = 0 the observation buffer as it stands, NEWEST FIRST (a column
+ * permutation of stable-baselines' newest-last order) -- and zeros where the episode is younger than j steps.  The same matrix chains
+ * and the same epilogue: for the same row the mean and the value have the bits auv_policy_eval gives with obs_dim = frames * obs_dim,
+ * and frames == 1 is auv_policy_act bit for bit (hist and stk are then not touched and may be NULL).
+ *   io        as for auv_policy_act with:  obs_dim the ENVIRONMENT's;  params auv_policy_param_floats(frames * obs_dim) floats, the
+ *             nets of the wider first layer;  O [T][ld][frames * obs_dim], the stacked rows;  params_bf16 NULL.
+ *   hist      [N][frames][obs_dim] f32, a ring per environment, indexed by GLOBAL environment (16-byte aligned)
+ *   stk       [N][2] int32 (8-byte aligned): word 0 = pos | tag << 8 -- pos the ring slot of the newest frame, tag marks the launch that
+ *             stored it: (generator step mod (2^23 - 1)) + 1, in 1 .. 2^23 - 1, so the word is never negative (policy and value workgroup
+ *             of one launch both need the state from BEFORE the launch, and the one that comes second recognises its own launch's tag;
+ *             0: no launch) -- word 1 = age, the number of valid frames.  All zero: an empty history; zeroing word 1 of an environment
+ *             empties its history.
+ *   REQUIRED  consecutive act launches on the same rows must have DIFFERENT generator steps (mod 2^23 - 1).  The device counter
+ *             (io.ctr[1]) and t0 / gstep0 advanced by the number of launches made -- what auv_policy_rollout's contract asks for anyway --
+ *             give that.  A launch repeated with the generator step of the launch before it (a determinism check, a captured one-step
+ *             rollout replayed with host counters) finds its own tag in stk and does NOT move the history: restore stk, or zero the tag
+ *             bits (stk word 0 &= 255), before such a replay.
+ *   a launch with t < T, per environment:  age' = min((done_in ? 0 : age) + 1, frames),  pos' = (pos + 1) mod frames;  frame j >= 1 of
+ *             the row is hist[(pos' - j) mod frames] if j < age', else zeros;  then hist[pos'] = obs, stk = (pos', age').
+ *   the flush launch (t == T) stores R[T - 1] / Dn[T - 1] only and leaves hist and stk alone: the next rollout's first launch sees
+ *             the same obs and done_in and adds that frame exactly once.
+ * Everything lives on the device: the launch can sit in a captured graph.  AUV_EINVAL, before anything is enqueued: what
+ * auv_policy_act refuses; frames outside [1, AUV_MAX_FRAMES]; frames * obs_dim too wide for the kernel's LDS tile; params_bf16 set;
+ * frames > 1 with hist or stk NULL or misaligned.
+ * auv_policy_rollout_stacked is auv_policy_rollout's loop with that launch: the same t0 / gstep0 contract -- with gstep0[i] of a call
+ * NOT equal to the generator step of the last act launch before it on that slice (REQUIRED, above) -- the same slices on their own
+ * streams; every slice must have the same `frames`.
+ * auv_stack_frames does the history update alone, no handle and no network: stacked rows out[ne][ldx] (ldx >= frames * obs_dim
+ * floats; row j is environment e0 + j of obs, done, hist and stk) on `stream`.  done NULL: no environment is done.  advance != 0: hist
+ * and stk move on as in an act launch (tag 0); advance == 0 is a PEEK -- the row the next act launch would form, nothing is stored to
+ * hist or stk.  16-byte accesses where obs_dim, ldx and the bases allow, 8- or 4-byte ones otherwise.                              */
+#define AUV_MAX_FRAMES 8
+typedef struct auv_policy_stack {
+  auv_policy_io_t io;
+  float* hist;               /* [N][frames][obs_dim]                                                           */
+  int32_t* stk;              /* [N][2]: pos | tag << 8, age                                                    */
+  int32_t frames, reserved;
+} auv_policy_stack_t;
+int auv_policy_act_stacked(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* io, void* stream);
+int auv_policy_rollout_stacked(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
+                               const auv_policy_stack_t* ios, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps,
+                               int32_t flush, const int64_t* t0, const int64_t* gstep0);
+int auv_stack_frames(int32_t device, const float* obs, const uint8_t* done, float* hist, int32_t* stk, float* out, int64_t ldx,
+                     int32_t e0, int32_t ne, int32_t obs_dim, int32_t frames, int32_t advance, void* stream);
+
 /* ---- the policy outside the rollout (scripts/run.py:175, 273, 567: agent.predict(obs, deterministic=True) of the enjoy / play /
  * test modes; csrc/k9_policy_eval.hip) --------------------------------------------------------------------------------------------
  * auv_policy_eval evaluates M observation rows through the policy net, the value net, or both, with ONE launch on `stream`: no
