@@ -2256,41 +2256,64 @@ int auv_policy_eval(int32_t device, const auv_policy_eval_t* ev, void* stream) {
   return AUV_OK;
 }
 
-int auv_policy_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
-                       float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
-                       const int64_t* gstep0) {
-  REQUIRE_READY(h);
-  int rc = check_slices(h, n_slices, bounds, streams, "auv_policy_rollout");
-  if (rc) return rc;
-  if (!ios || n_steps < 0 || (!t0) != (!gstep0)) return fail(AUV_EINVAL, "auv_policy_rollout: bad arguments");
-  for (int i = 0; i < n_slices; i++) {
-    rc = check_policy_io(h, bounds[i], bounds[i + 1] - bounds[i], ios + i, "auv_policy_rollout");
-    if (rc) return rc;
-    rc = check_actions(ios[i].actions_out, AUV_F32, "auv_policy_rollout");
-    if (rc) return rc;
-    if (t0 && (t0[i] < 0 || gstep0[i] < 0)) return fail(AUV_EINVAL, "auv_policy_rollout: negative counter for slice %d", i);
-  }
-  PAIR_CHECK(h, obs_dev);
-  HIP_TRY(auv_policy_prepare(ios[0].obs_dim));
-  // t0 / gstep0 (per slice; both or neither): the host names every launch's rollout position and generator step (this is a
-  // plain loop of launches, the values are known here) -- the launches then neither read nor count off on io.ctr, which
-  // is worth ~4 us per launch.  NULL: the device counters, as auv_policy_act.
+// ---- rollouts: a launch that acts, then a step of the environment, per slice on its own stream, n_steps times ----
+// The loop the three rollout calls share.  launch(i, k, flushing): the acting launch of slice i in front of step k of this call and,
+// flushing, the one behind the last step (k == n_steps) that only books what that step has left; actions_of(i): the [N][2] float
+// buffer the launch writes and the step reads.  The caller has checked its arguments, run PAIR_CHECK and prepared its kernel.  The
+// first error stops the enqueuing and is returned before anything is flushed.
+extern "C++" template <class ActionsOf, class Launch>
+static int rollout_loop(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, float* obs_dev, float* reward_dev,
+                        uint8_t* done_dev, int32_t n_steps, int32_t flush, ActionsOf actions_of, Launch launch) {
+  int rc = AUV_OK;
   for (int32_t k = 0; k < n_steps; k++) {
     if (rc == AUV_OK) rc = fw_tick(h, n_slices, bounds, streams);
     for (int i = 0; i < n_slices && rc == AUV_OK; i++) {
       const int ne = bounds[i + 1] - bounds[i];
-      auv_launch_policy(ios[i], bounds[i], ne, (hipStream_t)streams[i], t0 ? t0[i] + k : -1, t0 ? gstep0[i] + k : -1);
-      rc = enqueue_step(h, effective_mode(h, ne), bounds[i], ne, ios[i].actions_out, AUV_F32, obs_dev, reward_dev, done_dev,
+      launch(i, k, false);
+      rc = enqueue_step(h, effective_mode(h, ne), bounds[i], ne, actions_of(i), AUV_F32, obs_dev, reward_dev, done_dev,
                         (hipStream_t)streams[i], false);
     }
   }
   if (rc) return rc;
   if (flush)
-    for (int i = 0; i < n_slices; i++)
-      auv_launch_policy(ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], t0 ? t0[i] + n_steps : -1,
-                        t0 ? gstep0[i] + n_steps : -1);
+    for (int i = 0; i < n_slices; i++) launch(i, n_steps, true);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
+}
+
+// t0 / gstep0 of a policy rollout (per slice; both or neither): the host names every launch's rollout position and generator step
+// (a rollout is a plain loop of launches, the values are known on the host) -- the launches then neither read nor count off on
+// io.ctr, which is worth ~4 us per launch.  NULL: the device counters, as auv_policy_act; the kernel is told -1.
+struct RolloutCounters {
+  const int64_t *t0, *gstep0;
+  bool paired() const { return (!t0) == (!gstep0); }
+  bool negative(int i) const { return t0 && (t0[i] < 0 || gstep0[i] < 0); }
+  long long t(int i, int32_t k) const { return t0 ? t0[i] + k : -1; }
+  long long gstep(int i, int32_t k) const { return t0 ? gstep0[i] + k : -1; }
+};
+
+int auv_policy_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
+                       float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
+                       const int64_t* gstep0) {
+  REQUIRE_READY(h);
+  const RolloutCounters ctr = {t0, gstep0};
+  int rc = check_slices(h, n_slices, bounds, streams, "auv_policy_rollout");
+  if (rc) return rc;
+  if (!ios || n_steps < 0 || !ctr.paired()) return fail(AUV_EINVAL, "auv_policy_rollout: bad arguments");
+  for (int i = 0; i < n_slices; i++) {
+    rc = check_policy_io(h, bounds[i], bounds[i + 1] - bounds[i], ios + i, "auv_policy_rollout");
+    if (rc) return rc;
+    rc = check_actions(ios[i].actions_out, AUV_F32, "auv_policy_rollout");
+    if (rc) return rc;
+    if (ctr.negative(i)) return fail(AUV_EINVAL, "auv_policy_rollout: negative counter for slice %d", i);
+  }
+  PAIR_CHECK(h, obs_dev);
+  HIP_TRY(auv_policy_prepare(ios[0].obs_dim));
+  return rollout_loop(
+      h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].actions_out; },
+      [&](int i, int32_t k, bool) {
+        auv_launch_policy(ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k), ctr.gstep(i, k));
+      });
 }
 
 // ---- frame-stacked observations in the policy launch (include/auv_hip.h, auv_policy_stack; kernels: k12_policy_stacked.hip) ----
@@ -2325,35 +2348,25 @@ int auv_policy_rollout_stacked(auv_handle_t* h, int32_t n_slices, const int32_t*
                                float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
                                const int64_t* gstep0) {
   REQUIRE_READY(h);
+  const RolloutCounters ctr = {t0, gstep0};
   int rc = check_slices(h, n_slices, bounds, streams, "auv_policy_rollout_stacked");
   if (rc) return rc;
-  if (!ios || n_steps < 0 || (!t0) != (!gstep0)) return fail(AUV_EINVAL, "auv_policy_rollout_stacked: bad arguments");
+  if (!ios || n_steps < 0 || !ctr.paired()) return fail(AUV_EINVAL, "auv_policy_rollout_stacked: bad arguments");
   for (int i = 0; i < n_slices; i++) {
     rc = check_policy_stack(h, bounds[i], bounds[i + 1] - bounds[i], ios + i, "auv_policy_rollout_stacked");
     if (rc) return rc;
     rc = check_actions(ios[i].io.actions_out, AUV_F32, "auv_policy_rollout_stacked");
     if (rc) return rc;
     if (ios[i].frames != ios[0].frames) return fail(AUV_EINVAL, "auv_policy_rollout_stacked: slice %d has %d frames, slice 0 has %d", i, ios[i].frames, ios[0].frames);
-    if (t0 && (t0[i] < 0 || gstep0[i] < 0)) return fail(AUV_EINVAL, "auv_policy_rollout_stacked: negative counter for slice %d", i);
+    if (ctr.negative(i)) return fail(AUV_EINVAL, "auv_policy_rollout_stacked: negative counter for slice %d", i);
   }
   PAIR_CHECK(h, obs_dev);
   HIP_TRY(auv_policy_stacked_prepare(ios[0].frames * ios[0].io.obs_dim));
-  for (int32_t k = 0; k < n_steps; k++) {
-    if (rc == AUV_OK) rc = fw_tick(h, n_slices, bounds, streams);
-    for (int i = 0; i < n_slices && rc == AUV_OK; i++) {
-      const int ne = bounds[i + 1] - bounds[i];
-      auv_launch_policy_stacked(ios[i], bounds[i], ne, (hipStream_t)streams[i], t0 ? t0[i] + k : -1, t0 ? gstep0[i] + k : -1);
-      rc = enqueue_step(h, effective_mode(h, ne), bounds[i], ne, ios[i].io.actions_out, AUV_F32, obs_dev, reward_dev, done_dev,
-                        (hipStream_t)streams[i], false);
-    }
-  }
-  if (rc) return rc;
-  if (flush)
-    for (int i = 0; i < n_slices; i++)
-      auv_launch_policy_stacked(ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], t0 ? t0[i] + n_steps : -1,
-                                t0 ? gstep0[i] + n_steps : -1);
-  HIP_TRY(hipGetLastError());
-  return AUV_OK;
+  return rollout_loop(
+      h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].io.actions_out; },
+      [&](int i, int32_t k, bool) {
+        auv_launch_policy_stacked(ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k), ctr.gstep(i, k));
+      });
 }
 
 int auv_stack_frames(int32_t device, const float* obs, const uint8_t* done, float* hist, int32_t* stk, float* out, int64_t ldx, int32_t e0,
@@ -2455,24 +2468,13 @@ int auv_population_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bou
   }
   PAIR_CHECK(h, obs_dev);
   HIP_TRY(auv_population_prepare(D));
-  for (int32_t k = 0; k < n_steps; k++) {
-    if (rc == AUV_OK) rc = fw_tick(h, n_slices, bounds, streams);
-    for (int i = 0; i < n_slices && rc == AUV_OK; i++) {
-      const int ne = bounds[i + 1] - bounds[i];
-      io[i].accumulate = k > 0, io[i].act = 1;           // (the first launch of a call has no completed step of this window behind it)
-      auv_launch_population_act(io[i], (hipStream_t)streams[i]);
-      rc = enqueue_step(h, effective_mode(h, ne), bounds[i], ne, ios[i].action, AUV_F32, obs_dev, reward_dev, done_dev, (hipStream_t)streams[i],
-                        false);
-    }
-  }
-  if (rc) return rc;
-  if (flush)
-    for (int i = 0; i < n_slices; i++) {
-      io[i].accumulate = 1, io[i].act = 0;
-      auv_launch_population_act(io[i], (hipStream_t)streams[i]);
-    }
-  HIP_TRY(hipGetLastError());
-  return AUV_OK;
+  return rollout_loop(
+      h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].action; },
+      [&](int i, int32_t k, bool flushing) {
+        // (the first launch of a call has no completed step of this window behind it; the flush launch only books the last one)
+        io[i].accumulate = flushing || k > 0, io[i].act = !flushing;
+        auv_launch_population_act(io[i], (hipStream_t)streams[i]);
+      });
 }
 
 static int check_population_block(int32_t obs_dim, int32_t P, float sigma, const char* who) {

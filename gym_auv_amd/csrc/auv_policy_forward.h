@@ -1,0 +1,261 @@
+// The forward pass of the policy MLP as the four fused launches run it -- k6_policy_act, k9_policy_eval, k11_population_act,
+// k12_stacked_act -- written once: the packed net's pointers, the LDS carve-up, the prefetch / layer / barrier sequence (pol_trunk),
+// the counter-based generator, the action map, log pi(a), and the frame of an ACT launch (rollout position, transition, sampling
+// epilogue, counters) that k6 and k12 share.  What stays in the kernels is what differs between them: where the input rows come from
+// and what is stored of the outputs.  (The PPO update, k8_ppo_update.hip, has its own sequence and includes auv_policy_mfma.h only.)
+//
+// The order of requests and barriers in here was measured line by line (profiles/r04, profiles/policy_trunk); the library is built
+// with -ffp-contract=off and the tests compare bits across the launches.
+#ifndef AUV_POLICY_FORWARD_H
+#define AUV_POLICY_FORWARD_H
+#include "auv_policy_mfma.h"
+
+namespace {
+
+// ---- one packed net (layout: pol_net_floats) ----
+struct PolNet {
+  const float *W1, *b1, *W2, *b2, *W3, *b3, *W4, *b4;
+};
+__device__ __forceinline__ PolNet pol_net_ptrs(const float* P, const int K0) {
+  PolNet n;
+  n.W1 = P;
+  n.b1 = n.W1 + (size_t)POL_H1 * pol_pad16(K0);
+  n.W2 = n.b1 + POL_H1;
+  n.b2 = n.W2 + (size_t)POL_H2 * POL_H1;
+  n.W3 = n.b2 + POL_H2;
+  n.b3 = n.W3 + (size_t)POL_H3 * POL_H2;
+  n.W4 = n.b3 + POL_H3;
+  n.b4 = n.W4 + (size_t)POL_OUT * POL_H3;
+  return n;
+}
+
+// ---- the LDS of a forward workgroup (pol_lds_x_floats / pol_lds_bytes): X at the base, rows of pol_ldx floats; Y1 behind it ----
+// (plain values, not a struct of pointers and strides: with one between here and pol_layer the layers' epilogues lost their paired
+// LDS stores and every launch 1 - 2 % of its time)
+__device__ __forceinline__ int pol_ldx(const int K0) { return pol_pad16(K0) + 8; }
+__device__ __forceinline__ float* pol_tile_y1(float* X, const int K0) { return X + pol_lds_x_floats(K0); }
+__device__ __forceinline__ float* pol_tiles_end(float* X, const int K0) { return pol_tile_y1(X, K0) + (size_t)POL_ROWS * (POL_H1 + 8); }
+
+// the input tile starts as zeros: padding columns and the rows past the end stay so.  A barrier goes between this and the fill.
+__device__ __forceinline__ void pol_zero_tile(float* X, const int ldx, const int tid) {
+  for (int i = tid; i < POL_ROWS * (ldx / 2); i += POL_THREADS) *(float2*)(X + 2 * i) = make_float2(0.0f, 0.0f);
+}
+
+// `n` floats of one contiguous range -> the tile's rows of K0 columns, and into `dstO` (nullable: the rollout's O[t], whose rows of
+// the tile are one contiguous range too).  V = float2: K0 even, so rows start 8-byte aligned and no pair straddles two rows.
+template <class V>
+__device__ __forceinline__ void pol_fill_range(float* X, const int ldx, const float* src, float* dstO, const int n, const int K0,
+                                               const int tid) {
+  constexpr int W = sizeof(V) / sizeof(float);
+  for (int idx = W * tid; idx < n; idx += W * POL_THREADS) {
+    const V v = *(const V*)(src + idx);
+    const int row = idx / K0, c = idx - row * K0;
+    *(V*)(X + row * ldx + c) = v;
+    if (dstO) *(V*)(dstO + idx) = v;
+  }
+}
+
+// the policy net's output component a lane stands for: columns 0 and 1 of the last layer's n-tile are the two actions (the other
+// lanes compute along as component 0 and store nothing)
+__device__ __forceinline__ int pol_comp(const int lane) { return (lane & 15) < 2 ? (lane & 15) : 0; }
+
+// ---- the forward pass: from the barrier behind the tile fill to the last layer's raw outputs (on wave 0, in `o`) ----
+// X: the filled tile of K0 columns.  w1: requested by the caller BEFORE it fetched the tile (pol_prefetch).  log_std: nullable, this
+// lane asks for its component's log-std (returned; 0 without).
+template <bool BF>
+__device__ __forceinline__ float pol_trunk(float* X, const int K0, const PolNet& n, PolW<POL_H1 / 16, BF>& w1, const float* log_std,
+                                           const int wave, const int lane, f32x4 (*o)[POL_MT]) {
+  const int K0p = pol_pad16(K0);
+  const int ldx = pol_ldx(K0), ld1 = POL_H1 + 8, ld2 = POL_H2 + 8, ld3 = POL_H3 + 8;
+  float* Y1 = pol_tile_y1(X, K0);
+  float* Y2 = X;                                                   // (X is dead once layer 1 is through: a barrier lies in between)
+  float* Y3 = Y1;                                                  // (Y1 is dead once layer 2 is through)
+  PolW<POL_H2 / 16, BF> w2;
+  PolW<POL_H3 / 16, BF> w3;
+  PolW<1, BF> w4;
+  __syncthreads();
+  pol_prefetch(w2, n.W2, n.b2, POL_H1, wave, lane);                // (the next layer's weights: in flight during this layer)
+  pol_layer<POL_H1 / 16, 1, false, BF>(X, ldx, w1, n.b1, K0p, wave, lane, Y1, ld1, nullptr);
+  __syncthreads();
+  pol_prefetch(w3, n.W3, n.b3, POL_H2, wave, lane);
+  pol_layer<POL_H2 / 16, 1, false, BF>(Y1, ld1, w2, n.b2, POL_H1, wave, lane, Y2, ld2, nullptr);
+  __syncthreads();
+  pol_prefetch(w4, n.W4, n.b4, POL_H3, wave, lane);
+  // (the sampling's log-std with them: ahead of the barrier, so that the request is not moved down to its use)
+  float ls = 0.0f;
+  if (log_std) ls = log_std[pol_comp(lane)];
+  pol_layer<POL_H3 / 16, 2, false, BF>(Y2, ld2, w3, n.b3, POL_H2, wave, lane, Y3, ld3, nullptr);
+  __syncthreads();
+  if (wave == 0) pol_layer<1, 2, true, BF>(Y3, ld3, w4, n.b4, POL_H3, 0, lane, nullptr, 0, o);
+  return ls;
+}
+
+// ---- the counter-based generator of the policy launches ----
+// splitmix64 finaliser: (seed, step, row, component) -> 64 well-mixed bits
+__device__ __forceinline__ unsigned long long pol_mix(unsigned long long z) {
+  z += 0x9e3779b97f4a7c15ull;
+  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
+  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
+  return z ^ (z >> 31);
+}
+__device__ __forceinline__ float pol_gauss(unsigned long long seed, unsigned long long step, unsigned int row, unsigned int comp) {
+  const unsigned long long h = pol_mix(pol_mix(seed ^ (step * 0xd1342543de82ef95ull)) ^ (((unsigned long long)row << 1) | comp));
+  const float u1 = ((float)(unsigned int)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);      // (0, 1): 24 bits
+  const float u2 = ((float)(unsigned int)((h >> 8) & 0xffffffu)) * (1.0f / 16777216.0f);   // [0, 1)
+  return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
+}
+
+// ---- the action map of this lane's component: env action = act_mid + act_half * clamp(a, clip_lo, clip_hi) ----
+// IO: any launch argument struct with clip_lo[2], clip_hi[2], act_mid[2], act_half[2].  nc = pol_comp(lane).
+struct PolActMap {
+  float clip_lo, clip_hi, act_mid, act_half;
+  __device__ __forceinline__ float operator()(const float a) const {
+    const float ac = fminf(fmaxf(a, clip_lo), clip_hi);
+    return act_mid + act_half * ac;
+  }
+};
+template <class IO>
+__device__ __forceinline__ PolActMap pol_act_map(const IO& io, const int nc) {
+  // launch arguments picked by a select (indexed by the lane they are vector loads from the argument segment, behind the stores of
+  // every row: four trips to memory in the epilogue)
+  float cl0 = io.clip_lo[0], cl1 = io.clip_lo[1], ch0 = io.clip_hi[0], ch1 = io.clip_hi[1];
+  float am0 = io.act_mid[0], am1 = io.act_mid[1], ah0 = io.act_half[0], ah1 = io.act_half[1];
+  asm volatile("" : "+s"(cl0), "+s"(cl1), "+s"(ch0), "+s"(ch1), "+s"(am0), "+s"(am1), "+s"(ah0), "+s"(ah1));   // (or the selects become indexed loads again)
+  PolActMap m;
+  m.clip_lo = nc ? cl1 : cl0, m.clip_hi = nc ? ch1 : ch0, m.act_mid = nc ? am1 : am0, m.act_half = nc ? ah1 : ah0;
+  return m;
+}
+
+// log pi(a) of the diagonal Gaussian, both components summed (they sit on neighbouring lanes: every lane of the wave calls this)
+__device__ __forceinline__ float pol_logp(const float a, const float mu, const float sigma, const float ls) {
+  const float z = (a - mu) / sigma;
+  float lp = -0.5f * z * z - ls - POL_LOG_SQRT_2PI;
+  lp += __shfl_xor(lp, 1, AUV_WAVE);
+  return lp;
+}
+
+// ---- the frame of an ACT launch (k6_policy_act, k12_stacked_act): grid (ceil(ne / 16), 2), blockIdx.y = 0 the policy net, 1 the
+// value net; a kernel calls pol_act_begin first, pol_act_sample behind the trunk on wave 0, pol_act_end last ----
+struct PolAct {
+  bool host_counts, act, trans;
+  long long t;                       // position in the rollout; t == T: the flush call after a rollout's last step
+  unsigned long long gstep;          // the generator's step
+  int e0, cnt, r0, col0;             // the slice, the tile's first row inside it and its first column in a rollout row
+  float trans_r;
+  uint8_t trans_d;
+};
+
+// t_host, gstep_host >= 0: the host names the rollout position and the generator's step (a plain loop of launches); -1: both live
+// on the device (io.ctr) and the launch moves them on itself
+__device__ __forceinline__ PolAct pol_act_begin(const auv_policy_io_t& io, const int e0, const int ne, const long long t_host,
+                                                const long long gstep_host) {
+  PolAct p;
+  const int tid = threadIdx.x;
+  p.e0 = e0, p.cnt = ne;
+  p.r0 = blockIdx.x * POL_ROWS;
+  // position in the rollout and the generator's step counter: read by every workgroup before anybody moves them on
+  p.host_counts = t_host >= 0;
+  p.t = p.host_counts ? t_host : io.ctr[0];
+  p.gstep = (unsigned long long)(p.host_counts ? gstep_host : io.ctr[1]);
+  p.col0 = e0 - io.env_base + p.r0;
+  // ---- the transition the environment's last step completed: reward and done of step t - 1 ----
+  // (requested here, stored at the end: load - store - load - store at the head of the kernel were two trips to memory in
+  // front of everything wave 0 does, and wave 0 is the one that samples)
+  p.trans = blockIdx.y == 0 && p.t >= 1 && p.t <= io.T && tid < POL_ROWS && p.r0 + tid < ne;
+  p.trans_r = 0.0f, p.trans_d = 0;
+  if (p.trans) p.trans_r = io.reward_in[e0 + p.r0 + tid], p.trans_d = io.done_in[e0 + p.r0 + tid];
+  p.act = p.t < io.T;
+  return p;
+}
+
+// where the policy workgroup copies its input tile in the rollout: O[t]'s rows of the tile, `width` columns each (nullptr: no copy)
+__device__ __forceinline__ float* pol_act_obs_out(const auv_policy_io_t& io, const PolAct& p, const int width) {
+  return (blockIdx.y == 0 && io.O) ? io.O + ((size_t)p.t * (size_t)io.ld + p.col0) * width : nullptr;
+}
+// the input tile of unstacked rows: the tile's rows are consecutive rows of the observation buffer, one contiguous range, read two
+// floats per lane where obs_dim is even
+__device__ __forceinline__ void pol_act_fill_obs(float* X, const auv_policy_io_t& io, const PolAct& p, float* dstO, const int rows) {
+  const int K0 = io.obs_dim, ldx = pol_ldx(K0), tid = threadIdx.x;
+  const float* src = io.obs + (size_t)(p.e0 + p.r0) * K0;
+  if ((K0 & 1) == 0) pol_fill_range<float2>(X, ldx, src, dstO, rows * K0, K0, tid);
+  else pol_fill_range<float>(X, ldx, src, dstO, rows * K0, K0, tid);
+}
+
+// wave 0, behind the trunk: `o` the last layer's outputs, `ls` the log-std the trunk returned
+__device__ __forceinline__ void pol_act_sample(const auv_policy_io_t& io, const PolAct& p, const f32x4 (*o)[POL_MT], const float ls,
+                                               const int lane) {
+  const int n = lane & 15, g = lane >> 4;
+  const size_t ld = (size_t)io.ld;                                 // environments per rollout row
+  if (blockIdx.y == 0) {
+    // ---- diagonal Gaussian: sample, log-probability, action ----
+    const int nc = pol_comp(lane);
+    const float sigma = expf(ls);
+    const PolActMap map = pol_act_map(io, nc);
+#pragma unroll
+    for (int u = 0; u < POL_MT; u++)
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int rr = 16 * u + 4 * g + i;                         // row inside the tile
+        const int row = p.r0 + rr;
+        const int e = p.e0 + row;
+        const float mu = o[0][u][i];
+        const float eps = pol_gauss(io.seed, p.gstep, (unsigned int)e, (unsigned int)nc);
+        const float a = mu + sigma * eps;
+        const float lp = pol_logp(a, mu, sigma, ls);
+        if (n < 2 && row < p.cnt) {
+          const size_t q = (size_t)p.t * ld + p.col0 + rr;
+          io.A[2 * q + n] = a;
+          if (n == 0) io.LP[q] = lp;
+          io.actions_out[2 * (size_t)e + n] = map(a);
+          if (io.mu_out) io.mu_out[2 * (size_t)row + n] = mu;
+          if (io.eps_out) io.eps_out[2 * (size_t)row + n] = eps;
+        }
+      }
+  } else if (n == 0) {
+#pragma unroll
+    for (int u = 0; u < POL_MT; u++)
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int rr = 16 * u + 4 * g + i;
+        if (p.r0 + rr < p.cnt) io.V[(size_t)p.t * ld + p.col0 + rr] = o[0][u][i];
+      }
+  }
+}
+
+// every thread of the workgroup, last: the transition's store and the counters
+__device__ __forceinline__ void pol_act_end(const auv_policy_io_t& io, const PolAct& p) {
+  const int tid = threadIdx.x;
+  const long long t = p.t;
+  if (p.trans) {
+    float r = p.trans_r;
+    if (io.reward_clip > 0.0f) r = fminf(fmaxf(r, -io.reward_clip), io.reward_clip);
+    io.R[(size_t)(t - 1) * (size_t)io.ld + p.col0 + tid] = r * io.reward_scale;
+    io.Dn[(size_t)(t - 1) * (size_t)io.ld + p.col0 + tid] = p.trans_d ? 1.0f : 0.0f;
+  }
+  // ---- the rollout position and the generator's counter move on ----
+  if (p.host_counts) {
+    // the host named them (nobody in this launch reads io.ctr): one workgroup keeps the device copies in step, for a later
+    // auv_policy_act on the same buffers
+    if (blockIdx.x == 0 && blockIdx.y == 0 && tid == 0) {
+      if (t <= io.T) io.ctr[0] = t + 1;
+      io.ctr[1] = (long long)(p.gstep + 1);
+    }
+    return;
+  }
+  // on the device (a launch that may sit in a captured graph): every workgroup has read them by the time it counts itself off,
+  // the last one moves them.  (512 returning atomics on one word: ~4 of the 8 us an EMPTY launch of this grid takes -- why
+  // auv_policy_rollout, a plain host loop, names the counters itself.)
+  __syncthreads();
+  if (tid == 0) {
+    const unsigned long long total = (unsigned long long)gridDim.x * gridDim.y;
+    const unsigned long long old = atomicAdd((unsigned long long*)&io.ctr[2], 1ull);
+    if (old == total - 1) {
+      io.ctr[2] = 0;
+      if (t <= io.T) io.ctr[0] = t + 1;                            // (a flush call leaves T + 1: further calls do nothing)
+      io.ctr[1] = (long long)(p.gstep + 1);
+    }
+  }
+}
+
+}  // namespace
+#endif /* AUV_POLICY_FORWARD_H */

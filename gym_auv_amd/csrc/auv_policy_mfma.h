@@ -1,5 +1,6 @@
-// The policy MLP on the matrix cores: tile geometry, the packed-weight layout and the layer routine shared by the policy launch
-// (k6_policy.hip) and the PPO update (k8_ppo_update.hip).  Reference: scripts/run.py:332-357 (MlpPolicy, net_arch [256, 128, 64], tanh).
+// The policy MLP on the matrix cores: tile geometry, the packed-weight layout and the layer routine shared by the forward launches
+// (k6, k9, k11, k12 through auv_policy_forward.h, which holds their common forward pass) and the PPO update (k8_ppo_update.hip).
+// Reference: scripts/run.py:332-357 (MlpPolicy, net_arch [256, 128, 64], tanh).
 #ifndef AUV_POLICY_MFMA_H
 #define AUV_POLICY_MFMA_H
 #include "auv_device.h"
@@ -31,7 +32,7 @@ __host__ __device__ inline size_t pol_net_floats(int obs_dim) {
   return POL_H1 * k0 + POL_H1 + (size_t)POL_H2 * POL_H1 + POL_H2 + (size_t)POL_H3 * POL_H2 + POL_H3 + (size_t)POL_OUT * POL_H3 + POL_OUT;
 }
 
-// LDS of a forward workgroup (k6_policy_act, k9_policy_eval): X [ROWS][K0p + 8] | Y1 [ROWS][H1 + 8]; Y2 [ROWS][H2 + 8] re-uses X's
+// LDS of a forward workgroup (carved up in auv_policy_forward.h: pol_ldx, pol_tile_y1, pol_trunk): X [ROWS][K0p + 8] | Y1 [ROWS][H1 + 8]; Y2 [ROWS][H2 + 8] re-uses X's
 // place (dead after layer 1), Y3 [ROWS][H3 + 8] Y1's (dead after layer 2).  Row strides = 8 mod 64 floats: the 16-byte reads of an
 // A operand -- 16 rows x 4 k-groups -- then touch every bank once.
 __host__ __device__ inline size_t pol_lds_x_floats(int obs_dim) {

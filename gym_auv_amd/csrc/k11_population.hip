@@ -2,16 +2,16 @@
 // fold it back (auv_population_perturb, auv_population_update): evolution strategies, ARS on the reference's own [256, 128, 64]
 // actor (scripts/run.py:332-357), "evaluate these 256 checkpoints side by side".
 //
-// k11_population_act IS k9_policy_eval's policy net -- the same workgroup (16 rows of ONE net, eight waves), the same LDS tiles and row
-// strides, pol_prefetch / pol_layer in the same order with the same template arguments, the same epilogue expression -- with one
-// difference: the weight block is picked per TILE, members + (row / G) * stride, instead of once per launch.  G is a multiple of 16,
+// k11_population_act runs the forward pass k9_policy_eval runs for the policy net (auv_policy_forward.h: pol_trunk<false> and the
+// shared action map; the same workgroup of 16 rows of ONE net and eight waves) with one difference: the weight block is picked per
+// TILE, members + (row / G) * stride, instead of once per launch.  G is a multiple of 16,
 // so a tile never straddles two members, and every workgroup streams its net's weights on its own anyway.  For the same row and the
 // same block the mean has the bits auv_policy_eval gives (tests/test_gpu_population.py).
 //
 // The noise of k11_perturb / k11_es_update is a function of (seed, generation, pair, element) alone and has no logf / cosf in it:
 // the sum of the four 16-bit fields of a splitmix64 hash, centred and scaled to unit variance (an Irwin-Hall sum of four uniforms:
 // symmetric, |eps| <= 3.464).  gym_auv_amd/population.py mirrors it in NumPy bit for bit; the update regenerates it, nothing is stored.
-#include "auv_policy_mfma.h"
+#include "auv_policy_forward.h"
 
 namespace {
 
@@ -19,6 +19,20 @@ struct PopArgs {
   auv_population_io_t io;
   int32_t vec2;                      // every source row starts 8-byte aligned and holds an even number of floats (host-proven)
 };
+
+// rows of a strided matrix -> the tile.  V = float2: ldx and obs_dim even and the base 8-byte aligned, so no pair straddles two rows
+// or an 8-byte boundary
+template <class V>
+__device__ __forceinline__ void pop_fill_rows(float* X, const int ldx, const auv_population_io_t& io, const int r0, const int rows, const int tid) {
+  constexpr int W = sizeof(V) / sizeof(float);
+  const int K0 = io.obs_dim;
+  const float* src = io.X + (size_t)r0 * (size_t)io.ldx;
+  const size_t lds = (size_t)io.ldx;
+  for (int i = W * tid; i < rows * K0; i += W * POL_THREADS) {
+    const int row = i / K0, c = i - row * K0;
+    *(V*)(X + row * ldx + c) = *(const V*)(src + row * lds + c);
+  }
+}
 
 // grid ceil(M / 16)
 __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k11_population_act(PopArgs pa) {   // (two workgroups per CU, as k6)
@@ -37,63 +51,22 @@ __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k11_pop
   if (accum) acc_r = io.reward_in[r0 + tid], acc_d = io.done_in[r0 + tid], acc_f = io.fit[r0 + tid], acc_e = io.ends[r0 + tid];
   if (io.act) {                                                  // (uniform; 0: the flush launch behind a window's last step)
     const int K0 = io.obs_dim, K0p = pol_pad16(K0);
-    const int ldx = K0p + 8, ld1 = POL_H1 + 8, ld2 = POL_H2 + 8, ld3 = POL_H3 + 8;
     float* X = (float*)smem;
-    float* Y1 = X + pol_lds_x_floats(K0);
-    float* Y2 = X;                                               // (X is dead once layer 1 is through: a barrier lies in between)
-    float* Y3 = Y1;                                              // (Y1 is dead once layer 2 is through)
-    const float* P = io.members + (size_t)(r0 / io.G) * (size_t)io.stride;   // this tile's member
-    const float* W1 = P;
-    const float* b1 = W1 + (size_t)POL_H1 * K0p;
-    const float* W2 = b1 + POL_H1;
-    const float* b2 = W2 + (size_t)POL_H2 * POL_H1;
-    const float* W3 = b2 + POL_H2;
-    const float* b3 = W3 + (size_t)POL_H3 * POL_H2;
-    const float* W4 = b3 + POL_H3;
-    const float* b4 = W4 + (size_t)POL_OUT * POL_H3;
+    const int ldx = pol_ldx(K0);
+    const PolNet nw = pol_net_ptrs(io.members + (size_t)(r0 / io.G) * (size_t)io.stride, K0);   // this tile's member
     PolW<POL_H1 / 16, false> w1;
-    PolW<POL_H2 / 16, false> w2;
-    PolW<POL_H3 / 16, false> w3;
-    PolW<1, false> w4;
-    pol_prefetch(w1, W1, b1, K0p, wave, lane);                     // (in flight while the rows are fetched)
+    pol_prefetch(w1, nw.W1, nw.b1, K0p, wave, lane);               // (in flight while the rows are fetched)
     // ---- the tile's rows -> LDS; padding columns and the rows past M stay zero ----
     const int rows = (M - r0 < POL_ROWS) ? M - r0 : POL_ROWS;
-    for (int i = tid; i < POL_ROWS * (ldx / 2); i += POL_THREADS) *(float2*)(X + 2 * i) = make_float2(0.0f, 0.0f);
+    pol_zero_tile(X, ldx, tid);
     __syncthreads();
-    const float* src = io.X + (size_t)r0 * (size_t)io.ldx;
-    const size_t lds = (size_t)io.ldx;
-    if (pa.vec2) {
-      // two floats per lane: ldx and obs_dim even and the base 8-byte aligned, so no pair straddles two rows or an 8-byte boundary
-      for (int i = 2 * tid; i < rows * K0; i += 2 * POL_THREADS) {
-        const int row = i / K0, c = i - row * K0;
-        *(float2*)(X + row * ldx + c) = *(const float2*)(src + row * lds + c);
-      }
-    } else {
-      for (int i = tid; i < rows * K0; i += POL_THREADS) {
-        const int row = i / K0, c = i - row * K0;
-        X[row * ldx + c] = src[row * lds + c];
-      }
-    }
-    __syncthreads();
-    pol_prefetch(w2, W2, b2, POL_H1, wave, lane);                  // (the next layer's weights: in flight during this layer)
-    pol_layer<POL_H1 / 16, 1, false, false>(X, ldx, w1, b1, K0p, wave, lane, Y1, ld1, nullptr);
-    __syncthreads();
-    pol_prefetch(w3, W3, b3, POL_H2, wave, lane);
-    pol_layer<POL_H2 / 16, 1, false, false>(Y1, ld1, w2, b2, POL_H1, wave, lane, Y2, ld2, nullptr);
-    __syncthreads();
-    pol_prefetch(w4, W4, b4, POL_H3, wave, lane);
-    pol_layer<POL_H3 / 16, 2, false, false>(Y2, ld2, w3, b3, POL_H2, wave, lane, Y3, ld3, nullptr);
-    __syncthreads();
-    if (wave != 0) return;
+    if (pa.vec2) pop_fill_rows<float2>(X, ldx, io, r0, rows, tid);
+    else pop_fill_rows<float>(X, ldx, io, r0, rows, tid);
     f32x4 o[1][POL_MT];
-    pol_layer<1, 2, true, false>(Y3, ld3, w4, b4, POL_H3, 0, lane, nullptr, 0, o);
+    pol_trunk<false>(X, K0, nw, w1, nullptr, wave, lane, o);      // (no log-std: nothing is sampled)
+    if (wave != 0) return;
     const int n = lane & 15, g = lane >> 4;
-    const int nc = n < 2 ? n : 0;
-    // the action map of this lane's component: launch arguments picked by a select, as in k6_policy_act
-    float cl0 = io.clip_lo[0], cl1 = io.clip_lo[1], ch0 = io.clip_hi[0], ch1 = io.clip_hi[1];
-    float am0 = io.act_mid[0], am1 = io.act_mid[1], ah0 = io.act_half[0], ah1 = io.act_half[1];
-    asm volatile("" : "+s"(cl0), "+s"(cl1), "+s"(ch0), "+s"(ch1), "+s"(am0), "+s"(am1), "+s"(ah0), "+s"(ah1));   // (or the selects become indexed loads)
-    const float clip_lo = nc ? cl1 : cl0, clip_hi = nc ? ch1 : ch0, act_mid = nc ? am1 : am0, act_half = nc ? ah1 : ah0;
+    const PolActMap map = pol_act_map(io, pol_comp(lane));
 #pragma unroll
     for (int u = 0; u < POL_MT; u++)
 #pragma unroll
@@ -103,10 +76,7 @@ __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k11_pop
         if (n < 2 && rr < rows) {
           const float mu = o[0][u][i];
           if (io.mu) io.mu[2 * (size_t)row + n] = mu;
-          if (io.action) {
-            const float ac = fminf(fmaxf(mu, clip_lo), clip_hi);
-            io.action[(size_t)row * (size_t)io.action_ld + n] = act_mid + act_half * ac;
-          }
+          if (io.action) io.action[(size_t)row * (size_t)io.action_ld + n] = map(mu);
         }
       }
   }
@@ -117,20 +87,14 @@ __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k11_pop
 }
 
 // ---- counter-based noise: (seed, generation, pair, element) -> eps, unit variance, bit-reproducible on the host ----
-// splitmix64 finaliser (k6_policy.hip's pol_mix)
-__device__ __forceinline__ unsigned long long pop_mix(unsigned long long z) {
-  z += 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
+// (pol_mix: the splitmix64 finaliser of auv_policy_forward.h)
 // the part of the key all elements of a launch share
 __device__ __forceinline__ unsigned long long pop_key(unsigned long long seed, unsigned long long generation) {
-  return pop_mix(seed ^ (generation * 0xd1342543de82ef95ull));
+  return pol_mix(seed ^ (generation * 0xd1342543de82ef95ull));
 }
 // c = float32(1 / sqrt(4 (65536^2 - 1) / 12)), formed on the host
 __device__ __forceinline__ float pop_eps(unsigned long long key, unsigned int pair, unsigned int i, float c) {
-  const unsigned long long h = pop_mix(pop_mix(key ^ (unsigned long long)pair) ^ (unsigned long long)i);
+  const unsigned long long h = pol_mix(pol_mix(key ^ (unsigned long long)pair) ^ (unsigned long long)i);
   const int S = (int)(h & 0xffffu) + (int)((h >> 16) & 0xffffu) + (int)((h >> 32) & 0xffffu) + (int)(h >> 48);
   return __fmul_rn((float)(S - 131070), c);                     // |S - 131070| < 2^24: the conversion is exact
 }

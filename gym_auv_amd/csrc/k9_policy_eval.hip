@@ -3,15 +3,15 @@
 // agent in its enjoy / play / test modes -- agent.predict(obs, deterministic=True), scripts/run.py:175, 273, 567 -- plus the two
 // questions a planner and an update ask: what is this state worth, how likely was this action.
 //
-// The matrix part IS k6_policy_act's exact-f32 path: the same workgroup (16 rows of ONE net, eight waves), the same LDS tiles and
-// row strides, pol_prefetch / pol_layer in the same order with the same template arguments -- so the mean and the value of a row are
-// the same k-ordered fmaf chains, bit for bit, as the rollout launch computes for that row (tests/test_gpu_policy_eval.py).  What
-// differs is where rows come from (a strided matrix, optionally gathered through an index) and the epilogue: the mean itself, the
-// deterministic action (k6's action map applied to a = mu), the value, and log pi(a) of GIVEN actions written as k6 writes it.
+// The matrix part is the forward pass k6_policy_act runs (auv_policy_forward.h: pol_trunk<false>, the same workgroup of 16 rows of ONE
+// net and eight waves, the same LDS tiles) -- so the mean and the value of a row are the same k-ordered fmaf chains, bit for bit, as
+// the rollout launch computes for that row (tests/test_gpu_policy_eval.py).  What this file holds is what differs: where rows come from
+// (a strided matrix, optionally gathered through an index) and what is stored: the mean itself, the deterministic action (the shared
+// action map applied to a = mu), the value, and log pi(a) of GIVEN actions (pol_logp, the function the rollout launch calls).
 //
 // Also here: the value-terminated score of a shooting planner's candidates (auv_plan_score_v), auv_plan_score's loop with one
 // more term for a candidate that saw no done.
-#include "auv_policy_mfma.h"
+#include "auv_policy_forward.h"
 
 namespace {
 
@@ -20,6 +20,20 @@ struct EvalArgs {
   int32_t net0;                      // blockIdx.y = 0 evaluates this net (0 policy, 1 value): only the nets asked for are launched
   int32_t vec2;                      // every source row starts 8-byte aligned and holds an even number of floats (host-proven)
 };
+
+// rows of a strided matrix, optionally gathered through ev.idx, -> the tile.  V = float2: ldx and obs_dim even and the base 8-byte
+// aligned, so no pair straddles two rows or an 8-byte boundary
+template <class V>
+__device__ __forceinline__ void eval_fill_rows(float* X, const int ldx, const auv_policy_eval_t& ev, const int r0, const int rows, const int tid) {
+  constexpr int W = sizeof(V) / sizeof(float);
+  const int K0 = ev.obs_dim;
+  const size_t lds = (size_t)ev.ldx;
+  for (int i = W * tid; i < rows * K0; i += W * POL_THREADS) {
+    const int row = i / K0, c = i - row * K0;
+    const size_t srow = ev.idx ? (size_t)ev.idx[r0 + row] : (size_t)(r0 + row);
+    *(V*)(X + row * ldx + c) = *(const V*)(ev.X + srow * lds + c);
+  }
+}
 
 // grid (ceil(M / 16), nets launched)
 __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k9_policy_eval(EvalArgs ea) {   // (two workgroups per CU, as k6)
@@ -30,70 +44,25 @@ __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k9_poli
   const int M = ev.M;
   const int r0 = blockIdx.x * POL_ROWS;                          // first row of the tile (M <= 2^31 - 1: no overflow)
   const int K0 = ev.obs_dim, K0p = pol_pad16(K0);
-  const int ldx = K0p + 8, ld1 = POL_H1 + 8, ld2 = POL_H2 + 8, ld3 = POL_H3 + 8;
   float* X = (float*)smem;
-  float* Y1 = X + pol_lds_x_floats(K0);
-  float* Y2 = X;                                                 // (X is dead once layer 1 is through: a barrier lies in between)
-  float* Y3 = Y1;                                                // (Y1 is dead once layer 2 is through)
-  const float* P = ev.params + (size_t)net * pol_net_floats(K0);
-  const float* W1 = P;
-  const float* b1 = W1 + (size_t)POL_H1 * K0p;
-  const float* W2 = b1 + POL_H1;
-  const float* b2 = W2 + (size_t)POL_H2 * POL_H1;
-  const float* W3 = b2 + POL_H2;
-  const float* b3 = W3 + (size_t)POL_H3 * POL_H2;
-  const float* W4 = b3 + POL_H3;
-  const float* b4 = W4 + (size_t)POL_OUT * POL_H3;
+  const int ldx = pol_ldx(K0);
+  const PolNet nw = pol_net_ptrs(ev.params + (size_t)net * pol_net_floats(K0), K0);
   PolW<POL_H1 / 16, false> w1;
-  PolW<POL_H2 / 16, false> w2;
-  PolW<POL_H3 / 16, false> w3;
-  PolW<1, false> w4;
-  pol_prefetch(w1, W1, b1, K0p, wave, lane);                       // (in flight while the rows are fetched)
+  pol_prefetch(w1, nw.W1, nw.b1, K0p, wave, lane);                 // (in flight while the rows are fetched)
   // ---- the tile's rows -> LDS; padding columns and the rows past M stay zero ----
   const int rows = (M - r0 < POL_ROWS) ? M - r0 : POL_ROWS;
-  for (int i = tid; i < POL_ROWS * (ldx / 2); i += POL_THREADS) *(float2*)(X + 2 * i) = make_float2(0.0f, 0.0f);
+  pol_zero_tile(X, ldx, tid);
   __syncthreads();
-  const size_t lds = (size_t)ev.ldx;
-  if (ea.vec2) {
-    // two floats per lane: ldx and obs_dim even and the base 8-byte aligned, so no pair straddles two rows or an 8-byte boundary
-    for (int i = 2 * tid; i < rows * K0; i += 2 * POL_THREADS) {
-      const int row = i / K0, c = i - row * K0;
-      const size_t srow = ev.idx ? (size_t)ev.idx[r0 + row] : (size_t)(r0 + row);
-      *(float2*)(X + row * ldx + c) = *(const float2*)(ev.X + srow * lds + c);
-    }
-  } else {
-    for (int i = tid; i < rows * K0; i += POL_THREADS) {
-      const int row = i / K0, c = i - row * K0;
-      const size_t srow = ev.idx ? (size_t)ev.idx[r0 + row] : (size_t)(r0 + row);
-      X[row * ldx + c] = ev.X[srow * lds + c];
-    }
-  }
-  __syncthreads();
-  pol_prefetch(w2, W2, b2, POL_H1, wave, lane);                    // (the next layer's weights: in flight during this layer)
-  pol_layer<POL_H1 / 16, 1, false, false>(X, ldx, w1, b1, K0p, wave, lane, Y1, ld1, nullptr);
-  __syncthreads();
-  pol_prefetch(w3, W3, b3, POL_H2, wave, lane);
-  pol_layer<POL_H2 / 16, 1, false, false>(Y1, ld1, w2, b2, POL_H1, wave, lane, Y2, ld2, nullptr);
-  __syncthreads();
-  pol_prefetch(w4, W4, b4, POL_H3, wave, lane);
-  // (the log-std with them: ahead of the barrier, so that the request is not moved down to its use)
-  const int nc = (lane & 15) < 2 ? (lane & 15) : 0;
+  if (ea.vec2) eval_fill_rows<float2>(X, ldx, ev, r0, rows, tid);
+  else eval_fill_rows<float>(X, ldx, ev, r0, rows, tid);
   const bool want_lp = ev.logp != nullptr;                       // (uniform)
-  float ls = 0.0f;
-  if (wave == 0 && net == 0 && want_lp) ls = (ev.params + 2 * pol_net_floats(K0))[nc];
-  pol_layer<POL_H3 / 16, 2, false, false>(Y2, ld2, w3, b3, POL_H2, wave, lane, Y3, ld3, nullptr);
-  __syncthreads();
-  if (wave != 0) return;
   f32x4 o[1][POL_MT];
-  pol_layer<1, 2, true, false>(Y3, ld3, w4, b4, POL_H3, 0, lane, nullptr, 0, o);
+  const float ls = pol_trunk<false>(X, K0, nw, w1, (wave == 0 && net == 0 && want_lp) ? ev.params + 2 * pol_net_floats(K0) : nullptr, wave, lane, o);
+  if (wave != 0) return;
   const int n = lane & 15, g = lane >> 4;
   if (net == 0) {
     const float sigma = expf(ls);
-    // the action map of this lane's component: launch arguments picked by a select, as in k6_policy_act
-    float cl0 = ev.clip_lo[0], cl1 = ev.clip_lo[1], ch0 = ev.clip_hi[0], ch1 = ev.clip_hi[1];
-    float am0 = ev.act_mid[0], am1 = ev.act_mid[1], ah0 = ev.act_half[0], ah1 = ev.act_half[1];
-    asm volatile("" : "+s"(cl0), "+s"(cl1), "+s"(ch0), "+s"(ch1), "+s"(am0), "+s"(am1), "+s"(ah0), "+s"(ah1));   // (or the selects become indexed loads)
-    const float clip_lo = nc ? cl1 : cl0, clip_hi = nc ? ch1 : ch0, act_mid = nc ? am1 : am0, act_half = nc ? ah1 : ah0;
+    const PolActMap map = pol_act_map(ev, pol_comp(lane));
 #pragma unroll
     for (int u = 0; u < POL_MT; u++)
 #pragma unroll
@@ -104,18 +73,13 @@ __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k9_poli
         const float mu = o[0][u][i];
         float lp = 0.0f;
         if (want_lp) {
-          // log pi(a): k6_policy.hip's expression, operation for operation (the bits of LP[t] for the a the rollout stored)
+          // log pi(a): the rollout launch's own function (the bits of LP[t] for the a the rollout stored)
           const float a = live ? ev.A[2 * (size_t)row + n] : mu;
-          const float z = (a - mu) / sigma;
-          lp = -0.5f * z * z - ls - POL_LOG_SQRT_2PI;
-          lp += __shfl_xor(lp, 1, AUV_WAVE);                     // the two components sit on neighbouring lanes
+          lp = pol_logp(a, mu, sigma, ls);
         }
         if (live) {
           if (ev.mu) ev.mu[2 * (size_t)row + n] = mu;
-          if (ev.action) {
-            const float ac = fminf(fmaxf(mu, clip_lo), clip_hi);
-            ev.action[(size_t)row * (size_t)ev.action_ld + n] = act_mid + act_half * ac;
-          }
+          if (ev.action) ev.action[(size_t)row * (size_t)ev.action_ld + n] = map(mu);
           if (want_lp && n == 0) ev.logp[row] = lp;
         }
       }

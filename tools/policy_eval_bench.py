@@ -59,7 +59,7 @@ if not args.skip_plan:                                     # (the bank's worker 
     from gym_auv_amd.world import build_bank_parallel
     bank = build_bank_parallel("moving_obstacles_world", 1000 + np.arange(128), procs=16)
 
-sha = hashlib.sha256(open(_capi.LIB_PATH, "rb").read()).hexdigest()
+sha = hashlib.sha256(open(os.environ.get("AUV_HIP_LIB") or _capi.LIB_PATH, "rb").read()).hexdigest()   # (the library the loader picks)
 rows = []
 ok = True
 with torch.no_grad():
