@@ -28,12 +28,12 @@ from gym_auv_amd.policy import FusedActorCritic  # noqa: E402
 from gym_auv_amd.world import build_world, pack_bank  # noqa: E402
 
 
-def load_policy(ckpt, obs_dim, device, seed=0):
+def load_policy(ckpt, obs_dim, device, seed=0, hidden=(256, 128, 64)):
     """examples/ppo.py's ActorCritic, initialised (ckpt None) or with a state_dict loaded (a file holding the state_dict itself or a
     dict with it under "model")."""
     import ppo
     torch.manual_seed(seed)
-    net = ppo.ActorCritic(obs_dim).to(device)
+    net = ppo.ActorCritic(obs_dim, hidden=tuple(hidden)).to(device)
     if ckpt:
         sd = torch.load(ckpt, map_location=device)
         net.load_state_dict(sd["model"] if isinstance(sd, dict) and "model" in sd else sd)
@@ -99,6 +99,8 @@ def main():
     ap.add_argument("--frames", default=None, metavar="DIR", help="write frames of the first 16 environments every 50 steps: .npy stacks and .ppm pictures")
     ap.add_argument("--frame-stack", type=int, default=1, metavar="K",
                     help="the policy sees the last K observations as one row (examples/ppo.py --frames K; here --frames is the picture directory)")
+    ap.add_argument("--net-arch", default="256,128,64", metavar="H1,H2,H3",
+                    help="hidden widths of the checkpoint's nets (examples/ppo.py --net-arch): one of gym_auv_amd.policy.SUPPORTED_HIDDEN")
     ap.add_argument("--device", default="cuda:0")
     a = ap.parse_args()
     colav = a.task == "colav"
@@ -111,7 +113,7 @@ def main():
         warnings.simplefilter("ignore")
         env = BatchedAuvEnv(cfg, bank, a.envs, device=a.device, rewarder="colav" if colav else "pathfollow", auto_reset=True)
     env.reset()
-    net = load_policy(a.ckpt, a.frame_stack * env.obs_dim, a.device, a.seed)
+    net = load_policy(a.ckpt, a.frame_stack * env.obs_dim, a.device, a.seed, hidden=tuple(int(h) for h in a.net_arch.split(",")))
     kw = {}
     if a.act_space == "normalized":                        # the policy speaks [-1, 1]^2; the map stretches it onto the action space
         lo, hi = env.action_space.low, env.action_space.high

@@ -151,7 +151,7 @@ def average_gradients(params, world):
 def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print, worlds="fresh", regen=0, log_every=1,
           task="colav", step_mode=None, graph_rollout=False, sub_batches=4, minibatches=32,
           reward_scale=0.01, reward_clip=0.0, min_cumulative_reward=None, act_space="raw", ret_norm=False, orthogonal=False, ent_coef=0.01, log_std=-0.5, lr=2e-4,
-          fused_policy=True, graph_update=False, policy_bf16=False, feasibility_pooling=False, fused_update=False,
+          fused_policy=True, graph_update=False, policy_bf16=False, feasibility_pooling=False, fused_update=False, net_arch=(256, 128, 64),
           fused_bootstrap=False, frames=1):
     from gym_auv_amd import distributed as D
     from gym_auv_amd.batched_env import BatchedAuvEnv
@@ -200,7 +200,9 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
     frames = int(frames)
     if frames > 1 and not fused_policy:
         raise ValueError("--frames %d needs --fused-policy 1: the stacked rows are formed by the fused policy launch" % frames)
-    net = ActorCritic(frames * env.obs_dim, log_std=log_std, orthogonal=orthogonal).to(device)
+    # --net-arch: the hidden widths of both nets.  The fused policy launch is compiled for a closed list of them
+    # (gym_auv_amd.policy.SUPPORTED_HIDDEN) and refuses any other; the fused update (--fused-update 1) evaluates [256, 128, 64] only
+    net = ActorCritic(frames * env.obs_dim, hidden=tuple(int(h) for h in net_arch), log_std=log_std, orthogonal=orthogonal).to(device)
     params = list(net.parameters())
     pi_params, v_params = list(net.pi.parameters()) + [net.log_std], list(net.v.parameters())
     if world > 1:   # data parallel over GPUs: same initial weights, gradients averaged over RCCL
@@ -562,6 +564,9 @@ if __name__ == "__main__":
                          "0 (default): the torch module")
     ap.add_argument("--frames", type=int, default=1,
                     help="k > 1: the policy sees the last k observations as one row of k * obs_dim columns (frame stacking; needs --fused-policy 1)")
+    ap.add_argument("--net-arch", default="256,128,64", metavar="H1,H2,H3",
+                    help="hidden widths of the policy and the value net; with --fused-policy 1 one of 256,128,64 (the reference's) "
+                         "128,128,64  128,64,64  64,64,64; --fused-update 1 takes the reference's only")
     ap.add_argument("--step-mode", default=None, help="launch shape of a step (BatchedAuvEnv.STEP_MODES); default: the library's")
     ap.add_argument("--act-space", default="raw", choices=["raw", "normalized"])
     ap.add_argument("--ret-norm", type=int, default=0)
@@ -579,5 +584,5 @@ if __name__ == "__main__":
           task=a.task, step_mode=a.step_mode, graph_rollout=bool(a.graph_rollout), fused_policy=bool(a.fused_policy), graph_update=a.graph_update, policy_bf16=bool(a.policy_bf16),
           sub_batches=a.sub_batches, minibatches=a.minibatches, act_space=a.act_space, ret_norm=bool(a.ret_norm),
           orthogonal=bool(a.orthogonal), ent_coef=a.ent_coef, log_std=a.log_std, lr=a.lr, reward_clip=a.reward_clip,
-          min_cumulative_reward=a.min_cumulative_reward, feasibility_pooling=bool(a.feasibility_pooling), fused_update=bool(a.fused_update),
+          min_cumulative_reward=a.min_cumulative_reward, feasibility_pooling=bool(a.feasibility_pooling), fused_update=bool(a.fused_update), net_arch=tuple(int(h) for h in a.net_arch.split(",")),
           fused_bootstrap=bool(a.fused_bootstrap), frames=a.frames)

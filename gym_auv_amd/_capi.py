@@ -152,6 +152,16 @@ class AuvPolicyStack(C.Structure):
 MAX_FRAMES = 8
 
 
+class AuvPolicyArch(C.Structure):
+    """== auv_policy_arch_t (include/auv_hip.h): the hidden widths of a fused forward launch (the auv_policy_*_arch entries)"""
+    _fields_ = [("h1", C.c_int32), ("h2", C.c_int32), ("h3", C.c_int32)]
+
+
+# the closed list of hidden-width triples the forward launches are compiled for (csrc/auv_policy_mfma.h, POL_ARCH_LIST); the first is
+# the reference's net, the one every entry without _arch evaluates
+POLICY_ARCHS = ((256, 128, 64), (128, 128, 64), (128, 64, 64), (64, 64, 64))
+
+
 class AuvPolicyEval(C.Structure):
     """== auv_policy_eval_t (include/auv_hip.h): one evaluation of M observation rows (auv_policy_eval)"""
     _fields_ = [
@@ -251,6 +261,15 @@ def load_library(path: str = None) -> C.CDLL:
         "auv_policy_rollout_stacked": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(AuvPolicyStack), vp, vp, vp, i32, i32,
                                                  C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
         "auv_stack_frames": (C.c_int, [i32, vp, vp, vp, vp, vp, C.c_int64, i32, i32, i32, i32, i32, vp]),
+        "auv_policy_param_floats_arch": (sz, [i32, C.POINTER(AuvPolicyArch)]),
+        "auv_policy_act_arch": (C.c_int, [vp, i32, i32, C.POINTER(AuvPolicyIO), C.POINTER(AuvPolicyArch), vp]),
+        "auv_policy_rollout_arch": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(AuvPolicyIO), C.POINTER(AuvPolicyArch),
+                                              vp, vp, vp, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "auv_policy_act_stacked_arch": (C.c_int, [vp, i32, i32, C.POINTER(AuvPolicyStack), C.POINTER(AuvPolicyArch), vp]),
+        "auv_policy_rollout_stacked_arch": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(AuvPolicyStack),
+                                                      C.POINTER(AuvPolicyArch), vp, vp, vp, i32, i32, C.POINTER(C.c_int64),
+                                                      C.POINTER(C.c_int64)]),
+        "auv_policy_eval_arch": (C.c_int, [i32, C.POINTER(AuvPolicyEval), C.POINTER(AuvPolicyArch), vp]),
         "auv_step_pipelined_timed": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), vp, i32, vp, vp, vp, C.POINTER(C.c_float)]),
         "auv_streams_overlap": (C.c_int, [vp, vp, vp, C.POINTER(C.c_float)]),
         "auv_episode_log": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
@@ -332,6 +351,8 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_snapshot_row_bytes", "auv_snapshot_layout", "auv_snapshot", "auv_restore", "auv_snapshot_skipped", "auv_plan_score",
                     "auv_plan_score_v", "auv_policy_eval",
                     "auv_policy_act_stacked", "auv_policy_rollout_stacked", "auv_stack_frames",
+                    "auv_policy_param_floats_arch", "auv_policy_act_arch", "auv_policy_rollout_arch", "auv_policy_act_stacked_arch",
+                    "auv_policy_rollout_stacked_arch", "auv_policy_eval_arch",
                     "auv_population_member_floats", "auv_population_act", "auv_population_rollout", "auv_population_perturb", "auv_population_update",
                     "auv_ppo_param_floats", "auv_ppo_create", "auv_ppo_destroy", "auv_ppo_load", "auv_ppo_attach_policy", "auv_ppo_grad", "auv_ppo_adam",
                     "auv_ppo_grad_clone",

@@ -83,6 +83,21 @@ hipError_t auv_policy_stacked_prepare(int width);
 void auv_launch_policy_stacked(const auv_policy_stack_t& s, int e0, int ne, hipStream_t st, long long t_host = -1, long long gstep_host = -1);
 void auv_launch_stack_frames(const float* obs, const uint8_t* done, float* hist, int32_t* stk, float* out, long long ldx, int e0, int ne,
                              int obs_dim, int frames, int advance, hipStream_t st);
+// the forward launches for a hidden-width triple of the closed list (auv_policy_mfma.h, POL_ARCH_LIST; the reference's triple goes to
+// the launches above): k6_policy.hip, k9_policy_eval.hip, k12_policy_stacked.hip
+bool auv_policy_arch_listed(int h1, int h2, int h3);
+bool auv_policy_arch_is_ref(int h1, int h2, int h3);
+size_t auv_policy_param_floats_arch_impl(int h1, int h2, int h3, int obs_dim);
+size_t auv_policy_lds_bytes_arch(int h1, int h2, int h3, int obs_dim);
+hipError_t auv_policy_prepare_arch(int h1, int h2, int h3, int obs_dim);
+void auv_launch_policy_arch(int h1, int h2, int h3, const auv_policy_io_t& io, int e0, int ne, hipStream_t st, long long t_host = -1,
+                            long long gstep_host = -1);
+hipError_t auv_policy_eval_prepare_arch(int h1, int h2, int h3, int obs_dim);
+void auv_launch_policy_eval_arch(int h1, int h2, int h3, const auv_policy_eval_t& ev, bool want_pi, bool want_v, hipStream_t st);
+size_t auv_policy_stacked_lds_bytes_arch(int h1, int h2, int h3, int width);
+hipError_t auv_policy_stacked_prepare_arch(int h1, int h2, int h3, int width);
+void auv_launch_policy_stacked_arch(int h1, int h2, int h3, const auv_policy_stack_t& s, int e0, int ne, hipStream_t st, long long t_host = -1,
+                                    long long gstep_host = -1);
 void auv_launch_population_perturb(const float* theta, float* members, long long stride, int P, int obs_dim, float sigma, unsigned long long seed,
                                    unsigned long long generation, hipStream_t st);
 void auv_launch_population_update(float* theta, const float* w, float* grad, int P, int obs_dim, float sigma, float lr, unsigned long long seed,
@@ -2078,8 +2093,27 @@ int auv_render(auv_handle_t* h, void* stream, const int32_t* env_idx_host, int32
 
 size_t auv_policy_param_floats(int32_t obs_dim) { return obs_dim > 0 ? auv_policy_param_floats_impl(obs_dim) : 0; }
 
-static int check_policy_io(const auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const char* who) {
+// the hidden widths of a forward launch: the entries without _arch evaluate the reference's net
+static const auv_policy_arch_t POLICY_ARCH_REF = {256, 128, 64};
+static int check_policy_arch(const auv_policy_arch_t* a, const void* params_bf16, const char* who) {
+  if (!a) return fail(AUV_EINVAL, "%s: null arch", who);
+  if (!auv_policy_arch_listed(a->h1, a->h2, a->h3))
+    return fail(AUV_EINVAL, "%s: hidden widths (%d, %d, %d) are not compiled in: one of (256, 128, 64), (128, 128, 64), (128, 64, 64), (64, 64, 64)",
+                who, a->h1, a->h2, a->h3);
+  if (params_bf16 && !auv_policy_arch_is_ref(a->h1, a->h2, a->h3))
+    return fail(AUV_EINVAL, "%s: hidden widths (%d, %d, %d) are evaluated in exact f32 only (params_bf16 must be NULL)", who, a->h1, a->h2, a->h3);
+  return AUV_OK;
+}
+
+size_t auv_policy_param_floats_arch(int32_t obs_dim, const auv_policy_arch_t* arch) {
+  if (obs_dim <= 0 || !arch || !auv_policy_arch_listed(arch->h1, arch->h2, arch->h3)) return 0;
+  return auv_policy_param_floats_arch_impl(arch->h1, arch->h2, arch->h3, obs_dim);
+}
+
+static int check_policy_io(const auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const auv_policy_arch_t* a, const char* who) {
   if (!io) return fail(AUV_EINVAL, "%s: null io", who);
+  int rca = check_policy_arch(a, io->params_bf16, who);
+  if (rca) return rca;
   const int D = auv_obs_cols(h->d.cfg, h->d.pool_ns);
   if (io->obs_dim != D) return fail(AUV_EINVAL, "%s: obs_dim %d, the handle's observation has %d columns", who, io->obs_dim, D);
   if (e0 < 0 || ne < 1 || (int64_t)e0 + ne > h->d.n) return fail(AUV_EINVAL, "%s: slice [%d, %d) outside [0, %d)", who, e0, e0 + ne, h->d.n);
@@ -2090,18 +2124,26 @@ static int check_policy_io(const auv_handle_t* h, int32_t e0, int32_t ne, const 
     return fail(AUV_EINVAL, "%s: null buffer", who);
   if (((uintptr_t)io->params & 15) || ((uintptr_t)io->params_bf16 & 15) || ((uintptr_t)io->actions_out & 7) || ((uintptr_t)io->ctr & 7))
     return fail(AUV_EINVAL, "%s: params must be 16-byte, actions_out and ctr 8-byte aligned", who);
-  if (auv_policy_lds_bytes(io->obs_dim) > 160 * 1024) return fail(AUV_EINVAL, "%s: observation too wide for the policy kernel's LDS tile", who);
+  if (auv_policy_lds_bytes_arch(a->h1, a->h2, a->h3, io->obs_dim) > 160 * 1024)
+    return fail(AUV_EINVAL, "%s: observation too wide for the policy kernel's LDS tile", who);
   return AUV_OK;
 }
 
-int auv_policy_act(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, void* stream) {
+static int policy_act_impl(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const auv_policy_arch_t* a, void* stream,
+                           const char* who) {
   REQUIRE_READY(h);
-  int rc = check_policy_io(h, e0, ne, io, "auv_policy_act");
+  int rc = check_policy_io(h, e0, ne, io, a, who);
   if (rc) return rc;
-  HIP_TRY(auv_policy_prepare(io->obs_dim));
-  auv_launch_policy(*io, e0, ne, (hipStream_t)stream);
+  HIP_TRY(auv_policy_prepare_arch(a->h1, a->h2, a->h3, io->obs_dim));
+  auv_launch_policy_arch(a->h1, a->h2, a->h3, *io, e0, ne, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
+}
+int auv_policy_act(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, void* stream) {
+  return policy_act_impl(h, e0, ne, io, &POLICY_ARCH_REF, stream, "auv_policy_act");
+}
+int auv_policy_act_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const auv_policy_arch_t* arch, void* stream) {
+  return policy_act_impl(h, e0, ne, io, arch, stream, "auv_policy_act_arch");
 }
 
 int auv_gae(auv_handle_t* h, const float* R, const float* V, const float* Dn, const float* last_v, float gamma, float lam, float* adv_out,
@@ -2231,11 +2273,13 @@ int auv_plan_score_v(auv_handle_t* h, const float* reward_rec, const uint8_t* do
 }
 
 // ---- the policy on arbitrary rows (include/auv_hip.h, auv_policy_eval; kernel: k9_policy_eval.hip) ----
-int auv_policy_eval(int32_t device, const auv_policy_eval_t* ev, void* stream) {
+static int policy_eval_impl(int32_t device, const auv_policy_eval_t* ev, const auv_policy_arch_t* a, void* stream) {
   if (!ev) return fail(AUV_EINVAL, "auv_policy_eval: null ev");
+  int rca = check_policy_arch(a, nullptr, "auv_policy_eval");
+  if (rca) return rca;
   if (device < 0) return fail(AUV_EINVAL, "auv_policy_eval: device %d", device);
   if (ev->obs_dim < 1) return fail(AUV_EINVAL, "auv_policy_eval: obs_dim %d < 1", ev->obs_dim);
-  if (ev->obs_dim > 16384 || auv_policy_lds_bytes(ev->obs_dim) > 160 * 1024)
+  if (ev->obs_dim > 16384 || auv_policy_lds_bytes_arch(a->h1, a->h2, a->h3, ev->obs_dim) > 160 * 1024)
     return fail(AUV_EINVAL, "auv_policy_eval: obs_dim %d is too wide for the policy kernel's LDS tile", ev->obs_dim);
   if (ev->M < 0) return fail(AUV_EINVAL, "auv_policy_eval: M = %d < 0", ev->M);
   const bool want_pi = ev->mu || ev->action || ev->logp, want_v = ev->value != nullptr;
@@ -2250,10 +2294,14 @@ int auv_policy_eval(int32_t device, const auv_policy_eval_t* ev, void* stream) {
     return fail(AUV_EINVAL, "auv_policy_eval: float buffers must be 4-byte, idx 8-byte aligned");
   if (ev->M == 0) return AUV_OK;
   HIP_TRY(hipSetDevice(device));
-  HIP_TRY(auv_policy_eval_prepare(ev->obs_dim));
-  auv_launch_policy_eval(*ev, want_pi, want_v, (hipStream_t)stream);
+  HIP_TRY(auv_policy_eval_prepare_arch(a->h1, a->h2, a->h3, ev->obs_dim));
+  auv_launch_policy_eval_arch(a->h1, a->h2, a->h3, *ev, want_pi, want_v, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
+}
+int auv_policy_eval(int32_t device, const auv_policy_eval_t* ev, void* stream) { return policy_eval_impl(device, ev, &POLICY_ARCH_REF, stream); }
+int auv_policy_eval_arch(int32_t device, const auv_policy_eval_t* ev, const auv_policy_arch_t* arch, void* stream) {
+  return policy_eval_impl(device, ev, arch, stream);
 }
 
 // ---- rollouts: a launch that acts, then a step of the environment, per slice on its own stream, n_steps times ----
@@ -2292,39 +2340,53 @@ struct RolloutCounters {
   long long gstep(int i, int32_t k) const { return t0 ? gstep0[i] + k : -1; }
 };
 
-int auv_policy_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
-                       float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
-                       const int64_t* gstep0) {
+static int policy_rollout_impl(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
+                               const auv_policy_arch_t* a, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush,
+                               const int64_t* t0, const int64_t* gstep0, const char* who) {
   REQUIRE_READY(h);
   const RolloutCounters ctr = {t0, gstep0};
-  int rc = check_slices(h, n_slices, bounds, streams, "auv_policy_rollout");
+  int rc = check_slices(h, n_slices, bounds, streams, who);
   if (rc) return rc;
-  if (!ios || n_steps < 0 || !ctr.paired()) return fail(AUV_EINVAL, "auv_policy_rollout: bad arguments");
+  if (!ios || n_steps < 0 || !ctr.paired()) return fail(AUV_EINVAL, "%s: bad arguments", who);
   for (int i = 0; i < n_slices; i++) {
-    rc = check_policy_io(h, bounds[i], bounds[i + 1] - bounds[i], ios + i, "auv_policy_rollout");
+    rc = check_policy_io(h, bounds[i], bounds[i + 1] - bounds[i], ios + i, a, who);
     if (rc) return rc;
-    rc = check_actions(ios[i].actions_out, AUV_F32, "auv_policy_rollout");
+    rc = check_actions(ios[i].actions_out, AUV_F32, who);
     if (rc) return rc;
-    if (ctr.negative(i)) return fail(AUV_EINVAL, "auv_policy_rollout: negative counter for slice %d", i);
+    if (ctr.negative(i)) return fail(AUV_EINVAL, "%s: negative counter for slice %d", who, i);
   }
   PAIR_CHECK(h, obs_dev);
-  HIP_TRY(auv_policy_prepare(ios[0].obs_dim));
+  HIP_TRY(auv_policy_prepare_arch(a->h1, a->h2, a->h3, ios[0].obs_dim));
   return rollout_loop(
       h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].actions_out; },
       [&](int i, int32_t k, bool) {
-        auv_launch_policy(ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k), ctr.gstep(i, k));
+        auv_launch_policy_arch(a->h1, a->h2, a->h3, ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k),
+                               ctr.gstep(i, k));
       });
+}
+int auv_policy_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
+                       float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
+                       const int64_t* gstep0) {
+  return policy_rollout_impl(h, n_slices, bounds, streams, ios, &POLICY_ARCH_REF, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0,
+                             "auv_policy_rollout");
+}
+int auv_policy_rollout_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
+                            const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps,
+                            int32_t flush, const int64_t* t0, const int64_t* gstep0) {
+  return policy_rollout_impl(h, n_slices, bounds, streams, ios, arch, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0,
+                             "auv_policy_rollout_arch");
 }
 
 // ---- frame-stacked observations in the policy launch (include/auv_hip.h, auv_policy_stack; kernels: k12_policy_stacked.hip) ----
-static int check_policy_stack(const auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* s, const char* who) {
+static int check_policy_stack(const auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* s, const auv_policy_arch_t* a,
+                              const char* who) {
   if (!s) return fail(AUV_EINVAL, "%s: null io", who);
   if (s->frames < 1 || s->frames > AUV_MAX_FRAMES) return fail(AUV_EINVAL, "%s: frames = %d outside [1, %d]", who, s->frames, AUV_MAX_FRAMES);
-  int rc = check_policy_io(h, e0, ne, &s->io, who);
+  int rc = check_policy_io(h, e0, ne, &s->io, a, who);
   if (rc) return rc;
   if (s->io.params_bf16) return fail(AUV_EINVAL, "%s: stacked rows are evaluated in exact f32 only (params_bf16 must be NULL)", who);
   const int64_t width = (int64_t)s->frames * s->io.obs_dim;
-  if (width > 16384 || auv_policy_stacked_lds_bytes((int)width) > 160 * 1024)
+  if (width > 16384 || auv_policy_stacked_lds_bytes_arch(a->h1, a->h2, a->h3, (int)width) > 160 * 1024)
     return fail(AUV_EINVAL, "%s: %d frames of %d columns are too wide for the policy kernel's LDS tile", who, s->frames, s->io.obs_dim);
   if (s->frames > 1) {
     if (!s->hist || !s->stk) return fail(AUV_EINVAL, "%s: null hist or stk", who);
@@ -2333,40 +2395,62 @@ static int check_policy_stack(const auv_handle_t* h, int32_t e0, int32_t ne, con
   return AUV_OK;
 }
 
-int auv_policy_act_stacked(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* io, void* stream) {
+static int policy_act_stacked_impl(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* io, const auv_policy_arch_t* a,
+                                   void* stream, const char* who) {
   REQUIRE_READY(h);
-  int rc = check_policy_stack(h, e0, ne, io, "auv_policy_act_stacked");
+  int rc = check_policy_stack(h, e0, ne, io, a, who);
   if (rc) return rc;
-  HIP_TRY(auv_policy_stacked_prepare(io->frames * io->io.obs_dim));
-  auv_launch_policy_stacked(*io, e0, ne, (hipStream_t)stream);
+  HIP_TRY(auv_policy_stacked_prepare_arch(a->h1, a->h2, a->h3, io->frames * io->io.obs_dim));
+  auv_launch_policy_stacked_arch(a->h1, a->h2, a->h3, *io, e0, ne, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }
+int auv_policy_act_stacked(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* io, void* stream) {
+  return policy_act_stacked_impl(h, e0, ne, io, &POLICY_ARCH_REF, stream, "auv_policy_act_stacked");
+}
+int auv_policy_act_stacked_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* io, const auv_policy_arch_t* arch,
+                                void* stream) {
+  return policy_act_stacked_impl(h, e0, ne, io, arch, stream, "auv_policy_act_stacked_arch");
+}
 
 // auv_policy_rollout's loop with the stacked launch: the same t0 / gstep0 contract, the same slices on their own streams
-int auv_policy_rollout_stacked(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_stack_t* ios,
-                               float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
-                               const int64_t* gstep0) {
+static int policy_rollout_stacked_impl(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
+                                       const auv_policy_stack_t* ios, const auv_policy_arch_t* a, float* obs_dev, float* reward_dev,
+                                       uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0,
+                                       const char* who) {
   REQUIRE_READY(h);
   const RolloutCounters ctr = {t0, gstep0};
-  int rc = check_slices(h, n_slices, bounds, streams, "auv_policy_rollout_stacked");
+  int rc = check_slices(h, n_slices, bounds, streams, who);
   if (rc) return rc;
-  if (!ios || n_steps < 0 || !ctr.paired()) return fail(AUV_EINVAL, "auv_policy_rollout_stacked: bad arguments");
+  if (!ios || n_steps < 0 || !ctr.paired()) return fail(AUV_EINVAL, "%s: bad arguments", who);
   for (int i = 0; i < n_slices; i++) {
-    rc = check_policy_stack(h, bounds[i], bounds[i + 1] - bounds[i], ios + i, "auv_policy_rollout_stacked");
+    rc = check_policy_stack(h, bounds[i], bounds[i + 1] - bounds[i], ios + i, a, who);
     if (rc) return rc;
-    rc = check_actions(ios[i].io.actions_out, AUV_F32, "auv_policy_rollout_stacked");
+    rc = check_actions(ios[i].io.actions_out, AUV_F32, who);
     if (rc) return rc;
-    if (ios[i].frames != ios[0].frames) return fail(AUV_EINVAL, "auv_policy_rollout_stacked: slice %d has %d frames, slice 0 has %d", i, ios[i].frames, ios[0].frames);
-    if (ctr.negative(i)) return fail(AUV_EINVAL, "auv_policy_rollout_stacked: negative counter for slice %d", i);
+    if (ios[i].frames != ios[0].frames) return fail(AUV_EINVAL, "%s: slice %d has %d frames, slice 0 has %d", who, i, ios[i].frames, ios[0].frames);
+    if (ctr.negative(i)) return fail(AUV_EINVAL, "%s: negative counter for slice %d", who, i);
   }
   PAIR_CHECK(h, obs_dev);
-  HIP_TRY(auv_policy_stacked_prepare(ios[0].frames * ios[0].io.obs_dim));
+  HIP_TRY(auv_policy_stacked_prepare_arch(a->h1, a->h2, a->h3, ios[0].frames * ios[0].io.obs_dim));
   return rollout_loop(
       h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].io.actions_out; },
       [&](int i, int32_t k, bool) {
-        auv_launch_policy_stacked(ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k), ctr.gstep(i, k));
+        auv_launch_policy_stacked_arch(a->h1, a->h2, a->h3, ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k),
+                                       ctr.gstep(i, k));
       });
+}
+int auv_policy_rollout_stacked(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_stack_t* ios,
+                               float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
+                               const int64_t* gstep0) {
+  return policy_rollout_stacked_impl(h, n_slices, bounds, streams, ios, &POLICY_ARCH_REF, obs_dev, reward_dev, done_dev, n_steps, flush, t0,
+                                     gstep0, "auv_policy_rollout_stacked");
+}
+int auv_policy_rollout_stacked_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
+                                    const auv_policy_stack_t* ios, const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev,
+                                    uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0) {
+  return policy_rollout_stacked_impl(h, n_slices, bounds, streams, ios, arch, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0,
+                                     "auv_policy_rollout_stacked_arch");
 }
 
 int auv_stack_frames(int32_t device, const float* obs, const uint8_t* done, float* hist, int32_t* stk, float* out, int64_t ldx, int32_t e0,

@@ -16,16 +16,17 @@ namespace {
 struct PolNet {
   const float *W1, *b1, *W2, *b2, *W3, *b3, *W4, *b4;
 };
+template <class A = PolArchRef>
 __device__ __forceinline__ PolNet pol_net_ptrs(const float* P, const int K0) {
   PolNet n;
   n.W1 = P;
-  n.b1 = n.W1 + (size_t)POL_H1 * pol_pad16(K0);
-  n.W2 = n.b1 + POL_H1;
-  n.b2 = n.W2 + (size_t)POL_H2 * POL_H1;
-  n.W3 = n.b2 + POL_H2;
-  n.b3 = n.W3 + (size_t)POL_H3 * POL_H2;
-  n.W4 = n.b3 + POL_H3;
-  n.b4 = n.W4 + (size_t)POL_OUT * POL_H3;
+  n.b1 = n.W1 + (size_t)A::H1 * pol_pad16(K0);
+  n.W2 = n.b1 + A::H1;
+  n.b2 = n.W2 + (size_t)A::H2 * A::H1;
+  n.W3 = n.b2 + A::H2;
+  n.b3 = n.W3 + (size_t)A::H3 * A::H2;
+  n.W4 = n.b3 + A::H3;
+  n.b4 = n.W4 + (size_t)POL_OUT * A::H3;
   return n;
 }
 
@@ -33,8 +34,10 @@ __device__ __forceinline__ PolNet pol_net_ptrs(const float* P, const int K0) {
 // (plain values, not a struct of pointers and strides: with one between here and pol_layer the layers' epilogues lost their paired
 // LDS stores and every launch 1 - 2 % of its time)
 __device__ __forceinline__ int pol_ldx(const int K0) { return pol_pad16(K0) + 8; }
-__device__ __forceinline__ float* pol_tile_y1(float* X, const int K0) { return X + pol_lds_x_floats(K0); }
-__device__ __forceinline__ float* pol_tiles_end(float* X, const int K0) { return pol_tile_y1(X, K0) + (size_t)POL_ROWS * (POL_H1 + 8); }
+template <class A = PolArchRef>
+__device__ __forceinline__ float* pol_tile_y1(float* X, const int K0) { return X + pol_lds_x_floats<A>(K0); }
+template <class A = PolArchRef>
+__device__ __forceinline__ float* pol_tiles_end(float* X, const int K0) { return pol_tile_y1<A>(X, K0) + pol_lds_y1_floats_h(A::H1, A::H3); }
 
 // the input tile starts as zeros: padding columns and the rows past the end stay so.  A barrier goes between this and the fill.
 __device__ __forceinline__ void pol_zero_tile(float* X, const int ldx, const int tid) {
@@ -62,34 +65,34 @@ __device__ __forceinline__ int pol_comp(const int lane) { return (lane & 15) < 2
 // ---- the forward pass: from the barrier behind the tile fill to the last layer's raw outputs (on wave 0, in `o`) ----
 // X: the filled tile of K0 columns.  w1: requested by the caller BEFORE it fetched the tile (pol_prefetch).  log_std: nullable, this
 // lane asks for its component's log-std (returned; 0 without).
-template <bool BF>
-__device__ __forceinline__ float pol_trunk(float* X, const int K0, const PolNet& n, PolW<POL_H1 / 16, BF>& w1, const float* log_std,
+// A: the hidden widths (PolArch; the reference's unless named); the sequence is the same for every one of them.
+template <bool BF, class A = PolArchRef>
+__device__ __forceinline__ float pol_trunk(float* X, const int K0, const PolNet& n, PolW<A::H1 / 16, BF>& w1, const float* log_std,
                                            const int wave, const int lane, f32x4 (*o)[POL_MT]) {
   const int K0p = pol_pad16(K0);
-  const int ldx = pol_ldx(K0), ld1 = POL_H1 + 8, ld2 = POL_H2 + 8, ld3 = POL_H3 + 8;
-  float* Y1 = pol_tile_y1(X, K0);
+  const int ldx = pol_ldx(K0), ld1 = A::H1 + 8, ld2 = A::H2 + 8, ld3 = A::H3 + 8;
+  float* Y1 = pol_tile_y1<A>(X, K0);
   float* Y2 = X;                                                   // (X is dead once layer 1 is through: a barrier lies in between)
   float* Y3 = Y1;                                                  // (Y1 is dead once layer 2 is through)
-  PolW<POL_H2 / 16, BF> w2;
-  PolW<POL_H3 / 16, BF> w3;
+  PolW<A::H2 / 16, BF> w2;
+  PolW<A::H3 / 16, BF> w3;
   PolW<1, BF> w4;
   __syncthreads();
-  pol_prefetch(w2, n.W2, n.b2, POL_H1, wave, lane);                // (the next layer's weights: in flight during this layer)
-  pol_layer<POL_H1 / 16, 1, false, BF>(X, ldx, w1, n.b1, K0p, wave, lane, Y1, ld1, nullptr);
+  pol_prefetch(w2, n.W2, n.b2, A::H1, wave, lane);                 // (the next layer's weights: in flight during this layer)
+  pol_layer<A::H1 / 16, 1, false, BF>(X, ldx, w1, n.b1, K0p, wave, lane, Y1, ld1, nullptr);
   __syncthreads();
-  pol_prefetch(w3, n.W3, n.b3, POL_H2, wave, lane);
-  pol_layer<POL_H2 / 16, 1, false, BF>(Y1, ld1, w2, n.b2, POL_H1, wave, lane, Y2, ld2, nullptr);
+  pol_prefetch(w3, n.W3, n.b3, A::H2, wave, lane);
+  pol_layer<A::H2 / 16, 1, false, BF>(Y1, ld1, w2, n.b2, A::H1, wave, lane, Y2, ld2, nullptr);
   __syncthreads();
-  pol_prefetch(w4, n.W4, n.b4, POL_H3, wave, lane);
+  pol_prefetch(w4, n.W4, n.b4, A::H3, wave, lane);
   // (the sampling's log-std with them: ahead of the barrier, so that the request is not moved down to its use)
   float ls = 0.0f;
   if (log_std) ls = log_std[pol_comp(lane)];
-  pol_layer<POL_H3 / 16, 2, false, BF>(Y2, ld2, w3, n.b3, POL_H2, wave, lane, Y3, ld3, nullptr);
+  pol_layer<A::H3 / 16, 2, false, BF>(Y2, ld2, w3, n.b3, A::H2, wave, lane, Y3, ld3, nullptr);
   __syncthreads();
-  if (wave == 0) pol_layer<1, 2, true, BF>(Y3, ld3, w4, n.b4, POL_H3, 0, lane, nullptr, 0, o);
+  if (wave == 0) pol_layer<1, 2, true, BF>(Y3, ld3, w4, n.b4, A::H3, 0, lane, nullptr, 0, o);
   return ls;
 }
-
 // ---- the counter-based generator of the policy launches ----
 // splitmix64 finaliser: (seed, step, row, component) -> 64 well-mixed bits
 __device__ __forceinline__ unsigned long long pol_mix(unsigned long long z) {

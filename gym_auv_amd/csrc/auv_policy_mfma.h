@@ -25,23 +25,54 @@ typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 #define POL_OUT 16                 // the last layer's outputs (2 actions / 1 value) padded to one n-tile
 #define POL_LOG_SQRT_2PI 0.9189385332046727f
 
-__host__ __device__ inline int pol_pad16(int x) { return (x + 31) & ~31; }   // (the k-step of pol_layer: 32)
-// floats of ONE packed net: W1 [H1][K0p] b1 [H1] W2 [H2][H1] b2 [H2] W3 [H3][H2] b3 [H3] W4 [16][H3] b4 [16]
-__host__ __device__ inline size_t pol_net_floats(int obs_dim) {
-  const size_t k0 = (size_t)pol_pad16(obs_dim);
-  return POL_H1 * k0 + POL_H1 + (size_t)POL_H2 * POL_H1 + POL_H2 + (size_t)POL_H3 * POL_H2 + POL_H3 + (size_t)POL_OUT * POL_H3 + POL_OUT;
+// The hidden widths of the forward launches (k6, k9, k12) are a compile-time parameter: obs -> H1 -> H2 -> H3 -> out, tanh.  What the
+// layer routine and the LDS carve-up below rely on is asserted here: every width a multiple of 64 (the row strides H + 8 stay = 8 mod 64
+// floats -- the bank argument below -- and K / 32 stays even where a layer runs with KS = 2), H1 >= H3 (Y3 lives in Y1's place).
+template <int H1_, int H2_, int H3_>
+struct PolArch {
+  static constexpr int H1 = H1_, H2 = H2_, H3 = H3_;
+  static_assert(H1_ > 0 && H2_ > 0 && H3_ > 0 && H1_ % 64 == 0 && H2_ % 64 == 0 && H3_ % 64 == 0, "hidden widths: multiples of 64");
+  static_assert(H1_ >= H3_, "Y3 re-uses Y1's LDS");
+};
+typedef PolArch<POL_H1, POL_H2, POL_H3> PolArchRef;   // the reference's net: the default, and the only one k8 and k11 evaluate
+// THE LIST of the other triples the forward launches are instantiated for: a triple more is one line here (every file instantiates,
+// and every host-side dispatch decides, through this macro)
+#define POL_ARCH_LIST(X) \
+  X(128, 128, 64)        \
+  X(128, 64, 64)         \
+  X(64, 64, 64)
+__host__ inline bool pol_arch_is_ref(int h1, int h2, int h3) { return h1 == POL_H1 && h2 == POL_H2 && h3 == POL_H3; }
+__host__ inline bool pol_arch_listed(int h1, int h2, int h3) {
+#define POL_ARCH_IS(a, b, c) if (h1 == (a) && h2 == (b) && h3 == (c)) return true;
+  POL_ARCH_LIST(POL_ARCH_IS)
+#undef POL_ARCH_IS
+  return pol_arch_is_ref(h1, h2, h3);
 }
 
-// LDS of a forward workgroup (carved up in auv_policy_forward.h: pol_ldx, pol_tile_y1, pol_trunk): X [ROWS][K0p + 8] | Y1 [ROWS][H1 + 8]; Y2 [ROWS][H2 + 8] re-uses X's
-// place (dead after layer 1), Y3 [ROWS][H3 + 8] Y1's (dead after layer 2).  Row strides = 8 mod 64 floats: the 16-byte reads of an
-// A operand -- 16 rows x 4 k-groups -- then touch every bank once.
-__host__ __device__ inline size_t pol_lds_x_floats(int obs_dim) {
-  const size_t x = (size_t)pol_pad16(obs_dim) + 8, y2 = POL_H2 + 8;
+__host__ __device__ inline int pol_pad16(int x) { return (x + 31) & ~31; }   // (the k-step of pol_layer: 32)
+// floats of ONE packed net: W1 [H1][K0p] b1 [H1] W2 [H2][H1] b2 [H2] W3 [H3][H2] b3 [H3] W4 [16][H3] b4 [16]
+__host__ __device__ inline size_t pol_net_floats_h(int h1, int h2, int h3, int obs_dim) {
+  const size_t k0 = (size_t)pol_pad16(obs_dim);
+  return h1 * k0 + h1 + (size_t)h2 * h1 + h2 + (size_t)h3 * h2 + h3 + (size_t)POL_OUT * h3 + POL_OUT;
+}
+template <class A = PolArchRef>
+__host__ __device__ inline size_t pol_net_floats(int obs_dim) { return pol_net_floats_h(A::H1, A::H2, A::H3, obs_dim); }
+
+// LDS of a forward workgroup (carved up in auv_policy_forward.h: pol_ldx, pol_tile_y1, pol_trunk): X [ROWS][max(K0p, H2) + 8] |
+// Y1 [ROWS][max(H1, H3) + 8]; Y2 [ROWS][H2 + 8] re-uses X's place (dead after layer 1), Y3 [ROWS][H3 + 8] Y1's (dead after layer 2).
+// Row strides = 8 mod 64 floats: the 16-byte reads of an A operand -- 16 rows x 4 k-groups -- then touch every bank once.
+__host__ __device__ inline size_t pol_lds_x_floats_h(int h2, int obs_dim) {
+  const size_t x = (size_t)pol_pad16(obs_dim) + 8, y2 = (size_t)h2 + 8;
   return POL_ROWS * (x > y2 ? x : y2);
 }
-__host__ __device__ inline size_t pol_lds_bytes(int obs_dim) {
-  return sizeof(float) * (pol_lds_x_floats(obs_dim) + (size_t)POL_ROWS * (POL_H1 + 8));
+__host__ __device__ inline size_t pol_lds_y1_floats_h(int h1, int h3) { return (size_t)POL_ROWS * ((h1 > h3 ? h1 : h3) + 8); }
+__host__ __device__ inline size_t pol_lds_bytes_h(int h1, int h2, int h3, int obs_dim) {
+  return sizeof(float) * (pol_lds_x_floats_h(h2, obs_dim) + pol_lds_y1_floats_h(h1, h3));
 }
+template <class A = PolArchRef>
+__host__ __device__ inline size_t pol_lds_x_floats(int obs_dim) { return pol_lds_x_floats_h(A::H2, obs_dim); }
+template <class A = PolArchRef>
+__host__ __device__ inline size_t pol_lds_bytes(int obs_dim) { return pol_lds_bytes_h(A::H1, A::H2, A::H3, obs_dim); }
 
 // tanh: 1 - 2 / (exp(2 x) + 1) with the hardware's exp2 and reciprocal (absolute error ~2e-7, far inside the 1e-5 of the
 // parity test; saturates correctly: exp -> inf gives 1, exp -> 0 gives -1) instead of the library's ~40-instruction tanhf

@@ -56,6 +56,9 @@ __device__ __forceinline__ void stk_advance(const int2 s, const bool done, const
 
 // LDS: k6's tiles for frames * obs_dim columns, and behind them (pos', age') of the tile's 16 rows
 __host__ __device__ inline size_t stk_lds_bytes(int width) { return pol_lds_bytes(width) + sizeof(int32_t) * 2 * POL_ROWS; }
+__host__ __device__ inline size_t stk_lds_bytes_h(int h1, int h2, int h3, int width) {
+  return pol_lds_bytes_h(h1, h2, h3, width) + sizeof(int32_t) * 2 * POL_ROWS;
+}
 
 // the stacked tile: frame 0 from the observation buffer (and, `store`, into the ring's slot pos'), frame j >= 1 from the ring where
 // the episode is old enough; every row also into dstO (nullable; O[t]'s rows of the tile are one contiguous range).  S: (pos', age')
@@ -84,8 +87,9 @@ __device__ __forceinline__ void stk_fill_ring(float* X, const int ldx, const auv
   }
 }
 
-// grid (ceil(ne / 16), 2): blockIdx.y = 0 the policy net, 1 the value net.
-__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k12_stacked_act(StackArgs pa) {   // (two workgroups per CU, as k6)
+// The launch's body, written once for every hidden-width triple A (PolArch, auv_policy_mfma.h).
+template <class A>
+__device__ __forceinline__ void stacked_act_body(const StackArgs& pa) {
   extern __shared__ __align__(16) unsigned char smem[];
   const auv_policy_io_t& io = pa.s.io;
   const int tid = threadIdx.x, wave = tid / AUV_WAVE, lane = tid % AUV_WAVE;
@@ -94,14 +98,14 @@ __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k12_sta
   const int K0 = F * io.obs_dim, K0p = pol_pad16(K0);            // the net's input width
   float* X = (float*)smem;
   const int ldx = pol_ldx(K0);
-  int32_t* S = (int32_t*)pol_tiles_end(X, K0);                               // [ROWS][2]: pos', age'
+  int32_t* S = (int32_t*)pol_tiles_end<A>(X, K0);                            // [ROWS][2]: pos', age'
   const PolAct p = pol_act_begin(io, pa.e0, pa.ne, pa.t_host, pa.gstep_host);
   const int tag = (int)(p.gstep % 0x7fffffull) + 1;              // 1 .. 2^23 - 1: tag << 8 stays below 2^31, the word stays positive
   bool keep = false;                                             // this thread stores its row's (pos', age') at the end
   int my_pos = 0, my_age = 0;
   if (p.act) {
-    const PolNet nw = pol_net_ptrs(io.params + (size_t)net * pol_net_floats(K0), K0);
-    PolW<POL_H1 / 16, false> w1;
+    const PolNet nw = pol_net_ptrs<A>(io.params + (size_t)net * pol_net_floats<A>(K0), K0);
+    PolW<A::H1 / 16, false> w1;
     pol_prefetch(w1, nw.W1, nw.b1, K0p, wave, lane);               // (in flight while the tile is formed)
     const int rows = (p.cnt - p.r0 < POL_ROWS) ? p.cnt - p.r0 : POL_ROWS;
     // ---- the history's step of the tile's rows: requested ahead of the barrier behind the zeroing ----
@@ -121,11 +125,21 @@ __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k12_sta
     else if ((io.obs_dim & 1) == 0) stk_fill_ring<float2>(X, ldx, pa.s, S, dstO, pa.e0 + p.r0, rows, net == 0, tid);
     else stk_fill_ring<float>(X, ldx, pa.s, S, dstO, pa.e0 + p.r0, rows, net == 0, tid);
     f32x4 o[1][POL_MT];
-    const float ls = pol_trunk<false>(X, K0, nw, w1, (wave == 0 && net == 0) ? io.params + 2 * pol_net_floats(K0) : nullptr, wave, lane, o);
+    const float ls = pol_trunk<false, A>(X, K0, nw, w1, (wave == 0 && net == 0) ? io.params + 2 * pol_net_floats<A>(K0) : nullptr, wave, lane, o);
     if (wave == 0) pol_act_sample(io, p, o, ls, lane);
   }
   if (keep) *(int2*)(pa.s.stk + 2 * (size_t)(pa.e0 + p.r0 + tid)) = make_int2(my_pos | (tag << 8), my_age);
   pol_act_end(io, p);
+}
+
+// grid (ceil(ne / 16), 2): blockIdx.y = 0 the policy net, 1 the value net.  The reference's triple ...
+__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k12_stacked_act(StackArgs pa) {   // (two workgroups per CU, as k6)
+  stacked_act_body<PolArchRef>(pa);
+}
+// ... and every other triple of POL_ARCH_LIST
+template <class A>
+__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) policy_stacked_arch(StackArgs pa) {
+  stacked_act_body<A>(pa);
 }
 
 // ---- the history update alone: stacked rows out[ne][ldx] of environments [e0, e0 + ne), no network ----
@@ -211,6 +225,35 @@ void auv_launch_policy_stacked(const auv_policy_stack_t& s, int e0, int ne, hipS
   pa.t_host = t_host, pa.gstep_host = gstep_host;
   const dim3 grid((ne + POL_ROWS - 1) / POL_ROWS, 2), block(POL_THREADS);
   hipLaunchKernelGGL(k12_stacked_act, grid, block, stk_lds_bytes(s.frames * s.io.obs_dim), st, pa);
+}
+
+// a listed hidden-width triple (the caller has checked): the reference's goes to the kernel above
+size_t auv_policy_stacked_lds_bytes_arch(int h1, int h2, int h3, int width) { return stk_lds_bytes_h(h1, h2, h3, width); }
+
+hipError_t auv_policy_stacked_prepare_arch(int h1, int h2, int h3, int width) {
+  if (pol_arch_is_ref(h1, h2, h3)) return auv_policy_stacked_prepare(width);
+  const size_t b = stk_lds_bytes_h(h1, h2, h3, width);
+  if (b <= 64 * 1024) return hipSuccess;
+#define POL_ARCH_PREPARE(a, b_, c) \
+  if (h1 == (a) && h2 == (b_) && h3 == (c)) \
+    return hipFuncSetAttribute((const void*)policy_stacked_arch<PolArch<a, b_, c>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  POL_ARCH_LIST(POL_ARCH_PREPARE)
+#undef POL_ARCH_PREPARE
+  return hipErrorInvalidValue;
+}
+
+void auv_launch_policy_stacked_arch(int h1, int h2, int h3, const auv_policy_stack_t& s, int e0, int ne, hipStream_t st, long long t_host,
+                                    long long gstep_host) {
+  if (pol_arch_is_ref(h1, h2, h3)) return auv_launch_policy_stacked(s, e0, ne, st, t_host, gstep_host);
+  StackArgs pa;
+  pa.s = s, pa.e0 = e0, pa.ne = ne;
+  pa.t_host = t_host, pa.gstep_host = gstep_host;
+  const dim3 grid((ne + POL_ROWS - 1) / POL_ROWS, 2), block(POL_THREADS);
+  const size_t lds = stk_lds_bytes_h(h1, h2, h3, s.frames * s.io.obs_dim);
+#define POL_ARCH_LAUNCH(a, b, c) \
+  if (h1 == (a) && h2 == (b) && h3 == (c)) hipLaunchKernelGGL((policy_stacked_arch<PolArch<a, b, c>>), grid, block, lds, st, pa);
+  POL_ARCH_LIST(POL_ARCH_LAUNCH)
+#undef POL_ARCH_LAUNCH
 }
 
 void auv_launch_stack_frames(const float* obs, const uint8_t* done, float* hist, int32_t* stk, float* out, long long ldx, int e0, int ne,

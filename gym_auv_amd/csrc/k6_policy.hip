@@ -35,9 +35,9 @@ struct PolicyArgs {
                                      // loop of launches); -1: both live on the device (io.ctr) and the launch moves them on itself
 };
 
-// grid (ceil(ne / 16), 2): blockIdx.y = 0 the policy net, 1 the value net.
-template <bool BF>
-__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k6_policy_act(PolicyArgs pa) {   // (two workgroups per CU)
+// The launch's body, written once for every hidden-width triple A (PolArch, auv_policy_mfma.h).
+template <class A, bool BF>
+__device__ __forceinline__ void policy_act_body(const PolicyArgs& pa) {
   extern __shared__ __align__(16) unsigned char smem[];
   const auv_policy_io_t& io = pa.io;
   const int tid = threadIdx.x, wave = tid / AUV_WAVE, lane = tid % AUV_WAVE;
@@ -46,16 +46,16 @@ __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k6_poli
   float* X = (float*)smem;
   const PolAct p = pol_act_begin(io, pa.e0, pa.ne, pa.t_host, pa.gstep_host);
   if (p.act) {
-    PolNet nw = pol_net_ptrs(io.params + (size_t)net * pol_net_floats(K0), K0);
+    PolNet nw = pol_net_ptrs<A>(io.params + (size_t)net * pol_net_floats<A>(K0), K0);
     if (BF) {
       // bf16 weights: the four matrices of a net back to back, half the floats each (biases and log_std stay in `params`)
-      const float* Q = (const float*)io.params_bf16 + (size_t)net * (pol_net_floats(K0) - POL_H1 - POL_H2 - POL_H3 - POL_OUT) / 2;
+      const float* Q = (const float*)io.params_bf16 + (size_t)net * (pol_net_floats<A>(K0) - A::H1 - A::H2 - A::H3 - POL_OUT) / 2;
       nw.W1 = Q;
-      nw.W2 = nw.W1 + (size_t)POL_H1 * K0p / 2;
-      nw.W3 = nw.W2 + (size_t)POL_H2 * POL_H1 / 2;
-      nw.W4 = nw.W3 + (size_t)POL_H3 * POL_H2 / 2;
+      nw.W2 = nw.W1 + (size_t)A::H1 * K0p / 2;
+      nw.W3 = nw.W2 + (size_t)A::H2 * A::H1 / 2;
+      nw.W4 = nw.W3 + (size_t)A::H3 * A::H2 / 2;
     }
-    PolW<POL_H1 / 16, BF> w1;
+    PolW<A::H1 / 16, BF> w1;
     pol_prefetch(w1, nw.W1, nw.b1, K0p, wave, lane);                 // (in flight while the observation tile is fetched)
     // ---- observation tile -> LDS (zero padded), and into the rollout (policy workgroup) ----
     const int rows = (p.cnt - p.r0 < POL_ROWS) ? p.cnt - p.r0 : POL_ROWS;
@@ -63,10 +63,21 @@ __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k6_poli
     __syncthreads();
     pol_act_fill_obs(X, io, p, pol_act_obs_out(io, p, K0), rows);
     f32x4 o[1][POL_MT];
-    const float ls = pol_trunk<BF>(X, K0, nw, w1, (wave == 0 && net == 0) ? io.params + 2 * pol_net_floats(K0) : nullptr, wave, lane, o);
+    const float ls = pol_trunk<BF, A>(X, K0, nw, w1, (wave == 0 && net == 0) ? io.params + 2 * pol_net_floats<A>(K0) : nullptr, wave, lane, o);
     if (wave == 0) pol_act_sample(io, p, o, ls, lane);
   }
   pol_act_end(io, p);
+}
+
+// grid (ceil(ne / 16), 2): blockIdx.y = 0 the policy net, 1 the value net.  The reference's triple (optionally on bf16 weights) ...
+template <bool BF>
+__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k6_policy_act(PolicyArgs pa) {   // (two workgroups per CU)
+  policy_act_body<PolArchRef, BF>(pa);
+}
+// ... and every other triple of POL_ARCH_LIST, exact f32 only
+template <class A>
+__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) policy_act_arch(PolicyArgs pa) {
+  policy_act_body<A, false>(pa);
 }
 
 // Generalised advantage estimation over a rollout (what stable-baselines' PPO2 runner does on the host after n_steps,
@@ -100,6 +111,12 @@ void auv_launch_gae(const float* R, const float* V, const float* Dn, const float
 size_t auv_policy_param_floats_impl(int obs_dim) { return 2 * pol_net_floats(obs_dim) + 4; }
 size_t auv_policy_lds_bytes(int obs_dim) { return pol_lds_bytes(obs_dim); }
 
+// ---- the same for a hidden-width triple (h1, h2, h3) ----
+bool auv_policy_arch_listed(int h1, int h2, int h3) { return pol_arch_listed(h1, h2, h3); }
+bool auv_policy_arch_is_ref(int h1, int h2, int h3) { return pol_arch_is_ref(h1, h2, h3); }
+size_t auv_policy_param_floats_arch_impl(int h1, int h2, int h3, int obs_dim) { return 2 * pol_net_floats_h(h1, h2, h3, obs_dim) + 4; }
+size_t auv_policy_lds_bytes_arch(int h1, int h2, int h3, int obs_dim) { return pol_lds_bytes_h(h1, h2, h3, obs_dim); }
+
 hipError_t auv_policy_prepare(int obs_dim) {
   const size_t b = pol_lds_bytes(obs_dim);
   if (b <= 64 * 1024) return hipSuccess;
@@ -115,4 +132,31 @@ void auv_launch_policy(const auv_policy_io_t& io, int e0, int ne, hipStream_t st
   const dim3 grid((ne + POL_ROWS - 1) / POL_ROWS, 2), block(POL_THREADS);
   if (io.params_bf16) hipLaunchKernelGGL(k6_policy_act<true>, grid, block, pol_lds_bytes(io.obs_dim), st, pa);
   else hipLaunchKernelGGL(k6_policy_act<false>, grid, block, pol_lds_bytes(io.obs_dim), st, pa);
+}
+
+// a listed triple (the caller has checked; params_bf16 is NULL unless it is the reference's): the reference's goes to the kernels above
+hipError_t auv_policy_prepare_arch(int h1, int h2, int h3, int obs_dim) {
+  if (pol_arch_is_ref(h1, h2, h3)) return auv_policy_prepare(obs_dim);
+  const size_t b = pol_lds_bytes_h(h1, h2, h3, obs_dim);
+  if (b <= 64 * 1024) return hipSuccess;
+#define POL_ARCH_PREPARE(a, b_, c) \
+  if (h1 == (a) && h2 == (b_) && h3 == (c)) \
+    return hipFuncSetAttribute((const void*)policy_act_arch<PolArch<a, b_, c>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  POL_ARCH_LIST(POL_ARCH_PREPARE)
+#undef POL_ARCH_PREPARE
+  return hipErrorInvalidValue;
+}
+
+void auv_launch_policy_arch(int h1, int h2, int h3, const auv_policy_io_t& io, int e0, int ne, hipStream_t st, long long t_host,
+                            long long gstep_host) {
+  if (pol_arch_is_ref(h1, h2, h3)) return auv_launch_policy(io, e0, ne, st, t_host, gstep_host);
+  PolicyArgs pa;
+  pa.io = io, pa.e0 = e0, pa.ne = ne;
+  pa.t_host = t_host, pa.gstep_host = gstep_host;
+  const dim3 grid((ne + POL_ROWS - 1) / POL_ROWS, 2), block(POL_THREADS);
+#define POL_ARCH_LAUNCH(a, b, c) \
+  if (h1 == (a) && h2 == (b) && h3 == (c)) \
+    hipLaunchKernelGGL((policy_act_arch<PolArch<a, b, c>>), grid, block, (pol_lds_bytes<PolArch<a, b, c>>(io.obs_dim)), st, pa);
+  POL_ARCH_LIST(POL_ARCH_LAUNCH)
+#undef POL_ARCH_LAUNCH
 }

@@ -35,8 +35,9 @@ __device__ __forceinline__ void eval_fill_rows(float* X, const int ldx, const au
   }
 }
 
-// grid (ceil(M / 16), nets launched)
-__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k9_policy_eval(EvalArgs ea) {   // (two workgroups per CU, as k6)
+// The launch's body, written once for every hidden-width triple A (PolArch, auv_policy_mfma.h).
+template <class A>
+__device__ __forceinline__ void policy_eval_body(const EvalArgs& ea) {
   extern __shared__ __align__(16) unsigned char smem[];
   const auv_policy_eval_t& ev = ea.ev;
   const int tid = threadIdx.x, wave = tid / AUV_WAVE, lane = tid % AUV_WAVE;
@@ -46,8 +47,8 @@ __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k9_poli
   const int K0 = ev.obs_dim, K0p = pol_pad16(K0);
   float* X = (float*)smem;
   const int ldx = pol_ldx(K0);
-  const PolNet nw = pol_net_ptrs(ev.params + (size_t)net * pol_net_floats(K0), K0);
-  PolW<POL_H1 / 16, false> w1;
+  const PolNet nw = pol_net_ptrs<A>(ev.params + (size_t)net * pol_net_floats<A>(K0), K0);
+  PolW<A::H1 / 16, false> w1;
   pol_prefetch(w1, nw.W1, nw.b1, K0p, wave, lane);                 // (in flight while the rows are fetched)
   // ---- the tile's rows -> LDS; padding columns and the rows past M stay zero ----
   const int rows = (M - r0 < POL_ROWS) ? M - r0 : POL_ROWS;
@@ -57,7 +58,7 @@ __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k9_poli
   else eval_fill_rows<float>(X, ldx, ev, r0, rows, tid);
   const bool want_lp = ev.logp != nullptr;                       // (uniform)
   f32x4 o[1][POL_MT];
-  const float ls = pol_trunk<false>(X, K0, nw, w1, (wave == 0 && net == 0 && want_lp) ? ev.params + 2 * pol_net_floats(K0) : nullptr, wave, lane, o);
+  const float ls = pol_trunk<false, A>(X, K0, nw, w1, (wave == 0 && net == 0 && want_lp) ? ev.params + 2 * pol_net_floats<A>(K0) : nullptr, wave, lane, o);
   if (wave != 0) return;
   const int n = lane & 15, g = lane >> 4;
   if (net == 0) {
@@ -92,6 +93,16 @@ __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k9_poli
         if (rr < rows) ev.value[r0 + rr] = o[0][u][i];
       }
   }
+}
+
+// grid (ceil(M / 16), nets launched).  The reference's triple ...
+__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k9_policy_eval(EvalArgs ea) {   // (two workgroups per CU, as k6)
+  policy_eval_body<PolArchRef>(ea);
+}
+// ... and every other triple of POL_ARCH_LIST
+template <class A>
+__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) policy_eval_arch(EvalArgs ea) {
+  policy_eval_body<A>(ea);
 }
 
 // ---- the value-terminated score of a shooting planner's candidates ----
@@ -169,6 +180,33 @@ void auv_launch_policy_eval(const auv_policy_eval_t& ev, bool want_pi, bool want
   ea.vec2 = ((ev.ldx & 1) == 0 && (ev.obs_dim & 1) == 0 && ((uintptr_t)ev.X & 7) == 0) ? 1 : 0;
   const dim3 grid((unsigned)(((long long)ev.M + POL_ROWS - 1) / POL_ROWS), (want_pi ? 1 : 0) + (want_v ? 1 : 0)), block(POL_THREADS);
   hipLaunchKernelGGL(k9_policy_eval, grid, block, pol_lds_bytes(ev.obs_dim), st, ea);
+}
+
+// a listed hidden-width triple (the caller has checked): the reference's goes to the kernel above
+hipError_t auv_policy_eval_prepare_arch(int h1, int h2, int h3, int obs_dim) {
+  if (pol_arch_is_ref(h1, h2, h3)) return auv_policy_eval_prepare(obs_dim);
+  const size_t b = pol_lds_bytes_h(h1, h2, h3, obs_dim);
+  if (b <= 64 * 1024) return hipSuccess;
+#define POL_ARCH_PREPARE(a, b_, c) \
+  if (h1 == (a) && h2 == (b_) && h3 == (c)) \
+    return hipFuncSetAttribute((const void*)policy_eval_arch<PolArch<a, b_, c>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  POL_ARCH_LIST(POL_ARCH_PREPARE)
+#undef POL_ARCH_PREPARE
+  return hipErrorInvalidValue;
+}
+
+void auv_launch_policy_eval_arch(int h1, int h2, int h3, const auv_policy_eval_t& ev, bool want_pi, bool want_v, hipStream_t st) {
+  if (pol_arch_is_ref(h1, h2, h3)) return auv_launch_policy_eval(ev, want_pi, want_v, st);
+  EvalArgs ea;
+  ea.ev = ev;
+  ea.net0 = want_pi ? 0 : 1;
+  ea.vec2 = ((ev.ldx & 1) == 0 && (ev.obs_dim & 1) == 0 && ((uintptr_t)ev.X & 7) == 0) ? 1 : 0;
+  const dim3 grid((unsigned)(((long long)ev.M + POL_ROWS - 1) / POL_ROWS), (want_pi ? 1 : 0) + (want_v ? 1 : 0)), block(POL_THREADS);
+#define POL_ARCH_LAUNCH(a, b, c) \
+  if (h1 == (a) && h2 == (b) && h3 == (c)) \
+    hipLaunchKernelGGL((policy_eval_arch<PolArch<a, b, c>>), grid, block, (pol_lds_bytes<PolArch<a, b, c>>(ev.obs_dim)), st, ea);
+  POL_ARCH_LIST(POL_ARCH_LAUNCH)
+#undef POL_ARCH_LAUNCH
 }
 
 void auv_launch_plan_score_v(const float* reward, const uint8_t* done, const float* terminal, int T, int n, int group, float gamma, float* score,

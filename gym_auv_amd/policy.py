@@ -20,6 +20,10 @@ net whose first layers take k * obs_dim columns evaluates every environment on i
 is younger than j steps.  The history lives on the device (`fused.stack`: gym_auv_amd/framestack.py) and is moved on by the policy launch
 itself; O is then [T, N, k * obs_dim] and everything behind the first layer -- FusedPPOUpdate, policy_eval, the planner -- takes those rows
 as they are.  Call `fused.reset_frames()` behind an `env.reset()`.
+
+Hidden widths: read off `net.pi` / `net.v` (both the same triple), one of SUPPORTED_HIDDEN -- the reference's [256, 128, 64] and the
+narrower [128, 128, 64], [128, 64, 64], [64, 64, 64] the launches are also compiled for (csrc/auv_policy_mfma.h, POL_ARCH_LIST; the
+auv_policy_*_arch entries).  Anything else raises ValueError; bf16 exists for the reference's widths only.
 """
 import ctypes as C
 from typing import Dict, List, Optional, Sequence
@@ -30,11 +34,38 @@ import torch.nn as nn
 from . import _capi
 from .batched_env import BatchedAuvEnv, _check, _LIB
 
-HIDDEN = (256, 128, 64)
+HIDDEN = (256, 128, 64)                 # the reference's hidden widths: the default, evaluated by the entries without _arch
+SUPPORTED_HIDDEN = _capi.POLICY_ARCHS   # the closed list the forward launches are compiled for (csrc/auv_policy_mfma.h, POL_ARCH_LIST)
 
 
 def _pad16(x: int) -> int:
     return (x + 31) & ~31          # (rows are padded to the kernel's k-step of 32 columns)
+
+
+def check_hidden(hidden, who: str) -> tuple:
+    """`hidden` as a tuple of three ints if the fused forward launches are compiled for it; ValueError with the list otherwise."""
+    try:
+        h = tuple(int(x) for x in hidden)
+    except (TypeError, ValueError):
+        h = None
+    if h is None or len(h) != 3:
+        raise ValueError("%s: the fused kernels evaluate three hidden tanh layers (another depth is not compiled in), one of %s; got %r"
+                         % (who, list(SUPPORTED_HIDDEN), hidden))
+    if h not in SUPPORTED_HIDDEN:
+        raise ValueError("%s: hidden widths %s are not compiled in: the fused kernels evaluate one of %s" % (who, list(h), list(SUPPORTED_HIDDEN)))
+    return h
+
+
+def _arch_arg(hidden) -> "_capi.AuvPolicyArch":
+    return _capi.AuvPolicyArch(int(hidden[0]), int(hidden[1]), int(hidden[2]))
+
+
+def policy_param_floats(obs_dim: int, hidden=HIDDEN) -> int:
+    """Floats of the packed buffer (auv_policy_io::params) of a net with `hidden` widths on `obs_dim` input columns."""
+    hidden = check_hidden(hidden, "policy_param_floats")
+    if hidden == HIDDEN:
+        return int(_LIB.auv_policy_param_floats(int(obs_dim)))
+    return int(_LIB.auv_policy_param_floats_arch(int(obs_dim), C.byref(_arch_arg(hidden))))
 
 
 def pack_linear(weight: torch.Tensor, out_pad: int, in_pad: int) -> torch.Tensor:
@@ -55,18 +86,20 @@ def pack_linear_bf16(weight: torch.Tensor, out_pad: int, in_pad: int) -> torch.T
 
 
 @torch.no_grad()
-def pack_policy_params(net: nn.Module, obs_dim: int, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+def pack_policy_params(net: nn.Module, obs_dim: int, out: Optional[torch.Tensor] = None, hidden=HIDDEN) -> torch.Tensor:
     """The packed f32 weight buffer of auv_policy_io::params for `net` (net.pi / net.v: Linear-Tanh x 3 + Linear, net.log_std) without
-    an environment: what FusedActorCritic.refresh() writes into `self.params`.  For policy_eval on rows that come from elsewhere."""
+    an environment: what FusedActorCritic.refresh() writes into `self.params`.  For policy_eval on rows that come from elsewhere.
+    `hidden`: the hidden widths of both nets, one of SUPPORTED_HIDDEN."""
+    hidden = check_hidden(hidden, "pack_policy_params")
     k0p = _pad16(int(obs_dim))
     dev = net.log_std.device
-    n_float = int(_LIB.auv_policy_param_floats(int(obs_dim)))
+    n_float = policy_param_floats(obs_dim, hidden)
     p = torch.zeros(n_float, dtype=torch.float32, device=dev) if out is None else out
     off = 0
     for seq, n_out in ((net.pi, 2), (net.v, 1)):
         lin = [m for m in seq if isinstance(m, nn.Linear)]
-        if tuple(l.out_features for l in lin[:-1]) != HIDDEN or lin[-1].out_features != n_out or lin[0].in_features != int(obs_dim):
-            raise ValueError("pack_policy_params: the fused kernels evaluate obs[%d] -> %s tanh -> %d" % (int(obs_dim), list(HIDDEN), n_out))
+        if tuple(l.out_features for l in lin[:-1]) != hidden or lin[-1].out_features != n_out or lin[0].in_features != int(obs_dim):
+            raise ValueError("pack_policy_params: the fused kernels evaluate obs[%d] -> %s tanh -> %d" % (int(obs_dim), list(hidden), n_out))
         for j, l in enumerate(lin):
             out_p = l.out_features if j < 3 else 16
             in_p = k0p if j == 0 else l.in_features
@@ -92,7 +125,7 @@ def _eval_check(name: str, t, device, shape_tail, dtype=torch.float32):
 
 def policy_eval(params: torch.Tensor, obs_dim: int, X: torch.Tensor, idx: Optional[torch.Tensor] = None,
                 actions: Optional[torch.Tensor] = None, want: Sequence[str] = ("mu", "value"), action_map=None,
-                out: Optional[Dict[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
+                out: Optional[Dict[str, torch.Tensor]] = None, hidden=HIDDEN, arch_entry: Optional[bool] = None) -> Dict[str, torch.Tensor]:
     """auv_policy_eval (csrc/k9_policy_eval.hip) on the caller's current stream: M observation rows through the policy net, the
     value net, or both, in ONE launch -- no environment, no rollout position, no sampling.
 
@@ -106,9 +139,14 @@ def policy_eval(params: torch.Tensor, obs_dim: int, X: torch.Tensor, idx: Option
                 map without clipping
     out         tensors to write into instead of new ones, by name; "action" may be a row-strided [M, 2] view (rows of an
                 environment's action buffer)
+    hidden      the hidden widths `params` was packed for, one of SUPPORTED_HIDDEN
+    arch_entry  None: the default widths go through auv_policy_eval, any other through auv_policy_eval_arch; True: the _arch entry also
+                for the default widths (it dispatches to the same kernel)
     Returns a dict of the tensors asked for.  Raises ValueError for anything the launch would refuse."""
     want = tuple(want)
     out = dict(out or {})
+    hidden = check_hidden(hidden, "policy_eval")
+    n_params = policy_param_floats(obs_dim, hidden) if int(obs_dim) >= 1 else 0
     for w in want:
         if w not in _EVAL_OUTPUTS:
             raise ValueError("policy_eval: unknown output %r (one of %s)" % (w, ", ".join(_EVAL_OUTPUTS)))
@@ -121,9 +159,9 @@ def policy_eval(params: torch.Tensor, obs_dim: int, X: torch.Tensor, idx: Option
     if obs_dim < 1:
         raise ValueError("policy_eval: obs_dim must be >= 1")
     if not isinstance(params, torch.Tensor) or params.dtype != torch.float32 or not params.is_cuda or not params.is_contiguous() \
-            or params.numel() != int(_LIB.auv_policy_param_floats(obs_dim)) or params.data_ptr() % 16:
+            or params.numel() != n_params or params.data_ptr() % 16:
         raise ValueError("policy_eval: params must be a contiguous, 16-byte aligned float32 device tensor of auv_policy_param_floats(%d) = %d "
-                         "elements" % (obs_dim, int(_LIB.auv_policy_param_floats(obs_dim))))
+                         "elements%s" % (obs_dim, n_params, "" if hidden == HIDDEN else " (hidden widths %s)" % list(hidden)))
     dev = params.device
     _eval_check("X", X, dev, (obs_dim,))
     if X.stride(1) != 1 and X.shape[0] > 0:
@@ -174,15 +212,18 @@ def policy_eval(params: torch.Tensor, obs_dim: int, X: torch.Tensor, idx: Option
         for k in range(2):
             ev.act_mid[k], ev.act_half[k], ev.clip_lo[k], ev.clip_hi[k] = float(mid[k]), float(half[k]), float(lo[k]), float(hi[k])
         st = torch.cuda.current_stream(dev)
-        _check(_LIB.auv_policy_eval(dev.index if dev.index is not None else torch.cuda.current_device(), C.byref(ev),
-                                    C.c_void_p(st.cuda_stream)), "auv_policy_eval")
+        dev_i = dev.index if dev.index is not None else torch.cuda.current_device()
+        if hidden != HIDDEN or arch_entry:
+            _check(_LIB.auv_policy_eval_arch(dev_i, C.byref(ev), C.byref(_arch_arg(hidden)), C.c_void_p(st.cuda_stream)), "auv_policy_eval_arch")
+        else:
+            _check(_LIB.auv_policy_eval(dev_i, C.byref(ev), C.c_void_p(st.cuda_stream)), "auv_policy_eval")
     return res
 
 
 class FusedActorCritic:
     def __init__(self, net: nn.Module, env: BatchedAuvEnv, rollout: int, reward_scale: float = 1.0, reward_clip: float = 0.0,
                  act_mid=None, act_half=None, clip_lo=None, clip_hi=None, seed: int = 0, store_obs: bool = True, debug: bool = False,
-                 bf16: bool = False, frames: int = 1):
+                 bf16: bool = False, frames: int = 1, arch_entry: Optional[bool] = None):
         self.net, self.env, self.T = net, env, int(rollout)
         self.device = env.device
         # frames > 1: every environment is evaluated on its last `frames` observations (module docstring); 1: the plain launch
@@ -193,6 +234,8 @@ class FusedActorCritic:
             raise ValueError("FusedActorCritic: frames = %d with bf16 = True -- stacked rows are evaluated in exact f32 only" % self.frames)
         self.in_dim = self.frames * env.obs_dim                                        # the nets' input width
         self._lin = []
+        # the hidden widths are read off the modules: both nets the same triple, one of SUPPORTED_HIDDEN
+        self.hidden = None
         for seq, out in ((net.pi, 2), (net.v, 1)):
             lin = [m for m in seq if isinstance(m, nn.Linear)]
             act = [m for m in seq if not isinstance(m, nn.Linear)]
@@ -200,18 +243,28 @@ class FusedActorCritic:
             if lin and lin[0].in_features != self.in_dim:                              # the width, with both numbers (one frame or several)
                 raise ValueError("FusedActorCritic: frames = %d of %d columns need a first Linear with in_features == %d, got %d"
                                  % (self.frames, env.obs_dim, self.in_dim, lin[0].in_features))
-            if dims != HIDDEN or lin[-1].out_features != out or not all(isinstance(a, nn.Tanh) for a in act):
-                raise ValueError("FusedActorCritic evaluates the reference's architecture: obs -> %s tanh -> %d (scripts/run.py:332-357); "
-                                 "got %s -> %d" % (list(HIDDEN), out, list(dims), lin[-1].out_features))
+            if dims not in SUPPORTED_HIDDEN or lin[-1].out_features != out or not all(isinstance(a, nn.Tanh) for a in act):
+                raise ValueError("FusedActorCritic evaluates obs -> [h1, h2, h3] tanh -> %d with three hidden layers (another depth is not "
+                                 "compiled in) and [h1, h2, h3] one of %s (the reference's architecture, scripts/run.py:332-357, is the "
+                                 "first); got %s -> %d" % (out, list(SUPPORTED_HIDDEN), list(dims), lin[-1].out_features))
+            if self.hidden is not None and dims != self.hidden:
+                raise ValueError("FusedActorCritic: net.pi has the hidden widths %s, net.v %s -- one launch evaluates both nets with the same "
+                                 "widths, one of %s" % (list(self.hidden), list(dims), list(SUPPORTED_HIDDEN)))
+            self.hidden = dims
             self._lin.append(lin)
+        if bf16 and self.hidden != HIDDEN:
+            raise ValueError("FusedActorCritic: hidden widths %s with bf16 = True -- only %s has a bf16 path, the other widths are evaluated "
+                             "in exact f32 only" % (list(self.hidden), list(HIDDEN)))
+        # the default widths go through the entries without _arch (unless arch_entry: the _arch entries then dispatch to the same kernels)
+        self._arch = _arch_arg(self.hidden) if (self.hidden != HIDDEN or arch_entry) else None
         self.k0p = _pad16(self.in_dim)
-        n_float = int(_LIB.auv_policy_param_floats(self.in_dim))
+        n_float = policy_param_floats(self.in_dim, self.hidden)
         self.params = torch.zeros(n_float, dtype=torch.float32, device=self.device)
         assert self.params.data_ptr() % 16 == 0
         # bf16 = True: the weights also as bf16 fragments, and the launch multiplies on v_mfma_f32_16x16x32_bf16 (one MFMA where
         # the exact path issues eight; ~1e-2 on the means -- NOT the reference's arithmetic; default off)
         self.bf16 = bool(bf16)
-        n_w = (n_float - 4) // 2 - (sum(HIDDEN) + 16)                                  # weight elements of one net
+        n_w = (n_float - 4) // 2 - (sum(self.hidden) + 16)                                  # weight elements of one net
         self.params_bf16 = torch.zeros(2 * n_w, dtype=torch.bfloat16, device=self.device) if self.bf16 else None
         if env._slices is None:
             env.set_sub_batches(1)
@@ -304,7 +357,14 @@ class FusedActorCritic:
         slice's rows of `self.actions` and the transition at the chain's position t, then moves t on."""
         lo, cnt = self.slices[i]
         st = self.env._sub_streams[i] if stream is None else stream
-        if self.frames > 1:
+        if self._arch is not None:
+            a = C.byref(self._arch)
+            if self.frames > 1:
+                _check(_LIB.auv_policy_act_stacked_arch(self.env._h, lo, cnt, C.byref(self._sios[i]), a, C.c_void_p(st.cuda_stream)),
+                       "auv_policy_act_stacked_arch")
+            else:
+                _check(_LIB.auv_policy_act_arch(self.env._h, lo, cnt, C.byref(self._ios[i]), a, C.c_void_p(st.cuda_stream)), "auv_policy_act_arch")
+        elif self.frames > 1:
             _check(_LIB.auv_policy_act_stacked(self.env._h, lo, cnt, C.byref(self._sios[i]), C.c_void_p(st.cuda_stream)), "auv_policy_act_stacked")
         else:
             _check(_LIB.auv_policy_act(self.env._h, lo, cnt, C.byref(self._ios[i]), C.c_void_p(st.cuda_stream)), "auv_policy_act")
@@ -319,7 +379,17 @@ class FusedActorCritic:
         env = self.env
         k = len(self.slices)
         t0, g0 = (C.c_int64 * k)(*self._t), (C.c_int64 * k)(*self._g)
-        if self.frames > 1:
+        if self._arch is not None:
+            a = C.byref(self._arch)
+            tail = (C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()), int(n_steps),
+                    int(bool(flush)), t0, g0)
+            if self.frames > 1:
+                _check(_LIB.auv_policy_rollout_stacked_arch(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._sios, a, *tail),
+                       "auv_policy_rollout_stacked_arch")
+            else:
+                _check(_LIB.auv_policy_rollout_arch(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._ios, a, *tail),
+                       "auv_policy_rollout_arch")
+        elif self.frames > 1:
             _check(_LIB.auv_policy_rollout_stacked(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._sios,
                                                    C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()),
                                                    C.c_void_p(env.done.data_ptr()), int(n_steps), int(bool(flush)), t0, g0),
@@ -350,6 +420,9 @@ class FusedActorCritic:
         return adv, ret
 
     # ------------------------------------------------------------------------------ evaluation outside a rollout
+    def _eval_kw(self):
+        return dict(hidden=self.hidden, arch_entry=self._arch is not None)
+
     def _rows(self, obs):
         if obs is None and self.frames > 1:
             # the row the next policy launch would form: a peek, the history is not moved on
@@ -376,14 +449,14 @@ class FusedActorCritic:
             if X.dim() != 2 or X.shape[0] != self.env.n_envs:
                 raise ValueError("predict: %s rows do not fit self.actions [%d, 2]; pass out=" % (tuple(X.shape[:1]), self.env.n_envs))
             out = self.actions
-        return policy_eval(self.params, self.in_dim, X, want=("action",), action_map=self.action_map, out={"action": out})["action"]
+        return policy_eval(self.params, self.in_dim, X, want=("action",), action_map=self.action_map, out={"action": out}, **self._eval_kw())["action"]
 
     def value(self, obs: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The critic's value of every row of `obs` (None: the environment's observation buffer), [M] float32 in the units the
         critic was trained in (scaled rewards): one launch of the value net alone, on the caller's current stream."""
-        return policy_eval(self.params, self.in_dim, self._rows(obs), want=("value",))["value"]
+        return policy_eval(self.params, self.in_dim, self._rows(obs), want=("value",), **self._eval_kw())["value"]
 
     def evaluate(self, obs: torch.Tensor, actions: torch.Tensor):
         """(log pi(actions | obs) [M], value [M], mu [M, 2]) in one launch on the caller's current stream."""
-        r = policy_eval(self.params, self.in_dim, obs, actions=actions, want=("logp", "value", "mu"))
+        r = policy_eval(self.params, self.in_dim, obs, actions=actions, want=("logp", "value", "mu"), **self._eval_kw())
         return r["logp"], r["value"], r["mu"]

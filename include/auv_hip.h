@@ -756,6 +756,33 @@ typedef struct auv_policy_eval {
 } auv_policy_eval_t;
 int auv_policy_eval(int32_t device, const auv_policy_eval_t* ev, void* stream);
 
+/* ---- other hidden widths than [256, 128, 64] in the fused forward launches ------------------------------------------------------
+ * The launches above evaluate obs -> 256 -> 128 -> 64 -> out, the reference's net (scripts/run.py:332-357).  The *_arch entries take
+ * the three hidden widths beside the same argument structs and evaluate obs -> h1 -> h2 -> h3 -> out: three tanh layers, the same
+ * actor / critic shape, exact f32, outputs padded to one n-tile -- every word of the entries above holds, with the packed layout of
+ * auv_policy_io::params read with (h1, h2, h3) in the place of (256, 128, 64): auv_policy_param_floats_arch(obs_dim, arch) floats,
+ *   2 * (h1 * K0p + h1 + h2 * h1 + h2 + h3 * h2 + h3 + 16 * h3 + 16) + 4,   K0p = obs_dim rounded up to a multiple of 32.
+ * A CLOSED LIST of triples is compiled in (csrc/auv_policy_mfma.h, POL_ARCH_LIST):
+ *   (256, 128, 64)  (128, 128, 64)  (128, 64, 64)  (64, 64, 64)
+ * (256, 128, 64) through an _arch entry runs the very kernels of the entry without the suffix.  AUV_EINVAL, before anything is
+ * enqueued, beside what the plain entries refuse: arch NULL; a triple outside the list (it is never rounded to a listed one;
+ * auv_policy_param_floats_arch then returns 0); params_bf16 set with another triple than (256, 128, 64).  The population launches
+ * (auv_population_*) and the fused update (auv_ppo_*) evaluate (256, 128, 64) only.                                                */
+typedef struct auv_policy_arch {
+  int32_t h1, h2, h3;
+} auv_policy_arch_t;
+size_t auv_policy_param_floats_arch(int32_t obs_dim, const auv_policy_arch_t* arch);
+int auv_policy_act_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const auv_policy_arch_t* arch, void* stream);
+int auv_policy_rollout_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
+                            const auv_policy_io_t* ios, const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev,
+                            uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0);
+int auv_policy_act_stacked_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* io, const auv_policy_arch_t* arch,
+                                void* stream);
+int auv_policy_rollout_stacked_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
+                                    const auv_policy_stack_t* ios, const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev,
+                                    uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0);
+int auv_policy_eval_arch(int32_t device, const auv_policy_eval_t* ev, const auv_policy_arch_t* arch, void* stream);
+
 /* ---- a population of policies: one weight block per group of rows (csrc/k11_population.hip) ---------------------------------------
  * A MEMBER is the packed policy net of auv_policy_io::params -- W1 b1 W2 b2 W3 b3 W4 b4 in MFMA fragment order, what the first
  * net of that buffer holds -- auv_population_member_floats(obs_dim) floats (the net rounded up to a multiple of 4 floats).  Members

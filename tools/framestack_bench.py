@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Cost of frame stacking in the fused policy rollout (csrc/k12_policy_stacked.hip) against the plain launch it is built from:
-tools/framestack_bench.py [envs] [--chains K] [--steps T] [--passes P] [--quick]
+tools/framestack_bench.py [envs] [--chains K] [--steps T] [--passes P] [--quick] [--arch H1,H2,H3[:H1,H2,H3...]] [--only v1,v2,...]
 
 One process is ONE session: every variant is built once and then measured in P alternating passes (variant after variant, pass after
 pass), so that drift of the machine lands on all of them alike.  Per variant and pass, one JSON line:
@@ -16,9 +16,13 @@ Variants:
   torch_k2, torch_k4       the alternative in stock tensor operations: per step and chain a ring write, a gather of the older frames, the
               age mask and a cat into the row buffer, in front of the PLAIN launch and the environment's step.  The launch still runs the
               one-frame net, so this is a LOWER bound of that alternative (its first layer would be k times wider on top).
+--arch: hidden widths of the nets (gym_auv_amd.policy.SUPPORTED_HIDDEN); several, separated by ':', are measured side by side in the same
+passes, every variant once per triple (its name then ends in @H1-H2-H3).  --only: these variants only.  Every line carries the first 12
+hex digits of the loaded library's sha256.
 The last line summarises: median and min .. max over the passes.  Shape: 4096 x 180 beams, a fresh world on every reset, the chains of
 tools/policy_bench.py.  tools/framestack_bench.sh runs it under a time limit."""
 import ctypes as C
+import hashlib
 import json
 import os
 import statistics
@@ -47,18 +51,21 @@ pos_args = [a for i, a in enumerate(sys.argv[1:], 1) if not a.startswith("--") a
 N = int(pos_args[0]) if pos_args else 4096
 CHAINS, T, PASSES = arg("--chains", 4), arg("--steps", 64 if QUICK else 256), arg("--passes", 2 if QUICK else 5)
 DEV = "cuda:0"
+ARCHS = [tuple(int(x) for x in t.split(",")) for t in (sys.argv[sys.argv.index("--arch") + 1] if "--arch" in sys.argv else "256,128,64").split(":")]
+ONLY = sys.argv[sys.argv.index("--only") + 1].split(",") if "--only" in sys.argv else None
+LIB_HASH = hashlib.sha256(open(os.environ.get("AUV_HIP_LIB") or _capi.LIB_PATH, "rb").read()).hexdigest()[:12]
 
 
 class Variant:
-    def __init__(self, name, frames, mode, store_obs=True):
-        self.name, self.frames, self.mode = name, frames, mode
+    def __init__(self, name, frames, mode, store_obs=True, arch=(256, 128, 64)):
+        self.name, self.frames, self.mode, self.arch = name, frames, mode, arch
         cfg = effective_reference_config(use_lidar=True)
         self.env = env = BatchedAuvEnv(cfg, FreshWorlds(n_moving=17, n_static=11, seed=1000), N, device=DEV)
         env.reset()
         env.set_sub_batches(CHAINS)
         torch.manual_seed(0)
         k_net = frames if mode in ("stacked", "eval") else 1
-        net = ppo.ActorCritic(k_net * env.obs_dim).to(DEV)
+        net = ppo.ActorCritic(k_net * env.obs_dim, hidden=arch).to(DEV)
         self.fused = f = FusedActorCritic(net, env, rollout=T, reward_scale=0.01, frames=k_net, store_obs=store_obs)
         self.sios = None
         if mode == "stacked" and frames == 1:
@@ -70,7 +77,7 @@ class Variant:
             from gym_auv_amd.policy import policy_eval
             rows = torch.randn((N, k_net * env.obs_dim), device=DEV)
             outs = dict(mu=torch.empty((N, 2), device=DEV), value=torch.empty(N, device=DEV))
-            self.eval_once = lambda: policy_eval(f.params, k_net * env.obs_dim, rows, want=("mu", "value"), out=outs)
+            self.eval_once = lambda: policy_eval(f.params, k_net * env.obs_dim, rows, want=("mu", "value"), out=outs, hidden=arch)
         if mode == "torch":
             D = env.obs_dim
             self.ring = torch.zeros((frames, N, D), device=DEV)
@@ -83,8 +90,8 @@ class Variant:
         f = self.fused
         if self.sios is not None:
             lo, cnt = f.slices[i]
-            _check(_LIB.auv_policy_act_stacked(self.env._h, lo, cnt, C.byref(self.sios[i]), C.c_void_p(self.env._sub_streams[i].cuda_stream)),
-                   "auv_policy_act_stacked")
+            _check(_LIB.auv_policy_act_stacked_arch(self.env._h, lo, cnt, C.byref(self.sios[i]), C.byref(_capi.AuvPolicyArch(*self.arch)),
+                                                    C.c_void_p(self.env._sub_streams[i].cuda_stream)), "auv_policy_act_stacked_arch")
             f._t[i], f._g[i] = min(f._t[i] + 1, T + 1), f._g[i] + 1
         else:
             f.act(i)
@@ -121,9 +128,10 @@ class Variant:
         elif self.sios is not None:
             k = len(f.slices)
             t0, g0 = (C.c_int64 * k)(*f._t), (C.c_int64 * k)(*f._g)
-            _check(_LIB.auv_policy_rollout_stacked(env._h, env.sub_batches, env._bounds_c, env._streams_c, self.sios, C.c_void_p(env.obs.data_ptr()),
-                                                   C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()), T, 1, t0, g0),
-                   "auv_policy_rollout_stacked")
+            _check(_LIB.auv_policy_rollout_stacked_arch(env._h, env.sub_batches, env._bounds_c, env._streams_c, self.sios,
+                                                        C.byref(_capi.AuvPolicyArch(*self.arch)), C.c_void_p(env.obs.data_ptr()),
+                                                        C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()), T, 1, t0, g0),
+                   "auv_policy_rollout_stacked_arch")
             for i in range(k):
                 f._t[i], f._g[i] = min(f._t[i] + T + 1, T + 1), f._g[i] + T + 1
         else:
@@ -140,7 +148,8 @@ class Variant:
                 self.eval_once()
             b.record()
             torch.cuda.synchronize()
-            return dict(variant=self.name, envs=N, chains=1, steps=0, env_steps_per_s=0.0, step_us=0.0, policy_us=1e3 * a.elapsed_time(b) / 200)
+            return dict(variant=self.name, envs=N, chains=1, steps=0, env_steps_per_s=0.0, step_us=0.0, policy_us=1e3 * a.elapsed_time(b) / 200,
+                        lib=LIB_HASH)
         # the policy launch alone, by events on every chain's stream
         f.begin_rollout()
         torch.cuda.synchronize()
@@ -165,13 +174,19 @@ class Variant:
         self.rollout()
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        return dict(variant=self.name, envs=N, chains=env.sub_batches, steps=T, env_steps_per_s=N * T / dt, step_us=1e6 * dt / T, policy_us=policy_us)
+        return dict(variant=self.name, envs=N, chains=env.sub_batches, steps=T, env_steps_per_s=N * T / dt, step_us=1e6 * dt / T, policy_us=policy_us,
+                    lib=LIB_HASH)
 
 
 def main():
     specs = [("parent", 1, "plain"), ("stacked_k1", 1, "stacked"), ("stacked_k2", 2, "stacked"), ("stacked_k4", 4, "stacked"),
              ("stacked_k4_no_O", 4, "stacked", False), ("eval_k4", 4, "eval"), ("torch_k2", 2, "torch"), ("torch_k4", 4, "torch")]
-    variants = [Variant(*s) for s in specs]
+    if ONLY is not None:
+        specs = [s for s in specs if s[0] in ONLY]
+    if len(ARCHS) == 1:
+        variants = [Variant(*s, arch=ARCHS[0]) for s in specs]
+    else:
+        variants = [Variant(s[0] + "@" + "-".join(str(x) for x in h), *s[1:], arch=h) for s in specs for h in ARCHS]
     for v in variants:                                     # warm-up: every kernel loaded, every allocation made
         v.rollout()
         torch.cuda.synchronize()
@@ -188,7 +203,8 @@ def main():
         u = [r["policy_us"] for r in rows]
         summary[name] = dict(env_steps_per_s=dict(median=statistics.median(s), min=min(s), max=max(s)),
                              policy_us=dict(median=statistics.median(u), min=min(u), max=max(u)))
-    print(json.dumps(dict(summary=summary, envs=N, chains_asked=CHAINS, chains=variants[0].env.sub_batches, steps=T, passes=PASSES)), flush=True)
+    print(json.dumps(dict(summary=summary, envs=N, chains_asked=CHAINS, chains=variants[0].env.sub_batches, steps=T, passes=PASSES,
+                          lib=LIB_HASH)), flush=True)
     for v in variants:
         v.env.close()
 
