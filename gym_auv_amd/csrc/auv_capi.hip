@@ -15,6 +15,7 @@
 #include "auv_generate.h"
 #include "auv_multi_geom.h"
 #include "auv_snapshot.h"
+#include "auv_policy_mfma.h"
 #include "auv_ppo.h"
 #include "auv_render.h"
 
@@ -58,10 +59,13 @@ void auv_launch_rdv_arrive(unsigned long long* word, hipStream_t st);
 void auv_launch_rdv_wait(const unsigned long long* word, unsigned long long target, int32_t* err, int code, double limit_s, int32_t* abort_flag,
                          int32_t* report, hipStream_t st);
 hipError_t auv_launch_probe(unsigned int* words, int np, int nc, unsigned int tag, unsigned int* failures, uint32_t lds, hipStream_t st);
-size_t auv_policy_param_floats_impl(int obs_dim);
-size_t auv_policy_lds_bytes(int obs_dim);
-hipError_t auv_policy_prepare(int obs_dim);
-void auv_launch_policy(const auv_policy_io_t& io, int e0, int ne, hipStream_t st, long long t_host = -1, long long gstep_host = -1);
+// the forward launches (k6_policy.hip, k9_policy_eval.hip, k12_policy_stacked.hip) take a hidden-width triple of the closed list
+// (auv_policy_mfma.h, POL_ARCH_LIST)
+size_t auv_policy_param_floats_impl(int h1, int h2, int h3, int obs_dim);
+size_t auv_policy_lds_bytes(int h1, int h2, int h3, int obs_dim);
+hipError_t auv_policy_prepare(int h1, int h2, int h3, int obs_dim);
+void auv_launch_policy(int h1, int h2, int h3, const auv_policy_io_t& io, int e0, int ne, hipStream_t st, long long t_host = -1,
+                       long long gstep_host = -1);
 void auv_launch_gae(const float* R, const float* V, const float* Dn, const float* last_v, float gamma, float lam, float* adv, float* ret,
                     int T, int N, hipStream_t st);
 void auv_launch_k4(const AuvDev& d, const int32_t* sector_start, int n_sectors, double width, double* out_dist,
@@ -70,34 +74,20 @@ void auv_launch_snapshot(const AuvSnapArgs& a, const int32_t* env_idx, int m, vo
 void auv_launch_restore(const AuvSnapArgs& a, const AuvDev& d, const void* rows, int n_rows, const int32_t* row_idx, const int32_t* env_idx, int m,
                         float* obs, hipStream_t st);
 void auv_launch_plan_score(const float* reward, const uint8_t* done, int T, int n, int group, float gamma, float* score, int32_t* best, hipStream_t st);
-hipError_t auv_policy_eval_prepare(int obs_dim);
-void auv_launch_policy_eval(const auv_policy_eval_t& ev, bool want_pi, bool want_v, hipStream_t st);
+hipError_t auv_policy_eval_prepare(int h1, int h2, int h3, int obs_dim);
+void auv_launch_policy_eval(int h1, int h2, int h3, const auv_policy_eval_t& ev, bool want_pi, bool want_v, hipStream_t st);
 void auv_launch_plan_score_v(const float* reward, const uint8_t* done, const float* terminal, int T, int n, int group, float gamma, float* score,
                              int32_t* best, hipStream_t st);
 size_t auv_population_member_floats_impl(int obs_dim);
 hipError_t auv_population_prepare(int obs_dim);
 void auv_launch_population_act(const auv_population_io_t& io, hipStream_t st);
 // k12_policy_stacked.hip
-size_t auv_policy_stacked_lds_bytes(int width);
-hipError_t auv_policy_stacked_prepare(int width);
-void auv_launch_policy_stacked(const auv_policy_stack_t& s, int e0, int ne, hipStream_t st, long long t_host = -1, long long gstep_host = -1);
+size_t auv_policy_stacked_lds_bytes(int h1, int h2, int h3, int width);
+hipError_t auv_policy_stacked_prepare(int h1, int h2, int h3, int width);
+void auv_launch_policy_stacked(int h1, int h2, int h3, const auv_policy_stack_t& s, int e0, int ne, hipStream_t st, long long t_host = -1,
+                               long long gstep_host = -1);
 void auv_launch_stack_frames(const float* obs, const uint8_t* done, float* hist, int32_t* stk, float* out, long long ldx, int e0, int ne,
                              int obs_dim, int frames, int advance, hipStream_t st);
-// the forward launches for a hidden-width triple of the closed list (auv_policy_mfma.h, POL_ARCH_LIST; the reference's triple goes to
-// the launches above): k6_policy.hip, k9_policy_eval.hip, k12_policy_stacked.hip
-bool auv_policy_arch_listed(int h1, int h2, int h3);
-bool auv_policy_arch_is_ref(int h1, int h2, int h3);
-size_t auv_policy_param_floats_arch_impl(int h1, int h2, int h3, int obs_dim);
-size_t auv_policy_lds_bytes_arch(int h1, int h2, int h3, int obs_dim);
-hipError_t auv_policy_prepare_arch(int h1, int h2, int h3, int obs_dim);
-void auv_launch_policy_arch(int h1, int h2, int h3, const auv_policy_io_t& io, int e0, int ne, hipStream_t st, long long t_host = -1,
-                            long long gstep_host = -1);
-hipError_t auv_policy_eval_prepare_arch(int h1, int h2, int h3, int obs_dim);
-void auv_launch_policy_eval_arch(int h1, int h2, int h3, const auv_policy_eval_t& ev, bool want_pi, bool want_v, hipStream_t st);
-size_t auv_policy_stacked_lds_bytes_arch(int h1, int h2, int h3, int width);
-hipError_t auv_policy_stacked_prepare_arch(int h1, int h2, int h3, int width);
-void auv_launch_policy_stacked_arch(int h1, int h2, int h3, const auv_policy_stack_t& s, int e0, int ne, hipStream_t st, long long t_host = -1,
-                                    long long gstep_host = -1);
 void auv_launch_population_perturb(const float* theta, float* members, long long stride, int P, int obs_dim, float sigma, unsigned long long seed,
                                    unsigned long long generation, hipStream_t st);
 void auv_launch_population_update(float* theta, const float* w, float* grad, int P, int obs_dim, float sigma, float lr, unsigned long long seed,
@@ -2091,23 +2081,29 @@ int auv_render(auv_handle_t* h, void* stream, const int32_t* env_idx_host, int32
   return AUV_OK;
 }
 
-size_t auv_policy_param_floats(int32_t obs_dim) { return obs_dim > 0 ? auv_policy_param_floats_impl(obs_dim) : 0; }
-
 // the hidden widths of a forward launch: the entries without _arch evaluate the reference's net
-static const auv_policy_arch_t POLICY_ARCH_REF = {256, 128, 64};
+static const auv_policy_arch_t POLICY_ARCH_REF = {POL_H1, POL_H2, POL_H3};
+size_t auv_policy_param_floats(int32_t obs_dim) { return auv_policy_param_floats_arch(obs_dim, &POLICY_ARCH_REF); }
+
 static int check_policy_arch(const auv_policy_arch_t* a, const void* params_bf16, const char* who) {
   if (!a) return fail(AUV_EINVAL, "%s: null arch", who);
-  if (!auv_policy_arch_listed(a->h1, a->h2, a->h3))
-    return fail(AUV_EINVAL, "%s: hidden widths (%d, %d, %d) are not compiled in: one of (256, 128, 64), (128, 128, 64), (128, 64, 64), (64, 64, 64)",
-                who, a->h1, a->h2, a->h3);
-  if (params_bf16 && !auv_policy_arch_is_ref(a->h1, a->h2, a->h3))
+  if (!pol_arch_listed(a->h1, a->h2, a->h3)) {
+    char list[256] = "";                                  // "(256, 128, 64), (128, 128, 64), ..."
+    pol_arch_any([&](auto t) {
+      const size_t n = strlen(list);
+      snprintf(list + n, sizeof(list) - n, "%s(%d, %d, %d)", n ? ", " : "", t.H1, t.H2, t.H3);
+      return false;
+    });
+    return fail(AUV_EINVAL, "%s: hidden widths (%d, %d, %d) are not compiled in: one of %s", who, a->h1, a->h2, a->h3, list);
+  }
+  if (params_bf16 && !pol_arch_is_ref(a->h1, a->h2, a->h3))
     return fail(AUV_EINVAL, "%s: hidden widths (%d, %d, %d) are evaluated in exact f32 only (params_bf16 must be NULL)", who, a->h1, a->h2, a->h3);
   return AUV_OK;
 }
 
 size_t auv_policy_param_floats_arch(int32_t obs_dim, const auv_policy_arch_t* arch) {
-  if (obs_dim <= 0 || !arch || !auv_policy_arch_listed(arch->h1, arch->h2, arch->h3)) return 0;
-  return auv_policy_param_floats_arch_impl(arch->h1, arch->h2, arch->h3, obs_dim);
+  if (obs_dim <= 0 || !arch || !pol_arch_listed(arch->h1, arch->h2, arch->h3)) return 0;
+  return auv_policy_param_floats_impl(arch->h1, arch->h2, arch->h3, obs_dim);
 }
 
 static int check_policy_io(const auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const auv_policy_arch_t* a, const char* who) {
@@ -2124,7 +2120,7 @@ static int check_policy_io(const auv_handle_t* h, int32_t e0, int32_t ne, const 
     return fail(AUV_EINVAL, "%s: null buffer", who);
   if (((uintptr_t)io->params & 15) || ((uintptr_t)io->params_bf16 & 15) || ((uintptr_t)io->actions_out & 7) || ((uintptr_t)io->ctr & 7))
     return fail(AUV_EINVAL, "%s: params must be 16-byte, actions_out and ctr 8-byte aligned", who);
-  if (auv_policy_lds_bytes_arch(a->h1, a->h2, a->h3, io->obs_dim) > 160 * 1024)
+  if (auv_policy_lds_bytes(a->h1, a->h2, a->h3, io->obs_dim) > 160 * 1024)
     return fail(AUV_EINVAL, "%s: observation too wide for the policy kernel's LDS tile", who);
   return AUV_OK;
 }
@@ -2134,8 +2130,8 @@ static int policy_act_impl(auv_handle_t* h, int32_t e0, int32_t ne, const auv_po
   REQUIRE_READY(h);
   int rc = check_policy_io(h, e0, ne, io, a, who);
   if (rc) return rc;
-  HIP_TRY(auv_policy_prepare_arch(a->h1, a->h2, a->h3, io->obs_dim));
-  auv_launch_policy_arch(a->h1, a->h2, a->h3, *io, e0, ne, (hipStream_t)stream);
+  HIP_TRY(auv_policy_prepare(a->h1, a->h2, a->h3, io->obs_dim));
+  auv_launch_policy(a->h1, a->h2, a->h3, *io, e0, ne, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }
@@ -2279,7 +2275,7 @@ static int policy_eval_impl(int32_t device, const auv_policy_eval_t* ev, const a
   if (rca) return rca;
   if (device < 0) return fail(AUV_EINVAL, "auv_policy_eval: device %d", device);
   if (ev->obs_dim < 1) return fail(AUV_EINVAL, "auv_policy_eval: obs_dim %d < 1", ev->obs_dim);
-  if (ev->obs_dim > 16384 || auv_policy_lds_bytes_arch(a->h1, a->h2, a->h3, ev->obs_dim) > 160 * 1024)
+  if (ev->obs_dim > 16384 || auv_policy_lds_bytes(a->h1, a->h2, a->h3, ev->obs_dim) > 160 * 1024)
     return fail(AUV_EINVAL, "auv_policy_eval: obs_dim %d is too wide for the policy kernel's LDS tile", ev->obs_dim);
   if (ev->M < 0) return fail(AUV_EINVAL, "auv_policy_eval: M = %d < 0", ev->M);
   const bool want_pi = ev->mu || ev->action || ev->logp, want_v = ev->value != nullptr;
@@ -2294,8 +2290,8 @@ static int policy_eval_impl(int32_t device, const auv_policy_eval_t* ev, const a
     return fail(AUV_EINVAL, "auv_policy_eval: float buffers must be 4-byte, idx 8-byte aligned");
   if (ev->M == 0) return AUV_OK;
   HIP_TRY(hipSetDevice(device));
-  HIP_TRY(auv_policy_eval_prepare_arch(a->h1, a->h2, a->h3, ev->obs_dim));
-  auv_launch_policy_eval_arch(a->h1, a->h2, a->h3, *ev, want_pi, want_v, (hipStream_t)stream);
+  HIP_TRY(auv_policy_eval_prepare(a->h1, a->h2, a->h3, ev->obs_dim));
+  auv_launch_policy_eval(a->h1, a->h2, a->h3, *ev, want_pi, want_v, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }
@@ -2356,12 +2352,12 @@ static int policy_rollout_impl(auv_handle_t* h, int32_t n_slices, const int32_t*
     if (ctr.negative(i)) return fail(AUV_EINVAL, "%s: negative counter for slice %d", who, i);
   }
   PAIR_CHECK(h, obs_dev);
-  HIP_TRY(auv_policy_prepare_arch(a->h1, a->h2, a->h3, ios[0].obs_dim));
+  HIP_TRY(auv_policy_prepare(a->h1, a->h2, a->h3, ios[0].obs_dim));
   return rollout_loop(
       h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].actions_out; },
       [&](int i, int32_t k, bool) {
-        auv_launch_policy_arch(a->h1, a->h2, a->h3, ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k),
-                               ctr.gstep(i, k));
+        auv_launch_policy(a->h1, a->h2, a->h3, ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k),
+                          ctr.gstep(i, k));
       });
 }
 int auv_policy_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
@@ -2386,7 +2382,7 @@ static int check_policy_stack(const auv_handle_t* h, int32_t e0, int32_t ne, con
   if (rc) return rc;
   if (s->io.params_bf16) return fail(AUV_EINVAL, "%s: stacked rows are evaluated in exact f32 only (params_bf16 must be NULL)", who);
   const int64_t width = (int64_t)s->frames * s->io.obs_dim;
-  if (width > 16384 || auv_policy_stacked_lds_bytes_arch(a->h1, a->h2, a->h3, (int)width) > 160 * 1024)
+  if (width > 16384 || auv_policy_stacked_lds_bytes(a->h1, a->h2, a->h3, (int)width) > 160 * 1024)
     return fail(AUV_EINVAL, "%s: %d frames of %d columns are too wide for the policy kernel's LDS tile", who, s->frames, s->io.obs_dim);
   if (s->frames > 1) {
     if (!s->hist || !s->stk) return fail(AUV_EINVAL, "%s: null hist or stk", who);
@@ -2400,8 +2396,8 @@ static int policy_act_stacked_impl(auv_handle_t* h, int32_t e0, int32_t ne, cons
   REQUIRE_READY(h);
   int rc = check_policy_stack(h, e0, ne, io, a, who);
   if (rc) return rc;
-  HIP_TRY(auv_policy_stacked_prepare_arch(a->h1, a->h2, a->h3, io->frames * io->io.obs_dim));
-  auv_launch_policy_stacked_arch(a->h1, a->h2, a->h3, *io, e0, ne, (hipStream_t)stream);
+  HIP_TRY(auv_policy_stacked_prepare(a->h1, a->h2, a->h3, io->frames * io->io.obs_dim));
+  auv_launch_policy_stacked(a->h1, a->h2, a->h3, *io, e0, ne, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }
@@ -2432,12 +2428,12 @@ static int policy_rollout_stacked_impl(auv_handle_t* h, int32_t n_slices, const 
     if (ctr.negative(i)) return fail(AUV_EINVAL, "%s: negative counter for slice %d", who, i);
   }
   PAIR_CHECK(h, obs_dev);
-  HIP_TRY(auv_policy_stacked_prepare_arch(a->h1, a->h2, a->h3, ios[0].frames * ios[0].io.obs_dim));
+  HIP_TRY(auv_policy_stacked_prepare(a->h1, a->h2, a->h3, ios[0].frames * ios[0].io.obs_dim));
   return rollout_loop(
       h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].io.actions_out; },
       [&](int i, int32_t k, bool) {
-        auv_launch_policy_stacked_arch(a->h1, a->h2, a->h3, ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k),
-                                       ctr.gstep(i, k));
+        auv_launch_policy_stacked(a->h1, a->h2, a->h3, ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k),
+                                  ctr.gstep(i, k));
       });
 }
 int auv_policy_rollout_stacked(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_stack_t* ios,
@@ -2476,7 +2472,7 @@ size_t auv_population_member_floats(int32_t obs_dim) { return obs_dim > 0 ? auv_
 
 static int check_population_obs_dim(int32_t obs_dim, const char* who) {
   if (obs_dim < 1) return fail(AUV_EINVAL, "%s: obs_dim %d < 1", who, obs_dim);
-  if (obs_dim > 16384 || auv_policy_lds_bytes(obs_dim) > 160 * 1024)
+  if (obs_dim > 16384 || auv_policy_lds_bytes(POL_H1, POL_H2, POL_H3, obs_dim) > 160 * 1024)
     return fail(AUV_EINVAL, "%s: obs_dim %d is too wide for the policy kernel's LDS tile", who, obs_dim);
   return AUV_OK;
 }

@@ -35,19 +35,32 @@ struct PolArch {
   static_assert(H1_ >= H3_, "Y3 re-uses Y1's LDS");
 };
 typedef PolArch<POL_H1, POL_H2, POL_H3> PolArchRef;   // the reference's net: the default, and the only one k8 and k11 evaluate
-// THE LIST of the other triples the forward launches are instantiated for: a triple more is one line here (every file instantiates,
-// and every host-side dispatch decides, through this macro)
+// THE LIST of the triples the forward launches are instantiated for, the default first: a triple more is one line here.  It is expanded
+// once, in pol_arch_any; every host-side dispatch finds its kernel through pol_arch_visit, which also instantiates it.
 #define POL_ARCH_LIST(X) \
+  X(256, 128, 64)        \
   X(128, 128, 64)        \
   X(128, 64, 64)         \
   X(64, 64, 64)
-__host__ inline bool pol_arch_is_ref(int h1, int h2, int h3) { return h1 == POL_H1 && h2 == POL_H2 && h3 == POL_H3; }
-__host__ inline bool pol_arch_listed(int h1, int h2, int h3) {
-#define POL_ARCH_IS(a, b, c) if (h1 == (a) && h2 == (b) && h3 == (c)) return true;
-  POL_ARCH_LIST(POL_ARCH_IS)
-#undef POL_ARCH_IS
-  return pol_arch_is_ref(h1, h2, h3);
+// f(PolArch<a, b, c>{}) -> bool for the triples of the list in order, up to the first that answers true
+template <class F>
+__host__ inline bool pol_arch_any(F&& f) {
+#define POL_ARCH_TRY(a, b, c) if (f(PolArch<a, b, c>{})) return true;
+  POL_ARCH_LIST(POL_ARCH_TRY)
+#undef POL_ARCH_TRY
+  return false;
 }
+// f(PolArch<h1, h2, h3>{}) if the triple is listed; false, and f not called, if it is not
+template <class F>
+__host__ inline bool pol_arch_visit(int h1, int h2, int h3, F&& f) {
+  return pol_arch_any([&](auto a) {
+    if (h1 != a.H1 || h2 != a.H2 || h3 != a.H3) return false;
+    f(a);
+    return true;
+  });
+}
+__host__ inline bool pol_arch_is_ref(int h1, int h2, int h3) { return h1 == POL_H1 && h2 == POL_H2 && h3 == POL_H3; }
+__host__ inline bool pol_arch_listed(int h1, int h2, int h3) { return pol_arch_visit(h1, h2, h3, [](auto) {}); }
 
 __host__ __device__ inline int pol_pad16(int x) { return (x + 31) & ~31; }   // (the k-step of pol_layer: 32)
 // floats of ONE packed net: W1 [H1][K0p] b1 [H1] W2 [H2][H1] b2 [H2] W3 [H3][H2] b3 [H3] W4 [16][H3] b4 [16]

@@ -3,7 +3,7 @@
 // scripts/run.py:332-357): the last `frames` observations of an environment are ONE input row, so that a feed-forward policy sees how
 // the obstacles move.
 //
-// k12_stacked_act is k6_policy_act<false> with another input tile: both are written from the same pieces of auv_policy_forward.h --
+// k12_stacked_act<A> is k6_policy_act<A, false> with another input tile: both are written from the same pieces of auv_policy_forward.h --
 // the frame of an act launch (rollout position, transition, sampling epilogue, counters) and the forward pass -- and this file holds
 // only the history's step and the loader that reads the ring.  A row has frames * obs_dim columns; columns
 // [j * obs_dim, (j + 1) * obs_dim) hold the observation of
@@ -55,7 +55,6 @@ __device__ __forceinline__ void stk_advance(const int2 s, const bool done, const
 }
 
 // LDS: k6's tiles for frames * obs_dim columns, and behind them (pos', age') of the tile's 16 rows
-__host__ __device__ inline size_t stk_lds_bytes(int width) { return pol_lds_bytes(width) + sizeof(int32_t) * 2 * POL_ROWS; }
 __host__ __device__ inline size_t stk_lds_bytes_h(int h1, int h2, int h3, int width) {
   return pol_lds_bytes_h(h1, h2, h3, width) + sizeof(int32_t) * 2 * POL_ROWS;
 }
@@ -132,13 +131,9 @@ __device__ __forceinline__ void stacked_act_body(const StackArgs& pa) {
   pol_act_end(io, p);
 }
 
-// grid (ceil(ne / 16), 2): blockIdx.y = 0 the policy net, 1 the value net.  The reference's triple ...
-__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k12_stacked_act(StackArgs pa) {   // (two workgroups per CU, as k6)
-  stacked_act_body<PolArchRef>(pa);
-}
-// ... and every other triple of POL_ARCH_LIST
+// grid (ceil(ne / 16), 2): blockIdx.y = 0 the policy net, 1 the value net
 template <class A>
-__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) policy_stacked_arch(StackArgs pa) {
+__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k12_stacked_act(StackArgs pa) {   // (two workgroups per CU, as k6)
   stacked_act_body<A>(pa);
 }
 
@@ -211,49 +206,27 @@ __global__ void __launch_bounds__(STK_THREADS) k12_stack_frames(FramesArgs fa) {
 
 }  // namespace
 
-size_t auv_policy_stacked_lds_bytes(int width) { return stk_lds_bytes(width); }
+// (h1, h2, h3): a listed hidden-width triple (the caller has checked)
+size_t auv_policy_stacked_lds_bytes(int h1, int h2, int h3, int width) { return stk_lds_bytes_h(h1, h2, h3, width); }
 
-hipError_t auv_policy_stacked_prepare(int width) {
-  const size_t b = stk_lds_bytes(width);
-  if (b <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute((const void*)k12_stacked_act, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
-}
-
-void auv_launch_policy_stacked(const auv_policy_stack_t& s, int e0, int ne, hipStream_t st, long long t_host, long long gstep_host) {
-  StackArgs pa;
-  pa.s = s, pa.e0 = e0, pa.ne = ne;
-  pa.t_host = t_host, pa.gstep_host = gstep_host;
-  const dim3 grid((ne + POL_ROWS - 1) / POL_ROWS, 2), block(POL_THREADS);
-  hipLaunchKernelGGL(k12_stacked_act, grid, block, stk_lds_bytes(s.frames * s.io.obs_dim), st, pa);
-}
-
-// a listed hidden-width triple (the caller has checked): the reference's goes to the kernel above
-size_t auv_policy_stacked_lds_bytes_arch(int h1, int h2, int h3, int width) { return stk_lds_bytes_h(h1, h2, h3, width); }
-
-hipError_t auv_policy_stacked_prepare_arch(int h1, int h2, int h3, int width) {
-  if (pol_arch_is_ref(h1, h2, h3)) return auv_policy_stacked_prepare(width);
+hipError_t auv_policy_stacked_prepare(int h1, int h2, int h3, int width) {
   const size_t b = stk_lds_bytes_h(h1, h2, h3, width);
   if (b <= 64 * 1024) return hipSuccess;
-#define POL_ARCH_PREPARE(a, b_, c) \
-  if (h1 == (a) && h2 == (b_) && h3 == (c)) \
-    return hipFuncSetAttribute((const void*)policy_stacked_arch<PolArch<a, b_, c>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
-  POL_ARCH_LIST(POL_ARCH_PREPARE)
-#undef POL_ARCH_PREPARE
-  return hipErrorInvalidValue;
+  hipError_t e = hipErrorInvalidValue;
+  pol_arch_visit(h1, h2, h3, [&](auto a) {
+    e = hipFuncSetAttribute((const void*)k12_stacked_act<decltype(a)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  });
+  return e;
 }
 
-void auv_launch_policy_stacked_arch(int h1, int h2, int h3, const auv_policy_stack_t& s, int e0, int ne, hipStream_t st, long long t_host,
-                                    long long gstep_host) {
-  if (pol_arch_is_ref(h1, h2, h3)) return auv_launch_policy_stacked(s, e0, ne, st, t_host, gstep_host);
+void auv_launch_policy_stacked(int h1, int h2, int h3, const auv_policy_stack_t& s, int e0, int ne, hipStream_t st, long long t_host,
+                               long long gstep_host) {
   StackArgs pa;
   pa.s = s, pa.e0 = e0, pa.ne = ne;
   pa.t_host = t_host, pa.gstep_host = gstep_host;
   const dim3 grid((ne + POL_ROWS - 1) / POL_ROWS, 2), block(POL_THREADS);
   const size_t lds = stk_lds_bytes_h(h1, h2, h3, s.frames * s.io.obs_dim);
-#define POL_ARCH_LAUNCH(a, b, c) \
-  if (h1 == (a) && h2 == (b) && h3 == (c)) hipLaunchKernelGGL((policy_stacked_arch<PolArch<a, b, c>>), grid, block, lds, st, pa);
-  POL_ARCH_LIST(POL_ARCH_LAUNCH)
-#undef POL_ARCH_LAUNCH
+  pol_arch_visit(h1, h2, h3, [&](auto a) { hipLaunchKernelGGL((k12_stacked_act<decltype(a)>), grid, block, lds, st, pa); });
 }
 
 void auv_launch_stack_frames(const float* obs, const uint8_t* done, float* hist, int32_t* stk, float* out, long long ldx, int e0, int ne,

@@ -69,15 +69,10 @@ __device__ __forceinline__ void policy_act_body(const PolicyArgs& pa) {
   pol_act_end(io, p);
 }
 
-// grid (ceil(ne / 16), 2): blockIdx.y = 0 the policy net, 1 the value net.  The reference's triple (optionally on bf16 weights) ...
-template <bool BF>
+// grid (ceil(ne / 16), 2): blockIdx.y = 0 the policy net, 1 the value net.  BF (bf16 weights) is instantiated for the reference's triple only
+template <class A, bool BF>
 __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k6_policy_act(PolicyArgs pa) {   // (two workgroups per CU)
-  policy_act_body<PolArchRef, BF>(pa);
-}
-// ... and every other triple of POL_ARCH_LIST, exact f32 only
-template <class A>
-__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) policy_act_arch(PolicyArgs pa) {
-  policy_act_body<A, false>(pa);
+  policy_act_body<A, BF>(pa);
 }
 
 // Generalised advantage estimation over a rollout (what stable-baselines' PPO2 runner does on the host after n_steps,
@@ -108,55 +103,31 @@ void auv_launch_gae(const float* R, const float* V, const float* Dn, const float
   hipLaunchKernelGGL(k6_gae, dim3((N + 255) / 256), dim3(256), 0, st, R, V, Dn, last_v, gamma, lam, adv, ret, T, N);
 }
 
-size_t auv_policy_param_floats_impl(int obs_dim) { return 2 * pol_net_floats(obs_dim) + 4; }
-size_t auv_policy_lds_bytes(int obs_dim) { return pol_lds_bytes(obs_dim); }
+// ---- host side: every function takes the hidden-width triple (h1, h2, h3), a listed one (the caller has checked) ----
+size_t auv_policy_param_floats_impl(int h1, int h2, int h3, int obs_dim) { return 2 * pol_net_floats_h(h1, h2, h3, obs_dim) + 4; }
+size_t auv_policy_lds_bytes(int h1, int h2, int h3, int obs_dim) { return pol_lds_bytes_h(h1, h2, h3, obs_dim); }
 
-// ---- the same for a hidden-width triple (h1, h2, h3) ----
-bool auv_policy_arch_listed(int h1, int h2, int h3) { return pol_arch_listed(h1, h2, h3); }
-bool auv_policy_arch_is_ref(int h1, int h2, int h3) { return pol_arch_is_ref(h1, h2, h3); }
-size_t auv_policy_param_floats_arch_impl(int h1, int h2, int h3, int obs_dim) { return 2 * pol_net_floats_h(h1, h2, h3, obs_dim) + 4; }
-size_t auv_policy_lds_bytes_arch(int h1, int h2, int h3, int obs_dim) { return pol_lds_bytes_h(h1, h2, h3, obs_dim); }
-
-hipError_t auv_policy_prepare(int obs_dim) {
-  const size_t b = pol_lds_bytes(obs_dim);
-  if (b <= 64 * 1024) return hipSuccess;
-  hipError_t e = hipFuncSetAttribute((const void*)k6_policy_act<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
-  if (e != hipSuccess) return e;
-  return hipFuncSetAttribute((const void*)k6_policy_act<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
-}
-
-void auv_launch_policy(const auv_policy_io_t& io, int e0, int ne, hipStream_t st, long long t_host, long long gstep_host) {
-  PolicyArgs pa;
-  pa.io = io, pa.e0 = e0, pa.ne = ne;
-  pa.t_host = t_host, pa.gstep_host = gstep_host;
-  const dim3 grid((ne + POL_ROWS - 1) / POL_ROWS, 2), block(POL_THREADS);
-  if (io.params_bf16) hipLaunchKernelGGL(k6_policy_act<true>, grid, block, pol_lds_bytes(io.obs_dim), st, pa);
-  else hipLaunchKernelGGL(k6_policy_act<false>, grid, block, pol_lds_bytes(io.obs_dim), st, pa);
-}
-
-// a listed triple (the caller has checked; params_bf16 is NULL unless it is the reference's): the reference's goes to the kernels above
-hipError_t auv_policy_prepare_arch(int h1, int h2, int h3, int obs_dim) {
-  if (pol_arch_is_ref(h1, h2, h3)) return auv_policy_prepare(obs_dim);
+// (the reference's triple also runs on bf16 weights: the launch picks that variant by io.params_bf16, which is NULL for every other triple)
+hipError_t auv_policy_prepare(int h1, int h2, int h3, int obs_dim) {
   const size_t b = pol_lds_bytes_h(h1, h2, h3, obs_dim);
   if (b <= 64 * 1024) return hipSuccess;
-#define POL_ARCH_PREPARE(a, b_, c) \
-  if (h1 == (a) && h2 == (b_) && h3 == (c)) \
-    return hipFuncSetAttribute((const void*)policy_act_arch<PolArch<a, b_, c>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
-  POL_ARCH_LIST(POL_ARCH_PREPARE)
-#undef POL_ARCH_PREPARE
-  return hipErrorInvalidValue;
+  hipError_t e = hipErrorInvalidValue;
+  pol_arch_visit(h1, h2, h3, [&](auto a) {
+    e = hipFuncSetAttribute((const void*)k6_policy_act<decltype(a), false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  });
+  if (e != hipSuccess || !pol_arch_is_ref(h1, h2, h3)) return e;
+  return hipFuncSetAttribute((const void*)k6_policy_act<PolArchRef, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
 }
 
-void auv_launch_policy_arch(int h1, int h2, int h3, const auv_policy_io_t& io, int e0, int ne, hipStream_t st, long long t_host,
-                            long long gstep_host) {
-  if (pol_arch_is_ref(h1, h2, h3)) return auv_launch_policy(io, e0, ne, st, t_host, gstep_host);
+void auv_launch_policy(int h1, int h2, int h3, const auv_policy_io_t& io, int e0, int ne, hipStream_t st, long long t_host, long long gstep_host) {
   PolicyArgs pa;
   pa.io = io, pa.e0 = e0, pa.ne = ne;
   pa.t_host = t_host, pa.gstep_host = gstep_host;
   const dim3 grid((ne + POL_ROWS - 1) / POL_ROWS, 2), block(POL_THREADS);
-#define POL_ARCH_LAUNCH(a, b, c) \
-  if (h1 == (a) && h2 == (b) && h3 == (c)) \
-    hipLaunchKernelGGL((policy_act_arch<PolArch<a, b, c>>), grid, block, (pol_lds_bytes<PolArch<a, b, c>>(io.obs_dim)), st, pa);
-  POL_ARCH_LIST(POL_ARCH_LAUNCH)
-#undef POL_ARCH_LAUNCH
+  const size_t lds = pol_lds_bytes_h(h1, h2, h3, io.obs_dim);
+  if (io.params_bf16 && pol_arch_is_ref(h1, h2, h3)) {
+    hipLaunchKernelGGL((k6_policy_act<PolArchRef, true>), grid, block, lds, st, pa);
+    return;
+  }
+  pol_arch_visit(h1, h2, h3, [&](auto a) { hipLaunchKernelGGL((k6_policy_act<decltype(a), false>), grid, block, lds, st, pa); });
 }

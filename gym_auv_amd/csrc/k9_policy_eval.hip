@@ -95,13 +95,9 @@ __device__ __forceinline__ void policy_eval_body(const EvalArgs& ea) {
   }
 }
 
-// grid (ceil(M / 16), nets launched).  The reference's triple ...
-__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k9_policy_eval(EvalArgs ea) {   // (two workgroups per CU, as k6)
-  policy_eval_body<PolArchRef>(ea);
-}
-// ... and every other triple of POL_ARCH_LIST
+// grid (ceil(M / 16), nets launched)
 template <class A>
-__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) policy_eval_arch(EvalArgs ea) {
+__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k9_policy_eval(EvalArgs ea) {   // (two workgroups per CU, as k6)
   policy_eval_body<A>(ea);
 }
 
@@ -166,47 +162,26 @@ __global__ void __launch_bounds__(AUV_WAVE) k9_plan_score_v(const float* __restr
 
 }  // namespace
 
-hipError_t auv_policy_eval_prepare(int obs_dim) {
-  const size_t b = pol_lds_bytes(obs_dim);
+// (h1, h2, h3): a listed hidden-width triple (the caller has checked)
+hipError_t auv_policy_eval_prepare(int h1, int h2, int h3, int obs_dim) {
+  const size_t b = pol_lds_bytes_h(h1, h2, h3, obs_dim);
   if (b <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute((const void*)k9_policy_eval, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  hipError_t e = hipErrorInvalidValue;
+  pol_arch_visit(h1, h2, h3, [&](auto a) {
+    e = hipFuncSetAttribute((const void*)k9_policy_eval<decltype(a)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  });
+  return e;
 }
 
 // want_pi / want_v: which nets have an output asked for (at least one; the caller has checked)
-void auv_launch_policy_eval(const auv_policy_eval_t& ev, bool want_pi, bool want_v, hipStream_t st) {
+void auv_launch_policy_eval(int h1, int h2, int h3, const auv_policy_eval_t& ev, bool want_pi, bool want_v, hipStream_t st) {
   EvalArgs ea;
   ea.ev = ev;
   ea.net0 = want_pi ? 0 : 1;
   ea.vec2 = ((ev.ldx & 1) == 0 && (ev.obs_dim & 1) == 0 && ((uintptr_t)ev.X & 7) == 0) ? 1 : 0;
   const dim3 grid((unsigned)(((long long)ev.M + POL_ROWS - 1) / POL_ROWS), (want_pi ? 1 : 0) + (want_v ? 1 : 0)), block(POL_THREADS);
-  hipLaunchKernelGGL(k9_policy_eval, grid, block, pol_lds_bytes(ev.obs_dim), st, ea);
-}
-
-// a listed hidden-width triple (the caller has checked): the reference's goes to the kernel above
-hipError_t auv_policy_eval_prepare_arch(int h1, int h2, int h3, int obs_dim) {
-  if (pol_arch_is_ref(h1, h2, h3)) return auv_policy_eval_prepare(obs_dim);
-  const size_t b = pol_lds_bytes_h(h1, h2, h3, obs_dim);
-  if (b <= 64 * 1024) return hipSuccess;
-#define POL_ARCH_PREPARE(a, b_, c) \
-  if (h1 == (a) && h2 == (b_) && h3 == (c)) \
-    return hipFuncSetAttribute((const void*)policy_eval_arch<PolArch<a, b_, c>>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
-  POL_ARCH_LIST(POL_ARCH_PREPARE)
-#undef POL_ARCH_PREPARE
-  return hipErrorInvalidValue;
-}
-
-void auv_launch_policy_eval_arch(int h1, int h2, int h3, const auv_policy_eval_t& ev, bool want_pi, bool want_v, hipStream_t st) {
-  if (pol_arch_is_ref(h1, h2, h3)) return auv_launch_policy_eval(ev, want_pi, want_v, st);
-  EvalArgs ea;
-  ea.ev = ev;
-  ea.net0 = want_pi ? 0 : 1;
-  ea.vec2 = ((ev.ldx & 1) == 0 && (ev.obs_dim & 1) == 0 && ((uintptr_t)ev.X & 7) == 0) ? 1 : 0;
-  const dim3 grid((unsigned)(((long long)ev.M + POL_ROWS - 1) / POL_ROWS), (want_pi ? 1 : 0) + (want_v ? 1 : 0)), block(POL_THREADS);
-#define POL_ARCH_LAUNCH(a, b, c) \
-  if (h1 == (a) && h2 == (b) && h3 == (c)) \
-    hipLaunchKernelGGL((policy_eval_arch<PolArch<a, b, c>>), grid, block, (pol_lds_bytes<PolArch<a, b, c>>(ev.obs_dim)), st, ea);
-  POL_ARCH_LIST(POL_ARCH_LAUNCH)
-#undef POL_ARCH_LAUNCH
+  const size_t lds = pol_lds_bytes_h(h1, h2, h3, ev.obs_dim);
+  pol_arch_visit(h1, h2, h3, [&](auto a) { hipLaunchKernelGGL((k9_policy_eval<decltype(a)>), grid, block, lds, st, ea); });
 }
 
 void auv_launch_plan_score_v(const float* reward, const uint8_t* done, const float* terminal, int T, int n, int group, float gamma, float* score,

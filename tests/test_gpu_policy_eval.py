@@ -16,6 +16,7 @@ import torch
 
 from gym_auv_amd import planning
 from gym_auv_amd.config import effective_reference_config
+from gym_auv_amd.policy import SUPPORTED_HIDDEN
 from gym_auv_amd.scenarios import moving_obstacles_world
 from gym_auv_amd.world import build_world, pack_bank
 
@@ -133,6 +134,44 @@ def test_eval_matches_the_torch_modules_without_an_environment(obs_dim):
         z = (Aall[:M] - mu_ref[:M]) / sigma
         tol = 1e-5 * float((z.abs() / sigma).sum(-1).max()) + 4 * 1.2e-7 * float(lp_ref[:M].abs().max())
         assert float((r["logp"] - lp_ref[:M]).abs().max()) <= tol
+
+
+# ---- 3b. rows too wide for the LDS a launch gets unasked, at every compiled hidden-width triple ------------------------------------
+@pytest.mark.parametrize("hidden", SUPPORTED_HIDDEN)
+def test_eval_of_wide_rows_needs_the_prepared_instantiation(hidden):
+    """obs_dim 1000: K0p = 1024 and the tiles take 64 (1024 + 8 + max(H1, H3) + 8) bytes -- more than the 64 KiB a kernel may ask for
+    without hipFuncAttributeMaxDynamicSharedMemorySize, less than the 160 KiB the entry allows.  The launch therefore succeeds only if
+    the host dispatch set the attribute on the very instantiation it then launches.  17 rows: one full tile and one of a single row.
+    Reference: the torch modules in fp64 on the same weights.  Tolerance: 1e-5 was set for rows of at most 186 columns, so it is
+    measured here -- four times the error of torch's own fp32 CPU forward against that fp64 result (the factor covers another
+    summation order), and never less than 1e-5."""
+    import copy
+    import ppo
+    from gym_auv_amd.policy import pack_policy_params, policy_eval
+    obs_dim, M = 1000, 17
+    lds = 64 * (1024 + 8 + max(hidden[0], hidden[2]) + 8)
+    assert 64 * 1024 < lds < 160 * 1024
+    torch.manual_seed(1000 + hidden[0] + hidden[1])
+    net = ppo.ActorCritic(obs_dim, hidden=hidden)
+    with torch.no_grad():
+        for m in net.modules():
+            if isinstance(m, torch.nn.Linear):
+                m.bias.uniform_(-0.3, 0.3)
+    X = torch.rand((M, obs_dim), generator=torch.Generator().manual_seed(17)) * 2 - 1
+    net64 = copy.deepcopy(net).double()
+    with torch.no_grad():
+        mu64, v64 = net64.pi(X.double()), net64.v(X.double()).squeeze(-1)
+        mu32, v32 = net.pi(X), net.v(X).squeeze(-1)
+    net = net.to(DEV)
+    r = policy_eval(pack_policy_params(net, obs_dim, hidden=hidden), obs_dim, X.to(DEV), want=("mu", "value"), hidden=hidden)
+    torch.cuda.synchronize()
+    assert tuple(r["mu"].shape) == (M, 2) and tuple(r["value"].shape) == (M,)
+    for name, got, ref32, ref64 in (("mu", r["mu"], mu32, mu64), ("value", r["value"], v32, v64)):
+        e32 = float((ref32.double() - ref64).abs().max())
+        e = float((got.cpu().double() - ref64).abs().max())
+        tol = max(1e-5, 4.0 * e32)
+        print("hidden %s %s: |kernel - fp64| %.3e, |torch fp32 - fp64| %.3e, allowed %.3e" % (hidden, name, e, e32, tol))
+        assert e <= tol, (hidden, name, e, e32)
 
 
 # ---- 4. addressing ---------------------------------------------------------------------------------------------------------------

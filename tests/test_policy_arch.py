@@ -1,13 +1,11 @@
 """CPU: hidden widths other than [256, 128, 64] in the fused forward launches (csrc/auv_policy_mfma.h: PolArch, POL_ARCH_LIST) -- the C
 ABI's additions (auv_policy_arch_t, the *_arch entries), the packed layout for every listed triple, what is refused, and the register
-budget of every new kernel instantiation (cross-compile only, read from the code object's metadata)."""
+budget of every instantiation of the three forward launches (cross-compile only, read from the code object's metadata)."""
 import ctypes as C
 import os
 import re
-import shutil
 import subprocess
 import sys
-import tempfile
 
 import numpy as np
 import pytest
@@ -15,10 +13,10 @@ import torch
 
 from gym_auv_amd import _capi
 from gym_auv_amd.policy import HIDDEN, SUPPORTED_HIDDEN, _pad16, pack_policy_params, policy_param_floats
+from kernel_resources import HIPCC, assert_policy_budget, kernel_resources
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "examples"))
-HIPCC = "/opt/rocm/bin/hipcc"
 NEW = [(128, 128, 64), (128, 64, 64), (64, 64, 64)]
 ARCH_SYMBOLS = ["auv_policy_param_floats_arch", "auv_policy_act_arch", "auv_policy_rollout_arch", "auv_policy_act_stacked_arch",
                 "auv_policy_rollout_stacked_arch", "auv_policy_eval_arch"]
@@ -40,12 +38,14 @@ def _net(obs_dim, hidden, pi_hidden=None, seed=3):
 
 def test_the_list_of_triples_and_its_default():
     assert SUPPORTED_HIDDEN == ((256, 128, 64),) + tuple(NEW) and SUPPORTED_HIDDEN[0] == HIDDEN
-    # ... and it is the list of the header (one line per non-default triple)
+    # ... and it is the list of the header, in its order: one line per triple, the default first
     hdr = open(os.path.join(ROOT, "gym_auv_amd", "csrc", "auv_policy_mfma.h")).read()
     block = hdr[hdr.index("#define POL_ARCH_LIST(X)"):]
     block = block[:block.index("__host__")]
     listed = [tuple(int(x) for x in m) for m in re.findall(r"X\((\d+), (\d+), (\d+)\)", block)]
-    assert listed == NEW
+    assert tuple(listed) == SUPPORTED_HIDDEN and listed[0] == HIDDEN
+    ref = tuple(int(re.search(r"#define POL_H%d (\d+)" % i, hdr).group(1)) for i in (1, 2, 3))      # what PolArchRef is made of
+    assert ref == HIDDEN
 
 
 def test_arch_struct_has_the_header_s_size(tmp_path):
@@ -171,40 +171,21 @@ def test_fused_update_and_population_keep_refusing():
         population.pack_member(_net(6, (64, 64, 64)).pi, 6)
 
 
-# ---- the register budget of every new instantiation (the limits of tests/test_policy_eval_resources.py) ----
-def _metadata(src_name):
-    src = os.path.join(ROOT, "gym_auv_amd", "csrc", src_name)
-    tmp = tempfile.mkdtemp(prefix="auv_res_arch_")
-    try:
-        subprocess.run([HIPCC, "-O3", "--offload-arch=gfx950", "-std=c++17", "-ffp-contract=off", "-c", src,
-                        "-o", os.path.join(tmp, "k.o"), "-save-temps"], cwd=tmp, check=True,
-                       stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL, timeout=600)
-        asm = [f for f in os.listdir(tmp) if f.endswith("gfx950.s")]
-        assert asm, os.listdir(tmp)
-        return open(os.path.join(tmp, asm[0])).read()
-    finally:
-        shutil.rmtree(tmp, ignore_errors=True)
-
-
+# ---- the register budget of every instantiation of the three forward launches (tests/kernel_resources.py) ----
 @pytest.mark.skipif(not os.path.exists(HIPCC), reason="hipcc not installed")
-@pytest.mark.parametrize("src,kernel", [("k6_policy.hip", "policy_act_arch"), ("k9_policy_eval.hip", "policy_eval_arch"),
-                                        ("k12_policy_stacked.hip", "policy_stacked_arch")])
-def test_new_instantiations_fit_the_register_budget(src, kernel):
-    text = _metadata(src)
-    blocks = [b for b in re.split(r"\n\s+- \.agpr_count:", text) if re.search(r"\.name:\s+\S*%s" % kernel, b)]
-    names = sorted(re.search(r"\.name:\s+(\S+)", b).group(1) for b in blocks)
-    # one instantiation per non-default triple: the template arguments are in the mangled name
-    assert len(blocks) == len(NEW), names
-    for h in NEW:
-        assert sum("PolArchILi%dELi%dELi%dEE" % h in x for x in names) == 1, (h, names)
-    for b in blocks:
-        name = re.search(r"\.name:\s+(\S+)", b).group(1)
-        vgpr = int(re.search(r"\.vgpr_count:\s+(\d+)", b).group(1))
-        spill = int(re.search(r"\.vgpr_spill_count:\s+(\d+)", b).group(1))
-        sspill = int(re.search(r"\.sgpr_spill_count:\s+(\d+)", b).group(1))
-        private = int(re.search(r"\.private_segment_fixed_size:\s+(\d+)", b).group(1))
-        static_lds = int(re.search(r"\.group_segment_fixed_size:\s+(\d+)", b).group(1))
-        print("%s: %d VGPRs, %d + %d spilled, %d bytes private, %d bytes static LDS" % (name, vgpr, spill, sspill, private, static_lds))
-        assert vgpr <= 128, (name, vgpr)
-        assert spill == 0 and sspill == 0 and private == 0, (name, spill, sspill, private)
-        assert static_lds == 0, (name, static_lds)
+@pytest.mark.parametrize("src,kernel", [("k6_policy.hip", "k6_policy_act"), ("k9_policy_eval.hip", "k9_policy_eval"),
+                                        ("k12_policy_stacked.hip", "k12_stacked_act")])
+def test_every_instantiation_fits_the_register_budget(src, kernel):
+    blocks = [k for k in kernel_resources(src) if kernel in k["name"]]
+    names = sorted(k["name"] for k in blocks)
+    # one instantiation per listed triple: the template arguments are in the mangled name (k6: <triple, BF>, BF = true -- bf16 weights --
+    # for the default triple only)
+    f32 = [x for x in names if "EEELb1E" not in x]
+    assert len(f32) == len(SUPPORTED_HIDDEN), names
+    for h in SUPPORTED_HIDDEN:
+        assert sum("PolArchILi%dELi%dELi%dEE" % h in x for x in f32) == 1, (h, names)
+    bf = [x for x in names if "EEELb1E" in x]
+    assert len(bf) == (1 if kernel == "k6_policy_act" else 0), names
+    assert all("PolArchILi%dELi%dELi%dEEELb1E" % HIDDEN in x for x in bf), names
+    for k in blocks:
+        assert_policy_budget(k)

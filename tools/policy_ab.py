@@ -4,13 +4,15 @@
     AUV_HIP_LIB=<library A> python tools/policy_ab.py run a.npz
     AUV_HIP_LIB=<library B> python tools/policy_ab.py run b.npz        (each in a fresh process: the library is loaded once)
     python tools/policy_ab.py compare a.npz b.npz                      (exit status 1 unless every array is equal, bit for bit)
+    ... run a.npz --hidden 128,64,64                                   (another listed hidden-width triple; default 256,128,64)
 
 `run` drives one fixed scenario through auv_policy_act / auv_policy_rollout (device counters and host-named counters, mu_out /
 eps_out set, once with params_bf16), auv_policy_eval (with and without idx; policy only, value only, both; logp on stored actions),
 auv_population_act / auv_population_rollout (2 members of 16 rows) and auv_policy_act_stacked / auv_policy_rollout_stacked (frames 1
 and 3, episodes that end inside the window), each at an even (6, LiDAR off) and an odd (15, feasibility-pooled LiDAR) observation
 width, with 40 environments -- two full tiles and one of 8 rows -- and writes every output to the .npz.  tools/build_variant.sh builds
-a second library next to the product one.
+a second library next to the product one.  With another triple than the default the same scenario goes through the *_arch entries;
+the bf16 pass and the population launches, which exist for the default widths only, are left out.
 
 A one-off A/B aid, not an API example: it reaches into private attributes of FusedActorCritic and BatchedAuvEnv (_ios, _sios, _t, _g,
 _bounds_c, _streams_c, _sub_streams, _h) to call the C entry points the wrappers do not expose (NULL counters, frames = 1 through the
@@ -29,6 +31,7 @@ sys.path.insert(0, os.path.join(ROOT, "examples"))
 
 DEV = "cuda:0"
 N, MAX_T = 40, 5
+HIDDEN = (256, 128, 64)                # --hidden: the nets' hidden widths
 WIDTHS = {"d6": dict(use_lidar=False, pooled=False), "d15": dict(use_lidar=True, pooled=True)}
 
 
@@ -65,7 +68,7 @@ def _net(width, seed=5):
     import ppo
     import torch
     torch.manual_seed(seed)
-    net = ppo.ActorCritic(width).to(DEV)
+    net = ppo.ActorCritic(width, hidden=HIDDEN).to(DEV)
     with torch.no_grad():
         net.log_std.copy_(torch.tensor([-0.5, -1.1]))
         for m in net.modules():
@@ -97,6 +100,15 @@ def _check(lib, rc):
         raise RuntimeError(lib.auv_last_error())
 
 
+def _entry(lib, name, fused):
+    """The C entry `name` for fused's widths: itself for the default triple, name_arch (the triple goes in behind the io argument, the
+    fifth of a rollout call and the fourth of an act call) for any other."""
+    if fused._arch is None:
+        return getattr(lib, name)
+    fn, at = getattr(lib, name + "_arch"), 5 if "rollout" in name else 4
+    return lambda *a: fn(*a[:at], C.byref(fused._arch), *a[at:])
+
+
 def _policy(out, kind, bf16):
     """auv_policy_act (device counters), auv_policy_rollout with host-named and with device counters: T = 3 plus the flush launch"""
     import torch
@@ -115,7 +127,7 @@ def _policy(out, kind, bf16):
         elif how == "rollout_host":
             fused.rollout(T, flush=True)
         else:
-            _check(_LIB, _LIB.auv_policy_rollout(env._h, 1, env._bounds_c, env._streams_c, fused._ios, C.c_void_p(env.obs.data_ptr()),
+            _check(_LIB, _entry(_LIB, "auv_policy_rollout", fused)(env._h, 1, env._bounds_c, env._streams_c, fused._ios, C.c_void_p(env.obs.data_ptr()),
                                                  C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()), T, 1, None, None))
         _keep(out, "%s/%s" % (tag, how), fused, env)
         if how == "act" and not bf16:
@@ -134,7 +146,8 @@ def _eval(out, kind, fused):
     idx = torch.randint(0, N + 9, (N,), generator=g).to(DEV)
     for iname, rows, ix in (("rows", X[:N], None), ("idx", X, idx)):
         for wname, want in (("pi", ("mu", "action", "logp")), ("v", ("value",)), ("both", ("mu", "action", "value", "logp")), ("mu", ("mu",))):
-            r = policy_eval(fused.params, D, rows, idx=ix, actions=A if "logp" in want else None, want=want, action_map=fused.action_map)
+            r = policy_eval(fused.params, D, rows, idx=ix, actions=A if "logp" in want else None, want=want, action_map=fused.action_map,
+                            hidden=fused.hidden)
             torch.cuda.synchronize()
             for k, v in r.items():
                 out["eval/%s/%s/%s/%s" % (kind, iname, wname, k)] = v.cpu().numpy()
@@ -179,32 +192,38 @@ def _stacked(out, kind, frames):
         fused.begin_rollout()
         if how == "rollout":
             t0, g0 = (C.c_int64 * 1)(fused._t[0]), (C.c_int64 * 1)(fused._g[0])
-            _check(_LIB, _LIB.auv_policy_rollout_stacked(env._h, 1, env._bounds_c, env._streams_c, sios, C.c_void_p(env.obs.data_ptr()),
+            _check(_LIB, _entry(_LIB, "auv_policy_rollout_stacked", fused)(env._h, 1, env._bounds_c, env._streams_c, sios, C.c_void_p(env.obs.data_ptr()),
                                                          C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()), T, 1, t0, g0))
         else:
             st = C.c_void_p(env._sub_streams[0].cuda_stream)
             for _ in range(T):
-                _check(_LIB, _LIB.auv_policy_act_stacked(env._h, 0, N, C.byref(sios[0]), st))
+                _check(_LIB, _entry(_LIB, "auv_policy_act_stacked", fused)(env._h, 0, N, C.byref(sios[0]), st))
                 env.step_slice(0, fused.actions)
-            _check(_LIB, _LIB.auv_policy_act_stacked(env._h, 0, N, C.byref(sios[0]), st))
+            _check(_LIB, _entry(_LIB, "auv_policy_act_stacked", fused)(env._h, 0, N, C.byref(sios[0]), st))
         _keep(out, "stacked/%s/f%d/%s" % (kind, frames, how), fused, env)
         if how == "rollout":
             assert float(fused.buffers()[5].sum()) > 0, "no episode ended inside the window"
         env.close()
 
 
-def run(path):
+def run(path, hidden):
+    global HIDDEN
     from gym_auv_amd import _capi
+    from gym_auv_amd.policy import check_hidden
+    HIDDEN = check_hidden(hidden, "--hidden")
+    default = HIDDEN == _capi.POLICY_ARCHS[0]
     lib_path = os.environ.get("AUV_HIP_LIB") or _capi.LIB_PATH
     out = {}
     for kind in WIDTHS:
         _policy(out, kind, False)
-        _population(out, kind)
+        if default:
+            _population(out, kind)
         for frames in (1, 3):
             _stacked(out, kind, frames)
-    _policy(out, "d15", True)
+    if default:
+        _policy(out, "d15", True)
     np.savez(path, **out)
-    print("%s: %d arrays, library %s sha256 %s" % (path, len(out), lib_path, hashlib.sha256(open(lib_path, "rb").read()).hexdigest()))
+    print("%s: hidden %s, %d arrays, library %s sha256 %s" % (path, list(HIDDEN), len(out), lib_path, hashlib.sha256(open(lib_path, "rb").read()).hexdigest()))
 
 
 def compare(pa, pb):
@@ -220,7 +239,9 @@ def compare(pa, pb):
 
 if __name__ == "__main__":
     if len(sys.argv) == 3 and sys.argv[1] == "run":
-        run(sys.argv[2])
+        run(sys.argv[2], HIDDEN)
+    elif len(sys.argv) == 5 and sys.argv[1] == "run" and sys.argv[3] == "--hidden":
+        run(sys.argv[2], tuple(int(x) for x in sys.argv[4].split(",")))
     elif len(sys.argv) == 4 and sys.argv[1] == "compare":
         sys.exit(compare(sys.argv[2], sys.argv[3]))
     else:
