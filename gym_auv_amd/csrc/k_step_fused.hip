@@ -624,6 +624,15 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_roles(AuvD
 // k_fresh_record (the same body, STEP_MULTI_FW) bind only slots published before their call began (auv_device.h:
 // auv_next_world_multi).
 #define CARRY_WORDS 24
+// The second mark covers words 8..19, which lie in two 64-byte lines that are stored and loaded separately, so a reader CAN see
+// the old words 8..15 beside the new words 16..20.  A plain xor of the words lets that pass whenever the changes of two words
+// cancel: a cumulative reward and a cross-track sum that both double within their binade (r -> 2 r beside 4 -> 8) flip the same
+// exponent bits, and the reader took running sums one step old (tests/test_gpu_nav_edges.py: an environment at rest 4 m off its
+// path).  Every word is therefore multiplied by an odd constant of its position before the xor: equal words stay equal, and two
+// changed words cancel only if their products differ in the same bits -- 2^-63 for unrelated words.
+__device__ __forceinline__ unsigned long long carry_mix(const unsigned long long w, const int i) {
+  return w * (ROLES_MAGIC * (unsigned long long)(2 * i + 1));
+}
 
 // Diagnostic build only (-DAUV_STAMPS_MULTI, tools/multi_stamps.py): wall-clock stamps of the waves of ONE step in the middle of a
 // multi-step launch (the other steps stamp into a dummy half of the array), 16 words per environment:
@@ -678,11 +687,12 @@ __device__ __forceinline__ int carry_wait_wave(const AuvDev& d, const int e, con
     else if (lane < CARRY_WORDS) v = __hip_atomic_load(cw + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     const unsigned long long ma = roles_lane_word(v, 7), mb = roles_lane_word(v, 20);
     if (ma != 0ull && mb != 0ull) {
-      unsigned long long xa = roles_lane_word(v, 0), xb = roles_lane_word(v, 8);
+      const unsigned long long vm = carry_mix(v, lane);          // (lane i holds word i: one vector multiply serves words 8..19)
+      unsigned long long xa = roles_lane_word(v, 0), xb = roles_lane_word(vm, 8);
 #pragma unroll
       for (int i = 1; i < 7; i++) xa ^= roles_lane_word(v, i);
 #pragma unroll
-      for (int i = 9; i < 20; i++) xb ^= roles_lane_word(v, i);
+      for (int i = 9; i < 20; i++) xb ^= roles_lane_word(vm, i);
       if (roles_mark(xa ^ tagmix) == ma && roles_mark(xb ^ tagmix) == mb) break;
     }
     if ((polls & 31) == 31 && auv_uniform(__hip_atomic_load(d.abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) return 2;
@@ -955,7 +965,7 @@ __device__ __forceinline__ void roles_finish_wave_multi(const AuvDev& dk, const 
         v1 = __hip_atomic_load(cw + 8 + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         v2 = __hip_atomic_load(cw + 16 + c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       }
-      const unsigned long long xb = roles_group_xor(v1) ^ roles_group_xor(c < 4 ? v2 : 0ull), mb = roles_group_word(v2, 4);
+      const unsigned long long xb = roles_group_xor(carry_mix(v1, 8 + c)) ^ roles_group_xor(c < 4 ? carry_mix(v2, 16 + c) : 0ull), mb = roles_group_word(v2, 4);
       ok = !live || (roles_record_ok(v0, c, tagmix_prev) && mb != 0ull && roles_mark(xb ^ tagmix_prev) == mb);
       if (!__any(!ok)) break;
       if ((polls & 31) == 31 && auv_uniform(__hip_atomic_load(dc->abort_flag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT))) return;
@@ -1095,7 +1105,7 @@ __device__ __forceinline__ void roles_finish_wave_multi(const AuvDev& dk, const 
     w2 = c < 4 ? carry_ed_word(ne_, 4 + c) : 0ull;
   }
   const unsigned long long ma = roles_mark(roles_group_xor(c < 7 ? w0 : 0ull) ^ tagmix);
-  const unsigned long long mb = roles_mark(roles_group_xor(w1) ^ roles_group_xor(c < 4 ? w2 : 0ull) ^ tagmix);
+  const unsigned long long mb = roles_mark(roles_group_xor(carry_mix(w1, 8 + c)) ^ roles_group_xor(c < 4 ? carry_mix(w2, 16 + c) : 0ull) ^ tagmix);
   unsigned long long w2hi = 0ull;                           // words 21..23 (FB; else written as zero)
   if constexpr (FB) {
     // the next step's action.  x_0..5 are read back from the OBS64 row: the tail forms them in group lane 0 and keeps them to

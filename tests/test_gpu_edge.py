@@ -187,9 +187,10 @@ def test_cull_limits_at_integer_boundaries():
 @pytest.mark.parametrize("mode", ["one_launch", "side_by_side"])
 def test_vessel_far_from_the_path_many_surviving_chunks(mode):
     """Far from a curved path many 64-segment chunks can hold the nearest point: the navigation's survivor list is
-    longer than what it keeps in registers and takes the route through memory (and, at equal distances to two parts of
-    the path, the "first minimum wins" rule of GEOS project decides).  Vessels dropped 100 - 600 m off their paths,
-    at the centre of curvature included, in every launch shape."""
+    longer than what it keeps in registers and takes the route through memory.  Vessels dropped 100 - 600 m off their
+    paths, at the centre of curvature included, in every launch shape.  This covers the long survivor list only: the
+    poses are random draws, so two separated stretches of a path are never at a bit-equal distance; the exact ties and
+    the "first minimum wins" rule of GEOS project are pinned by tests/test_gpu_nav_edges.py."""
     specs = [sc.moving_obstacles_world(900 + i) for i in range(12)]
     n = 48
     rs = np.random.RandomState(8)
