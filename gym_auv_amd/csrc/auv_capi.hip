@@ -820,7 +820,9 @@ int auv_load_worlds(auv_handle_t* h, const auv_world_bank_t* b) {
   }
   for (int64_t m = 0; m < nM; m++) {
     if (b->mv_vtab_off[m + 1] - b->mv_vtab_off[m] < 1) return fail(AUV_EINVAL, "mover %lld: empty velocity table", (long long)m);
-    if (!(b->mv_param[4 * m + 3] >= 2.0)) return fail(AUV_EINVAL, "mover %lld: n_vel < 2", (long long)m);
+    // n_vel = 1 is a trajectory of two waypoints one tick apart: the reference rewinds it on every update and reads row 0
+    // (obstacles.py:200-205); with no row at all it raises
+    if (!(b->mv_param[4 * m + 3] >= 1.0)) return fail(AUV_EINVAL, "mover %lld: n_vel < 1", (long long)m);
   }
   d.n_worlds = W;
   d.k_max = k_max;

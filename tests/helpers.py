@@ -64,9 +64,10 @@ def scene_order(z, i):
     return np.array([base[int(k)] + int(j) for k, j in order], dtype=np.int64)
 
 
-def shape_run(shape_name, cfg, bank, n, ring, steps, fields=(), **kw):
+def shape_run(shape_name, cfg, bank, n, ring, steps, fields=(), lengths=(1, 6, 16, 64), **kw):
     """-m gpu: (obs, *fields read, reward, done) after every step (multi-step launches: after every launch) of one step
-    shape; auto-reset on, actions ring[t % slots].  kw: further BatchedAuvEnv arguments (rewarder, cull)."""
+    shape; auto-reset on, actions ring[t % slots].  lengths: steps per launch of the multi-step shapes, cycled through.
+    kw: further BatchedAuvEnv arguments (rewarder, cull)."""
     import warnings
 
     import torch
@@ -92,7 +93,6 @@ def shape_run(shape_name, cfg, bank, n, ring, steps, fields=(), **kw):
     slots = ring.shape[0]
     if shape_name.startswith("multi"):
         t = 0
-        lengths = [1, 6, 16, 64]
         while t < steps:
             T = min(lengths[len(out) % len(lengths)], steps - t)
             env.step_multi(ring, t % slots, T)
