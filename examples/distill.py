@@ -43,7 +43,8 @@ def metrics(log):
 
 
 def run(envs=64, candidates=32, horizon=16, decisions=400, every=20, epochs=2, batch=256, beta=0.5, kind="nll", lr=3e-4, eager=False,
-        capacity=65536, reward_scale=0.01, eval_episodes=1, eval_steps=2000, seed=0, device="cuda:0", log=print):
+        capacity=65536, reward_scale=0.01, eval_episodes=1, eval_steps=2000, seed=0, device="cuda:0", log=print,
+        net_arch=(256, 128, 64)):
     from evaluate import evaluate, load_policy
     cfg = effective_reference_config(use_lidar=True)
     bank = pack_bank([build_world(scenarios.moving_obstacles_world(seed + i)) for i in range(2 * envs)])
@@ -51,7 +52,7 @@ def run(envs=64, candidates=32, horizon=16, decisions=400, every=20, epochs=2, b
         warnings.simplefilter("ignore")
         env = BatchedAuvEnv(cfg, bank, envs, device=device, rewarder="colav", auto_reset=True)
     env.reset()
-    net = load_policy(None, env.obs_dim, device, seed).train()
+    net = load_policy(None, env.obs_dim, device, seed, hidden=tuple(int(h) for h in net_arch)).train()
     lo, hi = env.action_space.low, env.action_space.high              # the policy speaks [-1, 1]^2
     fused = FusedActorCritic(net, env, rollout=1, act_mid=((lo + hi) / 2).tolist(), act_half=((hi - lo) / 2).tolist(),
                              clip_lo=[-1.0, -1.0], clip_hi=[1.0, 1.0], seed=seed)
@@ -129,10 +130,12 @@ def main():
     ap.add_argument("--eval-steps", type=int, default=2000)
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--net-arch", default="256,128,64", metavar="H1,H2,H3",
+                    help="hidden widths of the policy and the value net: one of 256,128,64 (the reference's)  128,128,64  128,64,64  64,64,64")
     a = ap.parse_args()
     res = run(envs=a.envs, candidates=a.candidates, horizon=a.horizon, decisions=a.decisions, every=a.every, epochs=a.epochs, batch=a.batch,
               beta=a.beta, kind=a.kind, lr=a.lr, eager=bool(a.eager), eval_episodes=a.eval_episodes, eval_steps=a.eval_steps, seed=a.seed,
-              device=a.device)
+              device=a.device, net_arch=tuple(int(h) for h in a.net_arch.split(",")))
     print(json.dumps(res))
 
 

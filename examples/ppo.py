@@ -201,7 +201,7 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
     if frames > 1 and not fused_policy:
         raise ValueError("--frames %d needs --fused-policy 1: the stacked rows are formed by the fused policy launch" % frames)
     # --net-arch: the hidden widths of both nets.  The fused policy launch is compiled for a closed list of them
-    # (gym_auv_amd.policy.SUPPORTED_HIDDEN) and refuses any other; the fused update (--fused-update 1) evaluates [256, 128, 64] only
+    # (gym_auv_amd.policy.SUPPORTED_HIDDEN) and refuses any other; the fused update (--fused-update 1) trains the same list
     net = ActorCritic(frames * env.obs_dim, hidden=tuple(int(h) for h in net_arch), log_std=log_std, orthogonal=orthogonal).to(device)
     params = list(net.parameters())
     pi_params, v_params = list(net.pi.parameters()) + [net.log_std], list(net.v.parameters())
@@ -566,7 +566,7 @@ if __name__ == "__main__":
                     help="k > 1: the policy sees the last k observations as one row of k * obs_dim columns (frame stacking; needs --fused-policy 1)")
     ap.add_argument("--net-arch", default="256,128,64", metavar="H1,H2,H3",
                     help="hidden widths of the policy and the value net; with --fused-policy 1 one of 256,128,64 (the reference's) "
-                         "128,128,64  128,64,64  64,64,64; --fused-update 1 takes the reference's only")
+                         "128,128,64  128,64,64  64,64,64; --fused-update 1 takes the same list")
     ap.add_argument("--step-mode", default=None, help="launch shape of a step (BatchedAuvEnv.STEP_MODES); default: the library's")
     ap.add_argument("--act-space", default="raw", choices=["raw", "normalized"])
     ap.add_argument("--ret-norm", type=int, default=0)

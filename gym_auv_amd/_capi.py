@@ -320,6 +320,8 @@ def load_library(path: str = None) -> C.CDLL:
         "auv_ppo_grad": (C.c_int, [vp, C.POINTER(AuvPpoBatch), vp, vp, vp]),
         "auv_ppo_adam": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(AuvPpoAdam), vp, vp]),
         "auv_ppo_grad_clone": (C.c_int, [vp, C.POINTER(AuvPpoCloneBatch), vp, vp, vp]),
+        "auv_ppo_param_floats_arch": (sz, [i32, C.POINTER(AuvPolicyArch)]),
+        "auv_ppo_create_arch": (C.c_int, [i32, i32, i32, C.POINTER(AuvPolicyArch), C.POINTER(vp)]),
         "auv_render": (C.c_int, [vp, vp, C.POINTER(i32), i32, i32, i32, C.c_double, i32, C.c_double, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
         "auv_abi_version": (i32, []),
         "auv_last_error": (C.c_char_p, []),
@@ -355,7 +357,7 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_policy_rollout_stacked_arch", "auv_policy_eval_arch",
                     "auv_population_member_floats", "auv_population_act", "auv_population_rollout", "auv_population_perturb", "auv_population_update",
                     "auv_ppo_param_floats", "auv_ppo_create", "auv_ppo_destroy", "auv_ppo_load", "auv_ppo_attach_policy", "auv_ppo_grad", "auv_ppo_adam",
-                    "auv_ppo_grad_clone",
+                    "auv_ppo_grad_clone", "auv_ppo_param_floats_arch", "auv_ppo_create_arch",
                     "auv_render",
                     "auv_abi_version", "auv_last_error"]
 

@@ -2691,20 +2691,33 @@ int auv_step_timed(auv_handle_t* h, const void* actions_dev, int32_t action_dtyp
   return AUV_OK;
 }
 
-// ---- the PPO update (include/auv_hip.h, auv_ppo_*; kernels: k8_ppo_update.hip) ----
+// ---- the PPO update (include/auv_hip.h, auv_ppo_*; kernels: k8_ppo_update.hip, k13_ppo_update_arch.hip) ----
 struct auv_ppo {
   AuvPpoDev d;
+  auv_policy_arch_t arch;          // the hidden widths, a triple of POL_ARCH_LIST: every launch dispatches on them
   int device;
   float* arena;
 };
 
-size_t auv_ppo_param_floats(int32_t obs_dim) { return obs_dim > 0 ? auv_ppo_param_floats_impl(obs_dim) : 0; }
+size_t auv_ppo_param_floats(int32_t obs_dim) { return auv_ppo_param_floats_arch(obs_dim, &POLICY_ARCH_REF); }
+
+size_t auv_ppo_param_floats_arch(int32_t obs_dim, const auv_policy_arch_t* arch) {
+  if (obs_dim <= 0 || !arch || !pol_arch_listed(arch->h1, arch->h2, arch->h3)) return 0;
+  return auv_ppo_param_floats_impl(obs_dim, *arch);
+}
 
 int auv_ppo_create(int32_t device, int32_t obs_dim, int32_t max_batch, auv_ppo_t** out) {
+  return auv_ppo_create_arch(device, obs_dim, max_batch, &POLICY_ARCH_REF, out);
+}
+
+int auv_ppo_create_arch(int32_t device, int32_t obs_dim, int32_t max_batch, const auv_policy_arch_t* arch, auv_ppo_t** out) {
   if (!out) return fail(AUV_EINVAL, "auv_ppo_create: null out");
   *out = nullptr;
+  int rca = check_policy_arch(arch, nullptr, "auv_ppo_create");
+  if (rca != AUV_OK) return rca;
+  const auv_policy_arch_t a = *arch;
   if (obs_dim < 1) return fail(AUV_EINVAL, "auv_ppo_create: obs_dim %d < 1", obs_dim);
-  if (obs_dim > 16384 || auv_ppo_lds_bytes(obs_dim) > 160 * 1024)
+  if (obs_dim > 16384 || auv_ppo_lds_bytes(obs_dim, a) > 160 * 1024)
     return fail(AUV_EINVAL, "auv_ppo_create: obs_dim %d is too wide for the row pass' LDS tile", obs_dim);
   if (max_batch < 1 || max_batch > (1 << 24)) return fail(AUV_EINVAL, "auv_ppo_create: max_batch %d outside [1, 2^24]", max_batch);
   if (device < 0) return fail(AUV_EINVAL, "auv_ppo_create: device %d", device);
@@ -2712,15 +2725,15 @@ int auv_ppo_create(int32_t device, int32_t obs_dim, int32_t max_batch, auv_ppo_t
   HIP_TRY(hipGetDeviceCount(&ndev));
   if (device >= ndev) return fail(AUV_EINVAL, "auv_ppo_create: device %d not present (%d visible)", device, ndev);
   HIP_TRY(hipSetDevice(device));
-  HIP_TRY(auv_ppo_prepare(obs_dim));
+  HIP_TRY(auv_ppo_prepare(obs_dim, a));
   auv_ppo* p = new auv_ppo();
-  p->device = device;
+  p->device = device, p->arch = a;
   AuvPpoDev& d = p->d;
   d.obs_dim = obs_dim, d.k0p = (obs_dim + 31) & ~31, d.max_batch = max_batch, d.rt_max = (max_batch + 15) / 16;
-  const size_t rows = (size_t)d.rt_max * 16, fwd = auv_ppo_fwd_floats(obs_dim), tr = auv_ppo_tr_floats();
+  const size_t rows = (size_t)d.rt_max * 16, fwd = auv_ppo_fwd_floats(obs_dim, a), tr = auv_ppo_tr_floats(a);
   // one allocation, carved into parts of a multiple of four floats each (16-byte aligned)
   const size_t n_part = (size_t)AUV_PPO_MAX_SPLIT * (fwd - 4);
-  size_t total = fwd + tr + 256 + rows * d.k0p + 2 * rows * (2 * (256 + 128 + 64) + 16) + n_part + (size_t)d.rt_max * 8 + 4 * AUV_PPO_NORM_BLOCKS;
+  size_t total = fwd + tr + 256 + rows * d.k0p + 2 * rows * (2 * (size_t)(a.h1 + a.h2 + a.h3) + 16) + n_part + (size_t)d.rt_max * 8 + 4 * AUV_PPO_NORM_BLOCKS;
   hipError_t e = hipMalloc((void**)&p->arena, total * sizeof(float));
   if (e != hipSuccess) {
     delete p;
@@ -2732,8 +2745,8 @@ int auv_ppo_create(int32_t device, int32_t obs_dim, int32_t max_batch, auv_ppo_t
   d.sqpart = (double*)take(4 * AUV_PPO_NORM_BLOCKS);
   d.X = take(rows * d.k0p);
   for (int net = 0; net < 2; net++) {
-    d.Y[net][0] = take(rows * 256), d.Y[net][1] = take(rows * 128), d.Y[net][2] = take(rows * 64);
-    d.dZ[net][0] = take(rows * 256), d.dZ[net][1] = take(rows * 128), d.dZ[net][2] = take(rows * 64), d.dZ[net][3] = take(rows * 16);
+    d.Y[net][0] = take(rows * a.h1), d.Y[net][1] = take(rows * a.h2), d.Y[net][2] = take(rows * a.h3);
+    d.dZ[net][0] = take(rows * a.h1), d.dZ[net][1] = take(rows * a.h2), d.dZ[net][2] = take(rows * a.h3), d.dZ[net][3] = take(rows * 16);
   }
   d.part = take(n_part), d.tstat = take((size_t)d.rt_max * 8);
   d.pol = nullptr;
@@ -2759,7 +2772,7 @@ void auv_ppo_destroy(auv_ppo_t* p) {
 int auv_ppo_load(auv_ppo_t* p, const float* theta, void* stream) {
   if (!p || !theta) return fail(AUV_EINVAL, "auv_ppo_load: null %s", !p ? "updater" : "theta");
   HIP_TRY(hipSetDevice(p->device));
-  auv_launch_ppo_load(p->d, theta, (hipStream_t)stream);
+  auv_launch_ppo_load(p->d, p->arch, theta, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }
@@ -2777,8 +2790,8 @@ int auv_ppo_grad(auv_ppo_t* p, const auv_ppo_batch_t* b, float* grad, float* sta
   if (b->B < 1 || b->B > p->d.max_batch) return fail(AUV_EINVAL, "auv_ppo_grad: B = %d outside [1, max_batch = %d]", b->B, p->d.max_batch);
   if (b->n_rows < 1 || (!b->idx && b->B > b->n_rows)) return fail(AUV_EINVAL, "auv_ppo_grad: B = %d rows of n_rows = %d", b->B, b->n_rows);
   HIP_TRY(hipSetDevice(p->device));
-  HIP_TRY(auv_ppo_prepare(p->d.obs_dim));
-  auv_launch_ppo_grad(p->d, *b, grad, stats, (hipStream_t)stream);
+  HIP_TRY(auv_ppo_prepare(p->d.obs_dim, p->arch));
+  auv_launch_ppo_grad(p->d, p->arch, *b, grad, stats, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }
@@ -2791,8 +2804,8 @@ int auv_ppo_grad_clone(auv_ppo_t* p, const auv_ppo_clone_batch_t* b, float* grad
   if (b->n_rows < 1 || (!b->idx && b->B > b->n_rows)) return fail(AUV_EINVAL, "auv_ppo_grad_clone: B = %d rows of n_rows = %d", b->B, b->n_rows);
   if (b->B > p->d.max_batch) return fail(AUV_EINVAL, "auv_ppo_grad_clone: B = %d above max_batch = %d", b->B, p->d.max_batch);
   HIP_TRY(hipSetDevice(p->device));
-  HIP_TRY(auv_ppo_prepare(p->d.obs_dim, true));
-  auv_launch_ppo_grad_clone(p->d, *b, grad, stats, (hipStream_t)stream);
+  HIP_TRY(auv_ppo_prepare(p->d.obs_dim, p->arch, true));
+  auv_launch_ppo_grad_clone(p->d, p->arch, *b, grad, stats, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }
@@ -2805,7 +2818,7 @@ int auv_ppo_adam(auv_ppo_t* p, float* theta, float* m, float* v, const float* gr
   h.step_size = (float)(a->lr / a->bc1), h.bc2_sqrt = (float)std::sqrt(a->bc2), h.eps = (float)a->eps;
   h.max_norm_pi = a->max_norm_pi, h.max_norm_v = a->max_norm_v;
   HIP_TRY(hipSetDevice(p->device));
-  auv_launch_ppo_adam(p->d, theta, m, v, grad, h, norms_out, (hipStream_t)stream);
+  auv_launch_ppo_adam(p->d, p->arch, theta, m, v, grad, h, norms_out, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }

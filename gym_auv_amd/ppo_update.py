@@ -1,4 +1,5 @@
-"""FusedPPOUpdate -- one PPO minibatch step of examples/ppo.py as a few HIP launches (csrc/k8_ppo_update.hip, auv_ppo_*).
+"""FusedPPOUpdate -- one PPO minibatch step of examples/ppo.py as a few HIP launches (csrc/k8_ppo_update.hip, k13_ppo_update_arch.hip,
+auv_ppo_*).
 
 The reference trains PPO2 with `MlpPolicy`, net_arch [256, 128, 64] for policy and value function, tanh, a diagonal Gaussian with a
 free log_std (the reference's scripts/run.py:332-357).  `minibatch_step` of examples/ppo.py evaluates that update with stock tensor
@@ -21,6 +22,9 @@ value net towards target values -- a planner's decisions (planning.DistillBuffer
                                                             #       |g_pi|, |g_v|;  kind "mse": squared error of the mean instead
     g, stats = upd.clone_grad(O, A, RET)                    # the two halves, as above
 
+Hidden widths: read off `net.pi` / `net.v` (both the same triple), one of SUPPORTED_HIDDEN -- the reference's [256, 128, 64] and the
+narrower nets the fused forward launches evaluate (policy.SUPPORTED_HIDDEN); anything else raises ValueError.  `upd.hidden` is the triple.
+
 The module's parameters become views of ONE flat tensor (`upd.theta`, torch layout: pi W1 b1 .. W4 b4, v W1 .. b4, log_std); the torch
 modules stay usable and stay the owners -- `net.v(obs)` sees every step.  Deterministic: the same inputs give the same bits.
 """
@@ -31,9 +35,10 @@ from typing import Optional, Tuple
 import torch
 import torch.nn as nn
 
-from . import _capi
+from . import _capi, policy
 
-HIDDEN = (256, 128, 64)
+HIDDEN = (256, 128, 64)                      # the reference's hidden widths: the default, through the entries without _arch
+SUPPORTED_HIDDEN = policy.SUPPORTED_HIDDEN   # the closed list the update is compiled for: the forward launches' (POL_ARCH_LIST)
 CLONE_KINDS = {"nll": 0, "mse": 1}
 _LIB = _capi.load_library()
 
@@ -69,16 +74,26 @@ class FusedPPOUpdate:
     LOG_ROWS = 8192
 
     def __init__(self, net: nn.Module, lr: float = 2e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, clip: float = 0.2,
-                 vf_coef: float = 0.5, ent_coef: float = 0.01, max_norm_pi: float = 0.5, max_norm_v: float = 0.5, max_batch: int = 16384):
+                 vf_coef: float = 0.5, ent_coef: float = 0.01, max_norm_pi: float = 0.5, max_norm_v: float = 0.5, max_batch: int = 16384,
+                 arch_entry: Optional[bool] = None):
+        """arch_entry  None: the default widths go through auv_ppo_create, any other through auv_ppo_create_arch; True: the _arch entries
+                    also for the default widths (they dispatch to the same kernels: tests compare the two)."""
         tensors = []
+        # the hidden widths are read off the modules: both nets the same triple, one of SUPPORTED_HIDDEN
+        self.hidden = None
         for seq, out in ((net.pi, 2), (net.v, 1)):
             lin = [m for m in seq if isinstance(m, nn.Linear)]
             act = [m for m in seq if not isinstance(m, nn.Linear)]
             dims = tuple(l.out_features for l in lin[:-1])
-            if (dims != HIDDEN or lin[-1].out_features != out or lin[0].in_features != net.pi[0].in_features
+            if (dims not in SUPPORTED_HIDDEN or lin[-1].out_features != out or lin[0].in_features != net.pi[0].in_features
                     or not all(isinstance(a, nn.Tanh) for a in act) or any(l.bias is None for l in lin)):
-                raise ValueError("FusedPPOUpdate trains the reference's architecture: obs -> %s tanh -> %d (scripts/run.py:332-357); "
-                                 "got %s -> %d" % (list(HIDDEN), out, list(dims), lin[-1].out_features))
+                raise ValueError("FusedPPOUpdate trains obs -> [h1, h2, h3] tanh -> %d with three hidden layers and biases (another depth "
+                                 "is not compiled in), [h1, h2, h3] one of %s (the reference's scripts/run.py:332-357 first); got %s -> %d"
+                                 % (out, list(SUPPORTED_HIDDEN), list(dims), lin[-1].out_features))
+            if self.hidden is not None and dims != self.hidden:
+                raise ValueError("FusedPPOUpdate: net.pi has the hidden widths %s, net.v %s -- one updater trains both nets with the same "
+                                 "widths, one of %s" % (list(self.hidden), list(dims), list(SUPPORTED_HIDDEN)))
+            self.hidden = dims
             for l in lin:
                 tensors += [l.weight, l.bias]
         if tuple(net.log_std.shape) != (2,):
@@ -88,7 +103,12 @@ class FusedPPOUpdate:
         self.device = tensors[0].device
         if self.device.type != "cuda" or any(t.device != self.device or t.dtype != torch.float32 for t in tensors):
             raise ValueError("FusedPPOUpdate: the module must hold float32 parameters on one GPU")
-        n = int(_LIB.auv_ppo_param_floats(self.obs_dim))
+        # the default widths go through the entries without _arch (unless arch_entry: the _arch entries then dispatch to the same kernels)
+        self._arch = policy._arch_arg(self.hidden) if (self.hidden != HIDDEN or arch_entry) else None
+        if self._arch is None:
+            n = int(_LIB.auv_ppo_param_floats(self.obs_dim))
+        else:
+            n = int(_LIB.auv_ppo_param_floats_arch(self.obs_dim, C.byref(self._arch)))
         assert n == sum(t.numel() for t in tensors)
         # ONE flat tensor; every parameter becomes a view of it (the modules stay the owners of the weights)
         self.theta = torch.empty(n, dtype=torch.float32, device=self.device)
@@ -111,7 +131,11 @@ class FusedPPOUpdate:
         self.n_steps = 0
         self._fused = None
         h = C.c_void_p()
-        _check(_LIB.auv_ppo_create(self.device.index or 0, self.obs_dim, self.max_batch, C.byref(h)), "auv_ppo_create")
+        if self._arch is None:
+            _check(_LIB.auv_ppo_create(self.device.index or 0, self.obs_dim, self.max_batch, C.byref(h)), "auv_ppo_create")
+        else:
+            _check(_LIB.auv_ppo_create_arch(self.device.index or 0, self.obs_dim, self.max_batch, C.byref(self._arch), C.byref(h)),
+                   "auv_ppo_create_arch")
         self._h = h
         self.load()
 
@@ -139,6 +163,10 @@ class FusedPPOUpdate:
             raise ValueError("FusedPPOUpdate.attach: the bf16 policy keeps a second copy of the weights that only refresh() packs")
         if getattr(fused, "in_dim", fused.env.obs_dim) != self.obs_dim or fused.params.device != self.device:   # (in_dim: frames * obs_dim)
             raise ValueError("FusedPPOUpdate.attach: the policy has another observation width or device")
+        hidden = tuple(getattr(fused, "hidden", HIDDEN))            # (the C side cannot see the buffer's length)
+        if hidden != self.hidden:
+            raise ValueError("FusedPPOUpdate.attach: the policy evaluates the hidden widths %s, the updater trains %s"
+                             % (list(hidden), list(self.hidden)))
         _check(_LIB.auv_ppo_attach_policy(self._h, C.c_void_p(fused.params.data_ptr())), "auv_ppo_attach_policy")
         self._fused = fused                                         # (keeps the buffer alive)
         self.load()

@@ -767,7 +767,7 @@ int auv_policy_eval(int32_t device, const auv_policy_eval_t* ev, void* stream);
  * (256, 128, 64) through an _arch entry runs the very kernels of the entry without the suffix.  AUV_EINVAL, before anything is
  * enqueued, beside what the plain entries refuse: arch NULL; a triple outside the list (it is never rounded to a listed one;
  * auv_policy_param_floats_arch then returns 0); params_bf16 set with another triple than (256, 128, 64).  The population launches
- * (auv_population_*) and the fused update (auv_ppo_*) evaluate (256, 128, 64) only.                                                */
+ * (auv_population_*) evaluate (256, 128, 64) only; the fused update takes the same list (auv_ppo_create_arch below).              */
 typedef struct auv_policy_arch {
   int32_t h1, h2, h3;
 } auv_policy_arch_t;
@@ -955,6 +955,16 @@ int auv_ppo_attach_policy(auv_ppo_t* p, float* policy_params);
 int auv_ppo_grad(auv_ppo_t* p, const auv_ppo_batch_t* batch, float* grad, float* stats, void* stream);
 int auv_ppo_adam(auv_ppo_t* p, float* theta, float* m, float* v, const float* grad, const auv_ppo_adam_t* adam, float* norms_out,
                  void* stream);
+/* The update at the other hidden widths of the forward launches (auv_policy_arch_t above; scripts/run.py:332-357 trains
+ * net_arch [256, 128, 64] only): the updater remembers its triple, and auv_ppo_load / attach_policy / grad / grad_clone / adam then act
+ * on obs -> h1 -> h2 -> h3 -> out with (h1, h2, h3) in the place of (256, 128, 64) in every layout above (kernels:
+ * csrc/k13_ppo_update_arch.hip; (256, 128, 64) runs the very kernels of auv_ppo_create's updaters).  The attached buffer holds
+ * auv_policy_param_floats_arch(obs_dim, arch) floats: its length is the caller's to match, it cannot be checked here.
+ *   auv_ppo_param_floats_arch   auv_ppo_param_floats for the triple; 0 for obs_dim <= 0, arch NULL or a triple outside the list.
+ *   auv_ppo_create_arch         auv_ppo_create for the triple; AUV_EINVAL, before any device call, also for arch NULL or a triple
+ *                               outside the list (never rounded to a listed one).                                                */
+size_t auv_ppo_param_floats_arch(int32_t obs_dim, const auv_policy_arch_t* arch);
+int auv_ppo_create_arch(int32_t device, int32_t obs_dim, int32_t max_batch, const auv_policy_arch_t* arch, auv_ppo_t** out);
 
 /* ---- the supervised (clone) row pass of the same updater: the policy trained towards given target actions, the value net towards
  * given targets -- distilling a planner's decisions (gym_auv_amd/planning.py, DistillBuffer), cloning an autopilot, warm-starting PPO.

@@ -3,6 +3,8 @@
 rows already gathered, that step behind its five gathers, and the fused step (gym_auv_amd/ppo_update.py).  B = 16384 rows of 131072
 stored ones, obs_dim 186 and 15; HIP events around every step, warm-up, the median of `--reps` steps.  With --train it then runs
 examples/ppo.py for a few updates with --fused-update off and on and reports `sps`.  One JSON line per measurement goes to --out.
+--arch H1,H2,H3[:H1,H2,H3...]: hidden widths of the nets (gym_auv_amd.ppo_update.SUPPORTED_HIDDEN); several, separated by ':', are
+measured one after the other in the same session, `--passes` times round (alternating passes show the spread between them).
 
     python tools/ppo_update_bench.py --out profiles/ppo_update/ppo_update_bench.jsonl --train 1
 """
@@ -36,13 +38,13 @@ def timed(fn, warmup, reps):
     return dict(median_ms=statistics.median(ms), min_ms=ms[0], p90_ms=ms[int(0.9 * (len(ms) - 1))], reps=reps)
 
 
-def bench_width(obs_dim, B, n_rows, warmup, reps, device):
+def bench_width(obs_dim, B, n_rows, warmup, reps, device, arch=(256, 128, 64)):
     import ppo
     from gym_auv_amd.ppo_update import FusedPPOUpdate
     torch.manual_seed(0)
     clip, ent_coef = 0.2, 0.01
-    net = ppo.ActorCritic(obs_dim).to(device)
-    twin = ppo.ActorCritic(obs_dim).to(device)
+    net = ppo.ActorCritic(obs_dim, hidden=arch).to(device)
+    twin = ppo.ActorCritic(obs_dim, hidden=arch).to(device)
     twin.load_state_dict(net.state_dict())
     O, A = torch.randn(n_rows, obs_dim, device=device), torch.randn(n_rows, 2, device=device) * 0.5
     with torch.no_grad():
@@ -76,7 +78,7 @@ def bench_width(obs_dim, B, n_rows, warmup, reps, device):
     idx = torch.randperm(n_rows, device=device)[:B].contiguous()
     rows = (O[idx], A[idx], LP[idx], ADV[idx], RET[idx])
     upd = FusedPPOUpdate(net, lr=2e-4, clip=clip, vf_coef=0.5, ent_coef=ent_coef, max_batch=B)
-    out = dict(obs_dim=obs_dim, B=B, n_rows=n_rows)
+    out = dict(obs_dim=obs_dim, B=B, n_rows=n_rows, arch=list(arch))
     out["eager"] = timed(lambda: eager(*rows), warmup, reps)
     out["eager_with_gathers"] = timed(lambda: eager(O[idx], A[idx], LP[idx], ADV[idx], RET[idx]), warmup, reps)
     out["fused"] = timed(lambda: upd.step(O, A, LP, ADV, RET, idx), warmup, reps)
@@ -97,7 +99,11 @@ if __name__ == "__main__":
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--rollout", type=int, default=128)
     ap.add_argument("--updates", type=int, default=4)
+    ap.add_argument("--arch", default="256,128,64", metavar="H1,H2,H3[:H1,H2,H3...]", help="hidden widths; several separated by ':'")
+    ap.add_argument("--obs-dims", default="186,15", help="observation widths, separated by ','")
+    ap.add_argument("--passes", type=int, default=1, help="times the list of widths is gone through")
     a = ap.parse_args()
+    archs = [tuple(int(x) for x in s.split(",")) for s in a.arch.split(":")]
     from gym_auv_amd import _capi
     sha = hashlib.sha256(open(_capi.LIB_PATH, "rb").read()).hexdigest()
     os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
@@ -108,14 +114,17 @@ if __name__ == "__main__":
             print(line, flush=True)
             f.write(line + "\n")
             f.flush()
-        for D in (186, 15):
-            emit(dict(kind="minibatch_step", device=torch.cuda.get_device_name(0), **bench_width(D, a.B, a.rows, a.warmup, a.reps, "cuda:0")))
+        for k in range(a.passes):
+            for arch in archs:
+                for D in (int(x) for x in a.obs_dims.split(",")):
+                    emit(dict(kind="minibatch_step", device=torch.cuda.get_device_name(0), **{"pass": k},
+                              **bench_width(D, a.B, a.rows, a.warmup, a.reps, "cuda:0", arch)))
         if a.train:
             import ppo
-            for flag in (0, 1):
-                hist = ppo.train(envs=a.envs, updates=a.updates, rollout=a.rollout, log=lambda *_: None, fused_update=bool(flag))
+            for arch, flag in ((h, f) for h in archs for f in (0, 1)):
+                hist = ppo.train(envs=a.envs, updates=a.updates, rollout=a.rollout, log=lambda *_: None, fused_update=bool(flag), net_arch=arch)
                 tail = hist[1:] or hist                          # (the first update pays for allocations and start-up)
-                emit(dict(kind="train", fused_update=flag, envs=a.envs, rollout=a.rollout, updates=a.updates,
+                emit(dict(kind="train", fused_update=flag, arch=list(arch), envs=a.envs, rollout=a.rollout, updates=a.updates,
                           sps=[h["sps"] for h in hist], sps_median_after_first=statistics.median(h["sps"] for h in tail),
                           rollout_sps_median=statistics.median(h["rollout_sps"] for h in tail),
                           nonfinite_steps=sum(h["minibatch_steps_nonfinite"] for h in hist)))
