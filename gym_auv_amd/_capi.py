@@ -312,6 +312,13 @@ def load_library(path: str = None) -> C.CDLL:
         "auv_population_rollout": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(AuvPopulationIO), vp, vp, vp, i32, i32]),
         "auv_population_perturb": (C.c_int, [i32, vp, vp, C.c_int64, i32, i32, C.c_float, C.c_uint64, C.c_int64, vp]),
         "auv_population_update": (C.c_int, [i32, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, C.c_int64, vp]),
+        "auv_population_member_floats_arch": (sz, [i32, C.POINTER(AuvPolicyArch)]),
+        "auv_population_act_arch": (C.c_int, [i32, C.POINTER(AuvPopulationIO), C.POINTER(AuvPolicyArch), vp]),
+        "auv_population_rollout_arch": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(AuvPopulationIO), C.POINTER(AuvPolicyArch),
+                                                  vp, vp, vp, i32, i32]),
+        "auv_population_perturb_arch": (C.c_int, [i32, vp, vp, C.c_int64, i32, i32, C.c_float, C.c_uint64, C.c_int64, C.POINTER(AuvPolicyArch), vp]),
+        "auv_population_update_arch": (C.c_int, [i32, vp, vp, vp, i32, i32, C.c_float, C.c_float, C.c_uint64, C.c_int64, C.POINTER(AuvPolicyArch),
+                                                 vp]),
         "auv_ppo_param_floats": (sz, [i32]),
         "auv_ppo_create": (C.c_int, [i32, i32, i32, C.POINTER(vp)]),
         "auv_ppo_destroy": (None, [vp]),
@@ -356,6 +363,8 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_policy_param_floats_arch", "auv_policy_act_arch", "auv_policy_rollout_arch", "auv_policy_act_stacked_arch",
                     "auv_policy_rollout_stacked_arch", "auv_policy_eval_arch",
                     "auv_population_member_floats", "auv_population_act", "auv_population_rollout", "auv_population_perturb", "auv_population_update",
+                    "auv_population_member_floats_arch", "auv_population_act_arch", "auv_population_rollout_arch", "auv_population_perturb_arch",
+                    "auv_population_update_arch",
                     "auv_ppo_param_floats", "auv_ppo_create", "auv_ppo_destroy", "auv_ppo_load", "auv_ppo_attach_policy", "auv_ppo_grad", "auv_ppo_adam",
                     "auv_ppo_grad_clone", "auv_ppo_param_floats_arch", "auv_ppo_create_arch",
                     "auv_render",

@@ -78,9 +78,10 @@ hipError_t auv_policy_eval_prepare(int h1, int h2, int h3, int obs_dim);
 void auv_launch_policy_eval(int h1, int h2, int h3, const auv_policy_eval_t& ev, bool want_pi, bool want_v, hipStream_t st);
 void auv_launch_plan_score_v(const float* reward, const uint8_t* done, const float* terminal, int T, int n, int group, float gamma, float* score,
                              int32_t* best, hipStream_t st);
-size_t auv_population_member_floats_impl(int obs_dim);
-hipError_t auv_population_prepare(int obs_dim);
-void auv_launch_population_act(const auv_population_io_t& io, hipStream_t st);
+// k14_population_arch.hip: the population launches at the widths `a` (a listed triple; the reference's lands on k11_population.hip)
+size_t auv_population_member_floats_impl(const auv_policy_arch_t& a, int obs_dim);
+hipError_t auv_population_prepare(const auv_policy_arch_t& a, int obs_dim);
+void auv_launch_population_act(const auv_policy_arch_t& a, const auv_population_io_t& io, hipStream_t st);
 // k12_policy_stacked.hip
 size_t auv_policy_stacked_lds_bytes(int h1, int h2, int h3, int width);
 hipError_t auv_policy_stacked_prepare(int h1, int h2, int h3, int width);
@@ -88,10 +89,10 @@ void auv_launch_policy_stacked(int h1, int h2, int h3, const auv_policy_stack_t&
                                long long gstep_host = -1);
 void auv_launch_stack_frames(const float* obs, const uint8_t* done, float* hist, int32_t* stk, float* out, long long ldx, int e0, int ne,
                              int obs_dim, int frames, int advance, hipStream_t st);
-void auv_launch_population_perturb(const float* theta, float* members, long long stride, int P, int obs_dim, float sigma, unsigned long long seed,
-                                   unsigned long long generation, hipStream_t st);
-void auv_launch_population_update(float* theta, const float* w, float* grad, int P, int obs_dim, float sigma, float lr, unsigned long long seed,
-                                  unsigned long long generation, hipStream_t st);
+void auv_launch_population_perturb(const auv_policy_arch_t& a, const float* theta, float* members, long long stride, int P, int obs_dim,
+                                   float sigma, unsigned long long seed, unsigned long long generation, hipStream_t st);
+void auv_launch_population_update(const auv_policy_arch_t& a, float* theta, const float* w, float* grad, int P, int obs_dim, float sigma,
+                                  float lr, unsigned long long seed, unsigned long long generation, hipStream_t st);
 
 static thread_local char g_err[512] = "";
 
@@ -2469,26 +2470,34 @@ int auv_stack_frames(int32_t device, const float* obs, const uint8_t* done, floa
   return AUV_OK;
 }
 
-// ---- a population of policies (include/auv_hip.h, auv_population_*; kernels: k11_population.hip) ----
-size_t auv_population_member_floats(int32_t obs_dim) { return obs_dim > 0 ? auv_population_member_floats_impl(obs_dim) : 0; }
+// ---- a population of policies (include/auv_hip.h, auv_population_*; kernels: k11_population.hip, k14_population_arch.hip) ----
+// The entries without _arch evaluate the reference's net: they are the _arch ones with POLICY_ARCH_REF, under their own names in the
+// error strings.  `a` is checked first (check_policy_arch); every check behind it is the plain entries', with the member size and the
+// LDS tile of the triple.
+size_t auv_population_member_floats(int32_t obs_dim) { return auv_population_member_floats_arch(obs_dim, &POLICY_ARCH_REF); }
 
-static int check_population_obs_dim(int32_t obs_dim, const char* who) {
+size_t auv_population_member_floats_arch(int32_t obs_dim, const auv_policy_arch_t* arch) {
+  if (obs_dim <= 0 || !arch) return 0;
+  return auv_population_member_floats_impl(*arch, obs_dim);          // (0 for an unlisted triple)
+}
+
+static int check_population_obs_dim(const auv_policy_arch_t& a, int32_t obs_dim, const char* who) {
   if (obs_dim < 1) return fail(AUV_EINVAL, "%s: obs_dim %d < 1", who, obs_dim);
-  if (obs_dim > 16384 || auv_policy_lds_bytes(POL_H1, POL_H2, POL_H3, obs_dim) > 160 * 1024)
+  if (obs_dim > 16384 || auv_policy_lds_bytes(a.h1, a.h2, a.h3, obs_dim) > 160 * 1024)
     return fail(AUV_EINVAL, "%s: obs_dim %d is too wide for the policy kernel's LDS tile", who, obs_dim);
   return AUV_OK;
 }
 
 // what every population launch needs of `io`, whatever its rows are
-static int check_population_io(const auv_population_io_t* io, const char* who) {
+static int check_population_io(const auv_policy_arch_t& a, const auv_population_io_t* io, const char* who) {
   if (!io) return fail(AUV_EINVAL, "%s: null io", who);
-  int rc = check_population_obs_dim(io->obs_dim, who);
+  int rc = check_population_obs_dim(a, io->obs_dim, who);
   if (rc) return rc;
   if (io->G < 16 || io->G % 16) return fail(AUV_EINVAL, "%s: G = %d rows per member must be a positive multiple of 16", who, io->G);
   if (!io->members || ((uintptr_t)io->members & 15)) return fail(AUV_EINVAL, "%s: members must be a 16-byte aligned device pointer", who);
-  if (io->stride < (int64_t)auv_population_member_floats_impl(io->obs_dim) || (io->stride & 3))
+  if (io->stride < (int64_t)auv_population_member_floats_impl(a, io->obs_dim) || (io->stride & 3))
     return fail(AUV_EINVAL, "%s: stride %lld must be a multiple of 4 and >= auv_population_member_floats(%d) = %zu", who, (long long)io->stride,
-                io->obs_dim, auv_population_member_floats_impl(io->obs_dim));
+                io->obs_dim, auv_population_member_floats_impl(a, io->obs_dim));
   if (io->M < 0) return fail(AUV_EINVAL, "%s: M = %d < 0", who, io->M);
   if (io->action && io->action_ld < 2) return fail(AUV_EINVAL, "%s: action_ld %d < 2", who, io->action_ld);
   if (((uintptr_t)io->mu & 3) || ((uintptr_t)io->action & 3) || ((uintptr_t)io->fit & 3) || ((uintptr_t)io->ends & 3))
@@ -2496,48 +2505,61 @@ static int check_population_io(const auv_population_io_t* io, const char* who) {
   return AUV_OK;
 }
 
-int auv_population_act(int32_t device, const auv_population_io_t* io, void* stream) {
-  if (device < 0) return fail(AUV_EINVAL, "auv_population_act: device %d", device);
-  int rc = check_population_io(io, "auv_population_act");
+static int population_act_impl(int32_t device, const auv_population_io_t* io, const auv_policy_arch_t* arch, void* stream, const char* who) {
+  if (device < 0) return fail(AUV_EINVAL, "%s: device %d", who, device);
+  int rc = check_policy_arch(arch, nullptr, who);
+  if (rc) return rc;
+  const auv_policy_arch_t a = *arch;
+  rc = check_population_io(a, io, who);
   if (rc) return rc;
   if (io->accumulate && (!io->reward_in || !io->done_in || !io->fit || !io->ends))
-    return fail(AUV_EINVAL, "auv_population_act: accumulate needs reward_in, done_in, fit and ends");
-  if (io->accumulate && ((uintptr_t)io->reward_in & 3)) return fail(AUV_EINVAL, "auv_population_act: reward_in must be 4-byte aligned");
+    return fail(AUV_EINVAL, "%s: accumulate needs reward_in, done_in, fit and ends", who);
+  if (io->accumulate && ((uintptr_t)io->reward_in & 3)) return fail(AUV_EINVAL, "%s: reward_in must be 4-byte aligned", who);
   if (io->act) {
-    if (!io->mu && !io->action && !io->accumulate) return fail(AUV_EINVAL, "auv_population_act: no output asked for (mu and action are NULL) and no accumulation");
-    if (!io->X || ((uintptr_t)io->X & 3)) return fail(AUV_EINVAL, "auv_population_act: X must be a 4-byte aligned device pointer");
-    if (io->ldx < io->obs_dim) return fail(AUV_EINVAL, "auv_population_act: ldx %lld < obs_dim %d", (long long)io->ldx, io->obs_dim);
+    if (!io->mu && !io->action && !io->accumulate) return fail(AUV_EINVAL, "%s: no output asked for (mu and action are NULL) and no accumulation", who);
+    if (!io->X || ((uintptr_t)io->X & 3)) return fail(AUV_EINVAL, "%s: X must be a 4-byte aligned device pointer", who);
+    if (io->ldx < io->obs_dim) return fail(AUV_EINVAL, "%s: ldx %lld < obs_dim %d", who, (long long)io->ldx, io->obs_dim);
   } else if (!io->accumulate) {
-    return fail(AUV_EINVAL, "auv_population_act: neither act nor accumulate");
+    return fail(AUV_EINVAL, "%s: neither act nor accumulate", who);
   }
   if (io->M == 0) return AUV_OK;
   HIP_TRY(hipSetDevice(device));
-  HIP_TRY(auv_population_prepare(io->obs_dim));
-  auv_launch_population_act(*io, (hipStream_t)stream);
+  HIP_TRY(auv_population_prepare(a, io->obs_dim));
+  auv_launch_population_act(a, *io, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }
+int auv_population_act(int32_t device, const auv_population_io_t* io, void* stream) {
+  return population_act_impl(device, io, &POLICY_ARCH_REF, stream, "auv_population_act");
+}
+int auv_population_act_arch(int32_t device, const auv_population_io_t* io, const auv_policy_arch_t* arch, void* stream) {
+  return population_act_impl(device, io, arch, stream, "auv_population_act_arch");
+}
 
-int auv_population_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_population_io_t* ios,
-                           float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush) {
+static int population_rollout_impl(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_population_io_t* ios,
+                                   const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps,
+                                   int32_t flush, const char* who) {
   REQUIRE_READY(h);
-  int rc = check_slices(h, n_slices, bounds, streams, "auv_population_rollout");
+  int rc = check_policy_arch(arch, nullptr, who);
   if (rc) return rc;
-  if (!ios || n_steps < 0 || !obs_dev || !reward_dev || !done_dev) return fail(AUV_EINVAL, "auv_population_rollout: bad arguments");
+  const auv_policy_arch_t a = *arch;
+  rc = check_slices(h, n_slices, bounds, streams, who);
+  if (rc) return rc;
+  if (!ios || n_steps < 0 || !obs_dev || !reward_dev || !done_dev) return fail(AUV_EINVAL, "%s: bad arguments", who);
   const int D = auv_obs_cols(h->d.cfg, h->d.pool_ns);
   auv_population_io_t io[AUV_MAX_CHAINS];                // the slices' own rows of ios[i]
   for (int i = 0; i < n_slices; i++) {
-    rc = check_population_io(ios + i, "auv_population_rollout");
+    rc = check_population_io(a, ios + i, who);
     if (rc) return rc;
     const auv_population_io_t& s = ios[i];
-    if (s.obs_dim != D) return fail(AUV_EINVAL, "auv_population_rollout: obs_dim %d, the handle's observation has %d columns", s.obs_dim, D);
-    if (s.M != h->d.n) return fail(AUV_EINVAL, "auv_population_rollout: ios[%d].M = %d, the handle has %d environments (whole-batch rows)", i, s.M, h->d.n);
+    if (s.obs_dim != D) return fail(AUV_EINVAL, "%s: obs_dim %d, the handle's observation has %d columns", who, s.obs_dim, D);
+    if (s.M != h->d.n) return fail(AUV_EINVAL, "%s: ios[%d].M = %d, the handle has %d environments (whole-batch rows)", who, i, s.M, h->d.n);
     if (bounds[i] % s.G || (bounds[i + 1] % s.G && bounds[i + 1] != h->d.n))
-      return fail(AUV_EINVAL, "auv_population_rollout: slice [%d, %d) does not start and end on a multiple of G = %d", bounds[i], bounds[i + 1], s.G);
-    if (!s.fit || !s.ends) return fail(AUV_EINVAL, "auv_population_rollout: null fit or ends");
-    rc = check_actions(s.action, AUV_F32, "auv_population_rollout");
+      return fail(AUV_EINVAL, "%s: slice [%d, %d) does not start and end on a multiple of G = %d", who, bounds[i], bounds[i + 1], s.G);
+    if (!s.fit || !s.ends) return fail(AUV_EINVAL, "%s: null fit or ends", who);
+    rc = check_actions(s.action, AUV_F32, who);
     if (rc) return rc;
-    if (s.action_ld != 2) return fail(AUV_EINVAL, "auv_population_rollout: action_ld %d (the environment reads an [N][2] buffer)", s.action_ld);
+    if (s.action_ld != 2) return fail(AUV_EINVAL, "%s: action_ld %d (the environment reads an [N][2] buffer)", who, s.action_ld);
     const size_t lo = (size_t)bounds[i];
     io[i] = s;
     io[i].members = s.members + (lo / (size_t)s.G) * (size_t)s.stride;
@@ -2549,55 +2571,91 @@ int auv_population_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bou
     io[i].M = bounds[i + 1] - bounds[i];
   }
   PAIR_CHECK(h, obs_dev);
-  HIP_TRY(auv_population_prepare(D));
+  HIP_TRY(auv_population_prepare(a, D));
   return rollout_loop(
       h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].action; },
       [&](int i, int32_t k, bool flushing) {
         // (the first launch of a call has no completed step of this window behind it; the flush launch only books the last one)
         io[i].accumulate = flushing || k > 0, io[i].act = !flushing;
-        auv_launch_population_act(io[i], (hipStream_t)streams[i]);
+        auv_launch_population_act(a, io[i], (hipStream_t)streams[i]);
       });
 }
+int auv_population_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_population_io_t* ios,
+                           float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush) {
+  return population_rollout_impl(h, n_slices, bounds, streams, ios, &POLICY_ARCH_REF, obs_dev, reward_dev, done_dev, n_steps, flush,
+                                 "auv_population_rollout");
+}
+int auv_population_rollout_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_population_io_t* ios,
+                                const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps,
+                                int32_t flush) {
+  return population_rollout_impl(h, n_slices, bounds, streams, ios, arch, obs_dev, reward_dev, done_dev, n_steps, flush,
+                                 "auv_population_rollout_arch");
+}
 
-static int check_population_block(int32_t obs_dim, int32_t P, float sigma, const char* who) {
-  int rc = check_population_obs_dim(obs_dim, who);
+static int check_population_block(const auv_policy_arch_t& a, int32_t obs_dim, int32_t P, float sigma, const char* who) {
+  int rc = check_population_obs_dim(a, obs_dim, who);
   if (rc) return rc;
   if (P < 1 || P > 65535) return fail(AUV_EINVAL, "%s: P = %d members outside [1, 65535]", who, P);
   if (!(sigma == sigma) || sigma - sigma != 0.0f) return fail(AUV_EINVAL, "%s: sigma must be finite", who);
   return AUV_OK;
 }
 
-int auv_population_perturb(int32_t device, const float* theta, float* members, int64_t stride, int32_t P, int32_t obs_dim, float sigma,
-                           uint64_t seed, int64_t generation, void* stream) {
-  if (device < 0) return fail(AUV_EINVAL, "auv_population_perturb: device %d", device);
-  int rc = check_population_block(obs_dim, P, sigma, "auv_population_perturb");
+static int population_perturb_impl(int32_t device, const float* theta, float* members, int64_t stride, int32_t P, int32_t obs_dim, float sigma,
+                                   uint64_t seed, int64_t generation, const auv_policy_arch_t* arch, void* stream, const char* who) {
+  if (device < 0) return fail(AUV_EINVAL, "%s: device %d", who, device);
+  int rc = check_policy_arch(arch, nullptr, who);
+  if (rc) return rc;
+  const auv_policy_arch_t a = *arch;
+  rc = check_population_block(a, obs_dim, P, sigma, who);
   if (rc) return rc;
   if (!theta || !members || ((uintptr_t)theta & 15) || ((uintptr_t)members & 15))
-    return fail(AUV_EINVAL, "auv_population_perturb: theta and members must be 16-byte aligned device pointers");
-  if (stride < (int64_t)auv_population_member_floats_impl(obs_dim) || (stride & 3) || stride > 0x7fffffff)
-    return fail(AUV_EINVAL, "auv_population_perturb: stride %lld must be a multiple of 4, >= auv_population_member_floats(%d) = %zu and < 2^31",
-                (long long)stride, obs_dim, auv_population_member_floats_impl(obs_dim));
+    return fail(AUV_EINVAL, "%s: theta and members must be 16-byte aligned device pointers", who);
+  if (stride < (int64_t)auv_population_member_floats_impl(a, obs_dim) || (stride & 3) || stride > 0x7fffffff)
+    return fail(AUV_EINVAL, "%s: stride %lld must be a multiple of 4, >= auv_population_member_floats(%d) = %zu and < 2^31", who,
+                (long long)stride, obs_dim, auv_population_member_floats_impl(a, obs_dim));
   HIP_TRY(hipSetDevice(device));
-  auv_launch_population_perturb(theta, members, (long long)stride, P, obs_dim, sigma, seed, (unsigned long long)generation, (hipStream_t)stream);
+  auv_launch_population_perturb(a, theta, members, (long long)stride, P, obs_dim, sigma, seed, (unsigned long long)generation, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }
+int auv_population_perturb(int32_t device, const float* theta, float* members, int64_t stride, int32_t P, int32_t obs_dim, float sigma,
+                           uint64_t seed, int64_t generation, void* stream) {
+  return population_perturb_impl(device, theta, members, stride, P, obs_dim, sigma, seed, generation, &POLICY_ARCH_REF, stream,
+                                 "auv_population_perturb");
+}
+int auv_population_perturb_arch(int32_t device, const float* theta, float* members, int64_t stride, int32_t P, int32_t obs_dim, float sigma,
+                                uint64_t seed, int64_t generation, const auv_policy_arch_t* arch, void* stream) {
+  return population_perturb_impl(device, theta, members, stride, P, obs_dim, sigma, seed, generation, arch, stream,
+                                 "auv_population_perturb_arch");
+}
 
-int auv_population_update(int32_t device, float* theta, const float* w, float* grad, int32_t P, int32_t obs_dim, float sigma, float lr,
-                          uint64_t seed, int64_t generation, void* stream) {
-  if (device < 0) return fail(AUV_EINVAL, "auv_population_update: device %d", device);
-  int rc = check_population_block(obs_dim, P, sigma, "auv_population_update");
+static int population_update_impl(int32_t device, float* theta, const float* w, float* grad, int32_t P, int32_t obs_dim, float sigma, float lr,
+                                  uint64_t seed, int64_t generation, const auv_policy_arch_t* arch, void* stream, const char* who) {
+  if (device < 0) return fail(AUV_EINVAL, "%s: device %d", who, device);
+  int rc = check_policy_arch(arch, nullptr, who);
   if (rc) return rc;
-  if (P < 2 || (P & 1)) return fail(AUV_EINVAL, "auv_population_update: P = %d must be even (mirrored pairs)", P);
-  if (!(sigma > 0.0f)) return fail(AUV_EINVAL, "auv_population_update: sigma must be > 0");
-  if (!(lr == lr) || lr - lr != 0.0f) return fail(AUV_EINVAL, "auv_population_update: lr must be finite");
+  const auv_policy_arch_t a = *arch;
+  rc = check_population_block(a, obs_dim, P, sigma, who);
+  if (rc) return rc;
+  if (P < 2 || (P & 1)) return fail(AUV_EINVAL, "%s: P = %d must be even (mirrored pairs)", who, P);
+  if (!(sigma > 0.0f)) return fail(AUV_EINVAL, "%s: sigma must be > 0", who);
+  if (!(lr == lr) || lr - lr != 0.0f) return fail(AUV_EINVAL, "%s: lr must be finite", who);
   if (!w || !grad || ((uintptr_t)w & 3) || ((uintptr_t)grad & 15) || ((uintptr_t)theta & 15))
-    return fail(AUV_EINVAL, "auv_population_update: w must be 4-byte, grad and theta 16-byte aligned device pointers");
-  if (lr != 0.0f && !theta) return fail(AUV_EINVAL, "auv_population_update: lr != 0 needs theta");
+    return fail(AUV_EINVAL, "%s: w must be 4-byte, grad and theta 16-byte aligned device pointers", who);
+  if (lr != 0.0f && !theta) return fail(AUV_EINVAL, "%s: lr != 0 needs theta", who);
   HIP_TRY(hipSetDevice(device));
-  auv_launch_population_update(theta, w, grad, P, obs_dim, sigma, lr, seed, (unsigned long long)generation, (hipStream_t)stream);
+  auv_launch_population_update(a, theta, w, grad, P, obs_dim, sigma, lr, seed, (unsigned long long)generation, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
+}
+int auv_population_update(int32_t device, float* theta, const float* w, float* grad, int32_t P, int32_t obs_dim, float sigma, float lr,
+                          uint64_t seed, int64_t generation, void* stream) {
+  return population_update_impl(device, theta, w, grad, P, obs_dim, sigma, lr, seed, generation, &POLICY_ARCH_REF, stream,
+                                "auv_population_update");
+}
+int auv_population_update_arch(int32_t device, float* theta, const float* w, float* grad, int32_t P, int32_t obs_dim, float sigma, float lr,
+                               uint64_t seed, int64_t generation, const auv_policy_arch_t* arch, void* stream) {
+  return population_update_impl(device, theta, w, grad, P, obs_dim, sigma, lr, seed, generation, arch, stream, "auv_population_update_arch");
 }
 
 int auv_graph_capture(auv_handle_t* h, const void* actions_dev, int32_t action_dtype, float* obs_dev,

@@ -34,7 +34,7 @@ struct PolArch {
   static_assert(H1_ > 0 && H2_ > 0 && H3_ > 0 && H1_ % 64 == 0 && H2_ % 64 == 0 && H3_ % 64 == 0, "hidden widths: multiples of 64");
   static_assert(H1_ >= H3_, "Y3 re-uses Y1's LDS");
 };
-typedef PolArch<POL_H1, POL_H2, POL_H3> PolArchRef;   // the reference's net: the default, and the only one k11 evaluates
+typedef PolArch<POL_H1, POL_H2, POL_H3> PolArchRef;   // the reference's net: the default (k8's and k11's own kernels; k13 / k14 hold the other triples')
 // THE LIST of the triples the forward launches and the fused update (k8, k13) are instantiated for, the default first: a triple more is one line here.  It is expanded
 // once, in pol_arch_any; every host-side dispatch finds its kernel through pol_arch_visit, which also instantiates it.
 #define POL_ARCH_LIST(X) \

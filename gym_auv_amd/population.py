@@ -14,6 +14,10 @@ strategies, ARS on that actor or "evaluate these checkpoints side by side" need:
 
 The NumPy functions below -- es_noise, padding_mask, perturb_reference, es_update_reference -- are the CONTRACT of the two kernels that
 make and fold a population: the kernels are held to them bit for bit (tests/test_gpu_population.py).  They need no device.
+
+Hidden widths: the reference's [256, 128, 64] unless named -- `hidden=` on the functions, read off the net by PolicyPopulation -- and
+then one of the triples the fused policy launches are compiled for (_capi.POLICY_ARCHS; the auv_population_*_arch entries,
+csrc/k14_population_arch.hip; tests/test_gpu_population_arch.py).
 """
 import ctypes as C
 from typing import Dict, Optional, Sequence
@@ -27,10 +31,25 @@ _U64 = 0xFFFFFFFFFFFFFFFF
 EPS_SCALE = np.float32(1.0 / np.sqrt(4.0 * (65536.0 * 65536.0 - 1.0) / 12.0))
 
 
-def member_floats(obs_dim: int) -> int:
-    """Floats of one member: the packed policy net of auv_policy_io::params (auv_population_member_floats)."""
+def _hidden(hidden, who: str) -> tuple:
+    """`hidden` as a tuple of three ints, one of the triples the population kernels are compiled for (_capi.POLICY_ARCHS; the list of
+    the fused policy launches); ValueError otherwise.  Needs no device and no library."""
+    from ._capi import POLICY_ARCHS
+    try:
+        h = tuple(int(x) for x in hidden)
+    except (TypeError, ValueError):
+        h = None
+    if h is None or h not in POLICY_ARCHS:
+        raise ValueError("%s: hidden widths %r are not compiled in: the population kernels evaluate one of %s" % (who, hidden, list(POLICY_ARCHS)))
+    return h
+
+
+def member_floats(obs_dim: int, hidden=HIDDEN) -> int:
+    """Floats of one member: the packed policy net of auv_policy_io::params (auv_population_member_floats, _arch for other `hidden`
+    widths than the reference's)."""
+    h1, h2, h3 = _hidden(hidden, "member_floats")
     k0p = (int(obs_dim) + 31) & ~31
-    n = 256 * k0p + 256 + 128 * 256 + 128 + 64 * 128 + 64 + 16 * 64 + 16
+    n = h1 * k0p + h1 + h2 * h1 + h2 + h3 * h2 + h3 + 16 * h3 + 16
     return (n + 3) & ~3
 
 
@@ -56,36 +75,39 @@ def es_noise(seed: int, generation: int, pair, idx) -> np.ndarray:
     return (S.astype(np.int64) - 131070).astype(np.float32) * EPS_SCALE
 
 
-def padding_mask(obs_dim: int) -> np.ndarray:
-    """[member_floats(obs_dim)] bool: True where an element of the packed block is PADDING -- a column of W1 beyond obs_dim, a row
-    2..15 of W4, an entry 2..15 of b4, the tail -- and so carries no noise and no gradient.  Found by packing all-ones weights with
+def padding_mask(obs_dim: int, hidden=HIDDEN) -> np.ndarray:
+    """[member_floats(obs_dim, hidden)] bool: True where an element of the packed block is PADDING -- a column of W1 beyond obs_dim, a
+    row 2..15 of W4, an entry 2..15 of b4, the tail -- and so carries no noise and no gradient.  Found by packing all-ones weights with
     the packing routine itself (policy.pack_linear), not from a second copy of the index formula."""
     import torch
     from .policy import pack_linear
+    h1, h2, h3 = _hidden(hidden, "padding_mask")
     obs_dim = int(obs_dim)
     if obs_dim < 1:
         raise ValueError("padding_mask: obs_dim must be >= 1")
     k0p = (obs_dim + 31) & ~31
     parts = []
-    for n_in, n_out, in_p, out_p in ((obs_dim, 256, k0p, 256), (256, 128, 256, 128), (128, 64, 128, 64), (64, 2, 64, 16)):
+    for n_in, n_out, in_p, out_p in ((obs_dim, h1, k0p, h1), (h1, h2, h1, h2), (h2, h3, h2, h3), (h3, 2, h3, 16)):
         parts.append(pack_linear(torch.ones((n_out, n_in)), out_p, in_p).numpy())
         b = np.zeros(out_p, dtype=np.float32)
         b[:n_out] = 1.0
         parts.append(b)
     live = np.concatenate(parts)
-    mask = np.ones(member_floats(obs_dim), dtype=bool)
+    mask = np.ones(member_floats(obs_dim, hidden), dtype=bool)
     mask[:live.size] = live == 0.0
     return mask
 
 
-def perturb_reference(theta: np.ndarray, P: int, obs_dim: int, sigma: float, seed: int, generation: int, stride: Optional[int] = None) -> np.ndarray:
+def perturb_reference(theta: np.ndarray, P: int, obs_dim: int, sigma: float, seed: int, generation: int, stride: Optional[int] = None,
+                      hidden=HIDDEN) -> np.ndarray:
     """What auv_population_perturb writes, [P, stride] float32: member p = theta + s_p * (sigma * eps(seed, generation, p // 2, i)),
-    s_p = +1 for even p and -1 for odd p, two rounded float32 operations; padding keeps theta's value, the tail behind the block is 0."""
-    nf = member_floats(obs_dim)
+    s_p = +1 for even p and -1 for odd p, two rounded float32 operations; padding keeps theta's value, the tail behind the block is 0.
+    `hidden`: the widths of the packed net (they decide what is padding; the noise does not depend on them)."""
+    nf = member_floats(obs_dim, hidden)
     stride = nf if stride is None else int(stride)
     theta = np.asarray(theta, dtype=np.float32)
     assert theta.shape == (nf,) and stride >= nf
-    live = ~padding_mask(obs_dim)
+    live = ~padding_mask(obs_dim, hidden)
     idx = np.arange(nf, dtype=np.uint64)
     out = np.zeros((int(P), stride), dtype=np.float32)
     for p in range(int(P)):
@@ -95,16 +117,17 @@ def perturb_reference(theta: np.ndarray, P: int, obs_dim: int, sigma: float, see
     return out
 
 
-def es_update_reference(theta: np.ndarray, w: np.ndarray, obs_dim: int, sigma: float, lr: float, seed: int, generation: int):
+def es_update_reference(theta: np.ndarray, w: np.ndarray, obs_dim: int, sigma: float, lr: float, seed: int, generation: int, hidden=HIDDEN):
     """What auv_population_update writes, (grad, theta_new): grad[i] = acc_i * float32(1 / (P sigma)), acc_i the float32 sum over pairs
     in increasing order of (w[2 pair] - w[2 pair + 1]) * eps(seed, generation, pair, i) -- a rounded difference, a rounded product and
-    a rounded add per pair; padding gets exactly 0.  theta_new = theta + lr * grad (two rounded operations) where lr != 0."""
-    nf = member_floats(obs_dim)
+    a rounded add per pair; padding gets exactly 0.  theta_new = theta + lr * grad (two rounded operations) where lr != 0.
+    `hidden`: the widths of the packed net, as in perturb_reference."""
+    nf = member_floats(obs_dim, hidden)
     theta = np.asarray(theta, dtype=np.float32)
     w = np.asarray(w, dtype=np.float32)
     P = int(w.size)
     assert theta.shape == (nf,) and P >= 2 and P % 2 == 0
-    live = ~padding_mask(obs_dim)
+    live = ~padding_mask(obs_dim, hidden)
     idx = np.arange(nf, dtype=np.uint64)
     acc = np.zeros(nf, dtype=np.float32)
     for pair in range(P // 2):
@@ -138,18 +161,32 @@ def _lib():
     return _LIB, _check
 
 
-def pack_member(pi, obs_dim: int, out=None):
-    """One member block from a policy net `pi` (Linear-Tanh x 3 + Linear: obs -> [256, 128, 64] -> 2): what pack_policy_params writes
-    for the first net.  Device-side copies on the current stream."""
+def _arch_arg(hidden):
+    from . import _capi
+    return _capi.AuvPolicyArch(int(hidden[0]), int(hidden[1]), int(hidden[2]))
+
+
+def net_hidden(pi) -> tuple:
+    """The hidden widths of a policy net `pi` (a Sequential of Linear and activation modules): the out_features of every Linear but
+    the last, as FusedActorCritic reads them."""
+    import torch.nn as nn
+    lin = [m for m in pi if isinstance(m, nn.Linear)]
+    return tuple(int(l.out_features) for l in lin[:-1])
+
+
+def pack_member(pi, obs_dim: int, out=None, hidden=HIDDEN):
+    """One member block from a policy net `pi` (Linear-Tanh x 3 + Linear: obs -> `hidden` -> 2; the reference's [256, 128, 64] unless
+    named): what pack_policy_params writes for the first net.  Device-side copies on the current stream."""
     import torch
     import torch.nn as nn
     from .policy import pack_linear
+    hidden = _hidden(hidden, "pack_member")
     lin = [m for m in pi if isinstance(m, nn.Linear)]
     act = [m for m in pi if not isinstance(m, nn.Linear)]
-    if tuple(l.out_features for l in lin[:-1]) != HIDDEN or lin[-1].out_features != 2 or lin[0].in_features != int(obs_dim) \
+    if tuple(l.out_features for l in lin[:-1]) != hidden or lin[-1].out_features != 2 or lin[0].in_features != int(obs_dim) \
             or not all(isinstance(a, nn.Tanh) for a in act):
-        raise ValueError("pack_member: the population kernel evaluates obs[%d] -> %s tanh -> 2" % (int(obs_dim), list(HIDDEN)))
-    nf = member_floats(obs_dim)
+        raise ValueError("pack_member: the population kernel evaluates obs[%d] -> %s tanh -> 2" % (int(obs_dim), list(hidden)))
+    nf = member_floats(obs_dim, hidden)
     with torch.no_grad():
         p = torch.zeros(nf, dtype=torch.float32, device=lin[0].weight.device) if out is None else out
         off = 0
@@ -168,11 +205,15 @@ def pack_member(pi, obs_dim: int, out=None):
 _ACT_OUTPUTS = ("mu", "action")
 
 
-def population_act(members, obs_dim: int, G: int, X, want: Sequence[str] = ("mu",), action_map=None, out: Optional[Dict] = None):
+def population_act(members, obs_dim: int, G: int, X, want: Sequence[str] = ("mu",), action_map=None, out: Optional[Dict] = None,
+                   hidden=HIDDEN, arch_entry: Optional[bool] = None):
     """auv_population_act on the caller's current stream: row j of X through the policy net of member j // G, ONE launch.
 
-    members     [P, stride] float32 device tensor, rows contiguous and 16-byte aligned, stride >= member_floats(obs_dim) and a
+    members     [P, stride] float32 device tensor, rows contiguous and 16-byte aligned, stride >= member_floats(obs_dim, hidden) and a
                 multiple of 4; P * G >= the number of rows
+    hidden      the hidden widths the members were packed for, one of _capi.POLICY_ARCHS
+    arch_entry  None: the default widths go through auv_population_act, any other through auv_population_act_arch; True: the _arch
+                entry also for the default widths (it runs the same kernel)
     X           [M, obs_dim] float32; rows may be strided, columns may not
     want        any of "mu" [M, 2], "action" [M, 2]
     action_map  (act_mid, act_half, clip_lo, clip_hi), each two floats; None: the identity map without clipping
@@ -183,13 +224,14 @@ def population_act(members, obs_dim: int, G: int, X, want: Sequence[str] = ("mu"
     LIB, check = _lib()
     want, out = tuple(want), dict(out or {})
     obs_dim, G = int(obs_dim), int(G)
+    hidden = _hidden(hidden, "population_act")
     if not want or any(w not in _ACT_OUTPUTS for w in want) or any(w not in want for w in out):
         raise ValueError("population_act: want must name some of %s, and out only what is wanted" % (_ACT_OUTPUTS,))
     if G < 16 or G % 16:
         raise ValueError("population_act: G = %d must be a positive multiple of 16" % G)
     if obs_dim < 1:
         raise ValueError("population_act: obs_dim must be >= 1")
-    nf = member_floats(obs_dim)
+    nf = member_floats(obs_dim, hidden)
     if not isinstance(members, torch.Tensor) or members.dtype != torch.float32 or not members.is_cuda or members.dim() != 2 \
             or members.stride(1) != 1 or members.shape[1] < nf or members.data_ptr() % 16:
         raise ValueError("population_act: members must be a 16-byte aligned [P, >= %d] float32 device tensor with contiguous rows" % nf)
@@ -231,8 +273,11 @@ def population_act(members, obs_dim: int, G: int, X, want: Sequence[str] = ("mu"
         io.accumulate, io.act = 0, 1
         _set_action_map(io, action_map)
         st = torch.cuda.current_stream(dev)
-        check(LIB.auv_population_act(dev.index if dev.index is not None else torch.cuda.current_device(), C.byref(io), C.c_void_p(st.cuda_stream)),
-              "auv_population_act")
+        dev_i = dev.index if dev.index is not None else torch.cuda.current_device()
+        if hidden != HIDDEN or arch_entry:
+            check(LIB.auv_population_act_arch(dev_i, C.byref(io), C.byref(_arch_arg(hidden)), C.c_void_p(st.cuda_stream)), "auv_population_act_arch")
+        else:
+            check(LIB.auv_population_act(dev_i, C.byref(io), C.c_void_p(st.cuda_stream)), "auv_population_act")
     return res
 
 
@@ -249,6 +294,8 @@ class PolicyPopulation:
     members           P; perturb / update use mirrored pairs (2 j, 2 j + 1) and want it even
     rows_per_member   G, a multiple of 16; default env.n_envs // members
     net               a module with a policy net `net.pi` (or the Sequential itself) to take the base block from; None: zeros
+    hidden            the hidden widths, one of _capi.POLICY_ARCHS: read off `net` where there is one, else this, else [256, 128, 64];
+                      ValueError for any other triple (csrc/k14_population_arch.hip holds the kernels of the non-default ones)
     action map        as FusedActorCritic: action = act_mid + act_half * clip(mu, clip_lo, clip_hi); default: raw units clipped to the
                       action space
     seed              keys the noise of perturb / update together with their `generation`
@@ -256,16 +303,31 @@ class PolicyPopulation:
     Owns `theta` [member_floats] (the base block), `members` [P, stride], `grad` [member_floats], `fit` [N] float32 (sum of rewards of
     the last rollout window), `ends` [N] int32 (episodes ended in it) and `actions` [N, 2].  No method synchronises with the host."""
 
+    @staticmethod
+    def resolve_hidden(net=None, hidden=None) -> tuple:
+        """The hidden widths of a population: read off `net.pi` (or `net`, a Sequential) as FusedActorCritic reads them off its
+        modules, else `hidden`, else the reference's.  ValueError for a triple that is not compiled in, or a `hidden` that
+        contradicts `net`.  Touches no device."""
+        if net is None:
+            return _hidden(HIDDEN if hidden is None else hidden, "PolicyPopulation")
+        h = _hidden(net_hidden(getattr(net, "pi", net)), "PolicyPopulation")
+        if hidden is not None and tuple(int(x) for x in hidden) != h:
+            raise ValueError("PolicyPopulation: hidden = %s, the net has the hidden widths %s" % (list(hidden), list(h)))
+        return h
+
     def __init__(self, env, members: int, rows_per_member: Optional[int] = None, net=None, act_mid=None, act_half=None, clip_lo=None,
-                 clip_hi=None, seed: int = 0):
+                 clip_hi=None, seed: int = 0, hidden=None):
         self.P, self.G = population_geometry(env.n_envs, members, rows_per_member)
+        self.hidden = self.resolve_hidden(net, hidden)
         import torch
         from . import _capi
         self.env, self.device, self.obs_dim = env, env.device, int(env.obs_dim)
         self.seed = int(seed) & _U64
         LIB, _ = _lib()
-        self.nf = int(LIB.auv_population_member_floats(self.obs_dim))
-        assert self.nf == member_floats(self.obs_dim)
+        # the default widths go through the entries without _arch (FusedActorCritic's rule)
+        self._arch = _arch_arg(self.hidden) if self.hidden != HIDDEN else None
+        self.nf = int(LIB.auv_population_member_floats_arch(self.obs_dim, C.byref(_arch_arg(self.hidden))))
+        assert self.nf == member_floats(self.obs_dim, self.hidden)
         self.stride = self.nf
         N = env.n_envs
         with torch.cuda.device(self.device):
@@ -296,7 +358,7 @@ class PolicyPopulation:
     # ------------------------------------------------------------------------------ weights
     def load(self, net):
         """The base block from `net.pi` (or from `net` itself, a Sequential), and every member a copy of it."""
-        pack_member(getattr(net, "pi", net), self.obs_dim, out=self.theta)
+        pack_member(getattr(net, "pi", net), self.obs_dim, out=self.theta, hidden=self.hidden)
         self.members.copy_(self.theta.unsqueeze(0).expand(self.P, self.stride))
 
     def base_state_into(self, fused):
@@ -304,14 +366,21 @@ class PolicyPopulation:
         fused.predict() / examples/evaluate.py.  The torch modules of `fused` are not touched: do not refresh() afterwards."""
         if int(fused.env.obs_dim) != self.obs_dim:
             raise ValueError("base_state_into: obs_dim %d, the population has %d" % (int(fused.env.obs_dim), self.obs_dim))
+        if tuple(getattr(fused, "hidden", HIDDEN)) != self.hidden:
+            raise ValueError("base_state_into: the policy has the hidden widths %s, the population %s"
+                             % (list(getattr(fused, "hidden", HIDDEN)), list(self.hidden)))
         fused.params[:self.nf].copy_(self.theta)
 
     def perturb(self, sigma: float, generation: int):
         """members[p] = theta +- sigma eps(seed, generation, p // 2, .) for every member, one launch (auv_population_perturb)."""
         LIB, check = _lib()
-        check(LIB.auv_population_perturb(self._dev_index(), C.c_void_p(self.theta.data_ptr()), C.c_void_p(self.members.data_ptr()), self.stride, self.P,
-                                         self.obs_dim, float(sigma), self.seed, int(generation), C.c_void_p(self._stream().cuda_stream)),
-              "auv_population_perturb")
+        head = (self._dev_index(), C.c_void_p(self.theta.data_ptr()), C.c_void_p(self.members.data_ptr()), self.stride, self.P, self.obs_dim,
+                float(sigma), self.seed, int(generation))
+        st = C.c_void_p(self._stream().cuda_stream)
+        if self._arch is not None:
+            check(LIB.auv_population_perturb_arch(*head, C.byref(self._arch), st), "auv_population_perturb_arch")
+        else:
+            check(LIB.auv_population_perturb(*head, st), "auv_population_perturb")
 
     def update(self, weights, lr: float, sigma: float, generation: int):
         """The ES gradient estimate of generation `generation` from the shaped fitness `weights` [P] into `grad`, and theta += lr * grad
@@ -323,9 +392,13 @@ class PolicyPopulation:
                 or not weights.is_contiguous():
             raise ValueError("update: weights must be a contiguous [%d] float32 tensor on %s" % (self.P, self.device))
         LIB, check = _lib()
-        check(LIB.auv_population_update(self._dev_index(), C.c_void_p(self.theta.data_ptr()), C.c_void_p(weights.data_ptr()),
-                                        C.c_void_p(self.grad.data_ptr()), self.P, self.obs_dim, float(sigma), float(lr), self.seed, int(generation),
-                                        C.c_void_p(self._stream().cuda_stream)), "auv_population_update")
+        head = (self._dev_index(), C.c_void_p(self.theta.data_ptr()), C.c_void_p(weights.data_ptr()), C.c_void_p(self.grad.data_ptr()), self.P,
+                self.obs_dim, float(sigma), float(lr), self.seed, int(generation))
+        st = C.c_void_p(self._stream().cuda_stream)
+        if self._arch is not None:
+            check(LIB.auv_population_update_arch(*head, C.byref(self._arch), st), "auv_population_update_arch")
+        else:
+            check(LIB.auv_population_update(*head, st), "auv_population_update")
         return self.grad
 
     @staticmethod
@@ -343,7 +416,8 @@ class PolicyPopulation:
         into `out` (default `self.actions`, which env.step takes as is): one launch on the caller's current stream."""
         X = self.env.obs if obs is None else obs
         out = self.actions if out is None else out
-        return population_act(self.members, self.obs_dim, self.G, X, want=("action",), action_map=self.action_map, out={"action": out})["action"]
+        return population_act(self.members, self.obs_dim, self.G, X, want=("action",), action_map=self.action_map, out={"action": out},
+                              hidden=self.hidden)["action"]
 
     def _io(self):
         io = self._io_type()
@@ -384,8 +458,11 @@ class PolicyPopulation:
         for st in subs:
             st.wait_stream(cur)
         ios = (self._io_type * k)(*[self._io() for _ in range(k)])
-        check(LIB.auv_population_rollout(env._h, k, bounds, streams, ios, C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()),
-                                         C.c_void_p(env.done.data_ptr()), int(n_steps), 1), "auv_population_rollout")
+        tail = (C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()), int(n_steps), 1)
+        if self._arch is not None:
+            check(LIB.auv_population_rollout_arch(env._h, k, bounds, streams, ios, C.byref(self._arch), *tail), "auv_population_rollout_arch")
+        else:
+            check(LIB.auv_population_rollout(env._h, k, bounds, streams, ios, *tail), "auv_population_rollout")
         for st in subs:
             cur.wait_stream(st)
         return self.fit.view(self.P, self.G).mean(dim=1), self.ends.view(self.P, self.G).sum(dim=1)

@@ -767,7 +767,7 @@ int auv_policy_eval(int32_t device, const auv_policy_eval_t* ev, void* stream);
  * (256, 128, 64) through an _arch entry runs the very kernels of the entry without the suffix.  AUV_EINVAL, before anything is
  * enqueued, beside what the plain entries refuse: arch NULL; a triple outside the list (it is never rounded to a listed one;
  * auv_policy_param_floats_arch then returns 0); params_bf16 set with another triple than (256, 128, 64).  The population launches
- * (auv_population_*) evaluate (256, 128, 64) only; the fused update takes the same list (auv_ppo_create_arch below).              */
+ * (auv_population_*_arch) and the fused update (auv_ppo_create_arch) take the same list, both below.                             */
 typedef struct auv_policy_arch {
   int32_t h1, h2, h3;
 } auv_policy_arch_t;
@@ -848,6 +848,25 @@ int auv_population_perturb(int32_t device, const float* theta, float* members, i
  * fitness; P even and >= 2; sigma finite and > 0; theta (needed with lr != 0) and grad: one member block each, 16-byte aligned.     */
 int auv_population_update(int32_t device, float* theta, const float* w, float* grad, int32_t P, int32_t obs_dim, float sigma, float lr,
                           uint64_t seed, int64_t generation, void* stream);
+/* The population at the other hidden widths of the forward launches (auv_policy_arch_t above; kernels: csrc/k14_population_arch.hip,
+ * the same bodies as k11's, csrc/auv_population_pass.h).  A member is then the packed policy net obs -> h1 -> h2 -> h3 -> 2 of
+ * auv_policy_param_floats_arch's layout: auv_population_member_floats_arch(obs_dim, arch) floats,
+ *   h1 * K0p + h1 + h2 * h1 + h2 + h3 * h2 + h3 + 16 * h3 + 16 rounded up to a multiple of 4,   K0p = obs_dim rounded up to 32,
+ * and the padding elements that get no noise and no gradient are those of that layout.  Every word, every check in its order and
+ * every error of the entries above holds, with the member size and the LDS tile of the triple; for the same row and the same block the
+ * mean has the bits of auv_policy_eval_arch at that triple; the noise does not depend on the widths.  AUV_EINVAL before anything is
+ * enqueued: arch NULL, or a triple outside the list -- it is never rounded to a listed one, and auv_population_member_floats_arch
+ * then returns 0 (as it does for obs_dim <= 0).  (256, 128, 64) through an _arch entry runs the very kernels of the entry without
+ * the suffix.                                                                                                                    */
+size_t auv_population_member_floats_arch(int32_t obs_dim, const auv_policy_arch_t* arch);
+int auv_population_act_arch(int32_t device, const auv_population_io_t* io, const auv_policy_arch_t* arch, void* stream);
+int auv_population_rollout_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
+                                const auv_population_io_t* ios, const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev,
+                                uint8_t* done_dev, int32_t n_steps, int32_t flush);
+int auv_population_perturb_arch(int32_t device, const float* theta, float* members, int64_t stride, int32_t P, int32_t obs_dim, float sigma,
+                                uint64_t seed, int64_t generation, const auv_policy_arch_t* arch, void* stream);
+int auv_population_update_arch(int32_t device, float* theta, const float* w, float* grad, int32_t P, int32_t obs_dim, float sigma, float lr,
+                               uint64_t seed, int64_t generation, const auv_policy_arch_t* arch, void* stream);
 
 /* Generalised advantage estimation over a rollout of T steps x N environments (row-major [T][N] device buffers; V and
  * last_v in the same units as R): adv and ret = adv + V, one launch on `stream`.                                       */
