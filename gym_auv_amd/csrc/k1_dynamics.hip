@@ -63,7 +63,7 @@ __device__ __forceinline__ void stage_sincos(const Heading0& h0, const double ps
     *s = fma(h0.s, cd, h0.c * sd);
     *c = fma(h0.c, cd, -(h0.s * sd));
   } else {
-    sincos(auv_princip(psi), s, c);                              // (a yaw rate beyond anything the model reaches)
+    sincos(auv_princip(psi), s, c);                              // (no rarity: at dt 0.5 any |r| above 0.25 gets here in a later stage)
   }
 }
 
