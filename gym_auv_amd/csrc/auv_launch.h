@@ -1,0 +1,87 @@
+// auv_launch.h — the host-side launchers the kernel files define (k1 .. k7, k9 .. k12, k14, k_step_fused.hip) and the C ABI's host
+// files (auv_capi*.hip) call: declared once, here, with their default arguments.  Definer and caller both include this header, so
+// a definition that drifts from what its caller believes is a compile error.  The launchers of the PPO update, the world
+// generator, the renderer and the k11 population pass are declared beside their argument structs (auv_ppo.h, auv_generate.h,
+// auv_render.h, auv_population_pass.h).
+#ifndef AUV_LAUNCH_H
+#define AUV_LAUNCH_H
+#include "auv_device.h"
+#include "auv_snapshot.h"
+
+void auv_launch_k1(const AuvDev& d, const void* actions, int dtype, hipStream_t st, hipEvent_t ev0 = nullptr,
+                   hipEvent_t ev1 = nullptr);
+void auv_launch_k2(const AuvDev& d, int advance_movers, hipStream_t st);
+void auv_launch_k2_fresh(const AuvDev& d, hipStream_t st);
+void auv_launch_k3(const AuvDev& d, int mode, float* obs, float* reward, uint8_t* done, hipStream_t st);
+void auv_launch_k3_fresh(const AuvDev& d, float* obs, hipStream_t st);
+void auv_launch_k3_nav(const AuvDev& d, float* obs, hipStream_t st);
+void auv_launch_k3_reward(const AuvDev& d, float* obs, float* reward, uint8_t* done, int lidar_obs, hipStream_t st,
+                          hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+void auv_launch_reset(const AuvDev& d, const uint8_t* mask, const int32_t* world_idx, float* obs, hipStream_t st);
+void auv_launch_harvest(const AuvDev& d, int count, hipStream_t st, const int32_t* count_dev = nullptr);
+void auv_launch_fw_shadow_reset(const AuvDev& d, const int32_t* count_dev, hipStream_t st);
+void auv_launch_refresh_desc(const AuvDev& d, hipStream_t st);
+void auv_launch_derive(const AuvDev& d, hipStream_t st);
+void auv_launch_ring_advance(const AuvDev& d, hipStream_t st);   // (no caller at present: the ring is advanced inside the step's launches)
+size_t auv_k2_lds_bytes(const AuvDev& d);
+hipError_t auv_k2_prepare(const AuvDev& d);
+bool auv_k23_ok(const AuvDev& d);
+void auv_launch_k23(const AuvDev& d, float* obs, hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+hipError_t auv_step_fused_prepare(const AuvDev& d);
+uint32_t auv_step_lds_bytes(const AuvDev& d);
+int auv_pick_seg_cap(const AuvDev& d);
+bool auv_roles_ok(const AuvDev& d);
+void auv_launch_step_roles(const AuvDev& d, const void* actions, int dtype, float* obs, float* reward, uint8_t* done,
+                           hipStream_t st, hipEvent_t ev0 = nullptr, hipEvent_t ev1 = nullptr);
+void auv_launch_k31(const AuvDev& d, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, hipStream_t st);
+void auv_launch_step_multi(const AuvDev& d, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, int n_steps, int first_slot,
+                           int n_slots, unsigned long long seq0, int order, int lead, int lag, hipStream_t st, unsigned int fw_call = 0u);
+void auv_launch_step_record(const AuvDev& d, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, float* obs_rec, float* reward_rec,
+                            uint8_t* done_rec, int n_steps, int first_slot, int n_slots, unsigned long long seq0, int order, int lead, int lag, hipStream_t st,
+                            unsigned int fw_call = 0u);
+void auv_launch_step_feedback(const AuvDev& d, const double* gains, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, float* obs_rec,
+                              float* reward_rec, uint8_t* done_rec, double* act_rec, int n_steps, int first_slot, int n_slots, unsigned long long seq0,
+                              int order, int lead, int lag, hipStream_t st, const double* sector_gains, const int32_t* sector_bounds,
+                              const double* hidden, int activation);
+void auv_launch_spin(unsigned long long ticks, hipStream_t st);
+void auv_launch_rdv_publish(unsigned long long* word, unsigned long long seq, hipStream_t st);
+void auv_launch_rdv_arrive(unsigned long long* word, hipStream_t st);
+void auv_launch_rdv_wait(const unsigned long long* word, unsigned long long target, int32_t* err, int code, double limit_s, int32_t* abort_flag,
+                         int32_t* report, hipStream_t st);
+hipError_t auv_launch_probe(unsigned int* words, int np, int nc, unsigned int tag, unsigned int* failures, uint32_t lds, hipStream_t st);
+// the forward launches (k6_policy.hip, k9_policy_eval.hip, k12_policy_stacked.hip) take a hidden-width triple of the closed list
+// (auv_policy_mfma.h, POL_ARCH_LIST)
+size_t auv_policy_param_floats_impl(int h1, int h2, int h3, int obs_dim);
+size_t auv_policy_lds_bytes(int h1, int h2, int h3, int obs_dim);
+hipError_t auv_policy_prepare(int h1, int h2, int h3, int obs_dim);
+void auv_launch_policy(int h1, int h2, int h3, const auv_policy_io_t& io, int e0, int ne, hipStream_t st, long long t_host = -1,
+                       long long gstep_host = -1);
+void auv_launch_gae(const float* R, const float* V, const float* Dn, const float* last_v, float gamma, float lam, float* adv, float* ret,
+                    int T, int N, hipStream_t st);
+void auv_launch_k4(const AuvDev& d, const int32_t* sector_start, int n_sectors, double width, double* out_dist,
+                   float* out_closeness, hipStream_t st);
+void auv_launch_snapshot(const AuvSnapArgs& a, const int32_t* env_idx, int m, void* rows, hipStream_t st);
+void auv_launch_restore(const AuvSnapArgs& a, const AuvDev& d, const void* rows, int n_rows, const int32_t* row_idx, const int32_t* env_idx, int m,
+                        float* obs, hipStream_t st);
+void auv_launch_plan_score(const float* reward, const uint8_t* done, int T, int n, int group, float gamma, float* score, int32_t* best, hipStream_t st);
+hipError_t auv_policy_eval_prepare(int h1, int h2, int h3, int obs_dim);
+void auv_launch_policy_eval(int h1, int h2, int h3, const auv_policy_eval_t& ev, bool want_pi, bool want_v, hipStream_t st);
+void auv_launch_plan_score_v(const float* reward, const uint8_t* done, const float* terminal, int T, int n, int group, float gamma, float* score,
+                             int32_t* best, hipStream_t st);
+// k14_population_arch.hip: the population launches at the widths `a` (a listed triple; the reference's lands on k11_population.hip)
+size_t auv_population_member_floats_impl(const auv_policy_arch_t& a, int obs_dim);
+hipError_t auv_population_prepare(const auv_policy_arch_t& a, int obs_dim);
+void auv_launch_population_act(const auv_policy_arch_t& a, const auv_population_io_t& io, hipStream_t st);
+// k12_policy_stacked.hip
+size_t auv_policy_stacked_lds_bytes(int h1, int h2, int h3, int width);
+hipError_t auv_policy_stacked_prepare(int h1, int h2, int h3, int width);
+void auv_launch_policy_stacked(int h1, int h2, int h3, const auv_policy_stack_t& s, int e0, int ne, hipStream_t st, long long t_host = -1,
+                               long long gstep_host = -1);
+void auv_launch_stack_frames(const float* obs, const uint8_t* done, float* hist, int32_t* stk, float* out, long long ldx, int e0, int ne,
+                             int obs_dim, int frames, int advance, hipStream_t st);
+void auv_launch_population_perturb(const auv_policy_arch_t& a, const float* theta, float* members, long long stride, int P, int obs_dim,
+                                   float sigma, unsigned long long seed, unsigned long long generation, hipStream_t st);
+void auv_launch_population_update(const auv_policy_arch_t& a, float* theta, const float* w, float* grad, int P, int obs_dim, float sigma,
+                                  float lr, unsigned long long seed, unsigned long long generation, hipStream_t st);
+
+#endif  // AUV_LAUNCH_H

@@ -1,6 +1,6 @@
 // auv_multi_geom.h -- the launch geometry of k_step_multi (auv_step_multi): which workgroup order a slice takes, how lead / lag are
 // clamped, how many workgroups the launch has, and which (step, role, index) each workgroup is.  One source for the kernel
-// (k_step_fused.hip), its launcher and the C ABI's checks (auv_capi.hip); plain C++ without HIP headers, so that
+// (k_step_fused.hip), its launcher and the C ABI's checks (auv_capi_step.hip); plain C++ without HIP headers, so that
 // tests/test_multi_geometry.py compiles it with the host compiler and checks every decode of small launches and the division at
 // every size the host accepts.
 #pragma once

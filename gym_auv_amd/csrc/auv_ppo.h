@@ -1,4 +1,4 @@
-// The PPO update object behind auv_ppo_* (include/auv_hip.h): what auv_capi.hip allocates and k8_ppo_update.hip launches on.
+// The PPO update object behind auv_ppo_* (include/auv_hip.h): what auv_capi_learn.hip allocates and k8_ppo_update.hip launches on.
 #ifndef AUV_PPO_H
 #define AUV_PPO_H
 #include <hip/hip_runtime.h>

@@ -1,4 +1,4 @@
-// auv_snapshot.h — layout of a snapshot row (auv_snapshot / auv_restore), shared by the host side (auv_capi.hip), which
+// auv_snapshot.h — layout of a snapshot row (auv_snapshot / auv_restore), shared by the host side (auv_capi_aux.hip), which
 // builds it from the handle's shape, and the copy kernels (k7_snapshot.hip), which walk it.  The documented layout is in
 // include/auv_hip.h; this is its machine form.
 #pragma once

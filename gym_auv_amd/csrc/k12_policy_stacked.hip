@@ -32,6 +32,7 @@
 // tile's zeroing, stk and the transition are stored at the very end (k6's rule: requests first, stores last).
 // The flush launch (t == T) stores R[T - 1] / Dn[T - 1] only: hist and stk stay as they are, so the next rollout's first launch, which
 // sees the same obs and done_in, adds that frame exactly once.
+#include "auv_launch.h"
 #include "auv_policy_forward.h"
 
 namespace {

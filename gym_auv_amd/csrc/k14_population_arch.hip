@@ -7,6 +7,7 @@
 // live in a file of their own so that k11_population.hip keeps exactly its three kernels; their names share no substring with those.
 #include <type_traits>
 
+#include "auv_launch.h"
 #include "auv_population_pass.h"
 
 namespace {
@@ -55,7 +56,7 @@ size_t auv_population_member_floats_impl(const auv_policy_arch_t& a, int obs_dim
 }
 
 hipError_t auv_population_prepare(const auv_policy_arch_t& a, int obs_dim) {
-  hipError_t e = hipErrorInvalidValue;                               // (an unlisted triple: refused before, by the entries of auv_capi.hip)
+  hipError_t e = hipErrorInvalidValue;                               // (an unlisted triple: refused before, by the entries of auv_capi_learn.hip)
   pop_dispatch(a, [&] { e = auv_k11_population_prepare(obs_dim); }, [&](auto t) { e = pop_prepare<decltype(t), K14<decltype(t)>>(obs_dim); });
   return e;
 }

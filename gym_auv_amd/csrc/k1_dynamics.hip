@@ -12,6 +12,7 @@
 #include <hip/hip_ext.h>
 
 #include "auv_device.h"
+#include "auv_launch.h"
 
 namespace {
 

@@ -42,6 +42,7 @@
 // + 24*K (cull circles) + 16*K (meta) + 24 (pose) + 16*S (d + closeness out) + K (nearby) + 4*S
 // (float32 closeness).
 #include "auv_device.h"
+#include "auv_launch.h"
 #include "auv_mover_segs.h"
 
 namespace {

@@ -33,6 +33,7 @@
 #endif
 
 #include "auv_device.h"
+#include "auv_launch.h"
 
 namespace {
 

@@ -11,6 +11,7 @@
 // then a per-sector minimum through LDS (non-negative fp64 ordered as uint64).
 // Roofline: HBM.  Algorithmic bytes per env: 8*S in + 12*n_sectors out.
 #include "auv_device.h"
+#include "auv_launch.h"
 
 namespace {
 

@@ -22,6 +22,7 @@
 //   * last layer: one n-tile (outputs padded to 16); its epilogue samples a = mu + sigma eps (counter-based generator,
 //     Box-Muller), forms log pi(a), maps a into the action space into the env's action buffer, and stores the transition.
 // Optional (flag): nothing else -- a bf16 variant would run the matrix pipe 16x faster but is not the reference's arithmetic.
+#include "auv_launch.h"
 #include "auv_policy_forward.h"
 
 namespace {

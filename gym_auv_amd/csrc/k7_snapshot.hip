@@ -7,6 +7,7 @@
 // scatter.  Plain loads and stores: the calls are stream-ordered behind and in front of whole launches.  A pair whose environment,
 // row or world index is out of range is skipped and counted, never accessed.
 #include "auv_device.h"
+#include "auv_launch.h"
 #include "auv_snapshot.h"
 
 namespace {

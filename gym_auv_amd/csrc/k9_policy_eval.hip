@@ -11,6 +11,7 @@
 //
 // Also here: the value-terminated score of a shooting planner's candidates (auv_plan_score_v), auv_plan_score's loop with one
 // more term for a candidate that saw no done.
+#include "auv_launch.h"
 #include "auv_policy_forward.h"
 
 namespace {

@@ -17,6 +17,7 @@
 #include <hip/hip_ext.h>
 
 #define AUV_DEVICE_FUNCS_ONLY
+#include "auv_launch.h"
 #include "auv_multi_geom.h"
 #include "k1_dynamics.hip"
 #include "k2_lidar.hip"
