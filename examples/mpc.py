@@ -7,6 +7,7 @@ episode ends.  Prints the return of every vessel and the plans per second.
 
     python examples/mpc.py --scenario TestScenario1 --vessels 4 --candidates 64 --horizon 16
     python examples/mpc.py --scenario moving --vessels 16 --iterations 3          # CEM
+    python examples/mpc.py --scenario moving --vessels 16 --iterations 3 --sampler device --method mppi --mppi-lambda 5 --warm-start
     python examples/mpc.py --value policy.pt --value-scale 100 --prior policy.pt  # a learned critic beyond the horizon, the actor as the mean
 """
 import argparse
@@ -45,6 +46,12 @@ def main():
     ap.add_argument("--value-shift", type=float, default=0.0)
     ap.add_argument("--prior", default=None, metavar="CKPT", help="state_dict of an ActorCritic: its deterministic action, held over the horizon, is "
                                                                   "the mean the candidates are drawn around")
+    ap.add_argument("--sampler", choices=("torch", "device"), default="torch", help="device: sample and refit in two HIP launches per iteration, "
+                                                                                     "counter-based noise (reproducible on the host)")
+    ap.add_argument("--method", choices=("cem", "mppi"), default="cem", help="mppi (path-integral weights over all candidates) needs --sampler device")
+    ap.add_argument("--mppi-lambda", type=float, default=1.0, help="temperature of the MPPI weights, in reward units")
+    ap.add_argument("--warm-start", action="store_true", help="receding horizon: start every plan from the previous one moved on one step "
+                                                             "(needs --sampler device)")
     args = ap.parse_args()
     cfg = effective_reference_config(use_lidar=True)
     B = args.vessels
@@ -64,13 +71,16 @@ def main():
             nets[ckpt] = FusedActorCritic(load_policy(ckpt, env.obs_dim, env.device), env, rollout=1)
         return nets.get(ckpt)
     planner = ShootingPlanner(env, candidates=args.candidates, horizon=args.horizon, gamma=args.gamma, iterations=args.iterations, seed=args.seed,
-                              value=fused_of(args.value), value_scale=args.value_scale, value_shift=args.value_shift, prior=fused_of(args.prior))
+                              value=fused_of(args.value), value_scale=args.value_scale, value_shift=args.value_shift, prior=fused_of(args.prior),
+                              sampler=args.sampler, method=args.method, mppi_lambda=args.mppi_lambda, warm_start=args.warm_start)
     ret = torch.zeros(B, dtype=torch.float64, device=env.device)
     running = torch.ones(B, dtype=torch.bool, device=env.device)
     torch.cuda.synchronize()
     t0, steps = time.perf_counter(), 0
+    done = None
     while steps < args.max_steps:
-        actions, _, _ = planner.plan()
+        # (warm start: a vessel whose episode has just ended plans afresh, the others carry their plan on by one step)
+        actions, _, _ = planner.plan(reset=done.contiguous() if args.warm_start and done is not None else None)
         _, reward, done, _ = env.step(actions)
         ret += torch.where(running, reward.double(), torch.zeros_like(ret))
         running &= ~done.bool()

@@ -21,6 +21,8 @@ AUV_CULL_REFERENCE, AUV_CULL_EXACT = 0, 1
 AUV_F32, AUV_F64 = 0, 1
 AUV_RDV_EVENTS, AUV_RDV_DEVICE, AUV_RDV_CP = 0, 1, 2
 AUV_VIEW_HEADING_UP, AUV_VIEW_NORTH_UP = 0, 1
+AUV_PLAN_CEM, AUV_PLAN_MPPI = 0, 1
+AUV_PLAN_MAX_GROUP = 1024
 
 FIELDS = dict(STATE=0, LIDAR_D=1, OBS64=2, REWARD64=3, INFO64=4, WORLD_IDX=5, COUNTERS=6,
               MOVER_STATE=7, NEARBY=8, EPISODE=9, CULL_LIMITS=10, NAV64=11, COLLISION=12, STAMPS=13, STEP_INFO=14, BROKEN=15, FW_STATE=16, FW_SERIAL=17,
@@ -306,6 +308,9 @@ def load_library(path: str = None) -> C.CDLL:
         "auv_snapshot_skipped": (C.c_int, [vp, C.POINTER(C.c_int64), vp]),
         "auv_plan_score": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp]),
         "auv_plan_score_v": (C.c_int, [vp, vp, vp, i32, i32, i32, C.c_float, vp, vp, vp, vp]),
+        "auv_plan_sample": (C.c_int, [vp, vp, vp, vp, vp, vp, i32, i32, i32, i32, C.POINTER(C.c_float), C.POINTER(C.c_float), C.c_uint64, C.c_uint64,
+                                      vp, vp]),
+        "auv_plan_refit": (C.c_int, [vp, vp, vp, vp, i32, i32, i32, i32, i32, C.c_float, C.c_float, vp, vp, vp, vp, vp, vp, vp]),
         "auv_policy_eval": (C.c_int, [i32, C.POINTER(AuvPolicyEval), vp]),
         "auv_population_member_floats": (sz, [i32]),
         "auv_population_act": (C.c_int, [i32, C.POINTER(AuvPopulationIO), vp]),
@@ -358,7 +363,7 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_generate_worlds", "auv_bank_bytes", "auv_read_bank",
                     "auv_fresh_worlds_create", "auv_fresh_worlds_refill", "auv_fresh_worlds_stats", "auv_fresh_worlds_draws", "auv_fresh_worlds_set_stream", "auv_fresh_worlds_multi",
                     "auv_snapshot_row_bytes", "auv_snapshot_layout", "auv_snapshot", "auv_restore", "auv_snapshot_skipped", "auv_plan_score",
-                    "auv_plan_score_v", "auv_policy_eval",
+                    "auv_plan_score_v", "auv_plan_sample", "auv_plan_refit", "auv_policy_eval",
                     "auv_policy_act_stacked", "auv_policy_rollout_stacked", "auv_stack_frames",
                     "auv_policy_param_floats_arch", "auv_policy_act_arch", "auv_policy_rollout_arch", "auv_policy_act_stacked_arch",
                     "auv_policy_rollout_stacked_arch", "auv_policy_eval_arch",

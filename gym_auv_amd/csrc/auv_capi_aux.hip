@@ -1,9 +1,10 @@
 // auv_capi_aux.hip — the C ABI's entries beside the step (include/auv_hip.h): pooled observations and feasibility pooling, the
-// device renderer, snapshot / restore of environments, and the planner's scores.
+// device renderer, snapshot / restore of environments, and the planner's scores, sampler and refit.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
 #include <cstring>
+#include <initializer_list>
 
 #include "auv_host.h"
 #include "auv_render.h"
@@ -250,6 +251,71 @@ int auv_plan_score_v(auv_handle_t* h, const float* reward_rec, const uint8_t* do
   if ((uintptr_t)terminal_value & 3) return fail(AUV_EINVAL, "auv_plan_score_v: terminal_value must be 4-byte aligned");
   HIP_TRY(hipSetDevice(h->device));
   auv_launch_plan_score_v(reward_rec, done_rec, terminal_value, n_steps, n, group, gamma, score_dev, best_dev, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+// ---- the planner's sampler and refit (kernels: k15_plan.hip) ----
+// the sizes both calls share
+static int plan_shape_check(const auv_handle_t* h, int32_t n_steps, int32_t n, int32_t group, const char* who) {
+  if (!h) return fail(AUV_EINVAL, "null handle");
+  if (n_steps < 1 || n < 1 || group < 1 || n % group)
+    return fail(AUV_EINVAL, "%s: bad arguments (n_steps, n, group >= 1; n a multiple of group)", who);
+  if (group > AUV_PLAN_MAX_GROUP) return fail(AUV_EINVAL, "%s: group = %d, at most %d candidates per group", who, group, AUV_PLAN_MAX_GROUP);
+  if (2ll * n_steps * n > 0x7fffffffll) return fail(AUV_EINVAL, "%s: n_steps * n * 2 = %lld does not fit 31 bits", who, 2ll * n_steps * n);
+  return AUV_OK;
+}
+
+static bool plan_misaligned(std::initializer_list<const void*> ptrs) {
+  for (const void* p : ptrs)
+    if ((uintptr_t)p & 3) return true;
+  return false;
+}
+
+int auv_plan_sample(auv_handle_t* h, const float* mean_dev, const float* sigma_dev, const float* mean0_dev, const float* sigma0_dev,
+                    const uint8_t* reset_dev, int32_t n_steps, int32_t n, int32_t group, int32_t shift, const float* lo_host, const float* hi_host,
+                    uint64_t seed, uint64_t draw, float* ring_dev, void* stream) {
+  int rc = plan_shape_check(h, n_steps, n, group, "auv_plan_sample");
+  if (rc) return rc;
+  if (!mean_dev || !sigma_dev || !ring_dev || !lo_host || !hi_host) return fail(AUV_EINVAL, "auv_plan_sample: null mean, sigma, ring or bounds");
+  if (shift != 0 && shift != 1) return fail(AUV_EINVAL, "auv_plan_sample: shift = %d must be 0 or 1", shift);
+  if (reset_dev && (!mean0_dev || !sigma0_dev)) return fail(AUV_EINVAL, "auv_plan_sample: a reset mask needs mean0 and sigma0");
+  if (plan_misaligned({mean_dev, sigma_dev, mean0_dev, sigma0_dev, ring_dev}))
+    return fail(AUV_EINVAL, "auv_plan_sample: mean, sigma, mean0, sigma0 and the ring must be 4-byte aligned");
+  HIP_TRY(hipSetDevice(h->device));
+  AuvPlanSample a;
+  a.mean = mean_dev, a.sigma = sigma_dev, a.mean0 = mean0_dev, a.sigma0 = sigma0_dev, a.reset = reset_dev, a.ring = ring_dev;
+  a.T = n_steps, a.n = n, a.group = group, a.shift = shift;
+  a.lo[0] = lo_host[0], a.lo[1] = lo_host[1], a.hi[0] = hi_host[0], a.hi[1] = hi_host[1];
+  a.seed = seed, a.draw = draw;
+  auv_launch_plan_sample(a, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+int auv_plan_refit(auv_handle_t* h, const float* ring_dev, const float* score_dev, const int32_t* best_dev, int32_t n_steps, int32_t n, int32_t group,
+                   int32_t method, int32_t n_elite, float sigma_min, float lambda, const float* mean_in_dev, const float* sigma_in_dev,
+                   float* mean_out_dev, float* sigma_out_dev, float* chosen_dev, float* predicted_dev, void* stream) {
+  int rc = plan_shape_check(h, n_steps, n, group, "auv_plan_refit");
+  if (rc) return rc;
+  if (!ring_dev || !score_dev || !best_dev) return fail(AUV_EINVAL, "auv_plan_refit: null ring, score or best");
+  if (method != AUV_PLAN_CEM && method != AUV_PLAN_MPPI) return fail(AUV_EINVAL, "auv_plan_refit: unknown method %d", method);
+  if ((mean_out_dev == nullptr) != (sigma_out_dev == nullptr)) return fail(AUV_EINVAL, "auv_plan_refit: mean_out and sigma_out go together");
+  if (mean_out_dev && method == AUV_PLAN_CEM && (n_elite < 1 || n_elite > group))
+    return fail(AUV_EINVAL, "auv_plan_refit: n_elite = %d must be in [1, group = %d]", n_elite, group);
+  if (mean_out_dev && method == AUV_PLAN_MPPI) {
+    if (!std::isfinite(lambda) || !(lambda > 0.0f)) return fail(AUV_EINVAL, "auv_plan_refit: lambda = %g must be finite and > 0", (double)lambda);
+    if (!mean_in_dev || !sigma_in_dev) return fail(AUV_EINVAL, "auv_plan_refit: MPPI needs mean_in and sigma_in");
+    if (mean_in_dev == mean_out_dev || sigma_in_dev == sigma_out_dev) return fail(AUV_EINVAL, "auv_plan_refit: the outputs must not be the inputs");
+  }
+  if (plan_misaligned({ring_dev, score_dev, best_dev, mean_in_dev, sigma_in_dev, mean_out_dev, sigma_out_dev, chosen_dev, predicted_dev}))
+    return fail(AUV_EINVAL, "auv_plan_refit: every buffer must be 4-byte aligned");
+  HIP_TRY(hipSetDevice(h->device));
+  AuvPlanRefit a;
+  a.ring = ring_dev, a.score = score_dev, a.best = best_dev, a.mean_in = mean_in_dev, a.sigma_in = sigma_in_dev;
+  a.mean_out = mean_out_dev, a.sigma_out = sigma_out_dev, a.chosen = chosen_dev, a.predicted = predicted_dev;
+  a.T = n_steps, a.n = n, a.group = group, a.method = method, a.n_elite = n_elite, a.sigma_min = sigma_min, a.lambda = lambda;
+  auv_launch_plan_refit(a, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }

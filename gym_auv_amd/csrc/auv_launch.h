@@ -1,4 +1,4 @@
-// auv_launch.h — the host-side launchers the kernel files define (k1 .. k7, k9 .. k12, k14, k_step_fused.hip) and the C ABI's host
+// auv_launch.h — the host-side launchers the kernel files define (k1 .. k7, k9 .. k12, k14, k15, k_step_fused.hip) and the C ABI's host
 // files (auv_capi*.hip) call: declared once, here, with their default arguments.  Definer and caller both include this header, so
 // a definition that drifts from what its caller believes is a compile error.  The launchers of the PPO update, the world
 // generator, the renderer and the k11 population pass are declared beside their argument structs (auv_ppo.h, auv_generate.h,
@@ -68,6 +68,28 @@ hipError_t auv_policy_eval_prepare(int h1, int h2, int h3, int obs_dim);
 void auv_launch_policy_eval(int h1, int h2, int h3, const auv_policy_eval_t& ev, bool want_pi, bool want_v, hipStream_t st);
 void auv_launch_plan_score_v(const float* reward, const uint8_t* done, const float* terminal, int T, int n, int group, float gamma, float* score,
                              int32_t* best, hipStream_t st);
+// k15_plan.hip: the planner's sampler and refit (contracts: include/auv_hip.h, auv_plan_sample / auv_plan_refit).  The host side has
+// checked every size (group <= AUV_PLAN_MAX_GROUP, T * n * 2 < 2^31) and every pointer the method reads or writes.
+struct AuvPlanSample {
+  const float *mean, *sigma;         // [T][B][2]
+  const float *mean0, *sigma0;       // [T][B][2]: what a group with reset[b] != 0 reads (with `reset` only)
+  const uint8_t* reset;              // [B] or NULL
+  float* ring;                       // [T][n][2]
+  int32_t T, n, group, shift;
+  float lo[2], hi[2];
+  unsigned long long seed, draw;
+};
+struct AuvPlanRefit {
+  const float *ring, *score;         // [T][n][2], [n]
+  const int32_t* best;               // [B]
+  const float *mean_in, *sigma_in;   // [T][B][2] (MPPI)
+  float *mean_out, *sigma_out;       // [T][B][2], both or neither
+  float *chosen, *predicted;         // [T][B][2], [B]; each nullable
+  int32_t T, n, group, method, n_elite;
+  float sigma_min, lambda;
+};
+void auv_launch_plan_sample(const AuvPlanSample& a, hipStream_t st);
+void auv_launch_plan_refit(const AuvPlanRefit& a, hipStream_t st);
 // k14_population_arch.hip: the population launches at the widths `a` (a listed triple; the reference's lands on k11_population.hip)
 size_t auv_population_member_floats_impl(const auv_policy_arch_t& a, int obs_dim);
 hipError_t auv_population_prepare(const auv_policy_arch_t& a, int obs_dim);

@@ -8,6 +8,7 @@
 // with -ffp-contract=off and the tests compare bits across the launches.
 #ifndef AUV_POLICY_FORWARD_H
 #define AUV_POLICY_FORWARD_H
+#include "auv_noise.h"
 #include "auv_policy_mfma.h"
 
 namespace {
@@ -94,13 +95,7 @@ __device__ __forceinline__ float pol_trunk(float* X, const int K0, const PolNet&
   return ls;
 }
 // ---- the counter-based generator of the policy launches ----
-// splitmix64 finaliser: (seed, step, row, component) -> 64 well-mixed bits
-__device__ __forceinline__ unsigned long long pol_mix(unsigned long long z) {
-  z += 0x9e3779b97f4a7c15ull;
-  z = (z ^ (z >> 30)) * 0xbf58476d1ce4e5b9ull;
-  z = (z ^ (z >> 27)) * 0x94d049bb133111ebull;
-  return z ^ (z >> 31);
-}
+// (seed, step, row, component) -> 64 well-mixed bits (pol_mix, the splitmix64 finaliser: auv_noise.h) -> a Gaussian
 __device__ __forceinline__ float pol_gauss(unsigned long long seed, unsigned long long step, unsigned int row, unsigned int comp) {
   const unsigned long long h = pol_mix(pol_mix(seed ^ (step * 0xd1342543de82ef95ull)) ^ (((unsigned long long)row << 1) | comp));
   const float u1 = ((float)(unsigned int)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);      // (0, 1): 24 bits

@@ -15,6 +15,7 @@
 // The widths enter those two only through pop_live<A>: which elements of a packed block are parameters of the net.
 #ifndef AUV_POPULATION_PASS_H
 #define AUV_POPULATION_PASS_H
+#include "auv_noise.h"
 #include "auv_policy_forward.h"
 
 namespace {
@@ -91,18 +92,7 @@ __device__ __forceinline__ void pop_act_pass(const PopArgs& pa) {
   }
 }
 
-// ---- counter-based noise: (seed, generation, pair, element) -> eps, unit variance, bit-reproducible on the host ----
-// (pol_mix: the splitmix64 finaliser of auv_policy_forward.h)
-// the part of the key all elements of a launch share
-__device__ __forceinline__ unsigned long long pop_key(unsigned long long seed, unsigned long long generation) {
-  return pol_mix(seed ^ (generation * 0xd1342543de82ef95ull));
-}
-// c = float32(1 / sqrt(4 (65536^2 - 1) / 12)), formed on the host
-__device__ __forceinline__ float pop_eps(unsigned long long key, unsigned int pair, unsigned int i, float c) {
-  const unsigned long long h = pol_mix(pol_mix(key ^ (unsigned long long)pair) ^ (unsigned long long)i);
-  const int S = (int)(h & 0xffffu) + (int)((h >> 16) & 0xffffu) + (int)((h >> 32) & 0xffffu) + (int)(h >> 48);
-  return __fmul_rn((float)(S - 131070), c);                     // |S - 131070| < 2^24: the conversion is exact
-}
+// (the counter-based noise, pop_key / pop_eps / pop_eps_scale: auv_noise.h, shared with the planner's sampler)
 
 // Is element i of a packed net (W1 b1 W2 b2 W3 b3 W4 b4, include/auv_hip.h: auv_policy_io) a parameter of the net -- or padding:
 // a column of W1 beyond obs_dim, a row 2..15 of W4, an entry 2..15 of b4?  The fragment-order formula inverted: in a matrix,
@@ -190,8 +180,6 @@ inline void pop_launch_act(const auv_population_io_t& io, hipStream_t st) {
   const dim3 grid((unsigned)(((long long)io.M + POL_ROWS - 1) / POL_ROWS)), block(POL_THREADS);
   hipLaunchKernelGGL(K::act, grid, block, io.act ? pol_lds_bytes<A>(io.obs_dim) : 0, st, pa);
 }
-
-inline float pop_eps_scale() { return (float)(1.0 / sqrt(4.0 * (65536.0 * 65536.0 - 1.0) / 12.0)); }
 
 template <class A, class K>
 inline void pop_launch_perturb(const float* theta, float* members, long long stride, int P, int obs_dim, float sigma, unsigned long long seed,

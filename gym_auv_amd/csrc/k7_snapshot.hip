@@ -8,6 +8,7 @@
 // row or world index is out of range is skipped and counted, never accessed.
 #include "auv_device.h"
 #include "auv_launch.h"
+#include "auv_plan.h"
 #include "auv_snapshot.h"
 
 namespace {
@@ -110,13 +111,7 @@ __device__ __forceinline__ float plan_score_env(const float* __restrict__ reward
   return s;
 }
 
-// (score, index) a beats b: a valid score (not NaN) beats none; the larger score wins; the lower index wins a tie
-#define PLAN_NONE 0x7fffffff
-__device__ __forceinline__ bool plan_beats(const float sa, const int ia, const float sb, const int ib) {
-  if (ia == PLAN_NONE) return false;
-  if (ib == PLAN_NONE) return true;
-  return sa > sb || (sa == sb && ia < ib);
-}
+// (plan_beats, the order of (score, index) pairs: auv_plan.h, shared with the refit of k15_plan.hip)
 
 // Lanes run across environments (row t of the record is read coalesced); a wave reduction gives the argmax.  A group of 1, 2, .. 64
 // (a power of two) environments shares its wave with 64 / group - 1 others (`span` = group: the butterfly stays inside the group's

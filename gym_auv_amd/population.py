@@ -55,7 +55,7 @@ def member_floats(obs_dim: int, hidden=HIDDEN) -> int:
 
 # ------------------------------------------------------------------------------------------------------------------ the contract
 def _mix(z: np.ndarray) -> np.ndarray:
-    """splitmix64 finaliser (csrc/k6_policy.hip: pol_mix) on uint64 arrays: 64-bit wrap-around arithmetic."""
+    """splitmix64 finaliser (csrc/auv_noise.h: pol_mix) on uint64 arrays: 64-bit wrap-around arithmetic."""
     z = z + np.uint64(0x9e3779b97f4a7c15)
     z = (z ^ (z >> np.uint64(30))) * np.uint64(0xbf58476d1ce4e5b9)
     z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94d049bb133111eb)

@@ -927,6 +927,42 @@ int auv_plan_score(auv_handle_t* h, const float* reward_rec, const uint8_t* done
 int auv_plan_score_v(auv_handle_t* h, const float* reward_rec, const uint8_t* done_rec, int32_t n_steps, int32_t n, int32_t group,
                      float gamma, const float* terminal_value, float* score_dev, int32_t* best_dev, void* stream);
 
+/* The planner's sampler and refit on the device (csrc/k15_plan.hip; gym_auv_amd/planning.py: reference_plan_sample and
+ * reference_plan_refit are the same arithmetic in NumPy).  n = B * group planner environments, environment e = b * group + k being
+ * candidate k of group b; mean / sigma / chosen are [n_steps][B][2] float32, the ring [n_steps][n][2] float32.  All arithmetic is
+ * float32, round to nearest, without contraction, in the order stated: the orders are part of the contract.  One launch each on
+ * `stream`, no allocation, no host synchronisation.  1 <= group <= AUV_PLAN_MAX_GROUP, n a multiple of group, n_steps * n * 2 < 2^31,
+ * every pointer 4-byte aligned; a failed check returns AUV_EINVAL and launches nothing.
+ *   auv_plan_sample   ring[t][e][j] = clip(m + s * eps), one rounded product, one rounded sum, then fmaxf(fminf(., hi[j]), lo[j]);
+ *                     candidate k = 0 is clip(m), without noise.  m, s = mean, sigma at row min(t + shift, n_steps - 1) of group b:
+ *                     shift 0, or 1 for a receding-horizon warm start (the previous plan moved on one step, its last step repeated).
+ *                     eps = the noise of auv_population_perturb at (seed, generation = draw, pair = e, element = 2 t + j).  reset_dev
+ *                     (nullable, [B] bytes): a group with reset[b] != 0 reads row t -- no shift -- of mean0 / sigma0 instead (both
+ *                     required with a mask, ignored without).  lo_host, hi_host: two floats each, on the host.
+ *   auv_plan_refit    chosen[t][b][:] = ring[t][b * group + best[b]][:] and predicted[b] = score[b * group + best[b]] (each nullable;
+ *                     best[b] is clamped into the group), and, with mean_out / sigma_out (both or neither; buffers of their own,
+ *                     not the inputs), the next sampling distribution of every group:
+ *                     AUV_PLAN_CEM   the elite are the n_elite first candidates in the total order of the scorer's argmax: larger score
+ *                       first, lower index on a tie; a NaN score ranks below every number, NaNs among themselves by index.  Per (t, j),
+ *                       over the elite in ascending candidate index: s = the sequential sum of a, mean = s / n_elite; q = the
+ *                       sequential sum of (a - mean) * (a - mean), difference, product and sum each rounded;
+ *                       sigma = fmaxf(sqrt(q / n_elite), sigma_min).  1 <= n_elite <= group.  mean_in / sigma_in are not read.
+ *                     AUV_PLAN_MPPI  w_k = 1 where score_k equals the group's largest valid score, else expf((score_k - max) / lambda)
+ *                       (difference and quotient rounded), 0 for a NaN score; mean = (sum_k w_k * a_k) / (sum_k w_k), both sums
+ *                       sequential over ALL candidates in ascending k, every product rounded; sigma_out = sigma_in.  A group without
+ *                       a valid score keeps mean_in.  lambda finite and > 0.  expf is the device's: reproducible run to run, not
+ *                       bit for bit on a host -- except where every weight but the maxima's underflows to 0.                       */
+#define AUV_PLAN_CEM 0
+#define AUV_PLAN_MPPI 1
+#define AUV_PLAN_MAX_GROUP 1024
+int auv_plan_sample(auv_handle_t* h, const float* mean_dev, const float* sigma_dev, const float* mean0_dev, const float* sigma0_dev,
+                    const uint8_t* reset_dev, int32_t n_steps, int32_t n, int32_t group, int32_t shift, const float* lo_host,
+                    const float* hi_host, uint64_t seed, uint64_t draw, float* ring_dev, void* stream);
+int auv_plan_refit(auv_handle_t* h, const float* ring_dev, const float* score_dev, const int32_t* best_dev, int32_t n_steps, int32_t n,
+                   int32_t group, int32_t method, int32_t n_elite, float sigma_min, float lambda, const float* mean_in_dev,
+                   const float* sigma_in_dev, float* mean_out_dev, float* sigma_out_dev, float* chosen_dev, float* predicted_dev,
+                   void* stream);
+
 /* ---- the PPO update (scripts/run.py:332-357: PPO2 with MlpPolicy, net_arch [256, 128, 64] for policy and value
  * function, tanh, a diagonal Gaussian with a free log_std[2]): one minibatch step of examples/ppo.py (minibatch_step) as a few
  * launches -- forward and backward of both nets on the matrix cores in exact f32, the clipped-surrogate / value / entropy loss, the
