@@ -11,7 +11,11 @@ Prints mean return and mean progress per iteration.  No learning result is promi
     python examples/ars.py --sectors [--out profiles/feedback_sectors/ars_curve.jsonl]
 also searches a 2 x 4 matrix Hs on the LiDAR's four sector inputs (the largest closeness in each of the configuration's 4 x 8
 sectors, step_feedback(..., sector_gains=)): the same directions d_k are drawn for (M, Hs) together, both matrices are perturbed
-and stepped alike.  Hs starts at zero."""
+and stepped alike.  Hs starts at zero.
+    python examples/ars.py --fresh-worlds 1
+runs every rollout on worlds nobody has seen (FreshWorlds(multi_step=True, closed_loop=True): the generator's 17 movers + 11
+circles, one chain) instead of the fixed bank -- every iteration's reset() moves every environment to its next unseen world, so
+the two environments of a direction no longer share a world -- and prints fresh_stats() (`reused`, `regenerated`) at the end."""
 import argparse
 import json
 import os
@@ -38,6 +42,8 @@ ap.add_argument("--alpha", type=float, default=0.02)
 ap.add_argument("--top", type=float, default=0.25, help="share of the directions an update uses")
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--out", default=None)
+ap.add_argument("--fresh-worlds", type=int, default=0, choices=(0, 1),
+                help="1: every rollout on worlds nobody has seen (FreshWorlds, closed loop allowed) instead of the fixed bank")
 ap.add_argument("--sectors", action="store_true", help="also perturb gains on the LiDAR's sector inputs")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
@@ -47,10 +53,17 @@ assert n == 2 * P and P >= 1
 cfg = effective_reference_config(use_lidar=True)
 cfg.vessel.n_sectors, cfg.vessel.n_sensors_per_sector = 4, 8
 cfg.episode.max_timesteps = H
-bank = build_bank_parallel("static_circles_world", 4000 + np.arange(P), procs=16, n_circles=8)
-with warnings.catch_warnings():
-    warnings.simplefilter("ignore")                        # (one world per pair of environments, on purpose)
-    env = BatchedAuvEnv(cfg, bank, n, device=dev, rewarder="pathfollow", auto_reset=True)
+if args.fresh_worlds:
+    # a fresh world on every reset, as the reference trains: reset() moves every environment to its next unseen world (the library
+    # chooses it), so the two environments of a direction meet two different worlds and r+ - r- carries that difference too
+    from gym_auv_amd.devgen import FreshWorlds  # noqa: E402
+    env = BatchedAuvEnv(cfg, FreshWorlds(depth=3, multi_step=True, closed_loop=True, seed=args.seed, batch_cap=min(n, 512)), n, device=dev, rewarder="pathfollow",
+                        auto_reset=True)
+else:
+    bank = build_bank_parallel("static_circles_world", 4000 + np.arange(P), procs=16, n_circles=8)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                        # (one world per pair of environments, on purpose)
+        env = BatchedAuvEnv(cfg, bank, n, device=dev, rewarder="pathfollow", auto_reset=True)
 env.set_sub_batches(1, inline_first=True)               # the one chain IS the caller's stream: launches, resets and scoring in order
 worlds = torch.arange(n, device=dev, dtype=torch.int32) % P
 gen = torch.Generator(device=dev)
@@ -76,7 +89,7 @@ for it in range(args.iterations):
         sgains = torch.zeros((n, 2, 16), dtype=torch.float64, device=dev)
         sgains[:P, :, :NS] = Hs + args.nu * ds
         sgains[P:, :, :NS] = Hs - args.nu * ds
-    env.reset(world_idx=worlds)
+    env.reset(world_idx=None if args.fresh_worlds else worlds)
     rew, done = [], []
     for t in range(0, H, 64):
         _, r, dn = env.step_feedback(gains, min(64, H - t), record="reward", sector_gains=sgains)
@@ -107,4 +120,7 @@ for it in range(args.iterations):
 if log:
     log.write(json.dumps(dict(final_policy=M.tolist(), final_sector_gains=Hs.tolist() if args.sectors else None)) + "\n")
     log.close()
+if args.fresh_worlds:
+    st = env.fresh_stats()
+    print(json.dumps(dict(fresh_stats=dict(reused=st["reused"], regenerated=st["regenerated"]))), flush=True)
 env.close()

@@ -9,7 +9,8 @@ W1 on the 6 + 4 inputs that carry something, b1 and V -- and the 2 x 7 matrix M.
 one per pair of environments: environment k runs theta + nu d_k, environment P + k runs theta - nu d_k, both in world k from its
 reset state, each with its OWN [16, 28] block in the launch; returns and the update are examples/ars.py's.  W1 and b1 start as
 N(0, 0.1) (with W1 = 0 and V = 0 together no direction changes the return to first order), V at zero -- the first rollouts are the
-affine policy's -- and M at half thrust.  Prints mean return and mean progress per iteration.  No learning result is promised."""
+affine policy's -- and M at half thrust.  Prints mean return and mean progress per iteration.  No learning result is promised.
+`--fresh-worlds 1`: as in examples/ars.py -- every rollout on worlds nobody has seen, fresh_stats() printed at the end."""
 import argparse
 import json
 import os
@@ -38,6 +39,8 @@ ap.add_argument("--alpha", type=float, default=0.02)
 ap.add_argument("--top", type=float, default=0.25, help="share of the directions an update uses")
 ap.add_argument("--seed", type=int, default=0)
 ap.add_argument("--out", default=None)
+ap.add_argument("--fresh-worlds", type=int, default=0, choices=(0, 1),
+                help="1: every rollout on worlds nobody has seen (FreshWorlds, closed loop allowed) instead of the fixed bank")
 args = ap.parse_args()
 dev = torch.device("cuda:0")
 n, H, U = args.envs, args.horizon, args.units
@@ -47,10 +50,17 @@ cfg = effective_reference_config(use_lidar=True)
 cfg.vessel.n_sectors, cfg.vessel.n_sensors_per_sector = 4, 8
 cfg.episode.max_timesteps = H
 NS = cfg.vessel.n_sectors
-bank = build_bank_parallel("static_circles_world", 4000 + np.arange(P), procs=16, n_circles=8)
-with warnings.catch_warnings():
-    warnings.simplefilter("ignore")                        # (one world per pair of environments, on purpose)
-    env = BatchedAuvEnv(cfg, bank, n, device=dev, rewarder="pathfollow", auto_reset=True)
+if args.fresh_worlds:
+    # a fresh world on every reset, as the reference trains: reset() moves every environment to its next unseen world (the library
+    # chooses it), so the two environments of a direction meet two different worlds and r+ - r- carries that difference too
+    from gym_auv_amd.devgen import FreshWorlds  # noqa: E402
+    env = BatchedAuvEnv(cfg, FreshWorlds(depth=3, multi_step=True, closed_loop=True, seed=args.seed, batch_cap=min(n, 512)), n, device=dev, rewarder="pathfollow",
+                        auto_reset=True)
+else:
+    bank = build_bank_parallel("static_circles_world", 4000 + np.arange(P), procs=16, n_circles=8)
+    with warnings.catch_warnings():
+        warnings.simplefilter("ignore")                        # (one world per pair of environments, on purpose)
+        env = BatchedAuvEnv(cfg, bank, n, device=dev, rewarder="pathfollow", auto_reset=True)
 env.set_sub_batches(1, inline_first=True)               # the one chain IS the caller's stream: launches, resets and scoring in order
 worlds = torch.arange(n, device=dev, dtype=torch.int32) % P
 gen = torch.Generator(device=dev)
@@ -78,7 +88,7 @@ for it in range(args.iterations):
     gains[:P, :, :7] = M + args.nu * d
     gains[P:, :, :7] = M - args.nu * d
     hidden = torch.cat([theta + args.nu * dh, theta - args.nu * dh])
-    env.reset(world_idx=worlds)
+    env.reset(world_idx=None if args.fresh_worlds else worlds)
     rew, done = [], []
     for t in range(0, H, 64):
         _, r, dn = env.step_feedback(gains, min(64, H - t), record="reward", sector_gains=zero_sectors, hidden=hidden, activation=args.activation)
@@ -109,4 +119,7 @@ for it in range(args.iterations):
 if log:
     log.write(json.dumps(dict(final_policy=M.tolist(), final_hidden=theta.tolist())) + "\n")
     log.close()
+if args.fresh_worlds:
+    st = env.fresh_stats()
+    print(json.dumps(dict(fresh_stats=dict(reused=st["reused"], regenerated=st["regenerated"]))), flush=True)
 env.close()

@@ -390,7 +390,13 @@ class BatchedAuvEnv:
         feedback.pack_hidden makes -- the law then has one hidden layer of 16 units over its 24 inputs (the six columns, the
         ring's action, the 16 sector inputs), `activation` "relu" or "hardtanh", added to the affine part as
         (s + (u + w)) + (ha + hb) (auv_step_feedback_hidden; feedback.hidden_action is the mirror).  Needs `sector_gains`
-        (zeros switch the affine sector terms off)."""
+        (zeros switch the affine sector terms off).
+
+        With worlds=FreshWorlds(...) only when built with multi_step=True, closed_loop=True (RuntimeError "fresh world"
+        otherwise).  Guaranteed as in step_multi: a reset inside the launch binds the environment's next slot if that slot was
+        published before the call began, else the environment restarts in the world it has just left and
+        `fresh_stats()["reused"]` counts it; either way the action of the step after the reset is the law of the reset row of the
+        world actually bound.  One chain recommended, as there."""
         from .feedback import check_feedback_args, check_hidden_args, check_sector_args
         if self._slices is None:
             self.set_sub_batches(1)
@@ -676,7 +682,8 @@ class BatchedAuvEnv:
     def fresh_worlds(self, spec: "FreshWorlds"):
         """Switch to a fresh world on every reset (auv_fresh_worlds_create): builds the bank of depth * n_envs slots on the
         device from the counter-based draws of (seed, global environment index, serial) and resets every environment.
-        `spec.multi_step` also allows `step_multi` on the handle (see devgen.FreshWorlds for what is guaranteed there)."""
+        `spec.multi_step` also allows `step_multi` on the handle, `spec.closed_loop` with it `step_feedback` (see
+        devgen.FreshWorlds for what is guaranteed there)."""
         from . import devgen
         if not self._cfg_struct.auto_reset:
             raise ValueError("FreshWorlds needs auto_reset=True")
@@ -689,7 +696,7 @@ class BatchedAuvEnv:
                                             unit.ctypes.data_as(C.c_void_p), nseg.ctypes.data_as(C.c_void_p), len(nseg)),
                "auv_fresh_worlds_create")
         if spec.multi_step:
-            _check(_LIB.auv_fresh_worlds_multi(self._h, 1), "auv_fresh_worlds_multi")
+            _check(_LIB.auv_fresh_worlds_multi(self._h, 2 if spec.closed_loop else 1), "auv_fresh_worlds_multi")
         self._fresh = spec
         self._worlds_arg = None
         # the passes' stream: one that runs side by side with the caller's current stream (set_sub_batches picks again for chains)

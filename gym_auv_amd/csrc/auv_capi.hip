@@ -297,7 +297,7 @@ static void fw_disable(auv_handle* h) {
   free_pool(f.allocs);
   f.on = false;
   f.issued = f.calls = f.paced = 0;
-  f.multi = false, f.multi_call = 0;
+  f.multi = f.feedback = false, f.multi_call = 0;
   h->d.fw_state = nullptr, h->d.fw_serial = nullptr, h->d.fw_queue = nullptr, h->d.fw_ctl = nullptr, h->d.fw_cap = 0;
 }
 
@@ -762,7 +762,7 @@ int auv_fresh_worlds_create(auv_handle_t* h, int32_t depth, int32_t n_moving, in
   f.side_owned = true;
   for (int b = 0; b < auv_handle::Fresh::NEV; b++) HIP_TRY(hipEventCreateWithFlags(&f.pace[b], hipEventDisableTiming));
   f.issued = f.calls = f.paced = 0;
-  f.multi = false, f.multi_call = 0;
+  f.multi = f.feedback = false, f.multi_call = 0;
   {
     // the eight kernels of a pass as ONE graph: a pass costs the host one launch, not eight (every argument is a fixed
     // device buffer of this mode; what a pass works on it learns on the device)
@@ -825,7 +825,7 @@ int auv_fresh_worlds_multi(auv_handle_t* h, int32_t on) {
   if (!f.on) return fail(AUV_ESTATE, "auv_fresh_worlds_multi: auv_fresh_worlds_create first");
   if (on && f.depth < 3)
     return fail(AUV_EINVAL, "auv_fresh_worlds_multi: depth >= 3 (with %d slots an environment could not reset twice without re-use in a launch that has used its spare)", f.depth);
-  f.multi = on != 0;
+  f.multi = on != 0, f.feedback = on == 2;   // (2: the closed-loop entries too)
   return AUV_OK;
 }
 

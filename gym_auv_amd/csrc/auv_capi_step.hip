@@ -350,7 +350,8 @@ static int step_feedback_any(auv_handle_t* h, int32_t n_slices, const int32_t* b
   }
   if (actions_dev && n_slots < 1) return fail(AUV_EINVAL, "%s: n_slots >= 1 with a ring", who);
   if (!actions_dev) n_slots = 1, first_slot = 0, action_dtype = AUV_F32;               // no ring: x_7 = 0, nothing is read
-  const int rc = check_multi(h, n_slices, bounds, streams, actions_dev, action_dtype, n_slots, first_slot, n_steps, who, true, AUV_EINVAL);
+  // (a fresh world per reset: only where the handle has opted in for the closed loop too -- auv_fresh_worlds_multi(h, 2))
+  const int rc = check_multi(h, n_slices, bounds, streams, actions_dev, action_dtype, n_slots, first_slot, n_steps, who, true, AUV_EINVAL, h->fw.feedback);
   if (rc) return rc;
   if (!obs_dev || !reward_dev || !done_dev) return fail(AUV_EINVAL, "%s: null obs / reward / done buffer", who);
   const int D = auv_obs_cols(h->d.cfg, h->d.pool_ns);                                    // (see auv_step_multi_record)
@@ -361,15 +362,17 @@ static int step_feedback_any(auv_handle_t* h, int32_t n_slices, const int32_t* b
   PAIR_CHECK(h, obs_dev);
   const unsigned long long seq0 = h->multi_seq;
   h->multi_seq += (unsigned long long)n_steps;
+  const unsigned int call = fw_multi_call(h);
   for (int i = 0; i < n_slices; i++) {
     AuvDev d = h->d;
     d.e0 = bounds[i], d.ne = bounds[i + 1] - bounds[i];
+    fw_multi_begin(h, call, (hipStream_t)streams[i]);
     auv_launch_step_feedback(d, gains_dev, actions_dev, action_dtype, obs_dev, reward_dev, done_dev, obs_rec, reward_rec, done_rec, act_rec, n_steps,
                              first_slot, n_slots, seq0, h->multi_order, h->multi_lead, h->multi_lag, (hipStream_t)streams[i],
-                             sectors ? sector_gains_dev : nullptr, sectors ? sb : nullptr, hidden ? hidden_dev : nullptr, activation);
+                             sectors ? sector_gains_dev : nullptr, sectors ? sb : nullptr, hidden ? hidden_dev : nullptr, activation, call);
   }
   HIP_TRY(hipGetLastError());
-  return AUV_OK;
+  return fw_tick(h, n_slices, bounds, streams, n_steps, true);   // (as auv_step_multi)
 }
 
 int auv_step_feedback(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const double* gains_dev, const void* actions_dev,

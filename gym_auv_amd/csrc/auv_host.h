@@ -98,7 +98,8 @@ struct auv_handle {
     hipEvent_t pace[NEV];
     unsigned long long issued = 0, calls = 0, paced = 0;   // passes enqueued, step calls counted, pacing events handed out
     bool multi = false;                       // auv_fresh_worlds_multi: launches of several steps allowed (k_fresh_multi / k_fresh_record)
-    unsigned int multi_call = 0;              // multi-step calls so far: the number the next one's launches carry is this + 1
+    bool feedback = false;                    // auv_fresh_worlds_multi(h, 2): the closed-loop entries too (k_fresh_feedback and its siblings)
+    unsigned int multi_call = 0;             // multi-step calls so far: the number the next one's launches carry is this + 1
     hipGraphExec_t pass_exec = nullptr;       // the pass as ONE graph launch (captured at create)
     hipGraph_t pass_graph = nullptr;
   } fw;

@@ -42,7 +42,7 @@ void auv_launch_step_record(const AuvDev& d, const void* actions, int dtype, flo
 void auv_launch_step_feedback(const AuvDev& d, const double* gains, const void* actions, int dtype, float* obs, float* reward, uint8_t* done, float* obs_rec,
                               float* reward_rec, uint8_t* done_rec, double* act_rec, int n_steps, int first_slot, int n_slots, unsigned long long seq0,
                               int order, int lead, int lag, hipStream_t st, const double* sector_gains, const int32_t* sector_bounds,
-                              const double* hidden, int activation);
+                              const double* hidden, int activation, unsigned int fw_call = 0u);
 void auv_launch_spin(unsigned long long ticks, hipStream_t st);
 void auv_launch_rdv_publish(unsigned long long* word, unsigned long long seq, hipStream_t st);
 void auv_launch_rdv_arrive(unsigned long long* word, hipStream_t st);

@@ -622,8 +622,8 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_roles(AuvD
 //     step t + 1's.
 // Bitwise the same as T launches of k_step_roles (tests/test_gpu_multi.py).  With a fresh world per reset a slot's tables may be
 // rebuilt beside the launch, and only the binding STEP reads them coherently: these kernels are refused there, and k_fresh_multi /
-// k_fresh_record (the same body, STEP_MULTI_FW) bind only slots published before their call began (auv_device.h:
-// auv_next_world_multi).
+// k_fresh_record (the same body, STEP_MULTI_FW; closed loop: k_fresh_feedback and its two siblings) bind only slots published before
+// their call began (auv_device.h: auv_next_world_multi).
 #define CARRY_WORDS 24
 // The second mark covers words 8..19, which lie in two 64-byte lines that are stored and loaded separately, so a reader CAN see
 // the old words 8..15 beside the new words 16..20.  A plain xor of the words lets that pass whenever the changes of two words
@@ -900,7 +900,8 @@ __device__ __forceinline__ double2 fb_hidden(const double2 a, const double x, co
 // step's action by the feedback law and hands it over in words 21..23 of the carry record (fb_gains: [N][2][8]; fb_actions / fb_slot:
 // the ring and the next step's slot, or nullptr; FB >= 2: fb_sgains, [N][2][16], and fb_sb, the sector bounds; FB 3: fb_hidden,
 // [N][16][28], and fb_activation)
-// FW (k_fresh_multi / k_fresh_record): a fresh world per reset.  The reset takes the environment's next slot only if it was published
+// FW (k_fresh_multi / k_fresh_record; with FB: k_fresh_feedback / _sector_feedback / _hidden_feedback, the argument at those
+// kernels): a fresh world per reset.  The reset takes the environment's next slot only if it was published
 // before this call began (auv_next_world_multi with `fw_call`, else the world just left, counted), binds it through the coherent
 // restore_env and hands the descriptor of the slot it actually took on in the carry record; the episode log's world column is
 // environment + N * serial of the world the carry record names.
@@ -1287,6 +1288,77 @@ __global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_step_hidden_fee
 #undef STEP_MULTI_REC
 }
 
+// The closed-loop launches on a fresh world per reset (auv_fresh_worlds_multi(h, 2)): the three kernels above with the gated slot
+// choice of k_fresh_record (STEP_MULTI_FB 1 / 2 / 3 with STEP_MULTI_FW 1), `fw_call` last.  Three further inclusions of the body: the
+// other ten kernels of this file keep their argument lists and their code.
+// Why the action handed over at a reset step is the law of the world actually bound -- with nothing added to what FB and FW each
+// already rely on (roles_finish_wave_multi<true, FB, 1>):
+//   * the restore loop writes the environment's OBS64 row -- all 6 + S columns -- from the reset row of slot w2, which is what
+//     auv_next_world_multi returned: the next slot if it was published before this call began, else (counted) the world just left.
+//     restore_env<true, true> reads that reset row with agent-scope loads in either case; the stores are THIS wave's;
+//   * auv_stores_done() stands between the restore loop and the FB block, and the FB block reads x_0..5 (FB >= 2: the closeness
+//     columns too) back from that row with agent-scope loads past L1 -- the argument of the cycling bank's closed loop, which does
+//     not ask where the restore took the row from.  Without a reset the row is the tail's and the sweep's, as there;
+//   * the carry record's descriptor words are auv_make_desc<true>(w_next), w_next = w2 of the group whose environment was restored:
+//     the next step's sweep, search and finish waves read the tables of the slot whose reset row the action was formed from, and a
+//     slot taken has a stamp below this call's number, so plain loads of its tables are sound for the rest of the launch
+//     (auv_next_world_multi);
+//   * words 21..23 carry the action and a mark mixed with the step's number as before; the dynamics wave accepts the record only
+//     when both marks are the previous step's.  Step 0 forms the law from the arrays behind the kernel boundary, as before.
+__global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_fresh_feedback(AuvDev dk, const void* __restrict__ actions, float* __restrict__ obs_out,
+                                                                               float* __restrict__ reward_out, uint8_t* __restrict__ done_out,
+                                                                               const int n_steps, const int first_slot, const int n_slots,
+                                                                               const unsigned long long seq0, const int lead_dyn, const int lag_fin, const unsigned magic_c,
+                                                                               const unsigned long long obs_stride, const unsigned long long reward_stride,
+                                                                               const unsigned long long done_stride, const double* __restrict__ gains,
+                                                                               double* __restrict__ act_rec, const unsigned int fw_call) {
+  AUV_KERNARG_DESC(d);
+#define STEP_MULTI_REC 1
+#define STEP_MULTI_FB 1
+#define STEP_MULTI_FW 1
+#include "k_step_multi_body.inc"
+#undef STEP_MULTI_FW
+#undef STEP_MULTI_FB
+#undef STEP_MULTI_REC
+}
+
+__global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_fresh_sector_feedback(AuvDev dk, const void* __restrict__ actions, float* __restrict__ obs_out,
+                                                                                       float* __restrict__ reward_out, uint8_t* __restrict__ done_out,
+                                                                                       const int n_steps, const int first_slot, const int n_slots,
+                                                                                       const unsigned long long seq0, const int lead_dyn, const int lag_fin, const unsigned magic_c,
+                                                                                       const unsigned long long obs_stride, const unsigned long long reward_stride,
+                                                                                       const unsigned long long done_stride, const double* __restrict__ gains,
+                                                                                       double* __restrict__ act_rec, const double* __restrict__ sgains,
+                                                                                       const FbBounds sb, const unsigned int fw_call) {
+  AUV_KERNARG_DESC(d);
+#define STEP_MULTI_REC 1
+#define STEP_MULTI_FB 2
+#define STEP_MULTI_FW 1
+#include "k_step_multi_body.inc"
+#undef STEP_MULTI_FW
+#undef STEP_MULTI_FB
+#undef STEP_MULTI_REC
+}
+
+__global__ void __launch_bounds__(AUV_WAVE, AUV_K23_MIN_WAVES) k_fresh_hidden_feedback(AuvDev dk, const void* __restrict__ actions, float* __restrict__ obs_out,
+                                                                                       float* __restrict__ reward_out, uint8_t* __restrict__ done_out,
+                                                                                       const int n_steps, const int first_slot, const int n_slots,
+                                                                                       const unsigned long long seq0, const int lead_dyn, const int lag_fin, const unsigned magic_c,
+                                                                                       const unsigned long long obs_stride, const unsigned long long reward_stride,
+                                                                                       const unsigned long long done_stride, const double* __restrict__ gains,
+                                                                                       double* __restrict__ act_rec, const double* __restrict__ sgains,
+                                                                                       const FbBounds sb, const double* __restrict__ hidden, const int activation,
+                                                                                       const unsigned int fw_call) {
+  AUV_KERNARG_DESC(d);
+#define STEP_MULTI_REC 1
+#define STEP_MULTI_FB 3
+#define STEP_MULTI_FW 1
+#include "k_step_multi_body.inc"
+#undef STEP_MULTI_FW
+#undef STEP_MULTI_FB
+#undef STEP_MULTI_REC
+}
+
 // Behind a closed-loop launch: k_record_last where any of the three records may be missing (a missing one was written in place)
 __global__ void __launch_bounds__(256) k_feedback_last(const float* __restrict__ obs_last, const float* __restrict__ reward_last,
                                                        const uint8_t* __restrict__ done_last, float* __restrict__ obs, float* __restrict__ reward,
@@ -1530,11 +1602,12 @@ void auv_launch_step_record(const AuvDev& d0, const void* actions, int dtype, fl
 // the closed-loop form: the record launch with the gain table, an optional ring and an optional action record; each of the three
 // output records may be missing (that output's every step then goes to obs / reward / done, and nothing is copied for it)
 // (sector_gains / sector_bounds: nullptr, or [N][2][16] fp64 and the table of 17 -- k_step_sector_feedback is launched instead;
-// hidden: nullptr, or with those two the [N][16][28] fp64 block and `activation` -- k_step_hidden_feedback)
+// hidden: nullptr, or with those two the [N][16][28] fp64 block and `activation` -- k_step_hidden_feedback; fw_call != 0: the
+// k_fresh_* kernel of the same law)
 void auv_launch_step_feedback(const AuvDev& d0, const double* gains, const void* actions, int dtype, float* obs, float* reward, uint8_t* done,
                               float* obs_rec, float* reward_rec, uint8_t* done_rec, double* act_rec, int n_steps, int first_slot, int n_slots,
                               unsigned long long seq0, int order, int lead, int lag, hipStream_t st, const double* sector_gains,
-                              const int32_t* sector_bounds, const double* hidden, int activation) {
+                              const int32_t* sector_bounds, const double* hidden, int activation, unsigned int fw_call) {
   AuvDev d = d0;
   d.act_f64 = dtype == AUV_F64;
   d.ring_slots = 1;
@@ -1543,22 +1616,35 @@ void auv_launch_step_feedback(const AuvDev& d0, const double* gains, const void*
   const dim3 grid((unsigned)auv_multi_grid(g)), block(AUV_WAVE);
   const int D = auv_obs_cols(d.cfg, d.pool_ns);
   const unsigned long long n = (unsigned long long)d.n, obs_stride = obs_rec ? n * (unsigned long long)D : 0ull;
+  // fw_call != 0: a fresh world per reset, this launch belongs to multi-step call number fw_call (as auv_launch_step_record)
+  float* const o = obs_rec ? obs_rec : obs;
+  float* const r = reward_rec ? reward_rec : reward;
+  uint8_t* const dn = done_rec ? done_rec : done;
+  const unsigned long long rs = reward_rec ? n : 0ull, ds = done_rec ? n : 0ull;
   if (hidden) {
     FbBounds sb;
     for (int i = 0; i < 17; i++) sb.b[i] = sector_bounds[i];
-    hipLaunchKernelGGL(k_step_hidden_feedback, grid, block, lds, st, d, actions, obs_rec ? obs_rec : obs, reward_rec ? reward_rec : reward,
-                       done_rec ? done_rec : done, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic, obs_stride, reward_rec ? n : 0ull,
-                       done_rec ? n : 0ull, gains, act_rec, sector_gains, sb, hidden, activation);
+    if (fw_call)
+      hipLaunchKernelGGL(k_fresh_hidden_feedback, grid, block, lds, st, d, actions, o, r, dn, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic,
+                         obs_stride, rs, ds, gains, act_rec, sector_gains, sb, hidden, activation, fw_call);
+    else
+      hipLaunchKernelGGL(k_step_hidden_feedback, grid, block, lds, st, d, actions, o, r, dn, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic,
+                         obs_stride, rs, ds, gains, act_rec, sector_gains, sb, hidden, activation);
   } else if (sector_gains) {
     FbBounds sb;
     for (int i = 0; i < 17; i++) sb.b[i] = sector_bounds[i];
-    hipLaunchKernelGGL(k_step_sector_feedback, grid, block, lds, st, d, actions, obs_rec ? obs_rec : obs, reward_rec ? reward_rec : reward,
-                       done_rec ? done_rec : done, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic, obs_stride, reward_rec ? n : 0ull,
-                       done_rec ? n : 0ull, gains, act_rec, sector_gains, sb);
+    if (fw_call)
+      hipLaunchKernelGGL(k_fresh_sector_feedback, grid, block, lds, st, d, actions, o, r, dn, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic,
+                         obs_stride, rs, ds, gains, act_rec, sector_gains, sb, fw_call);
+    else
+      hipLaunchKernelGGL(k_step_sector_feedback, grid, block, lds, st, d, actions, o, r, dn, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic,
+                         obs_stride, rs, ds, gains, act_rec, sector_gains, sb);
+  } else if (fw_call) {
+    hipLaunchKernelGGL(k_fresh_feedback, grid, block, lds, st, d, actions, o, r, dn, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic, obs_stride,
+                       rs, ds, gains, act_rec, fw_call);
   } else {
-    hipLaunchKernelGGL(k_step_feedback, grid, block, lds, st, d, actions, obs_rec ? obs_rec : obs, reward_rec ? reward_rec : reward,
-                       done_rec ? done_rec : done, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic, obs_stride, reward_rec ? n : 0ull,
-                       done_rec ? n : 0ull, gains, act_rec);
+    hipLaunchKernelGGL(k_step_feedback, grid, block, lds, st, d, actions, o, r, dn, n_steps, first_slot, n_slots, seq0, g.lead, g.lag, g.magic, obs_stride,
+                       rs, ds, gains, act_rec);
   }
   if (!obs_rec && !reward_rec && !done_rec) return;
   const size_t last = (size_t)(n_steps - 1), items = (size_t)d.ne * (size_t)(obs_rec ? D : 1);
@@ -1603,6 +1689,12 @@ hipError_t auv_step_fused_prepare(const AuvDev& d) {
   e = hipFuncSetAttribute((const void*)k_step_sector_feedback, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
   if (e != hipSuccess) return e;
   e = hipFuncSetAttribute((const void*)k_step_hidden_feedback, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute((const void*)k_fresh_feedback, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute((const void*)k_fresh_sector_feedback, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  if (e != hipSuccess) return e;
+  e = hipFuncSetAttribute((const void*)k_fresh_hidden_feedback, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
   if (e != hipSuccess) return e;
   return hipFuncSetAttribute((const void*)k_step_roles, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
 }

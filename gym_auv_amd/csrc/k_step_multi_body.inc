@@ -12,6 +12,9 @@
 //   STEP_MULTI_FW 1    k_fresh_multi / k_fresh_record (REC 0 / 1, FB 0)  a fresh world per reset: the finish wave's reset binds the
 //                      environment's next slot only if it was published before this call began (auv_next_world_multi).  Further
 //                      parameter: fw_call, the call's number.  (Not defined by the other inclusions: `#if` reads it as 0.)
+//   STEP_MULTI_FB 1 / 2 / 3 with STEP_MULTI_FW 1   k_fresh_feedback / k_fresh_sector_feedback / k_fresh_hidden_feedback (REC 1): the
+//                      closed-loop launch on a fresh world per reset; the closed-loop kernel's parameters, then fw_call.  The finish
+//                      role's branches for them stand in front of the others, whose text is as it was.
 // The includer has declared `d` (AUV_KERNARG_DESC) and the kernel's parameters: actions, obs_out, reward_out, done_out, n_steps,
 // first_slot, n_slots, seq0, lead_dyn, lag_fin, magic_c -- and, recording, obs_stride, reward_stride, done_stride (elements; 0: no
 // record of that output).  The record's offset is wave-uniform (the step is, the strides are kernel arguments): 64-bit scalar
@@ -254,7 +257,16 @@
     const bool fst = fer < ne && lane % K1_GROUP == 0;
 #endif
     MSTAMP_IF(fst, d.e0 + fer, 13);
-#if STEP_MULTI_FB == 3
+#if STEP_MULTI_FB == 3 && STEP_MULTI_FW
+    roles_finish_wave_multi<true, 3, 1>(d, f, lane, obs_out, reward_out, done_out, step, step == n_steps - 1, tagmix, tagmix_prev MSTAMP_ARG, gains,
+                                        actions, (first_slot + step + 1) % n_slots, sgains, &sb, hidden, activation, fw_call);
+#elif STEP_MULTI_FB == 2 && STEP_MULTI_FW
+    roles_finish_wave_multi<true, 2, 1>(d, f, lane, obs_out, reward_out, done_out, step, step == n_steps - 1, tagmix, tagmix_prev MSTAMP_ARG, gains,
+                                        actions, (first_slot + step + 1) % n_slots, sgains, &sb, nullptr, 0, fw_call);
+#elif STEP_MULTI_FB && STEP_MULTI_FW
+    roles_finish_wave_multi<true, 1, 1>(d, f, lane, obs_out, reward_out, done_out, step, step == n_steps - 1, tagmix, tagmix_prev MSTAMP_ARG, gains,
+                                        actions, (first_slot + step + 1) % n_slots, nullptr, nullptr, nullptr, 0, fw_call);
+#elif STEP_MULTI_FB == 3
     roles_finish_wave_multi<true, 3>(d, f, lane, obs_out, reward_out, done_out, step, step == n_steps - 1, tagmix, tagmix_prev MSTAMP_ARG, gains,
                                      actions, (first_slot + step + 1) % n_slots, sgains, &sb, hidden, activation);
 #elif STEP_MULTI_FB == 2

@@ -18,7 +18,7 @@ torch generator on the device).
 """
 import functools
 import math
-from dataclasses import dataclass
+from dataclasses import InitVar, dataclass
 from typing import Tuple
 
 import numpy as np
@@ -54,7 +54,12 @@ class FreshWorlds:
     they had just finished because the pass fell behind (0 when depth / period / batch_cap fit the turn-over rate).
 
     `multi_step=True` (auv_fresh_worlds_multi; needs depth >= 3, else ValueError) also allows `step_multi` -- several steps per
-    launch, with or without a record; the closed-loop `step_feedback` stays refused.  Guaranteed there: a launch binds only slots
+    launch, with or without a record; `closed_loop=True` (with multi_step=True, else ValueError; auv_fresh_worlds_multi(h, 2)) also
+    allows the closed-loop `step_feedback`, all three law kinds: the action of the step after a reset is the law of the reset row
+    of the world the reset actually bound, a counted re-use included.  Without it `step_feedback` is refused ("fresh world").
+    (A closed loop that starts over in the world it has just left repeats the episode it has just had, so where the passes fall
+    behind, re-use breeds re-use: size `batch_cap` to the turn-over and watch `reused` -- profiles/feedback_fresh/README.md.)
+    Guaranteed in both: a launch binds only slots
     that were rebuilt AND published before any kernel of its call began (its later steps read the tables with plain loads), the
     world of an environment's k-th episode is still the world of (seed, global index, k), and an environment whose next slot
     does not qualify starts over in the world it has just left, counted in `reused` -- never silently.  Every call counts its
@@ -72,8 +77,15 @@ class FreshWorlds:
     batch_cap: int = 64
     period: int = 16         # (a pass takes ~0.3 ms whatever it holds: fewer, fuller passes cost the chains less)
     multi_step: bool = False
+    # init-only, kept as a plain attribute: the record of fields (dataclasses.asdict, repr, ==) stays the one earlier callers know;
+    # name it again in dataclasses.replace() (whether an init-only value is carried over depends on the Python version)
+    closed_loop: InitVar[bool] = False
 
-    def __post_init__(self):
+    def __post_init__(self, closed_loop=False):
+        object.__setattr__(self, "closed_loop", bool(closed_loop))
+        if self.closed_loop and not self.multi_step:
+            raise ValueError("FreshWorlds(closed_loop=True) needs multi_step=True: the closed loop runs in launches of several steps "
+                             "and binds worlds by their rule")
         if self.multi_step and self.depth < 3:
             raise ValueError("FreshWorlds(multi_step=True) needs depth >= 3, got %d: with two slots an environment could never "
                              "reset without re-use inside a launch that has already used its spare" % self.depth)

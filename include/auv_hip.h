@@ -601,9 +601,12 @@ int auv_fresh_worlds_refill(auv_handle_t* h, int32_t n_slices, const int32_t* bo
  * caller's; it must outlive the mode.                                                                              */
 int auv_fresh_worlds_set_stream(auv_handle_t* h, void* stream);
 /* Launches of SEVERAL steps with a fresh world on every reset.  auv_step_multi / auv_step_multi_record refuse this mode ("not with a
- * fresh world per reset") until the handle opts in here; the closed-loop entries (auv_step_feedback*) refuse it either way.
+ * fresh world per reset") until the handle opts in here; the closed-loop entries (auv_step_feedback, _sectors, _hidden) refuse it
+ * (AUV_EINVAL) unless the handle opts in with on == 2, which allows them as well as the two open-loop calls (on == 1: those two only).
  * on != 0 needs depth >= 3 (AUV_EINVAL) and the mode itself (AUV_ESTATE); auv_fresh_worlds_create switches it off again.
- * What an opted-in handle does in those two calls:
+ * A closed-loop launch of an on == 2 handle forms the action of the step after a reset from the reset row of the slot the reset
+ * actually took -- the next slot, or in a counted re-use the world just left -- and everything below holds for it unchanged.
+ * What an opted-in handle does in those calls:
  *   - the steps of a launch read a bound slot's tables with plain loads and no kernel boundary in between, so a launch binds ONLY
  *     slots that were published before any kernel of its call began: every call has a number, a one-wave kernel in front of each
  *     chain's launch announces it on the device, the pass's last kernel stamps every slot it publishes with the latest number

@@ -22,7 +22,13 @@ measures, in the same alternating passes,
                            units over its 24 inputs (auv_step_feedback_hidden; per-environment N(0, 0.3) weights, every entry non-zero)
     (f) per_step_hidden    one step() per step with the same law as torch ops on env.obs (float32: a gather and a maximum for the
                            sector inputs, two matrix products for the layer)
-and writes the rows to feedback_hidden_bench.jsonl and the ranges, b / a and the verdict to README.md under --out."""
+and writes the rows to feedback_hidden_bench.jsonl and the ranges, b / a and the verdict to README.md under --out.
+    python tools/feedback_bench.py --fresh-worlds [--depth 3] [--batch-cap 256] [--out profiles/feedback_fresh]
+measures on the generator's moving28 worlds (17 movers + 11 circles), in the same alternating passes, the open-loop launch and the
+three closed-loop launches (affine, sectors, hidden) each on a cycling bank of 2 N generated worlds and -- `fresh_` -- on a handle
+with a fresh world on every reset (FreshWorlds(depth, multi_step=True, closed_loop=True, batch_cap), one chain), and `per_step_fresh`: one step()
+per step on that handle with the affine law as torch ops.  Fresh rows carry the re-uses counted during their timed pass; a census
+behind the passes counts the episodes of `--steps` steps.  Writes feedback_fresh_bench_depth<D>.jsonl and .md under --out."""
 import argparse
 import hashlib
 import json
@@ -48,13 +54,24 @@ ap.add_argument("--envs", type=int, default=4096)
 ap.add_argument("--steps", type=int, default=1920)
 ap.add_argument("--passes", type=int, default=5)
 ap.add_argument("--launch", type=int, default=64)
+ap.add_argument("--fresh-worlds", action="store_true", help="measure the closed-loop launches on a fresh world per reset (moving28) against a cycling bank")
+ap.add_argument("--depth", type=int, default=3, help="--fresh-worlds: bank slots per environment")
+ap.add_argument("--batch-cap", type=int, default=256, help="--fresh-worlds: worlds per refill pass at most (profiles/multi_fresh: 256)")
 args = ap.parse_args()
 if args.out is None:
     args.out = "profiles/feedback_hidden" if args.hidden else ("profiles/feedback_sectors" if args.sectors else "profiles/feedback")
+    if args.fresh_worlds:
+        args.out = "profiles/feedback_fresh"
 dev = torch.device("cuda:0")
 n, T, steps = args.envs, args.launch, args.steps
 cfg = effective_reference_config(use_lidar=True)
-bank = build_bank_parallel("polygon_world", 1000 + np.arange(2 * n), procs=16, n_polygons=50)
+if args.fresh_worlds:
+    # moving28 (17 movers, 11 circles: the generator's worlds) on both handles: a cycling bank of 2 N generated worlds, and a fresh
+    # world on every reset with the closed loop allowed
+    from gym_auv_amd.devgen import FreshWorlds, GeneratedWorlds  # noqa: E402
+    bank = GeneratedWorlds(2 * n, seed=0)
+else:
+    bank = build_bank_parallel("polygon_world", 1000 + np.arange(2 * n), procs=16, n_polygons=50)
 ring = torch.rand((T, n, 2), device=dev) * torch.tensor([2.0, 0.3], device=dev) - torch.tensor([1.0, 0.15], device=dev)
 g_np = los_gains(0.7, 0.8, 0.4, 0.5)
 gains = torch.as_tensor(np.broadcast_to(g_np, (n, 2, 8)).copy(), device=dev)
@@ -93,7 +110,7 @@ def feedback_sectors(m):
 # (e): one block per environment (the parameter traffic of a population), every entry non-zero
 _rs = np.random.RandomState(7)
 W1_np, b1_np, V_np = _rs.normal(0, 0.3, (n, 16, 24)), _rs.normal(0, 0.3, (n, 16)), _rs.normal(0, 0.05, (n, 2, 16))
-hidden = torch.as_tensor(pack_hidden(W1_np, b1_np, V_np), device=dev) if args.hidden else None
+hidden = torch.as_tensor(pack_hidden(W1_np, b1_np, V_np), device=dev) if (args.hidden or args.fresh_worlds) else None
 
 
 def feedback_hidden(m):
@@ -136,12 +153,32 @@ if args.sectors:
     FORMS = (("feedback", feedback), ("feedback_sectors", feedback_sectors))
 if args.hidden:
     FORMS = (("feedback_sectors", feedback_sectors), ("feedback_hidden", feedback_hidden), ("per_step_hidden", per_step_hidden))
+fre = None
+if args.fresh_worlds:
+    # every form on the cycling bank (`cyc`: the launches as they were) and on the fresh-world handle (`fre`), one after the other in
+    # every pass; the forms above step the global `env`, so a form is bound to its handle by naming it there
+    cyc = env
+    fre = BatchedAuvEnv(cfg, FreshWorlds(depth=args.depth, multi_step=True, closed_loop=True, batch_cap=args.batch_cap), n, device=dev, auto_reset=True)
+    fre.reset()
+    fre.set_sub_batches(1)
+
+    def on(handle, run):
+        def bound(m):
+            global env
+            env = handle
+            run(m)
+        return bound
+
+    FORMS = tuple((prefix + name, on(handle, run)) for name, run in (("open_loop", open_loop), ("feedback", feedback),
+                                                                      ("feedback_sectors", feedback_sectors), ("feedback_hidden", feedback_hidden))
+                  for prefix, handle in (("", cyc), ("fresh_", fre))) + (("per_step_fresh", on(fre, per_step)),)
 sha = hashlib.sha256(open(_capi.LIB_PATH, "rb").read()).hexdigest()
 rows = []
 for p in range(args.passes):
     for name, run in FORMS:
         run(steps // 2)
         torch.cuda.synchronize()
+        reused0 = fre.fresh_stats()["reused"] if fre is not None else 0
         t0 = time.perf_counter()
         run(steps)
         torch.cuda.synchronize()
@@ -149,8 +186,43 @@ for p in range(args.passes):
         row = dict(form=name, pass_=p, envs=n, beams=env.n_sensors, steps=steps, steps_per_launch=1 if name.startswith("per_step") else T,
                    rate_M=round(n * steps / dt / 1e6, 2), us_per_step=round(1e6 * dt / steps, 2), health=env.health(), lib_sha256=sha,
                    command=" ".join(sys.argv))
+        if fre is not None and env is fre:
+            row["reused"] = fre.fresh_stats()["reused"] - reused0
         rows.append(row)
         print(json.dumps(row), flush=True)
+if fre is not None:
+    # episodes per `steps` steps of the fresh closed loop (hidden law), counted beside the timed passes: the done record summed on
+    # the device behind the chain, read once at the end
+    fre.episode_log()
+    ep = torch.zeros((), dtype=torch.int64, device=dev)
+    reused0 = fre.fresh_stats()["reused"]
+    for i in range(0, steps, T):
+        _, _, dn = fre.step_feedback(gains, T, record="reward", sector_gains=sector_gains, hidden=hidden)
+        fre._join_chains()
+        ep += dn.sum()
+    torch.cuda.synchronize()
+    census = dict(form="census_fresh_feedback_hidden", depth=args.depth, steps=steps, episodes=int(ep), reused=fre.fresh_stats()["reused"] - reused0,
+                  fresh_stats=fre.fresh_stats(), health=fre.health(), lib_sha256=sha, command=" ".join(sys.argv))
+    rows.append(census)
+    print(json.dumps(census), flush=True)
+    cyc.close(), fre.close()
+    os.makedirs(args.out, exist_ok=True)
+    with open(os.path.join(args.out, "feedback_fresh_bench_depth%d.jsonl" % args.depth), "w") as f:
+        for r in rows:
+            f.write(json.dumps(r) + "\n")
+    med = lambda v: sorted(v)[len(v) // 2]
+    with open(os.path.join(args.out, "feedback_fresh_bench_depth%d.md" % args.depth), "w") as f:
+        f.write("`python %s`: %d environments x %d beams, moving28, one chain, %d steps per launch, depth %d, batch_cap %d; %d alternating passes over %d "
+                "steps.  Library sha256 `%s`.\n\n| form | M env-steps/s per pass | median | min | max | reused per pass |\n|---|---|---|---|---|---|\n"
+                % (" ".join(sys.argv), n, cyc.n_sensors, T, args.depth, args.batch_cap, args.passes, steps, sha))
+        for name, _ in FORMS:
+            v = [r["rate_M"] for r in rows if r["form"] == name]
+            ru = [str(r["reused"]) for r in rows if r["form"] == name and "reused" in r]
+            f.write("| %s | %s | %.1f | %.1f | %.1f | %s |\n" % (name, ", ".join("%.1f" % x for x in v), med(v), min(v), max(v), ", ".join(ru) or "-"))
+        f.write("\nfresh / cycling, medians: %s.\n\nCensus (hidden law, %d steps): %d episodes, %d re-used.\n"
+                % ("; ".join("%s %.3f" % (k, med([r["rate_M"] for r in rows if r["form"] == "fresh_" + k]) / med([r["rate_M"] for r in rows if r["form"] == k]))
+                             for k in ("open_loop", "feedback", "feedback_sectors", "feedback_hidden")), steps, census["episodes"], census["reused"]))
+    sys.exit(0)
 env.close()
 
 os.makedirs(args.out, exist_ok=True)
