@@ -152,7 +152,7 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
           task="colav", step_mode=None, graph_rollout=False, sub_batches=4, minibatches=32,
           reward_scale=0.01, reward_clip=0.0, min_cumulative_reward=None, act_space="raw", ret_norm=False, orthogonal=False, ent_coef=0.01, log_std=-0.5, lr=2e-4,
           fused_policy=True, graph_update=False, policy_bf16=False, feasibility_pooling=False, fused_update=False, net_arch=(256, 128, 64),
-          fused_bootstrap=False, frames=1):
+          fused_bootstrap=False, frames=1, normalize="none"):
     from gym_auv_amd import distributed as D
     from gym_auv_amd.batched_env import BatchedAuvEnv
     from gym_auv_amd.config import effective_reference_config
@@ -221,6 +221,17 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
     gamma, lam, clip, epochs, n_mb = 0.999, 0.98, 0.2, 4, int(minibatches)
     ret_mean, ret_std = torch.zeros((), device=device), torch.ones((), device=device)
     T, Dobs = int(rollout), frames * env.obs_dim
+    # --normalize: running statistics of the observations and / or of the discounted return (gym_auv_amd/normalize.py; what
+    # stable-baselines ships as VecNormalize), frozen during a rollout and folded behind it.  "reward" / "both": the return pass scales
+    # and clips the stored rewards, in the place of the hand clamp (--reward-clip) and --reward-scale
+    norm = None
+    if normalize != "none":
+        if not fused_policy:
+            raise ValueError("--normalize %s needs --fused-policy 1: the rows are normalised by the fused policy launch" % normalize)
+        from gym_auv_amd.normalize import RunningNorm
+        norm = RunningNorm(env.obs_dim, gamma, norm_obs=normalize in ("obs", "both"), norm_reward=normalize in ("reward", "both"))
+        if norm.norm_reward:
+            reward_scale, reward_clip = 1.0, 0.0
     env.reset()
     act_buf = torch.zeros((envs, 2), device=device)
     # per-chain rollout storage, written inside the chain's step at a device-side position
@@ -261,7 +272,7 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
         from gym_auv_amd.policy import FusedActorCritic
         fused = FusedActorCritic(net, env, rollout=T, reward_scale=reward_scale, reward_clip=reward_clip, act_mid=a_mid.tolist(),
                                  act_half=a_half.tolist(), clip_lo=c_lo.tolist(), clip_hi=c_hi.tolist(), seed=1000 * seed + rank,
-                                 bf16=policy_bf16, frames=frames)
+                                 bf16=policy_bf16, frames=frames, normalize=norm)
         graph_rollout = False
     graphs = None
     if graph_rollout:
@@ -337,6 +348,8 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
         with torch.no_grad():
             if fused is not None:
                 O, A, LP, V, R, Dn = fused.buffers()
+                if norm is not None:
+                    norm.returns(R, Dn)                   # returns into their moments, R scaled in place (this stream waits on every chain)
                 V = V * ret_std + ret_mean
             else:
                 O = torch.cat([b["O"] for b in buf], 1)
@@ -345,13 +358,15 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
                 V = torch.cat([b["V"] for b in buf], 1) * ret_std + ret_mean        # value head predicts normalised returns
                 R = torch.cat([b["R"] for b in buf], 1)
                 Dn = torch.cat([b["Dn"] for b in buf], 1)
-            if (fused_bootstrap or frames > 1) and fused is not None:      # (frames > 1: the bootstrap row is a stacked row, peeked)
+            if (fused_bootstrap or frames > 1 or (norm is not None and norm.norm_obs)) and fused is not None:      # (frames > 1: the bootstrap row is a stacked row, peeked)
                 # the bootstrap value through the fused critic (one launch, FusedActorCritic.value): the weights the rollout used
                 last_v = fused.value() * ret_std + ret_mean
             else:
                 last_v = net.v(env.obs).squeeze(-1) * ret_std + ret_mean
             if fused is not None:
                 adv, RET = fused.gae(V, last_v, gamma, lam)            # one launch (auv_gae) instead of T x 6 small ones
+                if norm is not None:
+                    norm.fold()                           # (behind the bootstrap value: it is taken under the table the rollout ran on)
             else:
                 adv = torch.zeros_like(R)
                 gae = torch.zeros(envs, device=device)
@@ -564,6 +579,9 @@ if __name__ == "__main__":
                          "0 (default): the torch module")
     ap.add_argument("--frames", type=int, default=1,
                     help="k > 1: the policy sees the last k observations as one row of k * obs_dim columns (frame stacking; needs --fused-policy 1)")
+    ap.add_argument("--normalize", default="none", choices=["none", "obs", "reward", "both"],
+                    help="running normalisation of observations and / or rewards (VecNormalize; gym_auv_amd/normalize.py), folded between "
+                         "rollouts; 'reward' / 'both' replace --reward-clip and --reward-scale by the return pass; needs --fused-policy 1")
     ap.add_argument("--net-arch", default="256,128,64", metavar="H1,H2,H3",
                     help="hidden widths of the policy and the value net; with --fused-policy 1 one of 256,128,64 (the reference's) "
                          "128,128,64  128,64,64  64,64,64; --fused-update 1 takes the same list")
@@ -585,4 +603,4 @@ if __name__ == "__main__":
           sub_batches=a.sub_batches, minibatches=a.minibatches, act_space=a.act_space, ret_norm=bool(a.ret_norm),
           orthogonal=bool(a.orthogonal), ent_coef=a.ent_coef, log_std=a.log_std, lr=a.lr, reward_clip=a.reward_clip,
           min_cumulative_reward=a.min_cumulative_reward, feasibility_pooling=bool(a.feasibility_pooling), fused_update=bool(a.fused_update), net_arch=tuple(int(h) for h in a.net_arch.split(",")),
-          fused_bootstrap=bool(a.fused_bootstrap), frames=a.frames)
+          fused_bootstrap=bool(a.fused_bootstrap), frames=a.frames, normalize=a.normalize)

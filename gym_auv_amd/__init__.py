@@ -20,4 +20,8 @@ def __getattr__(name):
     if name == "PolicyPopulation":
         from .population import PolicyPopulation
         return PolicyPopulation
+    # RunningNorm: running observation / reward normalisation for the fused rollout (normalize.py; the library is loaded by its launches)
+    if name == "RunningNorm":
+        from .normalize import RunningNorm
+        return RunningNorm
     raise AttributeError("module %r has no attribute %r" % (__name__, name))

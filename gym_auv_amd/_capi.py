@@ -154,6 +154,12 @@ class AuvPolicyStack(C.Structure):
 MAX_FRAMES = 8
 
 
+class AuvPolicyNorm(C.Structure):
+    """== auv_policy_norm_t (include/auv_hip.h): a policy launch that normalises its rows (auv_policy_act_norm / _rollout_norm)"""
+    _fields_ = [("io", AuvPolicyIO), ("table", C.c_void_p), ("part", C.c_void_p), ("pcnt", C.c_void_p), ("part_ld", C.c_int32),
+                ("part_base", C.c_int32), ("clip_obs", C.c_float), ("reserved", C.c_int32)]
+
+
 class AuvPolicyArch(C.Structure):
     """== auv_policy_arch_t (include/auv_hip.h): the hidden widths of a fused forward launch (the auv_policy_*_arch entries)"""
     _fields_ = [("h1", C.c_int32), ("h2", C.c_int32), ("h3", C.c_int32)]
@@ -272,6 +278,15 @@ def load_library(path: str = None) -> C.CDLL:
                                                       C.POINTER(AuvPolicyArch), vp, vp, vp, i32, i32, C.POINTER(C.c_int64),
                                                       C.POINTER(C.c_int64)]),
         "auv_policy_eval_arch": (C.c_int, [i32, C.POINTER(AuvPolicyEval), C.POINTER(AuvPolicyArch), vp]),
+        "auv_policy_act_norm": (C.c_int, [vp, i32, i32, C.POINTER(AuvPolicyNorm), vp]),
+        "auv_policy_act_norm_arch": (C.c_int, [vp, i32, i32, C.POINTER(AuvPolicyNorm), C.POINTER(AuvPolicyArch), vp]),
+        "auv_policy_rollout_norm": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(AuvPolicyNorm), vp, vp, vp, i32, i32,
+                                              C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "auv_policy_rollout_norm_arch": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(AuvPolicyNorm), C.POINTER(AuvPolicyArch),
+                                                   vp, vp, vp, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "auv_norm_rows": (C.c_int, [i32, vp, vp, C.c_int64, vp, C.c_float, vp, C.c_int64, i32, i32, vp]),
+        "auv_norm_fold": (C.c_int, [i32, vp, vp, i32, i32, C.c_double, vp, vp, vp]),
+        "auv_norm_returns": (C.c_int, [i32, vp, vp, vp, i32, i32, C.c_double, C.c_float, C.c_double, vp, vp, vp, i32, vp]),
         "auv_step_pipelined_timed": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), vp, i32, vp, vp, vp, C.POINTER(C.c_float)]),
         "auv_streams_overlap": (C.c_int, [vp, vp, vp, C.POINTER(C.c_float)]),
         "auv_episode_log": (C.c_int, [vp, vp, C.c_int64, C.c_int64, C.POINTER(C.c_int64), C.POINTER(C.c_int64), vp]),
@@ -367,6 +382,8 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_policy_act_stacked", "auv_policy_rollout_stacked", "auv_stack_frames",
                     "auv_policy_param_floats_arch", "auv_policy_act_arch", "auv_policy_rollout_arch", "auv_policy_act_stacked_arch",
                     "auv_policy_rollout_stacked_arch", "auv_policy_eval_arch",
+                    "auv_policy_act_norm", "auv_policy_act_norm_arch", "auv_policy_rollout_norm", "auv_policy_rollout_norm_arch",
+                    "auv_norm_rows", "auv_norm_fold", "auv_norm_returns",
                     "auv_population_member_floats", "auv_population_act", "auv_population_rollout", "auv_population_perturb", "auv_population_update",
                     "auv_population_member_floats_arch", "auv_population_act_arch", "auv_population_rollout_arch", "auv_population_perturb_arch",
                     "auv_population_update_arch",

@@ -1,5 +1,5 @@
-// auv_capi_learn.hip — the C ABI's learning entries (include/auv_hip.h): the fused policy launches (act, eval, stacked) and their
-// rollouts, auv_gae, the population of policies, and the PPO updater object.
+// auv_capi_learn.hip — the C ABI's learning entries (include/auv_hip.h): the fused policy launches (act, eval, stacked, normalising) and
+// their rollouts, auv_gae, the fold and the return pass of the running normalisation, the population of policies, and the PPO updater object.
 #include <hip/hip_runtime.h>
 
 #include <cmath>
@@ -280,6 +280,128 @@ int auv_stack_frames(int32_t device, const float* obs, const uint8_t* done, floa
   if (ne == 0) return AUV_OK;
   HIP_TRY(hipSetDevice(device));
   auv_launch_stack_frames(obs, done, hist, stk, out, ldx, e0, ne, obs_dim, frames, advance != 0, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+// ---- running normalisation in the policy launch (include/auv_hip.h, auv_policy_norm; kernels: k16_policy_norm.hip) ----
+static int check_policy_norm(const auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_norm_t* s, const auv_policy_arch_t* a,
+                             const char* who) {
+  if (!s) return fail(AUV_EINVAL, "%s: null io", who);
+  int rc = check_policy_io(h, e0, ne, &s->io, a, who);
+  if (rc) return rc;
+  if (s->io.params_bf16) return fail(AUV_EINVAL, "%s: normalised rows are evaluated in exact f32 only (params_bf16 must be NULL)", who);
+  if (!s->table || ((uintptr_t)s->table & 7)) return fail(AUV_EINVAL, "%s: table must be an 8-byte aligned device pointer", who);
+  if (!s->part || !s->pcnt) return fail(AUV_EINVAL, "%s: null part or pcnt", who);
+  if (((uintptr_t)s->part & 3) || ((uintptr_t)s->pcnt & 3)) return fail(AUV_EINVAL, "%s: part and pcnt must be 4-byte aligned", who);
+  if (!(s->clip_obs > 0.0f)) return fail(AUV_EINVAL, "%s: clip_obs must be > 0", who);
+  const int tiles = (ne + POL_ROWS - 1) / POL_ROWS;
+  if (s->part_base < 0 || (int64_t)s->part_base + tiles > s->part_ld)
+    return fail(AUV_EINVAL, "%s: %d tiles from part_base %d do not fit part_ld = %d", who, tiles, s->part_base, s->part_ld);
+  return AUV_OK;
+}
+
+static int policy_act_norm_impl(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_norm_t* io, const auv_policy_arch_t* a, void* stream,
+                                const char* who) {
+  REQUIRE_READY(h);
+  int rc = check_policy_norm(h, e0, ne, io, a, who);
+  if (rc) return rc;
+  HIP_TRY(auv_policy_norm_prepare(a->h1, a->h2, a->h3, io->io.obs_dim));
+  auv_launch_policy_norm(a->h1, a->h2, a->h3, *io, e0, ne, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+int auv_policy_act_norm(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_norm_t* io, void* stream) {
+  return policy_act_norm_impl(h, e0, ne, io, &POLICY_ARCH_REF, stream, "auv_policy_act_norm");
+}
+int auv_policy_act_norm_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_norm_t* io, const auv_policy_arch_t* arch, void* stream) {
+  return policy_act_norm_impl(h, e0, ne, io, arch, stream, "auv_policy_act_norm_arch");
+}
+
+// auv_policy_rollout's loop with the normalising launch: the same t0 / gstep0 contract, the same slices on their own streams
+static int policy_rollout_norm_impl(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_norm_t* ios,
+                                    const auv_policy_arch_t* a, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps,
+                                    int32_t flush, const int64_t* t0, const int64_t* gstep0, const char* who) {
+  REQUIRE_READY(h);
+  const RolloutCounters ctr = {t0, gstep0};
+  int rc = check_slices(h, n_slices, bounds, streams, who);
+  if (rc) return rc;
+  if (!ios || n_steps < 0 || !ctr.paired()) return fail(AUV_EINVAL, "%s: bad arguments", who);
+  for (int i = 0; i < n_slices; i++) {
+    rc = check_policy_norm(h, bounds[i], bounds[i + 1] - bounds[i], ios + i, a, who);
+    if (rc) return rc;
+    rc = check_actions(ios[i].io.actions_out, AUV_F32, who);
+    if (rc) return rc;
+    if (ctr.negative(i)) return fail(AUV_EINVAL, "%s: negative counter for slice %d", who, i);
+  }
+  PAIR_CHECK(h, obs_dev);
+  HIP_TRY(auv_policy_norm_prepare(a->h1, a->h2, a->h3, ios[0].io.obs_dim));
+  return rollout_loop(
+      h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].io.actions_out; },
+      [&](int i, int32_t k, bool) {
+        auv_launch_policy_norm(a->h1, a->h2, a->h3, ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k),
+                               ctr.gstep(i, k));
+      });
+}
+int auv_policy_rollout_norm(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_norm_t* ios,
+                            float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
+                            const int64_t* gstep0) {
+  return policy_rollout_norm_impl(h, n_slices, bounds, streams, ios, &POLICY_ARCH_REF, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0,
+                                  "auv_policy_rollout_norm");
+}
+int auv_policy_rollout_norm_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
+                                 const auv_policy_norm_t* ios, const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev,
+                                 uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0) {
+  return policy_rollout_norm_impl(h, n_slices, bounds, streams, ios, arch, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0,
+                                  "auv_policy_rollout_norm_arch");
+}
+
+static bool norm_finite(double x) { return x == x && x - x == 0.0; }
+
+int auv_norm_rows(int32_t device, const float* X, const int64_t* idx, int64_t ldx, const float* table, float clip_obs, float* out, int64_t ldo,
+                  int32_t M, int32_t obs_dim, void* stream) {
+  if (device < 0) return fail(AUV_EINVAL, "auv_norm_rows: device %d", device);
+  if (obs_dim < 1 || obs_dim > 16384) return fail(AUV_EINVAL, "auv_norm_rows: obs_dim %d outside [1, 16384]", obs_dim);
+  if (M < 0) return fail(AUV_EINVAL, "auv_norm_rows: M = %d < 0", M);
+  if (!X || !out || !table) return fail(AUV_EINVAL, "auv_norm_rows: null %s", !X ? "X" : !out ? "out" : "table");
+  if (((uintptr_t)table & 7) || ((uintptr_t)idx & 7) || ((uintptr_t)X & 3) || ((uintptr_t)out & 3))
+    return fail(AUV_EINVAL, "auv_norm_rows: table and idx must be 8-byte, X and out 4-byte aligned");
+  if (ldx < obs_dim || ldo < obs_dim) return fail(AUV_EINVAL, "auv_norm_rows: ldx %lld or ldo %lld < obs_dim %d", (long long)ldx, (long long)ldo, obs_dim);
+  if (!(clip_obs > 0.0f)) return fail(AUV_EINVAL, "auv_norm_rows: clip_obs must be > 0");
+  if (M == 0) return AUV_OK;
+  HIP_TRY(hipSetDevice(device));
+  auv_launch_norm_rows(X, idx, ldx, table, clip_obs, out, ldo, M, obs_dim, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+int auv_norm_fold(int32_t device, const float* part, const int32_t* pcnt, int32_t n_slots, int32_t obs_dim, double eps, double* mom, float* table,
+                  void* stream) {
+  if (device < 0) return fail(AUV_EINVAL, "auv_norm_fold: device %d", device);
+  if (obs_dim < 1 || obs_dim > 16384) return fail(AUV_EINVAL, "auv_norm_fold: obs_dim %d outside [1, 16384]", obs_dim);
+  if (n_slots < 1) return fail(AUV_EINVAL, "auv_norm_fold: n_slots = %d < 1", n_slots);
+  if (!part || !pcnt || !mom || !table) return fail(AUV_EINVAL, "auv_norm_fold: null buffer");
+  if (((uintptr_t)part & 3) || ((uintptr_t)pcnt & 3) || ((uintptr_t)mom & 7) || ((uintptr_t)table & 7))
+    return fail(AUV_EINVAL, "auv_norm_fold: part and pcnt must be 4-byte, mom and table 8-byte aligned");
+  if (!norm_finite(eps) || eps < 0.0) return fail(AUV_EINVAL, "auv_norm_fold: eps must be finite and >= 0");
+  HIP_TRY(hipSetDevice(device));
+  auv_launch_norm_fold(part, pcnt, n_slots, obs_dim, eps, mom, table, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+int auv_norm_returns(int32_t device, const float* R, const float* Dn, float* R_out, int32_t T, int32_t N, double gamma, float clip_reward,
+                     double eps, double* ret, double* rpart, double* rmom, int32_t update, void* stream) {
+  if (device < 0) return fail(AUV_EINVAL, "auv_norm_returns: device %d", device);
+  if (T < 1 || N < 1) return fail(AUV_EINVAL, "auv_norm_returns: T = %d, N = %d", T, N);
+  if (!R || !R_out || !rmom) return fail(AUV_EINVAL, "auv_norm_returns: null %s", !R ? "R" : !R_out ? "R_out" : "rmom");
+  if (update && (!Dn || !ret || !rpart)) return fail(AUV_EINVAL, "auv_norm_returns: update needs Dn, ret and rpart");
+  if (((uintptr_t)R & 3) || ((uintptr_t)R_out & 3) || ((uintptr_t)Dn & 3) || ((uintptr_t)ret & 7) || ((uintptr_t)rpart & 7) || ((uintptr_t)rmom & 7))
+    return fail(AUV_EINVAL, "auv_norm_returns: float buffers must be 4-byte, double buffers 8-byte aligned");
+  if (!(clip_reward > 0.0f)) return fail(AUV_EINVAL, "auv_norm_returns: clip_reward must be > 0");
+  if (!norm_finite(gamma) || !norm_finite(eps) || eps < 0.0) return fail(AUV_EINVAL, "auv_norm_returns: gamma and eps must be finite, eps >= 0");
+  HIP_TRY(hipSetDevice(device));
+  auv_launch_norm_returns(R, Dn, R_out, T, N, gamma, clip_reward, eps, ret, rpart, rmom, update != 0, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }

@@ -1,4 +1,4 @@
-// auv_launch.h — the host-side launchers the kernel files define (k1 .. k7, k9 .. k12, k14, k15, k_step_fused.hip) and the C ABI's host
+// auv_launch.h — the host-side launchers the kernel files define (k1 .. k7, k9 .. k12, k14 .. k16, k_step_fused.hip) and the C ABI's host
 // files (auv_capi*.hip) call: declared once, here, with their default arguments.  Definer and caller both include this header, so
 // a definition that drifts from what its caller believes is a compile error.  The launchers of the PPO update, the world
 // generator, the renderer and the k11 population pass are declared beside their argument structs (auv_ppo.h, auv_generate.h,
@@ -101,6 +101,17 @@ void auv_launch_policy_stacked(int h1, int h2, int h3, const auv_policy_stack_t&
                                long long gstep_host = -1);
 void auv_launch_stack_frames(const float* obs, const uint8_t* done, float* hist, int32_t* stk, float* out, long long ldx, int e0, int ne,
                              int obs_dim, int frames, int advance, hipStream_t st);
+// k16_policy_norm.hip: the normalising act launch (LDS: auv_policy_lds_bytes), the same expression on arbitrary rows, the fold of the
+// observation partials and the return pass (contracts: include/auv_hip.h, auv_policy_norm).  The host side has checked every pointer.
+hipError_t auv_policy_norm_prepare(int h1, int h2, int h3, int obs_dim);
+void auv_launch_policy_norm(int h1, int h2, int h3, const auv_policy_norm_t& s, int e0, int ne, hipStream_t st, long long t_host = -1,
+                            long long gstep_host = -1);
+void auv_launch_norm_rows(const float* X, const int64_t* idx, long long ldx, const float* table, float clip_obs, float* out, long long ldo,
+                          int M, int obs_dim, hipStream_t st);
+void auv_launch_norm_fold(const float* part, const int32_t* pcnt, int n_slots, int obs_dim, double eps, double* mom, float* table,
+                          hipStream_t st);
+void auv_launch_norm_returns(const float* R, const float* Dn, float* out, int T, int N, double gamma, float clip_reward, double eps, double* ret,
+                             double* rpart, double* rmom, bool update, hipStream_t st);
 void auv_launch_population_perturb(const auv_policy_arch_t& a, const float* theta, float* members, long long stride, int P, int obs_dim,
                                    float sigma, unsigned long long seed, unsigned long long generation, hipStream_t st);
 void auv_launch_population_update(const auv_policy_arch_t& a, float* theta, const float* w, float* grad, int P, int obs_dim, float sigma,

@@ -21,6 +21,12 @@ is younger than j steps.  The history lives on the device (`fused.stack`: gym_au
 itself; O is then [T, N, k * obs_dim] and everything behind the first layer -- FusedPPOUpdate, policy_eval, the planner -- takes those rows
 as they are.  Call `fused.reset_frames()` behind an `env.reset()`.
 
+Running normalisation (what stable-baselines ships as VecNormalize; gym_auv_amd/normalize.py, csrc/k16_policy_norm.hip):
+`FusedActorCritic(net, env, T, normalize=RunningNorm(env.obs_dim, gamma))` sends rollouts through the normalising launch -- O then holds the
+NORMALISED rows, so the fused update, gae() and the clone step take them as they are -- and predict / value / evaluate normalise the rows
+they are given.  The statistics are frozen during a rollout and folded behind it (`normalize.fold()`, `normalize.returns(R, Dn)`).  Not
+together with frames > 1 or bf16.
+
 Hidden widths: read off `net.pi` / `net.v` (both the same triple), one of SUPPORTED_HIDDEN -- the reference's [256, 128, 64] and the
 narrower [128, 128, 64], [128, 64, 64], [64, 64, 64] the launches are also compiled for (csrc/auv_policy_mfma.h, POL_ARCH_LIST; the
 auv_policy_*_arch entries).  Anything else raises ValueError; bf16 exists for the reference's widths only.
@@ -223,7 +229,7 @@ def policy_eval(params: torch.Tensor, obs_dim: int, X: torch.Tensor, idx: Option
 class FusedActorCritic:
     def __init__(self, net: nn.Module, env: BatchedAuvEnv, rollout: int, reward_scale: float = 1.0, reward_clip: float = 0.0,
                  act_mid=None, act_half=None, clip_lo=None, clip_hi=None, seed: int = 0, store_obs: bool = True, debug: bool = False,
-                 bf16: bool = False, frames: int = 1, arch_entry: Optional[bool] = None):
+                 bf16: bool = False, frames: int = 1, arch_entry: Optional[bool] = None, normalize=None):
         self.net, self.env, self.T = net, env, int(rollout)
         self.device = env.device
         # frames > 1: every environment is evaluated on its last `frames` observations (module docstring); 1: the plain launch
@@ -232,6 +238,16 @@ class FusedActorCritic:
             raise ValueError("FusedActorCritic: frames = %d outside [1, %d]" % (self.frames, _capi.MAX_FRAMES))
         if self.frames > 1 and bf16:
             raise ValueError("FusedActorCritic: frames = %d with bf16 = True -- stacked rows are evaluated in exact f32 only" % self.frames)
+        # normalize: a RunningNorm (gym_auv_amd/normalize.py); None: the plain launches, nothing below touches them
+        self.normalize = normalize
+        if normalize is not None:
+            if self.frames > 1:
+                raise ValueError("FusedActorCritic: frames = %d together with normalize -- frame stacking and normalisation are not combined" % self.frames)
+            if bf16:
+                raise ValueError("FusedActorCritic: bf16 = True together with normalize -- normalised rows are evaluated in exact f32 only")
+            if normalize.obs_dim != env.obs_dim:
+                raise ValueError("FusedActorCritic: normalize was made for %d columns, the environment's observation has %d"
+                                 % (normalize.obs_dim, env.obs_dim))
         self.in_dim = self.frames * env.obs_dim                                        # the nets' input width
         self._lin = []
         # the hidden widths are read off the modules: both nets the same triple, one of SUPPORTED_HIDDEN
@@ -320,6 +336,17 @@ class FusedActorCritic:
                 s = self._sios[i]
                 s.io = self._ios[i]
                 s.hist, s.stk, s.frames = self.stack.hist.data_ptr(), self.stack.stk.data_ptr(), self.frames
+        self._nios = None
+        if normalize is not None:
+            normalize.bind(N, self.T, self.slices, self.device)
+            if normalize.norm_obs:
+                # the launches' io blocks: the plain ones with the table and the partial buffers behind them
+                self._nios = (_capi.AuvPolicyNorm * len(self.slices))()
+                for i in range(len(self.slices)):
+                    s = self._nios[i]
+                    s.io = self._ios[i]
+                    s.table, s.part, s.pcnt = normalize.table.data_ptr(), normalize.part.data_ptr(), normalize.pcnt.data_ptr()
+                    s.part_ld, s.part_base, s.clip_obs = normalize.part_ld, normalize.part_base[i], normalize.clip_obs
         self.refresh()
 
     # ------------------------------------------------------------------------------ weights
@@ -357,7 +384,13 @@ class FusedActorCritic:
         slice's rows of `self.actions` and the transition at the chain's position t, then moves t on."""
         lo, cnt = self.slices[i]
         st = self.env._sub_streams[i] if stream is None else stream
-        if self._arch is not None:
+        if self._nios is not None:
+            if self._arch is not None:
+                _check(_LIB.auv_policy_act_norm_arch(self.env._h, lo, cnt, C.byref(self._nios[i]), C.byref(self._arch), C.c_void_p(st.cuda_stream)),
+                       "auv_policy_act_norm_arch")
+            else:
+                _check(_LIB.auv_policy_act_norm(self.env._h, lo, cnt, C.byref(self._nios[i]), C.c_void_p(st.cuda_stream)), "auv_policy_act_norm")
+        elif self._arch is not None:
             a = C.byref(self._arch)
             if self.frames > 1:
                 _check(_LIB.auv_policy_act_stacked_arch(self.env._h, lo, cnt, C.byref(self._sios[i]), a, C.c_void_p(st.cuda_stream)),
@@ -379,7 +412,16 @@ class FusedActorCritic:
         env = self.env
         k = len(self.slices)
         t0, g0 = (C.c_int64 * k)(*self._t), (C.c_int64 * k)(*self._g)
-        if self._arch is not None:
+        if self._nios is not None:
+            tail = (C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()), int(n_steps),
+                    int(bool(flush)), t0, g0)
+            if self._arch is not None:
+                _check(_LIB.auv_policy_rollout_norm_arch(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._nios,
+                                                         C.byref(self._arch), *tail), "auv_policy_rollout_norm_arch")
+            else:
+                _check(_LIB.auv_policy_rollout_norm(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._nios, *tail),
+                       "auv_policy_rollout_norm")
+        elif self._arch is not None:
             a = C.byref(self._arch)
             tail = (C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()), int(n_steps),
                     int(bool(flush)), t0, g0)
@@ -427,7 +469,11 @@ class FusedActorCritic:
         if obs is None and self.frames > 1:
             # the row the next policy launch would form: a peek, the history is not moved on
             return self.stack.peek(self.env.obs, self.env.done)
-        return self.env.obs if obs is None else obs
+        X = self.env.obs if obs is None else obs
+        if self._nios is not None:
+            # raw rows -> the rows the normalising launch would feed the nets (auv_norm_rows, the current table)
+            return self.normalize.normalize(X)
+        return X
 
     def reset_frames(self, envs: Optional[torch.Tensor] = None):
         """Empty the history of the environments `envs` (indices or a boolean mask; None: all) on the current stream: their next row
@@ -457,6 +503,7 @@ class FusedActorCritic:
         return policy_eval(self.params, self.in_dim, self._rows(obs), want=("value",), **self._eval_kw())["value"]
 
     def evaluate(self, obs: torch.Tensor, actions: torch.Tensor):
-        """(log pi(actions | obs) [M], value [M], mu [M, 2]) in one launch on the caller's current stream."""
-        r = policy_eval(self.params, self.in_dim, obs, actions=actions, want=("logp", "value", "mu"), **self._eval_kw())
+        """(log pi(actions | obs) [M], value [M], mu [M, 2]) in one launch on the caller's current stream.  With `normalize`, obs are RAW
+        rows (the rows stored in O are normalised already: evaluate those with policy_eval)."""
+        r = policy_eval(self.params, self.in_dim, self._rows(obs), actions=actions, want=("logp", "value", "mu"), **self._eval_kw())
         return r["logp"], r["value"], r["mu"]

@@ -786,6 +786,88 @@ int auv_policy_rollout_stacked_arch(auv_handle_t* h, int32_t n_slices, const int
                                     uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0);
 int auv_policy_eval_arch(int32_t device, const auv_policy_eval_t* ev, const auv_policy_arch_t* arch, void* stream);
 
+/* ---- running observation and reward normalisation (what stable-baselines ships as VecNormalize; csrc/k16_policy_norm.hip) ----------
+ * DEVIATION from stable-baselines: it updates its statistics at every step_wait, before normalising that step's batch.  Here the
+ * statistics are FROZEN while launches run and FOLDED between rollouts: a per-step update would be a reduction over all environments
+ * between the environment's launch and the policy launch of every step -- a barrier across chains that are not ordered against each
+ * other, and a result that depends on their timing.  So the first rollout runs on the initial table (mean 0, variance 1), every later
+ * one on the statistics of all rollouts before it, and a rollout's rewards are scaled by a deviation that already holds ALL of that
+ * rollout's returns (stable-baselines: the returns up to that step).  Initial state, stable-baselines' RunningMeanStd: mean 0, variance
+ * 1 (M2 = count), count 1e-4.
+ *
+ * auv_policy_act_norm is auv_policy_act's exact-f32 launch with one step between the tile's load and the matrix chains:
+ *   x' = min(max((x - mean[c]) * inv_std[c], -clip_obs), clip_obs)      three separately rounded f32 operations and the clamp
+ * The nets see x'; O[t] holds x' -- the rows the fused update gathers, so nothing behind the launch changes -- and for the same row the
+ * mean and the value have the bits auv_policy_eval gives on auv_norm_rows' output.
+ *   table     [obs_dim][2] f32 = (mean, inv_std) per column, 8-byte aligned; nobody may write it while launches that read it run
+ *   part      [T * part_ld][2][obs_dim] f32: per launch position t and 16-row tile, the moments of the tile's RAW rows -- [0] the mean
+ *             m = s / rows of the sequential f32 sum s over rows 0 .. rows - 1, [1] M2 = the sequential sum of (x_r - m)^2, every
+ *             operation separately rounded.  The tile `i` of a launch on [e0, e0 + ne) at position t writes slot t * part_ld +
+ *             part_base + i: part_base is the prefix sum of ceil(ne / 16) over the slices in front, part_ld the sum over all.
+ *   pcnt      [T * part_ld] int32: the rows of that tile (16, or fewer in a slice's last tile); 0 = an empty slot, skipped by the fold
+ *   the flush launch (t == T) stores R[T - 1] / Dn[T - 1] only, as auv_policy_act's does.
+ * Only the policy workgroup of a tile stores (O, part, pcnt); the value workgroup normalises its own copy of the tile.  Rewards are
+ * stored RAW, as by auv_policy_act (reward_scale and reward_clip of io apply as they do there).
+ * AUV_EINVAL, before anything is enqueued: what auv_policy_act refuses (obs_dim too wide for the LDS tile among it); table NULL or
+ * not 8-byte aligned; part or pcnt NULL or not 4-byte aligned; params_bf16 set; clip_obs not > 0; part_base < 0 or part_base +
+ * ceil(ne / 16) > part_ld; with _arch: arch NULL or a triple outside the list.  Frame stacking is not combined with it: there is no
+ * stacked form of this struct.
+ * auv_policy_rollout_norm is auv_policy_rollout's loop with that launch: the same t0 / gstep0 contract, the same slices on their own
+ * streams.
+ *
+ * auv_norm_rows: the same expression on M arbitrary rows, no handle and no network: out[j * ldo + c] = x'(X[(idx ? idx[j] : j) * ldx
+ * + c]) for c < obs_dim, on `stream` -- what goes in front of auv_policy_eval outside a rollout; the bits the act launch stores in O.
+ * AUV_EINVAL: device < 0; obs_dim outside [1, 16384]; M < 0; X, out or table NULL; table not 8-byte, idx not 8-byte, X or out not
+ * 4-byte aligned; ldx or ldo < obs_dim; clip_obs not > 0.  M == 0 succeeds and launches nothing.
+ *
+ * auv_norm_fold merges the n_slots partials of (part, pcnt) into the running moments and rewrites the table; one launch on `stream`.
+ *   mom       [obs_dim][3] f64 = (count, mean, M2) per column
+ *   merge     Chan's pairwise formula in fp64, every operation separately rounded; merge(a, b) with tot = a.n + b.n, delta = b.mean -
+ *             a.mean:  mean = a.mean + (delta * b.n) / tot,  M2 = (a.M2 + b.M2) + (((delta * delta) * a.n) * b.n) / tot;  b.n == 0
+ *             gives a, a.n == 0 gives b.
+ *   order     one wave per column: lane l merges the slots l, l + 64, ... in that order, each as b, skipping pcnt <= 0; the 64 lane
+ *             results merge as a tree -- for o = 32, 16, 8, 4, 2, 1: lane l < o becomes merge(lane l, lane l + o); the result merges
+ *             into the running moments as b.  No atomics: a rerun from the same state is bit-identical.
+ *   table     mean = (float)mean, inv_std = (float)(1 / sqrt(M2 / count + eps)).
+ * AUV_EINVAL: device < 0; obs_dim outside [1, 16384]; n_slots < 1; a NULL pointer; mom not 8-byte, table not 8-byte aligned; eps < 0
+ * or not finite.  The caller orders the launch behind every chain's last launch and in front of the next rollout's first (as auv_gae).
+ *
+ * auv_norm_returns is the reward pass over a stored rollout R[T][N] / Dn[T][N] (row-major, as auv_gae), at most three launches on
+ * `stream`, ordered by the caller like the fold:
+ *   update != 0   (1) one thread per environment walks t = 0 .. T - 1:  ret = ret * gamma + R[t] in fp64, the return taken into a
+ *                 Welford recursion over its T returns (d = ret - mean; mean += d / (t + 1); M2 += d * (ret - mean)), THEN ret = 0
+ *                 where Dn[t] != 0 (stable-baselines' order); ret[N] f64 is carried to the next call, rpart[N][2] f64 = (mean, M2)
+ *                 is scratch.  (2) one wave merges the N partials, each of count T, into rmom[3] f64 = (count, mean, M2): lane l the
+ *                 environments l, l + 64, ... in that order, then the tree and the merge into the running moments as above.
+ *   always        (3) R_out[i] = min(max(R[i] / (float)sqrt(M2 / count + eps), -clip_reward), clip_reward), an f32 division, with
+ *                 the UPDATED moments; R_out may be R.  update == 0 (VecNormalize.training == False) runs (3) alone: ret, rpart and
+ *                 rmom are not written (ret and rpart may then be NULL).
+ * AUV_EINVAL: device < 0; T < 1 or N < 1; R, R_out or rmom NULL; update with Dn, ret or rpart NULL; a float buffer not 4-byte or a
+ * double buffer not 8-byte aligned; clip_reward not > 0; gamma or eps not finite, eps < 0.                                          */
+typedef struct auv_policy_norm {
+  auv_policy_io_t io;
+  const float* table;        /* [obs_dim][2]: mean, inv_std                                                    */
+  float* part;               /* [T * part_ld][2][obs_dim]                                                      */
+  int32_t* pcnt;             /* [T * part_ld]                                                                  */
+  int32_t part_ld, part_base;
+  float clip_obs;
+  int32_t reserved;
+} auv_policy_norm_t;
+int auv_policy_act_norm(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_norm_t* io, void* stream);
+int auv_policy_act_norm_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_norm_t* io, const auv_policy_arch_t* arch, void* stream);
+int auv_policy_rollout_norm(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_norm_t* ios,
+                            float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
+                            const int64_t* gstep0);
+int auv_policy_rollout_norm_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
+                                 const auv_policy_norm_t* ios, const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev,
+                                 uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0);
+int auv_norm_rows(int32_t device, const float* X, const int64_t* idx, int64_t ldx, const float* table, float clip_obs, float* out,
+                  int64_t ldo, int32_t M, int32_t obs_dim, void* stream);
+int auv_norm_fold(int32_t device, const float* part, const int32_t* pcnt, int32_t n_slots, int32_t obs_dim, double eps, double* mom,
+                  float* table, void* stream);
+int auv_norm_returns(int32_t device, const float* R, const float* Dn, float* R_out, int32_t T, int32_t N, double gamma, float clip_reward,
+                     double eps, double* ret, double* rpart, double* rmom, int32_t update, void* stream);
+
 /* ---- a population of policies: one weight block per group of rows (csrc/k11_population.hip) ---------------------------------------
  * A MEMBER is the packed policy net of auv_policy_io::params -- W1 b1 W2 b2 W3 b3 W4 b4 in MFMA fragment order, what the first
  * net of that buffer holds -- auv_population_member_floats(obs_dim) floats (the net rounded up to a multiple of 4 floats).  Members
