@@ -98,7 +98,9 @@ __device__ __forceinline__ float pol_trunk(float* X, const int K0, const PolNet&
 // (seed, step, row, component) -> 64 well-mixed bits (pol_mix, the splitmix64 finaliser: auv_noise.h) -> a Gaussian
 __device__ __forceinline__ float pol_gauss(unsigned long long seed, unsigned long long step, unsigned int row, unsigned int comp) {
   const unsigned long long h = pol_mix(pol_mix(seed ^ (step * 0xd1342543de82ef95ull)) ^ (((unsigned long long)row << 1) | comp));
-  const float u1 = ((float)(unsigned int)(h >> 40) + 0.5f) * (1.0f / 16777216.0f);      // (0, 1): 24 bits
+  // (0, 1): 24 bits.  From 2^23 on field + 0.5 is a tie that rounds to even, and the top field's to 2^24 -- u1 = 1 and a draw that is
+  // exactly 0 -- so the product is held below 1: that one field in 2^24 moves, every other draw keeps its bits
+  const float u1 = fminf(((float)(unsigned int)(h >> 40) + 0.5f) * (1.0f / 16777216.0f), 0x1.fffffep-1f);
   const float u2 = ((float)(unsigned int)((h >> 8) & 0xffffffu)) * (1.0f / 16777216.0f);   // [0, 1)
   return sqrtf(-2.0f * logf(u1)) * cosf(6.283185307179586f * u2);
 }

@@ -34,11 +34,13 @@ auv_policy_*_arch entries).  Anything else raises ValueError; bf16 exists for th
 import ctypes as C
 from typing import Dict, List, Optional, Sequence
 
+import numpy as np
 import torch
 import torch.nn as nn
 
 from . import _capi
 from .batched_env import BatchedAuvEnv, _check, _LIB
+from .population import _GEN_MUL, _U64, _mix
 
 HIDDEN = (256, 128, 64)                 # the reference's hidden widths: the default, evaluated by the entries without _arch
 SUPPORTED_HIDDEN = _capi.POLICY_ARCHS   # the closed list the forward launches are compiled for (csrc/auv_policy_mfma.h, POL_ARCH_LIST)
@@ -64,6 +66,98 @@ def check_hidden(hidden, who: str) -> tuple:
 
 def _arch_arg(hidden) -> "_capi.AuvPolicyArch":
     return _capi.AuvPolicyArch(int(hidden[0]), int(hidden[1]), int(hidden[2]))
+
+
+# ------------------------------------------------------------------------------ NumPy mirrors of the act launch's epilogue and of k6_gae
+# (csrc/auv_policy_forward.h: pol_gauss, pol_act_sample, pol_logp, pol_act_map; csrc/k6_policy.hip: k6_gae.)  `dtype` = float64 is the
+# reference the tests hold the kernels to; float32 restates the kernel's own operations in its order, every operation rounded once
+# (log / cos / exp are evaluated in float64 and rounded, so that the restatement does not depend on the host's float32 libm) and
+# nothing contracted: what tests/policy_epilogue_cases.py derives its bounds from.  They need no device.
+def chain_seed(seed: int, i: int) -> int:
+    """The generator seed of sub-batch chain `i` of a FusedActorCritic made with `seed` (auv_policy_io::seed)."""
+    return (int(seed) * 0x9E3779B97F4A7C15 + int(i)) & _U64
+
+
+def _rounded(fn, x, dtype):
+    return fn(np.asarray(x, dtype=np.float64)).astype(dtype)
+
+
+def policy_noise_hash(seed: int, step, env, comp) -> np.ndarray:
+    """The 64 bits pol_gauss draws from for (chain seed, generator step, GLOBAL environment index, component), uint64:
+    mix(mix(seed ^ step * 0xd1342543de82ef95) ^ (env << 1 | comp)).  `step`, `env` and `comp` broadcast against each other."""
+    step, env, comp = (np.asarray(x).astype(np.uint64) for x in (step, env, comp))
+    shape = np.broadcast(step, env, comp).shape
+    key = _mix(np.uint64(int(seed) & _U64) ^ (np.atleast_1d(step) * np.uint64(_GEN_MUL)))
+    return _mix(key ^ ((np.atleast_1d(env) << np.uint64(1)) | np.atleast_1d(comp))).reshape(shape)
+
+
+def hash_fields(h):
+    """(u1, u2), float32, as pol_gauss forms them from the hash: u1 = min(((h >> 40) + 0.5) 2^-24, 1 - 2^-24) in (0, 1), u2 =
+    ((h >> 8) & 0xffffff) 2^-24 in [0, 1).  u2 is exact.  u1 is exact below 2^23; from there on field + 0.5 is a tie that float32 rounds
+    to even (one rounding, the same on every IEEE machine), which the top field would take to 1: hence the min."""
+    h = np.atleast_1d(np.asarray(h).astype(np.uint64))
+    scale = np.float32(1.0 / 16777216.0)
+    u1 = np.minimum(((h >> np.uint64(40)).astype(np.float32) + np.float32(0.5)) * scale, np.float32(1.0 - 1.0 / 16777216.0))
+    u2 = ((h >> np.uint64(8)) & np.uint64(0xffffff)).astype(np.float32) * scale
+    return u1.reshape(np.shape(h)), u2.reshape(np.shape(h))
+
+
+def policy_noise_fields(seed: int, step, env, comp):
+    """(u1, u2), float32, of the draw pol_gauss makes: hash_fields(policy_noise_hash(...))."""
+    h = policy_noise_hash(seed, step, env, comp)
+    u1, u2 = hash_fields(h)
+    return u1.reshape(h.shape), u2.reshape(h.shape)
+
+
+def box_muller(u1, u2, dtype=np.float64):
+    """sqrt(-2 ln u1) cos(2 pi u2) in `dtype`, in pol_gauss' order of operations (2 pi rounded to `dtype` first, as the kernel's literal)."""
+    u1, u2 = np.asarray(u1).astype(dtype), np.asarray(u2).astype(dtype)
+    r = np.sqrt(dtype(-2.0) * _rounded(np.log, u1, dtype))
+    return r * _rounded(np.cos, dtype(2.0 * np.pi) * u2, dtype)
+
+
+def policy_noise(seed: int, step, env, comp, dtype=np.float64):
+    """eps of pol_gauss: Box-Muller on policy_noise_fields in `dtype`."""
+    return box_muller(*policy_noise_fields(seed, step, env, comp), dtype=dtype)
+
+
+def sample_reference(mu, log_std, eps, dtype=np.float64):
+    """a = mu + exp(log_std) * eps in `dtype` (pol_act_sample); mu, eps [..., 2], log_std [2]."""
+    sigma = _rounded(np.exp, np.asarray(log_std).astype(dtype), dtype)
+    return np.asarray(mu).astype(dtype) + sigma * np.asarray(eps).astype(dtype)
+
+
+def logp_reference(a, mu, log_std, dtype=np.float64):
+    """log pi(a) of the diagonal Gaussian, the two components summed, in `dtype` and pol_logp's order: z = (a - mu) / exp(ls),
+    (-0.5 z) z - ls - log sqrt(2 pi); a, mu [..., 2] -> [...]."""
+    ls = np.asarray(log_std).astype(dtype)
+    z = (np.asarray(a).astype(dtype) - np.asarray(mu).astype(dtype)) / _rounded(np.exp, ls, dtype)
+    lp = dtype(-0.5) * z * z - ls - dtype(0.5 * np.log(2.0 * np.pi))
+    return lp[..., 0] + lp[..., 1]
+
+
+def action_map_reference(a, mid, half, lo, hi):
+    """mid + half * clamp(a, lo, hi) per component in float32 (PolActMap): what an act launch leaves in the environment's action buffer."""
+    f = np.float32
+    mid, half, lo, hi = (np.asarray(x, dtype=f) for x in (mid, half, lo, hi))
+    return mid + half * np.minimum(np.maximum(np.asarray(a, dtype=f), lo), hi)
+
+
+def gae_reference(R, V, Dn, last_v, gamma: float, lam: float, dtype=np.float64):
+    """(adv, ret) [T, N] of k6_gae's backward recursion in `dtype` and in its order: delta = R + (gamma nv) (1 - Dn) - V,
+    adv = delta + ((gamma lam) (1 - Dn)) adv', ret = adv + V.  gamma and lam are rounded to float32 first: the kernel takes them as
+    float, and the caller's rounding is not the kernel's error."""
+    R, V, Dn = (np.asarray(x).astype(dtype) for x in (R, V, Dn))
+    g, l = dtype(np.float32(gamma)), dtype(np.float32(lam))
+    nv, gae = np.asarray(last_v).astype(dtype), np.zeros(R.shape[1], dtype=dtype)
+    adv = np.empty_like(R)
+    for t in range(R.shape[0] - 1, -1, -1):
+        nd = dtype(1.0) - Dn[t]
+        delta = R[t] + g * nv * nd - V[t]
+        gae = delta + g * l * nd * gae
+        adv[t] = gae
+        nv = V[t]
+    return adv, adv + V
 
 
 def policy_param_floats(obs_dim: int, hidden=HIDDEN) -> int:
@@ -315,7 +409,7 @@ class FusedActorCritic:
             io.A, io.LP, io.V, io.R, io.Dn = (x.data_ptr() for x in (self.A, self.LP, self.V, self.R, self.Dn))
             io.mu_out = self.mu[lo:].data_ptr() if debug else None       # ([ne][2] views of the slice's rows)
             io.eps_out = self.eps[lo:].data_ptr() if debug else None
-            io.seed = (int(seed) * 0x9E3779B97F4A7C15 + i) & 0xFFFFFFFFFFFFFFFF
+            io.seed = chain_seed(seed, i)
             io.obs_dim, io.T, io.ld, io.env_base = D, self.T, N, 0
             io.params_bf16 = self.params_bf16.data_ptr() if self.bf16 else None
             for k in range(2):
