@@ -8,6 +8,7 @@ are auto-reset into the next world of the bank, and the episode log says how the
     python examples/evaluate.py --ckpt policy.pt --task pathfollow          # a state_dict of examples/ppo.py's ActorCritic
     python examples/evaluate.py --envs 64 --frames out/                     # and pictures of the first 16 environments
     python examples/evaluate.py --ckpt policy.pt --frame-stack 4            # a policy trained with examples/ppo.py --frames 4
+    python examples/evaluate.py --ckpt policy.pt --squash 1                 # a policy trained with examples/ppo.py --squash 1
 """
 import argparse
 import json
@@ -94,6 +95,9 @@ def main():
     ap.add_argument("--worlds", type=int, default=0, help="worlds of the bank (default: 2 per environment)")
     ap.add_argument("--feasibility-pooling", type=int, default=0)
     ap.add_argument("--act-space", default="raw", choices=["raw", "normalized"])
+    ap.add_argument("--squash", type=int, default=0, choices=[0, 1],
+                    help="1: the checkpoint is a tanh-squashed policy (examples/ppo.py --squash 1): action = mid + half * tanh(mu); implies "
+                         "--act-space normalized")
     ap.add_argument("--max-steps", type=int, default=100000, help="stop after this many steps even if episodes are still open")
     ap.add_argument("--seed", type=int, default=0)
     ap.add_argument("--frames", default=None, metavar="DIR", help="write frames of the first 16 environments every 50 steps: .npy stacks and .ppm pictures")
@@ -115,10 +119,10 @@ def main():
     env.reset()
     net = load_policy(a.ckpt, a.frame_stack * env.obs_dim, a.device, a.seed, hidden=tuple(int(h) for h in a.net_arch.split(",")))
     kw = {}
-    if a.act_space == "normalized":                        # the policy speaks [-1, 1]^2; the map stretches it onto the action space
+    if a.act_space == "normalized" or a.squash:                        # the policy speaks [-1, 1]^2; the map stretches it onto the action space
         lo, hi = env.action_space.low, env.action_space.high
         kw = dict(act_mid=((lo + hi) / 2).tolist(), act_half=((hi - lo) / 2).tolist(), clip_lo=[-1.0, -1.0], clip_hi=[1.0, 1.0])
-    fused = FusedActorCritic(net, env, rollout=1, frames=a.frame_stack, **kw)
+    fused = FusedActorCritic(net, env, rollout=1, frames=a.frame_stack, squash=bool(a.squash), **kw)
     torch.cuda.synchronize()
     t0 = time.perf_counter()
     if a.frames:

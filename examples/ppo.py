@@ -15,7 +15,9 @@ chain's stream.
 Trainer-side options (none of them changes the environment): --act-space normalized samples in the box [-1, 1]^2 and
 maps it onto the action space (default: raw units clipped to the space, as stable-baselines does with a Box -- with the
 rudder's range of +-0.15 a Gaussian of std 0.6 is then clipped most of the time, i.e. bang-bang steering, which is what
-learns fastest here); --ret-norm 1 normalises the returns by a running mean / std for the value head (a collision is
+learns fastest here); --squash 1 makes the policy a tanh-squashed Gaussian (implies --act-space normalized: the environment receives
+mid + half * tanh(u), and the entropy bonus is the squashed distribution's, which sees the box -- with the clipped map "entropy is
+free" and ent_coef 0.01 lets the std grow without bound, docs/HISTORY.md); --ret-norm 1 normalises the returns by a running mean / std for the value head (a collision is
 -5000 against step rewards of order 1); --orthogonal 1 starts the last policy layer small.  Progress is read from the
 library's episode log (auv_episode_log): goal / collision / give-up rates of the episodes that ended during each update.
 
@@ -152,7 +154,7 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
           task="colav", step_mode=None, graph_rollout=False, sub_batches=4, minibatches=32,
           reward_scale=0.01, reward_clip=0.0, min_cumulative_reward=None, act_space="raw", ret_norm=False, orthogonal=False, ent_coef=0.01, log_std=-0.5, lr=2e-4,
           fused_policy=True, graph_update=False, policy_bf16=False, feasibility_pooling=False, fused_update=False, net_arch=(256, 128, 64),
-          fused_bootstrap=False, frames=1, normalize="none"):
+          fused_bootstrap=False, frames=1, normalize="none", squash=False):
     from gym_auv_amd import distributed as D
     from gym_auv_amd.batched_env import BatchedAuvEnv
     from gym_auv_amd.config import effective_reference_config
@@ -189,6 +191,8 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
     streams = env._sub_streams
     low = torch.as_tensor(env.action_space.low, device=device)
     high = torch.as_tensor(env.action_space.high, device=device)
+    if squash:                        # a tanh-squashed Gaussian lives in [-1, 1]^2
+        act_space = "normalized"
     if act_space == "normalized":     # the policy's box is [-1, 1]^2, mapped onto the action space
         a_mid, a_half = 0.5 * (high + low), 0.5 * (high - low)
         c_lo, c_hi = -torch.ones_like(low), torch.ones_like(high)
@@ -255,7 +259,7 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
             b["A"].index_copy_(0, b["t"], a.unsqueeze(0))
             b["LP"].index_copy_(0, b["t"], net.log_prob(mu, a).unsqueeze(0))
             b["V"].index_copy_(0, b["t"], net.v(o).squeeze(-1).unsqueeze(0))
-            act_buf[lo:lo + cnt] = a_mid + a_half * torch.max(torch.min(a, c_hi), c_lo)
+            act_buf[lo:lo + cnt] = a_mid + a_half * (torch.tanh(a) if squash else torch.max(torch.min(a, c_hi), c_lo))
             env.step_slice(i, act_buf, stream=torch.cuda.current_stream(device))
             r = env.reward[lo:lo + cnt]
             if reward_clip > 0.0:       # the LEARNING signal only: a collision's -5000 against step rewards of order 1 leaves
@@ -272,7 +276,7 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
         from gym_auv_amd.policy import FusedActorCritic
         fused = FusedActorCritic(net, env, rollout=T, reward_scale=reward_scale, reward_clip=reward_clip, act_mid=a_mid.tolist(),
                                  act_half=a_half.tolist(), clip_lo=c_lo.tolist(), clip_hi=c_hi.tolist(), seed=1000 * seed + rank,
-                                 bf16=policy_bf16, frames=frames, normalize=norm)
+                                 bf16=policy_bf16, frames=frames, normalize=norm, squash=squash)
         graph_rollout = False
     graphs = None
     if graph_rollout:
@@ -304,7 +308,7 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
         if policy_bf16:
             raise ValueError("--fused-update repacks the exact f32 policy weights only: not with --policy-bf16")
         upd_fused = FusedPPOUpdate(net, lr=lr, clip=clip, vf_coef=0.5, ent_coef=ent_coef, max_norm_pi=0.5, max_norm_v=0.5,
-                                   max_batch=-(-n_total // n_mb))
+                                   max_batch=-(-n_total // n_mb), squash=squash)
         if fused is not None:
             upd_fused.attach(fused)
         graph_update = 0
@@ -399,9 +403,13 @@ def train(envs=4096, updates=10, rollout=32, device="cuda:0", seed=0, log=print,
         def minibatch_step(o, a, lp, advn, retn):
             mu = net.pi(o)
             ratio = (net.log_prob(mu, a) - lp).exp()
-            pg = -torch.min(ratio * advn, ratio.clamp(1 - clip, 1 + clip) * advn).mean()
-            vf = 0.5 * (net.v(o).squeeze(-1) - retn).pow(2).mean()
-            loss = pg + 0.5 * vf - ent_coef * net.entropy()
+            if squash:                  # the same pg and vf, the squashed distribution's entropy on the stored actions (a: pre-squash)
+                from gym_auv_amd.ppo_update import squash_loss_terms
+                loss = squash_loss_terms(net, o, a, lp, advn, retn, clip, 0.5, ent_coef)[0]
+            else:
+                pg = -torch.min(ratio * advn, ratio.clamp(1 - clip, 1 + clip) * advn).mean()
+                vf = 0.5 * (net.v(o).squeeze(-1) - retn).pow(2).mean()
+                loss = pg + 0.5 * vf - ent_coef * net.entropy()
             opt.zero_grad(set_to_none=not graph_update)
             loss.backward()
             average_gradients(params, world)
@@ -587,6 +595,9 @@ if __name__ == "__main__":
                          "128,128,64  128,64,64  64,64,64; --fused-update 1 takes the same list")
     ap.add_argument("--step-mode", default=None, help="launch shape of a step (BatchedAuvEnv.STEP_MODES); default: the library's")
     ap.add_argument("--act-space", default="raw", choices=["raw", "normalized"])
+    ap.add_argument("--squash", type=int, default=0, choices=[0, 1],
+                    help="1: a tanh-squashed Gaussian policy (implies --act-space normalized): the environment receives mid + half * tanh(u), "
+                         "the entropy bonus is the squashed distribution's; not with --frames > 1, --normalize or --policy-bf16")
     ap.add_argument("--ret-norm", type=int, default=0)
     ap.add_argument("--orthogonal", type=int, default=0)
     ap.add_argument("--ent-coef", type=float, default=0.01)
@@ -603,4 +614,4 @@ if __name__ == "__main__":
           sub_batches=a.sub_batches, minibatches=a.minibatches, act_space=a.act_space, ret_norm=bool(a.ret_norm),
           orthogonal=bool(a.orthogonal), ent_coef=a.ent_coef, log_std=a.log_std, lr=a.lr, reward_clip=a.reward_clip,
           min_cumulative_reward=a.min_cumulative_reward, feasibility_pooling=bool(a.feasibility_pooling), fused_update=bool(a.fused_update), net_arch=tuple(int(h) for h in a.net_arch.split(",")),
-          fused_bootstrap=bool(a.fused_bootstrap), frames=a.frames, normalize=a.normalize)
+          fused_bootstrap=bool(a.fused_bootstrap), frames=a.frames, normalize=a.normalize, squash=bool(a.squash))

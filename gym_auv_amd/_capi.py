@@ -199,6 +199,11 @@ class AuvPpoBatch(C.Structure):
     ]
 
 
+class AuvPpoSquashBatch(C.Structure):
+    """== auv_ppo_squash_batch_t: auv_ppo_batch_t's fields; the type selects the head with the squashed distribution's entropy"""
+    _fields_ = list(AuvPpoBatch._fields_)
+
+
 class AuvPpoCloneBatch(C.Structure):
     """== auv_ppo_clone_batch_t: the rows of one supervised (clone) step -- target actions, value targets, row weights"""
     _fields_ = [
@@ -278,6 +283,14 @@ def load_library(path: str = None) -> C.CDLL:
                                                       C.POINTER(AuvPolicyArch), vp, vp, vp, i32, i32, C.POINTER(C.c_int64),
                                                       C.POINTER(C.c_int64)]),
         "auv_policy_eval_arch": (C.c_int, [i32, C.POINTER(AuvPolicyEval), C.POINTER(AuvPolicyArch), vp]),
+        "auv_policy_act_squash": (C.c_int, [vp, i32, i32, C.POINTER(AuvPolicyIO), vp]),
+        "auv_policy_act_squash_arch": (C.c_int, [vp, i32, i32, C.POINTER(AuvPolicyIO), C.POINTER(AuvPolicyArch), vp]),
+        "auv_policy_rollout_squash": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(AuvPolicyIO), vp, vp, vp, i32, i32,
+                                                C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "auv_policy_rollout_squash_arch": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(AuvPolicyIO), C.POINTER(AuvPolicyArch),
+                                                     vp, vp, vp, i32, i32, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
+        "auv_policy_eval_squash": (C.c_int, [i32, C.POINTER(AuvPolicyEval), vp]),
+        "auv_policy_eval_squash_arch": (C.c_int, [i32, C.POINTER(AuvPolicyEval), C.POINTER(AuvPolicyArch), vp]),
         "auv_policy_act_norm": (C.c_int, [vp, i32, i32, C.POINTER(AuvPolicyNorm), vp]),
         "auv_policy_act_norm_arch": (C.c_int, [vp, i32, i32, C.POINTER(AuvPolicyNorm), C.POINTER(AuvPolicyArch), vp]),
         "auv_policy_rollout_norm": (C.c_int, [vp, i32, C.POINTER(i32), C.POINTER(vp), C.POINTER(AuvPolicyNorm), vp, vp, vp, i32, i32,
@@ -347,6 +360,7 @@ def load_library(path: str = None) -> C.CDLL:
         "auv_ppo_grad": (C.c_int, [vp, C.POINTER(AuvPpoBatch), vp, vp, vp]),
         "auv_ppo_adam": (C.c_int, [vp, vp, vp, vp, vp, C.POINTER(AuvPpoAdam), vp, vp]),
         "auv_ppo_grad_clone": (C.c_int, [vp, C.POINTER(AuvPpoCloneBatch), vp, vp, vp]),
+        "auv_ppo_grad_squash": (C.c_int, [vp, C.POINTER(AuvPpoSquashBatch), vp, vp, vp]),
         "auv_ppo_param_floats_arch": (sz, [i32, C.POINTER(AuvPolicyArch)]),
         "auv_ppo_create_arch": (C.c_int, [i32, i32, i32, C.POINTER(AuvPolicyArch), C.POINTER(vp)]),
         "auv_render": (C.c_int, [vp, vp, C.POINTER(i32), i32, i32, i32, C.c_double, i32, C.c_double, vp, i32, vp, i32, vp, vp, vp, vp, vp, vp]),
@@ -384,6 +398,8 @@ EXPORTED_SYMBOLS = ["auv_create", "auv_destroy", "auv_load_worlds", "auv_reset",
                     "auv_policy_rollout_stacked_arch", "auv_policy_eval_arch",
                     "auv_policy_act_norm", "auv_policy_act_norm_arch", "auv_policy_rollout_norm", "auv_policy_rollout_norm_arch",
                     "auv_norm_rows", "auv_norm_fold", "auv_norm_returns",
+                    "auv_policy_act_squash", "auv_policy_act_squash_arch", "auv_policy_rollout_squash", "auv_policy_rollout_squash_arch",
+                    "auv_policy_eval_squash", "auv_policy_eval_squash_arch", "auv_ppo_grad_squash",
                     "auv_population_member_floats", "auv_population_act", "auv_population_rollout", "auv_population_perturb", "auv_population_update",
                     "auv_population_member_floats_arch", "auv_population_act_arch", "auv_population_rollout_arch", "auv_population_perturb_arch",
                     "auv_population_update_arch",

@@ -58,15 +58,35 @@ static int check_policy_io(const auv_handle_t* h, int32_t e0, int32_t ne, const 
   return AUV_OK;
 }
 
+// squash: the launch of a tanh-squashed policy (k17_policy_squash.hip) in the place of the plain one: the same checks, exact f32 only
+static int check_policy_squash(const auv_policy_io_t* io, const char* who) {
+  if (io->params_bf16) return fail(AUV_EINVAL, "%s: a squashed policy is evaluated in exact f32 only (params_bf16 must be NULL)", who);
+  return AUV_OK;
+}
+
 static int policy_act_impl(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const auv_policy_arch_t* a, void* stream,
-                           const char* who) {
+                           const char* who, bool squash = false) {
   REQUIRE_READY(h);
   int rc = check_policy_io(h, e0, ne, io, a, who);
   if (rc) return rc;
-  HIP_TRY(auv_policy_prepare(a->h1, a->h2, a->h3, io->obs_dim));
-  auv_launch_policy(a->h1, a->h2, a->h3, *io, e0, ne, (hipStream_t)stream);
+  if (squash) {
+    rc = check_policy_squash(io, who);
+    if (rc) return rc;
+    HIP_TRY(auv_policy_squash_prepare(a->h1, a->h2, a->h3, io->obs_dim, false));
+    auv_launch_policy_squash(a->h1, a->h2, a->h3, *io, e0, ne, (hipStream_t)stream);
+  } else {
+    HIP_TRY(auv_policy_prepare(a->h1, a->h2, a->h3, io->obs_dim));
+    auv_launch_policy(a->h1, a->h2, a->h3, *io, e0, ne, (hipStream_t)stream);
+  }
   HIP_TRY(hipGetLastError());
   return AUV_OK;
+}
+int auv_policy_act_squash(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, void* stream) {
+  return policy_act_impl(h, e0, ne, io, &POLICY_ARCH_REF, stream, "auv_policy_act_squash", true);
+}
+int auv_policy_act_squash_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const auv_policy_arch_t* arch,
+                               void* stream) {
+  return policy_act_impl(h, e0, ne, io, arch, stream, "auv_policy_act_squash_arch", true);
 }
 int auv_policy_act(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, void* stream) {
   return policy_act_impl(h, e0, ne, io, &POLICY_ARCH_REF, stream, "auv_policy_act");
@@ -86,7 +106,7 @@ int auv_gae(auv_handle_t* h, const float* R, const float* V, const float* Dn, co
 }
 
 // ---- the policy on arbitrary rows (include/auv_hip.h, auv_policy_eval; kernel: k9_policy_eval.hip) ----
-static int policy_eval_impl(int32_t device, const auv_policy_eval_t* ev, const auv_policy_arch_t* a, void* stream) {
+static int policy_eval_impl(int32_t device, const auv_policy_eval_t* ev, const auv_policy_arch_t* a, void* stream, bool squash = false) {
   if (!ev) return fail(AUV_EINVAL, "auv_policy_eval: null ev");
   int rca = check_policy_arch(a, nullptr, "auv_policy_eval");
   if (rca) return rca;
@@ -107,10 +127,22 @@ static int policy_eval_impl(int32_t device, const auv_policy_eval_t* ev, const a
     return fail(AUV_EINVAL, "auv_policy_eval: float buffers must be 4-byte, idx 8-byte aligned");
   if (ev->M == 0) return AUV_OK;
   HIP_TRY(hipSetDevice(device));
-  HIP_TRY(auv_policy_eval_prepare(a->h1, a->h2, a->h3, ev->obs_dim));
-  auv_launch_policy_eval(a->h1, a->h2, a->h3, *ev, want_pi, want_v, (hipStream_t)stream);
+  if (squash) {
+    HIP_TRY(auv_policy_squash_prepare(a->h1, a->h2, a->h3, ev->obs_dim, true));
+    auv_launch_policy_eval_squash(a->h1, a->h2, a->h3, *ev, want_pi, want_v, (hipStream_t)stream);
+  } else {
+    HIP_TRY(auv_policy_eval_prepare(a->h1, a->h2, a->h3, ev->obs_dim));
+    auv_launch_policy_eval(a->h1, a->h2, a->h3, *ev, want_pi, want_v, (hipStream_t)stream);
+  }
   HIP_TRY(hipGetLastError());
   return AUV_OK;
+}
+// (the messages name auv_policy_eval: the checks are its own)
+int auv_policy_eval_squash(int32_t device, const auv_policy_eval_t* ev, void* stream) {
+  return policy_eval_impl(device, ev, &POLICY_ARCH_REF, stream, true);
+}
+int auv_policy_eval_squash_arch(int32_t device, const auv_policy_eval_t* ev, const auv_policy_arch_t* arch, void* stream) {
+  return policy_eval_impl(device, ev, arch, stream, true);
 }
 int auv_policy_eval(int32_t device, const auv_policy_eval_t* ev, void* stream) { return policy_eval_impl(device, ev, &POLICY_ARCH_REF, stream); }
 int auv_policy_eval_arch(int32_t device, const auv_policy_eval_t* ev, const auv_policy_arch_t* arch, void* stream) {
@@ -155,7 +187,7 @@ struct RolloutCounters {
 
 static int policy_rollout_impl(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
                                const auv_policy_arch_t* a, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush,
-                               const int64_t* t0, const int64_t* gstep0, const char* who) {
+                               const int64_t* t0, const int64_t* gstep0, const char* who, bool squash = false) {
   REQUIRE_READY(h);
   const RolloutCounters ctr = {t0, gstep0};
   int rc = check_slices(h, n_slices, bounds, streams, who);
@@ -164,11 +196,21 @@ static int policy_rollout_impl(auv_handle_t* h, int32_t n_slices, const int32_t*
   for (int i = 0; i < n_slices; i++) {
     rc = check_policy_io(h, bounds[i], bounds[i + 1] - bounds[i], ios + i, a, who);
     if (rc) return rc;
+    if (squash && (rc = check_policy_squash(ios + i, who)) != AUV_OK) return rc;
     rc = check_actions(ios[i].actions_out, AUV_F32, who);
     if (rc) return rc;
     if (ctr.negative(i)) return fail(AUV_EINVAL, "%s: negative counter for slice %d", who, i);
   }
   PAIR_CHECK(h, obs_dev);
+  if (squash) {
+    HIP_TRY(auv_policy_squash_prepare(a->h1, a->h2, a->h3, ios[0].obs_dim, false));
+    return rollout_loop(
+        h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].actions_out; },
+        [&](int i, int32_t k, bool) {
+          auv_launch_policy_squash(a->h1, a->h2, a->h3, ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k),
+                                   ctr.gstep(i, k));
+        });
+  }
   HIP_TRY(auv_policy_prepare(a->h1, a->h2, a->h3, ios[0].obs_dim));
   return rollout_loop(
       h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].actions_out; },
@@ -176,6 +218,18 @@ static int policy_rollout_impl(auv_handle_t* h, int32_t n_slices, const int32_t*
         auv_launch_policy(a->h1, a->h2, a->h3, ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k),
                           ctr.gstep(i, k));
       });
+}
+int auv_policy_rollout_squash(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
+                              float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
+                              const int64_t* gstep0) {
+  return policy_rollout_impl(h, n_slices, bounds, streams, ios, &POLICY_ARCH_REF, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0,
+                             "auv_policy_rollout_squash", true);
+}
+int auv_policy_rollout_squash_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
+                                   const auv_policy_io_t* ios, const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev,
+                                   uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0) {
+  return policy_rollout_impl(h, n_slices, bounds, streams, ios, arch, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0,
+                             "auv_policy_rollout_squash_arch", true);
 }
 int auv_policy_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
                        float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
@@ -636,7 +690,7 @@ int auv_ppo_create_arch(int32_t device, int32_t obs_dim, int32_t max_batch, cons
   const size_t rows = (size_t)d.rt_max * 16, fwd = auv_ppo_fwd_floats(obs_dim, a), tr = auv_ppo_tr_floats(a);
   // one allocation, carved into parts of a multiple of four floats each (16-byte aligned)
   const size_t n_part = (size_t)AUV_PPO_MAX_SPLIT * (fwd - 4);
-  size_t total = fwd + tr + 256 + rows * d.k0p + 2 * rows * (2 * (size_t)(a.h1 + a.h2 + a.h3) + 16) + n_part + (size_t)d.rt_max * 8 + 4 * AUV_PPO_NORM_BLOCKS;
+  size_t total = fwd + tr + 256 + rows * d.k0p + 2 * rows * (2 * (size_t)(a.h1 + a.h2 + a.h3) + 16) + n_part + (size_t)d.rt_max * 12 + 4 * AUV_PPO_NORM_BLOCKS;
   hipError_t e = hipMalloc((void**)&p->arena, total * sizeof(float));
   if (e != hipSuccess) {
     delete p;
@@ -651,7 +705,7 @@ int auv_ppo_create_arch(int32_t device, int32_t obs_dim, int32_t max_batch, cons
     d.Y[net][0] = take(rows * a.h1), d.Y[net][1] = take(rows * a.h2), d.Y[net][2] = take(rows * a.h3);
     d.dZ[net][0] = take(rows * a.h1), d.dZ[net][1] = take(rows * a.h2), d.dZ[net][2] = take(rows * a.h3), d.dZ[net][3] = take(rows * 16);
   }
-  d.part = take(n_part), d.tstat = take((size_t)d.rt_max * 8);
+  d.part = take(n_part), d.tstat = take((size_t)d.rt_max * 12);   // ([rt_max][8], then the squash head's [rt_max]; 12: a multiple of four)
   d.pol = nullptr;
   e = hipMemset(p->arena, 0, total * sizeof(float));
   if (e == hipSuccess) e = hipDeviceSynchronize();
@@ -707,8 +761,20 @@ int auv_ppo_grad_clone(auv_ppo_t* p, const auv_ppo_clone_batch_t* b, float* grad
   if (b->n_rows < 1 || (!b->idx && b->B > b->n_rows)) return fail(AUV_EINVAL, "auv_ppo_grad_clone: B = %d rows of n_rows = %d", b->B, b->n_rows);
   if (b->B > p->d.max_batch) return fail(AUV_EINVAL, "auv_ppo_grad_clone: B = %d above max_batch = %d", b->B, p->d.max_batch);
   HIP_TRY(hipSetDevice(p->device));
-  HIP_TRY(auv_ppo_prepare(p->d.obs_dim, p->arch, true));
+  HIP_TRY(auv_ppo_prepare(p->d.obs_dim, p->arch, AUV_PPO_HEAD_CLONE));
   auv_launch_ppo_grad_clone(p->d, p->arch, *b, grad, stats, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return AUV_OK;
+}
+
+int auv_ppo_grad_squash(auv_ppo_t* p, const auv_ppo_squash_batch_t* b, float* grad, float* stats, void* stream) {
+  if (!p || !b || !grad || !stats) return fail(AUV_EINVAL, "auv_ppo_grad_squash: null argument");
+  if (!b->O || !b->A || !b->LP || !b->ADV || !b->RET) return fail(AUV_EINVAL, "auv_ppo_grad_squash: null batch buffer");
+  if (b->B < 1 || b->B > p->d.max_batch) return fail(AUV_EINVAL, "auv_ppo_grad_squash: B = %d outside [1, max_batch = %d]", b->B, p->d.max_batch);
+  if (b->n_rows < 1 || (!b->idx && b->B > b->n_rows)) return fail(AUV_EINVAL, "auv_ppo_grad_squash: B = %d rows of n_rows = %d", b->B, b->n_rows);
+  HIP_TRY(hipSetDevice(p->device));
+  HIP_TRY(auv_ppo_prepare(p->d.obs_dim, p->arch, AUV_PPO_HEAD_SQUASH));
+  auv_launch_ppo_grad_squash(p->d, p->arch, *b, grad, stats, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }

@@ -1,4 +1,4 @@
-// auv_launch.h — the host-side launchers the kernel files define (k1 .. k7, k9 .. k12, k14 .. k16, k_step_fused.hip) and the C ABI's host
+// auv_launch.h — the host-side launchers the kernel files define (k1 .. k7, k9 .. k12, k14 .. k17, k_step_fused.hip) and the C ABI's host
 // files (auv_capi*.hip) call: declared once, here, with their default arguments.  Definer and caller both include this header, so
 // a definition that drifts from what its caller believes is a compile error.  The launchers of the PPO update, the world
 // generator, the renderer and the k11 population pass are declared beside their argument structs (auv_ppo.h, auv_generate.h,
@@ -112,6 +112,12 @@ void auv_launch_norm_fold(const float* part, const int32_t* pcnt, int n_slots, i
                           hipStream_t st);
 void auv_launch_norm_returns(const float* R, const float* Dn, float* out, int T, int N, double gamma, float clip_reward, double eps, double* ret,
                              double* rpart, double* rmom, bool update, hipStream_t st);
+// k17_policy_squash.hip: the act and the eval launch of a tanh-squashed policy (exact f32, LDS: auv_policy_lds_bytes); `eval` names
+// the kernel auv_policy_squash_prepare sets up
+hipError_t auv_policy_squash_prepare(int h1, int h2, int h3, int obs_dim, bool eval);
+void auv_launch_policy_squash(int h1, int h2, int h3, const auv_policy_io_t& io, int e0, int ne, hipStream_t st, long long t_host = -1,
+                              long long gstep_host = -1);
+void auv_launch_policy_eval_squash(int h1, int h2, int h3, const auv_policy_eval_t& ev, bool want_pi, bool want_v, hipStream_t st);
 void auv_launch_population_perturb(const auv_policy_arch_t& a, const float* theta, float* members, long long stride, int P, int obs_dim,
                                    float sigma, unsigned long long seed, unsigned long long generation, hipStream_t st);
 void auv_launch_population_update(const auv_policy_arch_t& a, float* theta, const float* w, float* grad, int P, int obs_dim, float sigma,

@@ -126,6 +126,27 @@ __device__ __forceinline__ PolActMap pol_act_map(const IO& io, const int nc) {
   return m;
 }
 
+// ---- the action map of a squashed policy: env action = act_mid + act_half * tanh(a); clip_lo / clip_hi are not read ----
+// (pol_squash_tanh: odd, exactly +-1 for large |a|, never NaN for a finite a; the launch arguments pinned as pol_act_map's)
+struct PolSquashMap {
+  float act_mid, act_half;
+  __device__ __forceinline__ float operator()(const float a) const { return act_mid + act_half * pol_squash_tanh(a); }
+};
+template <class IO>
+__device__ __forceinline__ PolSquashMap pol_squash_map(const IO& io, const int nc) {
+  float am0 = io.act_mid[0], am1 = io.act_mid[1], ah0 = io.act_half[0], ah1 = io.act_half[1];
+  asm volatile("" : "+s"(am0), "+s"(am1), "+s"(ah0), "+s"(ah1));
+  PolSquashMap m;
+  m.act_mid = nc ? am1 : am0, m.act_half = nc ? ah1 : ah0;
+  return m;
+}
+// the map of a launch: SQUASH picks the functor at compile time (false: the clipped affine map, what every launch but k17's applies)
+template <bool SQUASH, class IO>
+__device__ __forceinline__ auto pol_map_of(const IO& io, const int nc) {
+  if constexpr (SQUASH) return pol_squash_map(io, nc);
+  else return pol_act_map(io, nc);
+}
+
 // log pi(a) of the diagonal Gaussian, both components summed (they sit on neighbouring lanes: every lane of the wave calls this)
 __device__ __forceinline__ float pol_logp(const float a, const float mu, const float sigma, const float ls) {
   const float z = (a - mu) / sigma;
@@ -181,7 +202,9 @@ __device__ __forceinline__ void pol_act_fill_obs(float* X, const auv_policy_io_t
   else pol_fill_range<float>(X, ldx, src, dstO, rows * K0, K0, tid);
 }
 
-// wave 0, behind the trunk: `o` the last layer's outputs, `ls` the log-std the trunk returned
+// wave 0, behind the trunk: `o` the last layer's outputs, `ls` the log-std the trunk returned.  SQUASH: what actions_out gets of the
+// sample (pol_map_of); A, LP and everything else stored are the same either way
+template <bool SQUASH = false>
 __device__ __forceinline__ void pol_act_sample(const auv_policy_io_t& io, const PolAct& p, const f32x4 (*o)[POL_MT], const float ls,
                                                const int lane) {
   const int n = lane & 15, g = lane >> 4;
@@ -190,7 +213,7 @@ __device__ __forceinline__ void pol_act_sample(const auv_policy_io_t& io, const 
     // ---- diagonal Gaussian: sample, log-probability, action ----
     const int nc = pol_comp(lane);
     const float sigma = expf(ls);
-    const PolActMap map = pol_act_map(io, nc);
+    const auto map = pol_map_of<SQUASH>(io, nc);
 #pragma unroll
     for (int u = 0; u < POL_MT; u++)
 #pragma unroll
@@ -254,6 +277,89 @@ __device__ __forceinline__ void pol_act_end(const auv_policy_io_t& io, const Pol
       if (t <= io.T) io.ctr[0] = t + 1;                            // (a flush call leaves T + 1: further calls do nothing)
       io.ctr[1] = (long long)(p.gstep + 1);
     }
+  }
+}
+
+// ---- the frame of an EVAL launch (k9_policy_eval, k17_squash_eval): grid (ceil(M / 16), nets launched), no environment, no
+// rollout position, no counters, no sampling ----
+struct EvalArgs {
+  auv_policy_eval_t ev;
+  int32_t net0;                      // blockIdx.y = 0 evaluates this net (0 policy, 1 value): only the nets asked for are launched
+  int32_t vec2;                      // every source row starts 8-byte aligned and holds an even number of floats (host-proven)
+};
+
+// rows of a strided matrix, optionally gathered through ev.idx, -> the tile.  V = float2: ldx and obs_dim even and the base 8-byte
+// aligned, so no pair straddles two rows or an 8-byte boundary
+template <class V>
+__device__ __forceinline__ void eval_fill_rows(float* X, const int ldx, const auv_policy_eval_t& ev, const int r0, const int rows, const int tid) {
+  constexpr int W = sizeof(V) / sizeof(float);
+  const int K0 = ev.obs_dim;
+  const size_t lds = (size_t)ev.ldx;
+  for (int i = W * tid; i < rows * K0; i += W * POL_THREADS) {
+    const int row = i / K0, c = i - row * K0;
+    const size_t srow = ev.idx ? (size_t)ev.idx[r0 + row] : (size_t)(r0 + row);
+    *(V*)(X + row * ldx + c) = *(const V*)(ev.X + srow * lds + c);
+  }
+}
+
+// The launch's body, written once for every hidden-width triple A (PolArch, auv_policy_mfma.h).  SQUASH: the deterministic action is
+// act_mid + act_half * tanh(mu) (k17_squash_eval); mean, value and log pi(a) are the same either way.
+template <class A, bool SQUASH = false>
+__device__ __forceinline__ void policy_eval_body(const EvalArgs& ea) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const auv_policy_eval_t& ev = ea.ev;
+  const int tid = threadIdx.x, wave = tid / AUV_WAVE, lane = tid % AUV_WAVE;
+  const int net = ea.net0 + blockIdx.y;
+  const int M = ev.M;
+  const int r0 = blockIdx.x * POL_ROWS;                          // first row of the tile (M <= 2^31 - 1: no overflow)
+  const int K0 = ev.obs_dim, K0p = pol_pad16(K0);
+  float* X = (float*)smem;
+  const int ldx = pol_ldx(K0);
+  const PolNet nw = pol_net_ptrs<A>(ev.params + (size_t)net * pol_net_floats<A>(K0), K0);
+  PolW<A::H1 / 16, false> w1;
+  pol_prefetch(w1, nw.W1, nw.b1, K0p, wave, lane);                 // (in flight while the rows are fetched)
+  // ---- the tile's rows -> LDS; padding columns and the rows past M stay zero ----
+  const int rows = (M - r0 < POL_ROWS) ? M - r0 : POL_ROWS;
+  pol_zero_tile(X, ldx, tid);
+  __syncthreads();
+  if (ea.vec2) eval_fill_rows<float2>(X, ldx, ev, r0, rows, tid);
+  else eval_fill_rows<float>(X, ldx, ev, r0, rows, tid);
+  const bool want_lp = ev.logp != nullptr;                       // (uniform)
+  f32x4 o[1][POL_MT];
+  const float ls = pol_trunk<false, A>(X, K0, nw, w1, (wave == 0 && net == 0 && want_lp) ? ev.params + 2 * pol_net_floats<A>(K0) : nullptr, wave, lane, o);
+  if (wave != 0) return;
+  const int n = lane & 15, g = lane >> 4;
+  if (net == 0) {
+    const float sigma = expf(ls);
+    const auto map = pol_map_of<SQUASH>(ev, pol_comp(lane));
+#pragma unroll
+    for (int u = 0; u < POL_MT; u++)
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int rr = 16 * u + 4 * g + i;                       // row inside the tile
+        const int row = r0 + rr;
+        const bool live = n < 2 && rr < rows;
+        const float mu = o[0][u][i];
+        float lp = 0.0f;
+        if (want_lp) {
+          // log pi(a): the rollout launch's own function (the bits of LP[t] for the a the rollout stored)
+          const float a = live ? ev.A[2 * (size_t)row + n] : mu;
+          lp = pol_logp(a, mu, sigma, ls);
+        }
+        if (live) {
+          if (ev.mu) ev.mu[2 * (size_t)row + n] = mu;
+          if (ev.action) ev.action[(size_t)row * (size_t)ev.action_ld + n] = map(mu);
+          if (want_lp && n == 0) ev.logp[row] = lp;
+        }
+      }
+  } else if (n == 0) {
+#pragma unroll
+    for (int u = 0; u < POL_MT; u++)
+#pragma unroll
+      for (int i = 0; i < 4; i++) {
+        const int rr = 16 * u + 4 * g + i;
+        if (rr < rows) ev.value[r0 + rr] = o[0][u][i];
+      }
   }
 }
 

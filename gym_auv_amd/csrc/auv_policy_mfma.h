@@ -98,6 +98,14 @@ __device__ __forceinline__ float pol_tanh(const float x) {
 #endif
 }
 
+// tanh of a squashed policy's action (PolSquashMap, the squash head of the update): (1 - t) / (1 + t), t = exp(-2 |u|), with the
+// library's expf and a rounded division.  Odd bit for bit (|u| goes in, the sign comes back on), exactly +-1 from t < 2^-25 on
+// (|u| > 8.7) and for u = +-inf, never NaN for a u that is not; absolute error ~1e-7 (the rounding of t near 1).
+__device__ __forceinline__ float pol_squash_tanh(const float u) {
+  const float t = expf(-2.0f * fabsf(u));
+  return copysignf((1.0f - t) / (1.0f + t), u);
+}
+
 // One layer for this wave's n-tiles: Y = tanh(X W^T + b) (or the raw pre-activation rows of the last layer).
 //   X  LDS [16][ldx], columns [0, Kp) valid (zero padded); W global, the [N][Kp] matrix of torch's Linear.weight (K padded
 //   to a multiple of 32) re-ordered into MFMA fragment order; wave w takes the n-tiles w, w + 4, ... (NT of them).

@@ -8,6 +8,10 @@
 
 #define AUV_PPO_MAX_SPLIT 16       // split-K factor of the weight-gradient pass (workgroups per output unit), at most
 #define AUV_PPO_NORM_BLOCKS 64     // partial sums of squares per gradient-norm launch
+// the heads of the row pass (auv_ppo_pass.h, ppo_head): which kernel a launch or auv_ppo_prepare means
+#define AUV_PPO_HEAD_PPO 0
+#define AUV_PPO_HEAD_CLONE 1
+#define AUV_PPO_HEAD_SQUASH 2
 
 // Device memory of one updater of hidden widths (H1, H2, H3), a triple of POL_ARCH_LIST (auv_policy_mfma.h); the widths themselves are
 // not stored here: the kernels take them as a template parameter, the host keeps them beside this struct.  Every matrix of the row pass' scratch is stored in 16 x 16 blocks [row tile][column tile][256]:
@@ -24,6 +28,7 @@ struct AuvPpoDev {
   float* part;         // [AUV_PPO_MAX_SPLIT][2][net floats]: split-K partials of dW (row-major, padded like the forward copy) and db
   float* tstat;        // [rt][8]: per row tile sum pg, sum vf, max |adv|, max ratio, non-finite inputs, clipped rows, d log_std[2]
                        // (k8_clone: sum bc, sum vf, max |a - mu|, sum w, non-finite inputs, 0, d log_std[2])
+                       // and behind them [rt_max]: the squash head's sum of log(1 - tanh^2 a) per row tile (its reduction alone reads it)
   double* sqpart;      // [AUV_PPO_NORM_BLOCKS][2]: partial sums of squares of the policy and the value group
   float* pol;          // attached auv_policy_io::params buffer (nullable)
 };
@@ -39,18 +44,21 @@ size_t auv_ppo_param_floats_impl(int obs_dim, const auv_policy_arch_t& a);
 size_t auv_ppo_fwd_floats(int obs_dim, const auv_policy_arch_t& a);
 size_t auv_ppo_tr_floats(const auv_policy_arch_t& a);
 size_t auv_ppo_lds_bytes(int obs_dim, const auv_policy_arch_t& a);
-hipError_t auv_ppo_prepare(int obs_dim, const auv_policy_arch_t& a, bool clone = false);    // clone: the row pass of auv_ppo_grad_clone
+hipError_t auv_ppo_prepare(int obs_dim, const auv_policy_arch_t& a, int head = AUV_PPO_HEAD_PPO);    // head: whose row pass (AUV_PPO_HEAD_*)
 void auv_launch_ppo_load(const AuvPpoDev& d, const auv_policy_arch_t& a, const float* theta, hipStream_t st);
 void auv_launch_ppo_grad(const AuvPpoDev& d, const auv_policy_arch_t& a, const auv_ppo_batch_t& b, float* grad, float* stats, hipStream_t st);
 void auv_launch_ppo_grad_clone(const AuvPpoDev& d, const auv_policy_arch_t& a, const auv_ppo_clone_batch_t& b, float* grad, float* stats,
                                hipStream_t st);
+void auv_launch_ppo_grad_squash(const AuvPpoDev& d, const auv_policy_arch_t& a, const auv_ppo_squash_batch_t& b, float* grad, float* stats,
+                                hipStream_t st);
 void auv_launch_ppo_adam(const AuvPpoDev& d, const auv_policy_arch_t& a, float* theta, float* m, float* v, const float* grad,
                          const AuvPpoAdamDev& h, float* norms_out, hipStream_t st);
 // k8_ppo_update.hip: the same at the reference's widths
-hipError_t auv_k8_ppo_prepare(int obs_dim, bool clone);
+hipError_t auv_k8_ppo_prepare(int obs_dim, int head);
 void auv_k8_ppo_load(const AuvPpoDev& d, const float* theta, hipStream_t st);
 void auv_k8_ppo_grad(const AuvPpoDev& d, const auv_ppo_batch_t& b, float* grad, float* stats, hipStream_t st);
 void auv_k8_ppo_grad_clone(const AuvPpoDev& d, const auv_ppo_clone_batch_t& b, float* grad, float* stats, hipStream_t st);
+void auv_k8_ppo_grad_squash(const AuvPpoDev& d, const auv_ppo_squash_batch_t& b, float* grad, float* stats, hipStream_t st);
 void auv_k8_ppo_adam(const AuvPpoDev& d, float* theta, float* m, float* v, const float* grad, const AuvPpoAdamDev& h, float* norms_out,
                      hipStream_t st);
 #endif /* AUV_PPO_H */

@@ -81,7 +81,8 @@ __device__ inline PpoWhere ppo_where(long long p, const int D, const int K0p) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- row pass
-template <class Batch>                                             // auv_ppo_batch_t: the PPO head; auv_ppo_clone_batch_t: the supervised head
+template <class Batch>                                             // auv_ppo_batch_t: the PPO head; auv_ppo_squash_batch_t: PPO with the squashed
+                                                                   // distribution's entropy; auv_ppo_clone_batch_t: the supervised head
 struct RowArgs {
   AuvPpoDev d;
   Batch b;
@@ -128,10 +129,16 @@ __device__ __forceinline__ void ppo_back_store(f32x4 (*o)[POL_MT], const float* 
 
 // The head of k8_rows (wave 0, between the forward and the backward pass): o = this lane's four rows 4 g + i of output column n of
 // the net (the policy's mean, the value), srow the tile's source rows (-1: padding).  Returns d loss / d o and writes the tile's
-// statistics; the overload on the batch's type is the supervised head of k8_clone.
-template <class A>
-__device__ __forceinline__ f32x4 ppo_head(const AuvPpoDev& d, const auv_ppo_batch_t& b, const int net, const int rt, const int lane, const f32x4 o,
-                                          const long long* __restrict__ srow, const int* __restrict__ nbad) {
+// statistics; the overloads on the batch's type pick the head: PPO's (SQUASH false), PPO's with the squashed distribution's entropy
+// (true, auv_ppo_squash_batch_t: the same fields), the supervised head of k8_clone below.
+//   SQUASH (include/auv_hip.h, auv_ppo_grad_squash): ent_i = sum_k [0.5 + log sqrt(2 pi) + log_std_k + log(1 - tanh^2 a_ik)] of the
+//   STORED action a = mu + sigma sg(z), log(1 - tanh^2 a) = 2 (log 2 - |a| - log1p(exp(-2 |a|))).  On top of PPO's gradients:
+//   d loss / d mu_ik += ent_coef 2 tanh(a_ik) / B;  d loss / d log_std_k += ent_coef (1 / B) sum_i 2 tanh(a_ik) (a_ik - mu_ik) (folded
+//   into the tile's d log_std slots: the reduction still subtracts the constant ent_coef).  The tile's sum of log(1 - tanh^2) goes to
+//   a ninth slot behind the [rt_max][8] table.  With ent_coef == 0 nothing is added anywhere: PPO's bits.
+template <class A, bool SQUASH, class Batch>
+__device__ __forceinline__ f32x4 ppo_head_pg(const AuvPpoDev& d, const Batch& b, const int net, const int rt, const int lane, const f32x4 o,
+                                             const long long* __restrict__ srow, const int* __restrict__ nbad) {
   const size_t netf = pol_net_floats<A>(d.obs_dim);
   const int B = b.B;
   const int n = lane & 15, g = lane >> 4;
@@ -144,6 +151,8 @@ __device__ __forceinline__ f32x4 ppo_head(const AuvPpoDev& d, const auv_ppo_batc
     const float sigma = expf(ls);
     const float lo = 1.0f - b.clip, hi = 1.0f + b.clip;
     float s_pg = 0.0f, s_clip = 0.0f, s_dls = 0.0f, mx_adv = 0.0f, mx_ratio = 0.0f;
+    float s_lj = 0.0f, s_tu = 0.0f;                                // SQUASH: sums of log(1 - tanh^2 a) and of 2 tanh(a) (a - mu)
+    const bool ent_on = SQUASH && b.ent_coef != 0.0f;
     int bad = 0;
 #pragma unroll
     for (int i = 0; i < 4; i++) {
@@ -164,6 +173,12 @@ __device__ __forceinline__ f32x4 ppo_head(const AuvPpoDev& d, const auv_ppo_batc
         d4[i] = glp * ((a - mu) / (sigma * sigma));
         s_dls += glp * (z * z - 1.0f);
         bad += ppo_bad(a);
+        if (SQUASH) {
+          const float au = fabsf(a), th2 = 2.0f * pol_squash_tanh(a);
+          s_lj += 2.0f * (0.6931471805599453f - au - log1pf(expf(-2.0f * au)));
+          s_tu += th2 * (a - mu);
+          if (ent_on) d4[i] += b.ent_coef * th2 * invB;
+        }
       }
       if (valid && n == 0) {
         s_pg += pgi, s_clip += clipped ? 1.0f : 0.0f;
@@ -177,8 +192,14 @@ __device__ __forceinline__ f32x4 ppo_head(const AuvPpoDev& d, const auv_ppo_batc
       s_pg += __shfl_xor(s_pg, sh, AUV_WAVE), s_clip += __shfl_xor(s_clip, sh, AUV_WAVE), s_dls += __shfl_xor(s_dls, sh, AUV_WAVE);
       mx_adv = fmaxf(mx_adv, __shfl_xor(mx_adv, sh, AUV_WAVE)), mx_ratio = fmaxf(mx_ratio, __shfl_xor(mx_ratio, sh, AUV_WAVE));
       bad += __shfl_xor(bad, sh, AUV_WAVE);
+      if (SQUASH) s_lj += __shfl_xor(s_lj, sh, AUV_WAVE), s_tu += __shfl_xor(s_tu, sh, AUV_WAVE);
     }
     bad += __shfl_xor(bad, 1, AUV_WAVE);                         // (lane 1 counted the second action component)
+    if (SQUASH) {
+      if (ent_on) s_dls += b.ent_coef * invB * s_tu;
+      s_lj += __shfl_xor(s_lj, 1, AUV_WAVE);
+      if (lane == 0) d.tstat[8 * (size_t)d.rt_max + rt] = s_lj;
+    }
     if (lane == 0) ts[0] = s_pg, ts[2] = mx_adv, ts[3] = mx_ratio, ts[4] = (float)(bad + *nbad), ts[5] = s_clip, ts[6] = s_dls;
     if (lane == 1) ts[7] = s_dls;
   } else {
@@ -196,6 +217,17 @@ __device__ __forceinline__ f32x4 ppo_head(const AuvPpoDev& d, const auv_ppo_batc
     if (lane == 0) ts[1] = s_vf;
   }
   return d4;
+}
+
+template <class A>
+__device__ __forceinline__ f32x4 ppo_head(const AuvPpoDev& d, const auv_ppo_batch_t& b, const int net, const int rt, const int lane, const f32x4 o,
+                                          const long long* __restrict__ srow, const int* __restrict__ nbad) {
+  return ppo_head_pg<A, false>(d, b, net, rt, lane, o, srow, nbad);
+}
+template <class A>
+__device__ __forceinline__ f32x4 ppo_head(const AuvPpoDev& d, const auv_ppo_squash_batch_t& b, const int net, const int rt, const int lane,
+                                          const f32x4 o, const long long* __restrict__ srow, const int* __restrict__ nbad) {
+  return ppo_head_pg<A, true>(d, b, net, rt, lane, o, srow, nbad);
 }
 
 // The supervised head of k8_clone (include/auv_hip.h, auv_ppo_grad_clone): the policy towards the target actions A (kind 0: the
@@ -475,8 +507,9 @@ struct RedArgs {
   float vf_coef, ent_coef;
 };
 
-// blocks 0 .. ceil(P / 256) - 1: the flat gradient; the last block: statistics and the log_std gradient
-template <class A>
+// blocks 0 .. ceil(P / 256) - 1: the flat gradient; the last block: statistics and the log_std gradient.  SQ: the tiles are the squash
+// head's -- a ninth sum, of log(1 - tanh^2 a), lies behind the table; the entropy of the loss and of slot 7 is the squashed one
+template <class A, bool SQ = false>
 __global__ void __launch_bounds__(256) k8_reduce(RedArgs a) {
   const AuvPpoDev& d = a.d;
   const int tid = threadIdx.x;
@@ -491,7 +524,8 @@ __global__ void __launch_bounds__(256) k8_reduce(RedArgs a) {
     a.grad[p] = s;
     return;
   }
-  __shared__ float red[8][256];
+  constexpr int JQ = SQ ? 8 : 0;                                  // the ninth row (SQ only)
+  __shared__ float red[SQ ? 9 : 8][256];
   float v[8] = {0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f, 0.0f};
   for (int t = tid; t < a.rt; t += 256) {
     const float* ts = d.tstat + 8 * (size_t)t;
@@ -500,12 +534,18 @@ __global__ void __launch_bounds__(256) k8_reduce(RedArgs a) {
   }
 #pragma unroll
   for (int j = 0; j < 8; j++) red[j][tid] = v[j];
+  if (SQ) {
+    float vq = 0.0f;
+    for (int t = tid; t < a.rt; t += 256) vq += d.tstat[8 * (size_t)d.rt_max + t];
+    red[JQ][tid] = vq;
+  }
   __syncthreads();
   for (int h = 128; h >= 1; h >>= 1) {
     if (tid < h) {
 #pragma unroll
       for (int j = 0; j < 8; j++)
         red[j][tid] = (j == 2 || (j == 3 && !a.clone)) ? fmaxf(red[j][tid], red[j][tid + h]) : red[j][tid] + red[j][tid + h];
+      if (SQ) red[JQ][tid] += red[JQ][tid + h];
     }
     __syncthreads();
   }
@@ -513,10 +553,11 @@ __global__ void __launch_bounds__(256) k8_reduce(RedArgs a) {
     const float invB = 1.0f / (float)a.B;
     const float* ls = d.fwd + 2 * pol_net_floats<A>(d.obs_dim);
     const float pg = red[0][0] * invB, vf = red[1][0] * invB;
-    const float ent = (0.5f + POL_LOG_SQRT_2PI + ls[0]) + (0.5f + POL_LOG_SQRT_2PI + ls[1]);
+    float ent = (0.5f + POL_LOG_SQRT_2PI + ls[0]) + (0.5f + POL_LOG_SQRT_2PI + ls[1]);
+    if (SQ) ent += red[JQ][0] * invB;                              // + mean_i sum_k log(1 - tanh^2 a_ik)
     a.stats[0] = pg + a.vf_coef * vf - a.ent_coef * ent;
     a.stats[1] = pg, a.stats[2] = vf, a.stats[3] = red[2][0], a.stats[4] = red[3][0], a.stats[5] = red[4][0];
-    a.stats[6] = red[5][0] * invB, a.stats[7] = 0.0f;
+    a.stats[6] = red[5][0] * invB, a.stats[7] = SQ ? ent : 0.0f;
     a.grad[a.P - 2] = red[6][0] - a.ent_coef;
     a.grad[a.P - 1] = red[7][0] - a.ent_coef;
   }
@@ -596,18 +637,19 @@ __global__ void __launch_bounds__(256) k8_adam(AdamArgs a) {
 }
 
 // ------------------------------------------------------------------------------------------------------- host: the launches
-// K names a translation unit's two row-pass kernels of width A, rows and clone (pointers to __global__ functions); every other kernel is a
-// template of this header.
+// K names a translation unit's three row-pass kernels of width A -- rows, clone and squash (pointers to __global__ functions), picked by
+// a head number (auv_ppo.h, AUV_PPO_HEAD_*); every other kernel is a template of this header.
 template <class A>
 inline size_t ppo_lds_bytes(int obs_dim) { return sizeof(float) * ppo_lds_floats_h(A::H1, A::H2, A::H3, obs_dim); }
 
 // The dynamic LDS a row pass may ask for is an attribute of the KERNEL -- of the one instantiation that is launched -- not of an updater: it is
 // set in front of every launch that needs more than the 64 KiB a kernel gets unasked, so updaters of different widths can live side by side.
 template <class A, class K>
-inline hipError_t ppo_prepare(int obs_dim, bool clone) {
+inline hipError_t ppo_prepare(int obs_dim, int head) {
   const size_t b = ppo_lds_bytes<A>(obs_dim);
   if (b <= 64 * 1024) return hipSuccess;
-  return hipFuncSetAttribute(clone ? (const void*)K::clone : (const void*)K::rows, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  const void* k = head == AUV_PPO_HEAD_CLONE ? (const void*)K::clone : head == AUV_PPO_HEAD_SQUASH ? (const void*)K::squash : (const void*)K::rows;
+  return hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
 }
 
 // The split-K factor, a function of B, obs_dim and the widths alone (so the summation order is): about 16 row tiles per wave for large
@@ -628,9 +670,11 @@ inline void ppo_launch_load(const AuvPpoDev& d, const float* theta, hipStream_t 
   hipLaunchKernelGGL((k8_adam<A, true>), dim3((unsigned)((a.P + 255) / 256)), dim3(256), 0, st, a);
 }
 
-// the launches behind a row pass: weight gradients, then the flat gradient and the statistics
+// the launches behind a row pass: weight gradients, then the flat gradient and the statistics (squash: the reduction that reads the
+// squash head's ninth slot; the two other modes launch what they always did)
 template <class A>
-inline void ppo_launch_after_rows(const AuvPpoDev& d, int B, bool clone, float vf_coef, float ent_coef, float* grad, float* stats, hipStream_t st) {
+inline void ppo_launch_after_rows(const AuvPpoDev& d, int B, bool clone, float vf_coef, float ent_coef, float* grad, float* stats, hipStream_t st,
+                                  bool squash = false) {
   const int rt = (B + 15) / 16, nsplit = ppo_nsplit<A>(rt, d.k0p);
   WgArgs wa;
   wa.d = d, wa.rt = rt, wa.nsplit = nsplit;
@@ -638,7 +682,8 @@ inline void ppo_launch_after_rows(const AuvPpoDev& d, int B, bool clone, float v
   RedArgs re;
   re.d = d, re.grad = grad, re.stats = stats, re.P = (long long)ppo_params<A>(d.obs_dim);
   re.nsplit = nsplit, re.rt = rt, re.B = B, re.clone = clone, re.vf_coef = vf_coef, re.ent_coef = ent_coef;
-  hipLaunchKernelGGL(k8_reduce<A>, dim3((unsigned)((re.P + 255) / 256) + 1), dim3(256), 0, st, re);
+  if (squash) hipLaunchKernelGGL((k8_reduce<A, true>), dim3((unsigned)((re.P + 255) / 256) + 1), dim3(256), 0, st, re);
+  else hipLaunchKernelGGL(k8_reduce<A>, dim3((unsigned)((re.P + 255) / 256) + 1), dim3(256), 0, st, re);
 }
 
 template <class A, class K>
@@ -655,6 +700,14 @@ inline void ppo_launch_grad_clone(const AuvPpoDev& d, const auv_ppo_clone_batch_
   ra.d = d, ra.b = b;
   hipLaunchKernelGGL(K::clone, dim3((b.B + 15) / 16, 2), dim3(POL_THREADS), ppo_lds_bytes<A>(d.obs_dim), st, ra);
   ppo_launch_after_rows<A>(d, b.B, true, b.vf_coef, b.ent_coef, grad, stats, st);
+}
+
+template <class A, class K>
+inline void ppo_launch_grad_squash(const AuvPpoDev& d, const auv_ppo_squash_batch_t& b, float* grad, float* stats, hipStream_t st) {
+  RowArgs<auv_ppo_squash_batch_t> ra;
+  ra.d = d, ra.b = b;
+  hipLaunchKernelGGL(K::squash, dim3((b.B + 15) / 16, 2), dim3(POL_THREADS), ppo_lds_bytes<A>(d.obs_dim), st, ra);
+  ppo_launch_after_rows<A>(d, b.B, false, b.vf_coef, b.ent_coef, grad, stats, st, true);
 }
 
 template <class A>

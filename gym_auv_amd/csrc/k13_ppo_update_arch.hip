@@ -18,9 +18,13 @@ template <class A>
 __global__ void __launch_bounds__(POL_THREADS, 4) k13_ppo_clone(RowArgs<auv_ppo_clone_batch_t> ra) { ppo_row_pass<A>(ra.d, ra.b, blockIdx.y, blockIdx.x); }
 
 template <class A>
+__global__ void __launch_bounds__(POL_THREADS, 4) k13_ppo_squash(RowArgs<auv_ppo_squash_batch_t> ra) { ppo_row_pass<A>(ra.d, ra.b, blockIdx.y, blockIdx.x); }
+
+template <class A>
 struct K13 {
   static constexpr auto rows = k13_ppo_rows<A>;
   static constexpr auto clone = k13_ppo_clone<A>;
+  static constexpr auto squash = k13_ppo_squash<A>;
 };
 
 // ref() for the reference's triple, other(PolArch<...>{}) for any other listed one: only those instantiate kernels here
@@ -39,10 +43,10 @@ size_t auv_ppo_fwd_floats(int obs_dim, const auv_policy_arch_t& a) { return 2 * 
 size_t auv_ppo_tr_floats(const auv_policy_arch_t& a) { return 2 * ppo_tr_floats_h(a.h1, a.h2, a.h3); }
 size_t auv_ppo_lds_bytes(int obs_dim, const auv_policy_arch_t& a) { return sizeof(float) * ppo_lds_floats_h(a.h1, a.h2, a.h3, obs_dim); }
 
-hipError_t auv_ppo_prepare(int obs_dim, const auv_policy_arch_t& a, bool clone) {
+hipError_t auv_ppo_prepare(int obs_dim, const auv_policy_arch_t& a, int head) {
   hipError_t e = hipErrorInvalidValue;                               // (an unlisted triple: refused before, in auv_ppo_create_arch)
-  ppo_dispatch(a, [&] { e = auv_k8_ppo_prepare(obs_dim, clone); },
-               [&](auto t) { e = ppo_prepare<decltype(t), K13<decltype(t)>>(obs_dim, clone); });
+  ppo_dispatch(a, [&] { e = auv_k8_ppo_prepare(obs_dim, head); },
+               [&](auto t) { e = ppo_prepare<decltype(t), K13<decltype(t)>>(obs_dim, head); });
   return e;
 }
 
@@ -59,6 +63,12 @@ void auv_launch_ppo_grad_clone(const AuvPpoDev& d, const auv_policy_arch_t& a, c
                                hipStream_t st) {
   ppo_dispatch(a, [&] { auv_k8_ppo_grad_clone(d, b, grad, stats, st); },
                [&](auto t) { ppo_launch_grad_clone<decltype(t), K13<decltype(t)>>(d, b, grad, stats, st); });
+}
+
+void auv_launch_ppo_grad_squash(const AuvPpoDev& d, const auv_policy_arch_t& a, const auv_ppo_squash_batch_t& b, float* grad, float* stats,
+                                hipStream_t st) {
+  ppo_dispatch(a, [&] { auv_k8_ppo_grad_squash(d, b, grad, stats, st); },
+               [&](auto t) { ppo_launch_grad_squash<decltype(t), K13<decltype(t)>>(d, b, grad, stats, st); });
 }
 
 void auv_launch_ppo_adam(const AuvPpoDev& d, const auv_policy_arch_t& a, float* theta, float* m, float* v, const float* grad,

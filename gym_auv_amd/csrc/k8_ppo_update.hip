@@ -17,6 +17,8 @@
 //              output tiles of one row of tiles, four waves on four row ranges, summed in a fixed order.
 //   k8_reduce  sums the split partials in a fixed order into the flat gradient (torch layout), and the tile statistics.
 // auv_ppo_grad_clone: the same three with k8_clone in place of k8_rows -- the same row pass with a supervised head (ppo_head).
+// auv_ppo_grad_squash: the same three with k8_squash -- PPO's head with the entropy of the tanh-squashed distribution, estimated on the
+// stored actions (ppo_head_pg<SQUASH>), and the reduction that also reads its ninth per-tile sum (k8_reduce<A, true>).
 // Launches of auv_ppo_adam: k8_norm (partial sums of squares per group), k8_adam (clip, Adam, and the scatter of every updated
 // weight into the forward copy, the transposed copy and an attached auv_policy_io::params buffer).
 // No floating-point atomics anywhere: every sum crosses workgroups through memory and a kernel boundary, in an order that depends
@@ -36,20 +38,29 @@ __global__ void __launch_bounds__(POL_THREADS, 4) k8_clone(RowArgs<auv_ppo_clone
   ppo_row_pass<PolArchRef>(ra.d, ra.b, blockIdx.y, blockIdx.x);
 }
 
+// the same grid with the squashed distribution's entropy in PPO's head: the row pass of auv_ppo_grad_squash
+__global__ void __launch_bounds__(POL_THREADS, 4) k8_squash(RowArgs<auv_ppo_squash_batch_t> ra) {
+  ppo_row_pass<PolArchRef>(ra.d, ra.b, blockIdx.y, blockIdx.x);
+}
+
 struct K8 {
   static constexpr auto rows = k8_rows;
   static constexpr auto clone = k8_clone;
+  static constexpr auto squash = k8_squash;
 };
 
 }  // namespace
 
-hipError_t auv_k8_ppo_prepare(int obs_dim, bool clone) { return ppo_prepare<PolArchRef, K8>(obs_dim, clone); }
+hipError_t auv_k8_ppo_prepare(int obs_dim, int head) { return ppo_prepare<PolArchRef, K8>(obs_dim, head); }
 void auv_k8_ppo_load(const AuvPpoDev& d, const float* theta, hipStream_t st) { ppo_launch_load<PolArchRef>(d, theta, st); }
 void auv_k8_ppo_grad(const AuvPpoDev& d, const auv_ppo_batch_t& b, float* grad, float* stats, hipStream_t st) {
   ppo_launch_grad<PolArchRef, K8>(d, b, grad, stats, st);
 }
 void auv_k8_ppo_grad_clone(const AuvPpoDev& d, const auv_ppo_clone_batch_t& b, float* grad, float* stats, hipStream_t st) {
   ppo_launch_grad_clone<PolArchRef, K8>(d, b, grad, stats, st);
+}
+void auv_k8_ppo_grad_squash(const AuvPpoDev& d, const auv_ppo_squash_batch_t& b, float* grad, float* stats, hipStream_t st) {
+  ppo_launch_grad_squash<PolArchRef, K8>(d, b, grad, stats, st);
 }
 void auv_k8_ppo_adam(const AuvPpoDev& d, float* theta, float* m, float* v, const float* grad, const AuvPpoAdamDev& h, float* norms_out,
                      hipStream_t st) {

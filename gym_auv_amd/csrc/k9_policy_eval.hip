@@ -16,86 +16,8 @@
 
 namespace {
 
-struct EvalArgs {
-  auv_policy_eval_t ev;
-  int32_t net0;                      // blockIdx.y = 0 evaluates this net (0 policy, 1 value): only the nets asked for are launched
-  int32_t vec2;                      // every source row starts 8-byte aligned and holds an even number of floats (host-proven)
-};
-
-// rows of a strided matrix, optionally gathered through ev.idx, -> the tile.  V = float2: ldx and obs_dim even and the base 8-byte
-// aligned, so no pair straddles two rows or an 8-byte boundary
-template <class V>
-__device__ __forceinline__ void eval_fill_rows(float* X, const int ldx, const auv_policy_eval_t& ev, const int r0, const int rows, const int tid) {
-  constexpr int W = sizeof(V) / sizeof(float);
-  const int K0 = ev.obs_dim;
-  const size_t lds = (size_t)ev.ldx;
-  for (int i = W * tid; i < rows * K0; i += W * POL_THREADS) {
-    const int row = i / K0, c = i - row * K0;
-    const size_t srow = ev.idx ? (size_t)ev.idx[r0 + row] : (size_t)(r0 + row);
-    *(V*)(X + row * ldx + c) = *(const V*)(ev.X + srow * lds + c);
-  }
-}
-
-// The launch's body, written once for every hidden-width triple A (PolArch, auv_policy_mfma.h).
-template <class A>
-__device__ __forceinline__ void policy_eval_body(const EvalArgs& ea) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  const auv_policy_eval_t& ev = ea.ev;
-  const int tid = threadIdx.x, wave = tid / AUV_WAVE, lane = tid % AUV_WAVE;
-  const int net = ea.net0 + blockIdx.y;
-  const int M = ev.M;
-  const int r0 = blockIdx.x * POL_ROWS;                          // first row of the tile (M <= 2^31 - 1: no overflow)
-  const int K0 = ev.obs_dim, K0p = pol_pad16(K0);
-  float* X = (float*)smem;
-  const int ldx = pol_ldx(K0);
-  const PolNet nw = pol_net_ptrs<A>(ev.params + (size_t)net * pol_net_floats<A>(K0), K0);
-  PolW<A::H1 / 16, false> w1;
-  pol_prefetch(w1, nw.W1, nw.b1, K0p, wave, lane);                 // (in flight while the rows are fetched)
-  // ---- the tile's rows -> LDS; padding columns and the rows past M stay zero ----
-  const int rows = (M - r0 < POL_ROWS) ? M - r0 : POL_ROWS;
-  pol_zero_tile(X, ldx, tid);
-  __syncthreads();
-  if (ea.vec2) eval_fill_rows<float2>(X, ldx, ev, r0, rows, tid);
-  else eval_fill_rows<float>(X, ldx, ev, r0, rows, tid);
-  const bool want_lp = ev.logp != nullptr;                       // (uniform)
-  f32x4 o[1][POL_MT];
-  const float ls = pol_trunk<false, A>(X, K0, nw, w1, (wave == 0 && net == 0 && want_lp) ? ev.params + 2 * pol_net_floats<A>(K0) : nullptr, wave, lane, o);
-  if (wave != 0) return;
-  const int n = lane & 15, g = lane >> 4;
-  if (net == 0) {
-    const float sigma = expf(ls);
-    const PolActMap map = pol_act_map(ev, pol_comp(lane));
-#pragma unroll
-    for (int u = 0; u < POL_MT; u++)
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const int rr = 16 * u + 4 * g + i;                       // row inside the tile
-        const int row = r0 + rr;
-        const bool live = n < 2 && rr < rows;
-        const float mu = o[0][u][i];
-        float lp = 0.0f;
-        if (want_lp) {
-          // log pi(a): the rollout launch's own function (the bits of LP[t] for the a the rollout stored)
-          const float a = live ? ev.A[2 * (size_t)row + n] : mu;
-          lp = pol_logp(a, mu, sigma, ls);
-        }
-        if (live) {
-          if (ev.mu) ev.mu[2 * (size_t)row + n] = mu;
-          if (ev.action) ev.action[(size_t)row * (size_t)ev.action_ld + n] = map(mu);
-          if (want_lp && n == 0) ev.logp[row] = lp;
-        }
-      }
-  } else if (n == 0) {
-#pragma unroll
-    for (int u = 0; u < POL_MT; u++)
-#pragma unroll
-      for (int i = 0; i < 4; i++) {
-        const int rr = 16 * u + 4 * g + i;
-        if (rr < rows) ev.value[r0 + rr] = o[0][u][i];
-      }
-  }
-}
-
+// (EvalArgs, the gather of the tile's rows and the launch's body, policy_eval_body: auv_policy_forward.h, shared with k17's squashed
+// evaluation)
 // grid (ceil(M / 16), nets launched)
 template <class A>
 __global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k9_policy_eval(EvalArgs ea) {   // (two workgroups per CU, as k6)

@@ -27,6 +27,13 @@ NORMALISED rows, so the fused update, gae() and the clone step take them as they
 they are given.  The statistics are frozen during a rollout and folded behind it (`normalize.fold()`, `normalize.returns(R, Dn)`).  Not
 together with frames > 1 or bf16.
 
+Tanh-squashed actions (what stable-baselines3 calls squash_output; csrc/k17_policy_squash.hip): `FusedActorCritic(net, env, T, squash=True)`
+hands the environment act_mid + act_half * tanh(u) of the sample u = mu + sigma eps -- a bounded action whose entropy the update can see
+(FusedPPOUpdate(..., squash=True)) -- in the place of the clipped affine map; clip_lo / clip_hi are not consulted.  A holds u itself and LP
+its Gaussian log-density, exactly as without the option (the PPO ratio needs no Jacobian), so everything behind the rollout takes the
+buffers as they are; predict() gives act_mid + act_half * tanh(mu), and evaluate() takes PRE-SQUASH actions (rows of A).  Not together
+with frames > 1, normalize, bf16 or a PolicyPopulation: those launches have no squashed variant.
+
 Hidden widths: read off `net.pi` / `net.v` (both the same triple), one of SUPPORTED_HIDDEN -- the reference's [256, 128, 64] and the
 narrower [128, 128, 64], [128, 64, 64], [64, 64, 64] the launches are also compiled for (csrc/auv_policy_mfma.h, POL_ARCH_LIST; the
 auv_policy_*_arch entries).  Anything else raises ValueError; bf16 exists for the reference's widths only.
@@ -143,6 +150,16 @@ def action_map_reference(a, mid, half, lo, hi):
     return mid + half * np.minimum(np.maximum(np.asarray(a, dtype=f), lo), hi)
 
 
+def squash_map_reference(u, mid, half, dtype=np.float64):
+    """mid + half * tanh(u) per component in `dtype`, as PolSquashMap forms it: t = exp(-2 |u|), tanh = copysign((1 - t) / (1 + t), u) --
+    odd bit for bit, exactly +-1 once t drops below half an ulp of 1, never NaN for a finite u.  mid and half are rounded to float32
+    first: the launch takes them as floats.  float64: the reference the tests hold actions_out to; float32: the kernel's own operations."""
+    u = np.asarray(u).astype(dtype)
+    mid, half = (np.asarray(x, dtype=np.float32).astype(dtype) for x in (mid, half))
+    t = _rounded(np.exp, dtype(-2.0) * np.abs(u), dtype)
+    return mid + half * np.copysign((dtype(1.0) - t) / (dtype(1.0) + t), u)
+
+
 def gae_reference(R, V, Dn, last_v, gamma: float, lam: float, dtype=np.float64):
     """(adv, ret) [T, N] of k6_gae's backward recursion in `dtype` and in its order: delta = R + (gamma nv) (1 - Dn) - V,
     adv = delta + ((gamma lam) (1 - Dn)) adv', ret = adv + V.  gamma and lam are rounded to float32 first: the kernel takes them as
@@ -225,7 +242,8 @@ def _eval_check(name: str, t, device, shape_tail, dtype=torch.float32):
 
 def policy_eval(params: torch.Tensor, obs_dim: int, X: torch.Tensor, idx: Optional[torch.Tensor] = None,
                 actions: Optional[torch.Tensor] = None, want: Sequence[str] = ("mu", "value"), action_map=None,
-                out: Optional[Dict[str, torch.Tensor]] = None, hidden=HIDDEN, arch_entry: Optional[bool] = None) -> Dict[str, torch.Tensor]:
+                out: Optional[Dict[str, torch.Tensor]] = None, hidden=HIDDEN, arch_entry: Optional[bool] = None,
+                squash: bool = False) -> Dict[str, torch.Tensor]:
     """auv_policy_eval (csrc/k9_policy_eval.hip) on the caller's current stream: M observation rows through the policy net, the
     value net, or both, in ONE launch -- no environment, no rollout position, no sampling.
 
@@ -242,6 +260,8 @@ def policy_eval(params: torch.Tensor, obs_dim: int, X: torch.Tensor, idx: Option
     hidden      the hidden widths `params` was packed for, one of SUPPORTED_HIDDEN
     arch_entry  None: the default widths go through auv_policy_eval, any other through auv_policy_eval_arch; True: the _arch entry also
                 for the default widths (it dispatches to the same kernel)
+    squash      True: auv_policy_eval_squash -- action = mid + half * tanh(mu), lo and hi are not read; mu, value and logp are the same
+                either way, and `actions` are PRE-SQUASH actions (rows of a rollout's A)
     Returns a dict of the tensors asked for.  Raises ValueError for anything the launch would refuse."""
     want = tuple(want)
     out = dict(out or {})
@@ -313,17 +333,25 @@ def policy_eval(params: torch.Tensor, obs_dim: int, X: torch.Tensor, idx: Option
             ev.act_mid[k], ev.act_half[k], ev.clip_lo[k], ev.clip_hi[k] = float(mid[k]), float(half[k]), float(lo[k]), float(hi[k])
         st = torch.cuda.current_stream(dev)
         dev_i = dev.index if dev.index is not None else torch.cuda.current_device()
+        name = "auv_policy_eval_squash" if squash else "auv_policy_eval"
         if hidden != HIDDEN or arch_entry:
-            _check(_LIB.auv_policy_eval_arch(dev_i, C.byref(ev), C.byref(_arch_arg(hidden)), C.c_void_p(st.cuda_stream)), "auv_policy_eval_arch")
+            _check(getattr(_LIB, name + "_arch")(dev_i, C.byref(ev), C.byref(_arch_arg(hidden)), C.c_void_p(st.cuda_stream)), name + "_arch")
         else:
-            _check(_LIB.auv_policy_eval(dev_i, C.byref(ev), C.c_void_p(st.cuda_stream)), "auv_policy_eval")
+            _check(getattr(_LIB, name)(dev_i, C.byref(ev), C.c_void_p(st.cuda_stream)), name)
     return res
 
 
 class FusedActorCritic:
     def __init__(self, net: nn.Module, env: BatchedAuvEnv, rollout: int, reward_scale: float = 1.0, reward_clip: float = 0.0,
                  act_mid=None, act_half=None, clip_lo=None, clip_hi=None, seed: int = 0, store_obs: bool = True, debug: bool = False,
-                 bf16: bool = False, frames: int = 1, arch_entry: Optional[bool] = None, normalize=None):
+                 bf16: bool = False, frames: int = 1, arch_entry: Optional[bool] = None, normalize=None, squash: bool = False):
+        # squash: the environment receives act_mid + act_half * tanh(u) (module docstring); the plain, exact-f32 launches only
+        self.squash = bool(squash)
+        if self.squash:
+            for bad, what in ((int(frames) > 1, "frames = %d" % int(frames)), (normalize is not None, "normalize"), (bool(bf16), "bf16 = True")):
+                if bad:
+                    raise ValueError("FusedActorCritic: squash = True together with %s -- the stacked, normalising and bf16 launches have no "
+                                     "squashed variant" % what)
         self.net, self.env, self.T = net, env, int(rollout)
         self.device = env.device
         # frames > 1: every environment is evaluated on its last `frames` observations (module docstring); 1: the plain launch
@@ -478,7 +506,13 @@ class FusedActorCritic:
         slice's rows of `self.actions` and the transition at the chain's position t, then moves t on."""
         lo, cnt = self.slices[i]
         st = self.env._sub_streams[i] if stream is None else stream
-        if self._nios is not None:
+        if self.squash:
+            if self._arch is not None:
+                _check(_LIB.auv_policy_act_squash_arch(self.env._h, lo, cnt, C.byref(self._ios[i]), C.byref(self._arch), C.c_void_p(st.cuda_stream)),
+                       "auv_policy_act_squash_arch")
+            else:
+                _check(_LIB.auv_policy_act_squash(self.env._h, lo, cnt, C.byref(self._ios[i]), C.c_void_p(st.cuda_stream)), "auv_policy_act_squash")
+        elif self._nios is not None:
             if self._arch is not None:
                 _check(_LIB.auv_policy_act_norm_arch(self.env._h, lo, cnt, C.byref(self._nios[i]), C.byref(self._arch), C.c_void_p(st.cuda_stream)),
                        "auv_policy_act_norm_arch")
@@ -506,7 +540,16 @@ class FusedActorCritic:
         env = self.env
         k = len(self.slices)
         t0, g0 = (C.c_int64 * k)(*self._t), (C.c_int64 * k)(*self._g)
-        if self._nios is not None:
+        if self.squash:
+            tail = (C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()), int(n_steps),
+                    int(bool(flush)), t0, g0)
+            if self._arch is not None:
+                _check(_LIB.auv_policy_rollout_squash_arch(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._ios,
+                                                           C.byref(self._arch), *tail), "auv_policy_rollout_squash_arch")
+            else:
+                _check(_LIB.auv_policy_rollout_squash(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._ios, *tail),
+                       "auv_policy_rollout_squash")
+        elif self._nios is not None:
             tail = (C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()), int(n_steps),
                     int(bool(flush)), t0, g0)
             if self._arch is not None:
@@ -557,7 +600,7 @@ class FusedActorCritic:
 
     # ------------------------------------------------------------------------------ evaluation outside a rollout
     def _eval_kw(self):
-        return dict(hidden=self.hidden, arch_entry=self._arch is not None)
+        return dict(hidden=self.hidden, arch_entry=self._arch is not None, squash=self.squash)
 
     def _rows(self, obs):
         if obs is None and self.frames > 1:
@@ -578,7 +621,7 @@ class FusedActorCritic:
 
     def predict(self, obs: Optional[torch.Tensor] = None, deterministic: bool = True, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """The deterministic action of the policy -- the reference's agent.predict(obs, deterministic=True) of its enjoy / play /
-        test modes (scripts/run.py:175, 273, 567): act_mid + act_half * clip(mu(obs)), one launch (auv_policy_eval) on the caller's
+        test modes (scripts/run.py:175, 273, 567): act_mid + act_half * clip(mu(obs)) (squash: act_mid + act_half * tanh(mu(obs))), one launch (auv_policy_eval) on the caller's
         current stream, written into `out` (default: `self.actions`, which env.step takes as is).  obs = None: the environment's
         observation buffer (with frames > 1: the stacked row of it, peeked; rows passed in are stacked rows already).  Reads `self.params`: refresh() after optimiser steps, as for rollouts.  Touches no rollout buffer and
         no counter."""
@@ -598,6 +641,7 @@ class FusedActorCritic:
 
     def evaluate(self, obs: torch.Tensor, actions: torch.Tensor):
         """(log pi(actions | obs) [M], value [M], mu [M, 2]) in one launch on the caller's current stream.  With `normalize`, obs are RAW
-        rows (the rows stored in O are normalised already: evaluate those with policy_eval)."""
+        rows (the rows stored in O are normalised already: evaluate those with policy_eval).  With `squash`, `actions` are PRE-SQUASH actions:
+        rows of A, not what the environment received."""
         r = policy_eval(self.params, self.in_dim, self._rows(obs), actions=actions, want=("logp", "value", "mu"), **self._eval_kw())
         return r["logp"], r["value"], r["mu"]

@@ -316,7 +316,10 @@ class PolicyPopulation:
         return h
 
     def __init__(self, env, members: int, rows_per_member: Optional[int] = None, net=None, act_mid=None, act_half=None, clip_lo=None,
-                 clip_hi=None, seed: int = 0, hidden=None):
+                 clip_hi=None, seed: int = 0, hidden=None, squash: bool = False):
+        if squash:
+            raise ValueError("PolicyPopulation: squash = True -- the population launches have no tanh-squashed variant (FusedActorCritic's "
+                             "plain launches do)")
         self.P, self.G = population_geometry(env.n_envs, members, rows_per_member)
         self.hidden = self.resolve_hidden(net, hidden)
         import torch
@@ -364,6 +367,9 @@ class PolicyPopulation:
     def base_state_into(self, fused):
         """`theta` into the policy half of a FusedActorCritic's packed buffer (a slice copy): the champion can then be run through
         fused.predict() / examples/evaluate.py.  The torch modules of `fused` are not touched: do not refresh() afterwards."""
+        if getattr(fused, "squash", False):
+            raise ValueError("base_state_into: the policy was made with squash = True -- the population's members act through the clipped "
+                             "affine map, a squashed predict() would run another policy")
         if int(fused.env.obs_dim) != self.obs_dim:
             raise ValueError("base_state_into: obs_dim %d, the population has %d" % (int(fused.env.obs_dim), self.obs_dim))
         if tuple(getattr(fused, "hidden", HIDDEN)) != self.hidden:

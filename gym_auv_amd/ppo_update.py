@@ -22,6 +22,12 @@ value net towards target values -- a planner's decisions (planning.DistillBuffer
                                                             #       |g_pi|, |g_v|;  kind "mse": squared error of the mean instead
     g, stats = upd.clone_grad(O, A, RET)                    # the two halves, as above
 
+A tanh-squashed policy (policy.FusedActorCritic(..., squash=True)) is trained by an updater made with the CONSTRUCTOR flag
+`FusedPPOUpdate(net, ..., squash=True)` -- one flag per updater, not per call, because it belongs to the policy the rows came from: grad()
+and step() then go through auv_ppo_grad_squash, whose entropy term is the squashed distribution's, estimated on the stored actions
+(squash_loss_terms below is the same loss in stock tensor operations); slot 7 of the record is then the mean entropy.  A holds PRE-SQUASH
+actions and LP their Gaussian log-density, as the squash launches store them.  The clone steps do not look at the flag.
+
 Hidden widths: read off `net.pi` / `net.v` (both the same triple), one of SUPPORTED_HIDDEN -- the reference's [256, 128, 64] and the
 narrower nets the fused forward launches evaluate (policy.SUPPORTED_HIDDEN); anything else raises ValueError.  `upd.hidden` is the triple.
 
@@ -70,13 +76,38 @@ def clone_loss_terms(net, o, a, ret, w=None, kind="nll", vf_coef=0.5, ent_coef=0
     return loss, bc, vf
 
 
+def squash_loss_terms(net, o, a, lp, adv, ret, clip, vf_coef, ent_coef):
+    """The loss of auv_ppo_grad_squash in stock tensor operations, on any device and dtype: (loss, pg, vf, ent).  `net`: pi, v, log_std as
+    examples/ppo.ActorCritic holds them; o [B, D], a [B, 2] STORED (pre-squash) actions, lp [B] their Gaussian log-density under the
+    collecting policy, adv and ret [B].
+        pg, vf: minibatch_step's of examples/ppo.py -- ratio = exp(log N(a; mu, sigma) - lp), the clipped surrogate, 0.5 mean (v - ret)^2
+        ent = mean_i sum_k [0.5 + log sqrt(2 pi) + log_std_k + log(1 - tanh^2 u_ik)],   u = mu + sigma * ((a - mu) / sigma).detach()
+        loss = pg + vf_coef vf - ent_coef ent
+    u has the value of the stored action and the gradient of a reparameterised sample: the noise is held, mu and sigma move it.
+    log(1 - tanh^2 u) = 2 (log 2 - |u| - log1p(exp(-2 |u|))), finite for every finite u."""
+    mu, log_std = net.pi(o), net.log_std
+    sigma = log_std.exp()
+    c = 0.5 * math.log(2.0 * math.pi)
+    z = (a - mu) / sigma
+    logp = (-0.5 * z * z - log_std - c).sum(-1)
+    ratio = (logp - lp).exp()
+    pg = -torch.min(ratio * adv, ratio.clamp(1 - clip, 1 + clip) * adv).mean()
+    vf = 0.5 * ((net.v(o).squeeze(-1) - ret) ** 2).mean()
+    u = mu + sigma * z.detach()
+    au = u.abs()
+    ent = (0.5 + c + log_std + 2.0 * (math.log(2.0) - au - torch.log1p(torch.exp(-2.0 * au)))).sum(-1).mean()
+    loss = pg + vf_coef * vf - ent_coef * ent
+    return loss, pg, vf, ent
+
+
 class FusedPPOUpdate:
     LOG_ROWS = 8192
 
     def __init__(self, net: nn.Module, lr: float = 2e-4, betas: Tuple[float, float] = (0.9, 0.999), eps: float = 1e-8, clip: float = 0.2,
                  vf_coef: float = 0.5, ent_coef: float = 0.01, max_norm_pi: float = 0.5, max_norm_v: float = 0.5, max_batch: int = 16384,
-                 arch_entry: Optional[bool] = None):
-        """arch_entry  None: the default widths go through auv_ppo_create, any other through auv_ppo_create_arch; True: the _arch entries
+                 arch_entry: Optional[bool] = None, squash: bool = False):
+        """squash      True: grad() / step() train a tanh-squashed policy (auv_ppo_grad_squash; module docstring)
+        arch_entry  None: the default widths go through auv_ppo_create, any other through auv_ppo_create_arch; True: the _arch entries
                     also for the default widths (they dispatch to the same kernels: tests compare the two)."""
         tensors = []
         # the hidden widths are read off the modules: both nets the same triple, one of SUPPORTED_HIDDEN
@@ -126,6 +157,7 @@ class FusedPPOUpdate:
         self.clip, self.vf_coef, self.ent_coef = float(clip), float(vf_coef), float(ent_coef)
         self.max_norm_pi, self.max_norm_v = float(max_norm_pi), float(max_norm_v)
         self.max_batch = int(max_batch)
+        self.squash = bool(squash)
         # the record of every step, written by the launches themselves: row = stats[8] + the two norms; read it once per update
         self.log = torch.zeros((self.LOG_ROWS, 10), dtype=torch.float32, device=self.device)
         self.n_steps = 0
@@ -163,6 +195,9 @@ class FusedPPOUpdate:
             raise ValueError("FusedPPOUpdate.attach: the bf16 policy keeps a second copy of the weights that only refresh() packs")
         if getattr(fused, "in_dim", fused.env.obs_dim) != self.obs_dim or fused.params.device != self.device:   # (in_dim: frames * obs_dim)
             raise ValueError("FusedPPOUpdate.attach: the policy has another observation width or device")
+        if bool(getattr(fused, "squash", False)) != self.squash:
+            raise ValueError("FusedPPOUpdate.attach: the policy was made with squash = %s, the updater with squash = %s"
+                             % (bool(getattr(fused, "squash", False)), self.squash))
         hidden = tuple(getattr(fused, "hidden", HIDDEN))            # (the C side cannot see the buffer's length)
         if hidden != self.hidden:
             raise ValueError("FusedPPOUpdate.attach: the policy evaluates the hidden widths %s, the updater trains %s"
@@ -192,12 +227,13 @@ class FusedPPOUpdate:
 
     def grad(self, O, A, LP, ADV, RET, idx: Optional[torch.Tensor] = None, B: Optional[int] = None):
         """The flat gradient of minibatch_step's loss over rows `idx` (int64; None: rows 0 .. B - 1, B default: all rows) of the stored
-        transitions, and the statistics row.  Returns (grad, stats): the updater's own buffers, overwritten by the next call."""
+        transitions, and the statistics row (squash: of squash_loss_terms, slot 7 the mean entropy).  Returns (grad, stats): the updater's own buffers, overwritten by the next call."""
         n_rows, B = self._rows(((O, (self.obs_dim,)), (A, (2,)), (LP, ()), (ADV, ()), (RET, ())), idx, B)
-        b = _capi.AuvPpoBatch(O.data_ptr(), A.data_ptr(), LP.data_ptr(), ADV.data_ptr(), RET.data_ptr(),
-                              idx.data_ptr() if idx is not None else None, int(B), n_rows, self.clip, self.vf_coef, self.ent_coef)
+        batch, entry = (_capi.AuvPpoSquashBatch, "auv_ppo_grad_squash") if self.squash else (_capi.AuvPpoBatch, "auv_ppo_grad")
+        b = batch(O.data_ptr(), A.data_ptr(), LP.data_ptr(), ADV.data_ptr(), RET.data_ptr(),
+                  idx.data_ptr() if idx is not None else None, int(B), n_rows, self.clip, self.vf_coef, self.ent_coef)
         row = self._row()
-        _check(_LIB.auv_ppo_grad(self._h, C.byref(b), C.c_void_p(self.g.data_ptr()), C.c_void_p(row.data_ptr()), self._stream()), "auv_ppo_grad")
+        _check(getattr(_LIB, entry)(self._h, C.byref(b), C.c_void_p(self.g.data_ptr()), C.c_void_p(row.data_ptr()), self._stream()), entry)
         return self.g, row[:8]
 
     def apply(self, grad: Optional[torch.Tensor] = None):

@@ -786,6 +786,28 @@ int auv_policy_rollout_stacked_arch(auv_handle_t* h, int32_t n_slices, const int
                                     uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0);
 int auv_policy_eval_arch(int32_t device, const auv_policy_eval_t* ev, const auv_policy_arch_t* arch, void* stream);
 
+/* ---- a tanh-squashed Gaussian policy (what stable-baselines3 calls squash_output; csrc/k17_policy_squash.hip) ---------------------
+ * The launches above hand the environment act_mid + act_half * clamp(a, clip_lo, clip_hi) of the sample a: a box the Gaussian's
+ * entropy does not see.  The *_squash entries hand it
+ *     act_mid + act_half * tanh(u),   u = mu + sigma eps   (the deterministic action of the evaluation: u = mu)
+ * and read neither clip_lo nor clip_hi.  EVERYTHING ELSE IS THE PLAIN ENTRY'S, BIT FOR BIT, for the same weights, seed and step: the
+ * stored action A is u itself, LP the Gaussian log-density of u (the PPO ratio needs no Jacobian: it cancels), V, R, Dn, O, mu_out,
+ * eps_out, the counters and their hand-over; the evaluation's mu, value and logp, which takes PRE-SQUASH actions (rows of A).  Exact
+ * f32 only, at every triple of the list.  tanh is (1 - t) / (1 + t), t = exp(-2 |u|), with u's sign: odd bit for bit, exactly +-1 from
+ * |u| = 20 on (so the action is exactly act_mid +- act_half there), never NaN for a finite u.  AUV_EINVAL beside what the plain
+ * entries refuse: params_bf16 set.  The update that goes with it: auv_ppo_grad_squash, below.                                       */
+int auv_policy_act_squash(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, void* stream);
+int auv_policy_act_squash_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const auv_policy_arch_t* arch,
+                               void* stream);
+int auv_policy_rollout_squash(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
+                              float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
+                              const int64_t* gstep0);
+int auv_policy_rollout_squash_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
+                                   const auv_policy_io_t* ios, const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev,
+                                   uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0);
+int auv_policy_eval_squash(int32_t device, const auv_policy_eval_t* ev, void* stream);
+int auv_policy_eval_squash_arch(int32_t device, const auv_policy_eval_t* ev, const auv_policy_arch_t* arch, void* stream);
+
 /* ---- running observation and reward normalisation (what stable-baselines ships as VecNormalize; csrc/k16_policy_norm.hip) ----------
  * DEVIATION from stable-baselines: it updates its statistics at every step_wait, before normalising that step's batch.  Here the
  * statistics are FROZEN while launches run and FOLDED between rollouts: a per-step update would be a reduction over all environments
@@ -1130,6 +1152,29 @@ typedef struct auv_ppo_clone_batch {
   float vf_coef, ent_coef;
 } auv_ppo_clone_batch_t;
 int auv_ppo_grad_clone(auv_ppo_t* p, const auv_ppo_clone_batch_t* batch, float* grad, float* stats, void* stream);
+
+/* ---- the PPO row pass for a tanh-squashed policy (auv_policy_*_squash above): auv_ppo_grad's contract, batch layout and gradients with
+ * the entropy of the SQUASHED distribution in the place of the Gaussian's, estimated on the stored rows:
+ *     loss  = pg + vf_coef vf - ent_coef (1/B) sum_i ent_i
+ *     ent_i = sum_k [0.5 + log sqrt(2 pi) + log_std_k + log(1 - tanh^2(u_ik))],   u_ik = mu_ik + sigma_k sg(z_ik),  z = (a - mu) / sigma
+ * sg: stop-gradient, so u_ik has the VALUE of the stored action a_ik and the gradient of a reparameterised sample; log(1 - tanh^2 u)
+ * is evaluated as 2 (log 2 - |u| - log1p(exp(-2 |u|))), finite for every finite u.  On top of auv_ppo_grad's gradients:
+ *     d loss / d mu_ik     += ent_coef 2 tanh(a_ik) / B
+ *     d loss / d log_std_k  = (PPO's) - ent_coef (1 - (1/B) sum_i 2 tanh(a_ik) (a_ik - mu_ik))       in the place of (PPO's) - ent_coef
+ * A holds PRE-SQUASH actions and LP their Gaussian log-density, as the squash launches store them: pg needs no Jacobian.  stats[8] as
+ * auv_ppo_grad's with slot 7 = (1/B) sum_i ent_i.  With ent_coef == 0 the gradient has the bits of auv_ppo_grad's on the same batch.
+ * A non-finite a counts as a bad input, as there.  The type selects the head; the fields are auv_ppo_batch_t's.                   */
+typedef struct auv_ppo_squash_batch {
+  const float* O;            /* [n_rows][obs_dim]                                                            */
+  const float* A;            /* [n_rows][2]  stored (pre-squash) actions u                                   */
+  const float* LP;           /* [n_rows]     Gaussian log-density of u under the collecting policy           */
+  const float* ADV;          /* [n_rows]                                                                     */
+  const float* RET;          /* [n_rows]                                                                     */
+  const int64_t* idx;        /* [B]; NULL: rows 0 .. B - 1                                                   */
+  int32_t B, n_rows;
+  float clip, vf_coef, ent_coef;
+} auv_ppo_squash_batch_t;
+int auv_ppo_grad_squash(auv_ppo_t* p, const auv_ppo_squash_batch_t* batch, float* grad, float* stats, void* stream);
 
 /* ---- rendering: rgb_array frames of B environments, drawn on the device (BaseEnvironment.render, environment.py:410-437; the
  * reference draws ONE environment on the host with pygame: a vessel-centred top view, render2d/renderer.py:62-120) -------------

@@ -83,6 +83,12 @@ def bench_width(obs_dim, B, n_rows, warmup, reps, device, arch=(256, 128, 64)):
     out["eager_with_gathers"] = timed(lambda: eager(O[idx], A[idx], LP[idx], ADV[idx], RET[idx]), warmup, reps)
     out["fused"] = timed(lambda: upd.step(O, A, LP, ADV, RET, idx), warmup, reps)
     out["fused_grad_only"] = timed(lambda: upd.grad(O, A, LP, ADV, RET, idx), warmup, reps)
+    # the same step for a tanh-squashed policy (auv_ppo_grad_squash), on a net of its own, in the same session
+    sq_net = ppo.ActorCritic(obs_dim, hidden=arch).to(device)
+    sq_net.load_state_dict(twin.state_dict())
+    sq = FusedPPOUpdate(sq_net, lr=2e-4, clip=clip, vf_coef=0.5, ent_coef=ent_coef, max_batch=B, squash=True)
+    out["fused_squash"] = timed(lambda: sq.step(O, A, LP, ADV, RET, idx), warmup, reps)
+    out["fused_again"] = timed(lambda: upd.step(O, A, LP, ADV, RET, idx), warmup, reps)
     out["speedup_vs_eager"] = out["eager"]["median_ms"] / out["fused"]["median_ms"]
     out["speedup_vs_eager_with_gathers"] = out["eager_with_gathers"]["median_ms"] / out["fused"]["median_ms"]
     return out
