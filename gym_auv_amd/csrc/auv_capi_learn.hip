@@ -58,43 +58,6 @@ static int check_policy_io(const auv_handle_t* h, int32_t e0, int32_t ne, const 
   return AUV_OK;
 }
 
-// squash: the launch of a tanh-squashed policy (k17_policy_squash.hip) in the place of the plain one: the same checks, exact f32 only
-static int check_policy_squash(const auv_policy_io_t* io, const char* who) {
-  if (io->params_bf16) return fail(AUV_EINVAL, "%s: a squashed policy is evaluated in exact f32 only (params_bf16 must be NULL)", who);
-  return AUV_OK;
-}
-
-static int policy_act_impl(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const auv_policy_arch_t* a, void* stream,
-                           const char* who, bool squash = false) {
-  REQUIRE_READY(h);
-  int rc = check_policy_io(h, e0, ne, io, a, who);
-  if (rc) return rc;
-  if (squash) {
-    rc = check_policy_squash(io, who);
-    if (rc) return rc;
-    HIP_TRY(auv_policy_squash_prepare(a->h1, a->h2, a->h3, io->obs_dim, false));
-    auv_launch_policy_squash(a->h1, a->h2, a->h3, *io, e0, ne, (hipStream_t)stream);
-  } else {
-    HIP_TRY(auv_policy_prepare(a->h1, a->h2, a->h3, io->obs_dim));
-    auv_launch_policy(a->h1, a->h2, a->h3, *io, e0, ne, (hipStream_t)stream);
-  }
-  HIP_TRY(hipGetLastError());
-  return AUV_OK;
-}
-int auv_policy_act_squash(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, void* stream) {
-  return policy_act_impl(h, e0, ne, io, &POLICY_ARCH_REF, stream, "auv_policy_act_squash", true);
-}
-int auv_policy_act_squash_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const auv_policy_arch_t* arch,
-                               void* stream) {
-  return policy_act_impl(h, e0, ne, io, arch, stream, "auv_policy_act_squash_arch", true);
-}
-int auv_policy_act(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, void* stream) {
-  return policy_act_impl(h, e0, ne, io, &POLICY_ARCH_REF, stream, "auv_policy_act");
-}
-int auv_policy_act_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const auv_policy_arch_t* arch, void* stream) {
-  return policy_act_impl(h, e0, ne, io, arch, stream, "auv_policy_act_arch");
-}
-
 int auv_gae(auv_handle_t* h, const float* R, const float* V, const float* Dn, const float* last_v, float gamma, float lam, float* adv_out,
             float* ret_out, int32_t T, int32_t N, void* stream) {
   if (!h) return fail(AUV_EINVAL, "null handle");
@@ -185,141 +148,193 @@ struct RolloutCounters {
   long long gstep(int i, int32_t k) const { return t0 ? gstep0[i] + k : -1; }
 };
 
-static int policy_rollout_impl(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
-                               const auv_policy_arch_t* a, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush,
-                               const int64_t* t0, const int64_t* gstep0, const char* who, bool squash = false) {
-  REQUIRE_READY(h);
-  const RolloutCounters ctr = {t0, gstep0};
-  int rc = check_slices(h, n_slices, bounds, streams, who);
-  if (rc) return rc;
-  if (!ios || n_steps < 0 || !ctr.paired()) return fail(AUV_EINVAL, "%s: bad arguments", who);
-  for (int i = 0; i < n_slices; i++) {
-    rc = check_policy_io(h, bounds[i], bounds[i + 1] - bounds[i], ios + i, a, who);
-    if (rc) return rc;
-    if (squash && (rc = check_policy_squash(ios + i, who)) != AUV_OK) return rc;
-    rc = check_actions(ios[i].actions_out, AUV_F32, who);
-    if (rc) return rc;
-    if (ctr.negative(i)) return fail(AUV_EINVAL, "%s: negative counter for slice %d", who, i);
+// ---- the four act launches behind the sixteen act / rollout entries: one variant trait each ----
+// V::io_t the entry's io struct; V::check one slice's io (check_policy_io first, then the variant's own); V::check_uniform what must
+// agree between the slices of a rollout; V::prepare / V::launch the kernel file's pair; V::actions_out the [N][2] buffer the launch
+// writes and the step reads.
+namespace {
+struct PolicyPlain {
+  typedef auv_policy_io_t io_t;
+  static int check(const auv_handle_t* h, int32_t e0, int32_t ne, const io_t* io, const auv_policy_arch_t* a, const char* who) {
+    return check_policy_io(h, e0, ne, io, a, who);
   }
-  PAIR_CHECK(h, obs_dev);
-  if (squash) {
-    HIP_TRY(auv_policy_squash_prepare(a->h1, a->h2, a->h3, ios[0].obs_dim, false));
-    return rollout_loop(
-        h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].actions_out; },
-        [&](int i, int32_t k, bool) {
-          auv_launch_policy_squash(a->h1, a->h2, a->h3, ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k),
-                                   ctr.gstep(i, k));
-        });
+  static int check_uniform(const io_t*, int, const char*) { return AUV_OK; }
+  static hipError_t prepare(const auv_policy_arch_t* a, const io_t& io) { return auv_policy_prepare(a->h1, a->h2, a->h3, io.obs_dim); }
+  static void launch(const auv_policy_arch_t* a, const io_t& io, int32_t e0, int32_t ne, hipStream_t st, long long t, long long gstep) {
+    auv_launch_policy(a->h1, a->h2, a->h3, io, e0, ne, st, t, gstep);
   }
-  HIP_TRY(auv_policy_prepare(a->h1, a->h2, a->h3, ios[0].obs_dim));
-  return rollout_loop(
-      h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].actions_out; },
-      [&](int i, int32_t k, bool) {
-        auv_launch_policy(a->h1, a->h2, a->h3, ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k),
-                          ctr.gstep(i, k));
-      });
-}
-int auv_policy_rollout_squash(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
-                              float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
-                              const int64_t* gstep0) {
-  return policy_rollout_impl(h, n_slices, bounds, streams, ios, &POLICY_ARCH_REF, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0,
-                             "auv_policy_rollout_squash", true);
-}
-int auv_policy_rollout_squash_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
-                                   const auv_policy_io_t* ios, const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev,
-                                   uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0) {
-  return policy_rollout_impl(h, n_slices, bounds, streams, ios, arch, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0,
-                             "auv_policy_rollout_squash_arch", true);
-}
-int auv_policy_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
-                       float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
-                       const int64_t* gstep0) {
-  return policy_rollout_impl(h, n_slices, bounds, streams, ios, &POLICY_ARCH_REF, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0,
-                             "auv_policy_rollout");
-}
-int auv_policy_rollout_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios,
-                            const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps,
-                            int32_t flush, const int64_t* t0, const int64_t* gstep0) {
-  return policy_rollout_impl(h, n_slices, bounds, streams, ios, arch, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0,
-                             "auv_policy_rollout_arch");
-}
+  static float* actions_out(const io_t& io) { return io.actions_out; }
+};
 
-// ---- frame-stacked observations in the policy launch (include/auv_hip.h, auv_policy_stack; kernels: k12_policy_stacked.hip) ----
-static int check_policy_stack(const auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* s, const auv_policy_arch_t* a,
-                              const char* who) {
-  if (!s) return fail(AUV_EINVAL, "%s: null io", who);
-  if (s->frames < 1 || s->frames > AUV_MAX_FRAMES) return fail(AUV_EINVAL, "%s: frames = %d outside [1, %d]", who, s->frames, AUV_MAX_FRAMES);
-  int rc = check_policy_io(h, e0, ne, &s->io, a, who);
-  if (rc) return rc;
-  if (s->io.params_bf16) return fail(AUV_EINVAL, "%s: stacked rows are evaluated in exact f32 only (params_bf16 must be NULL)", who);
-  const int64_t width = (int64_t)s->frames * s->io.obs_dim;
-  if (width > 16384 || auv_policy_stacked_lds_bytes(a->h1, a->h2, a->h3, (int)width) > 160 * 1024)
-    return fail(AUV_EINVAL, "%s: %d frames of %d columns are too wide for the policy kernel's LDS tile", who, s->frames, s->io.obs_dim);
-  if (s->frames > 1) {
-    if (!s->hist || !s->stk) return fail(AUV_EINVAL, "%s: null hist or stk", who);
-    if (((uintptr_t)s->hist & 15) || ((uintptr_t)s->stk & 7)) return fail(AUV_EINVAL, "%s: hist must be 16-byte, stk 8-byte aligned", who);
+// the launch of a tanh-squashed policy (k17_policy_squash.hip) in the place of the plain one: the same checks, exact f32 only
+struct PolicySquash : PolicyPlain {
+  static int check(const auv_handle_t* h, int32_t e0, int32_t ne, const io_t* io, const auv_policy_arch_t* a, const char* who) {
+    int rc = check_policy_io(h, e0, ne, io, a, who);
+    if (rc) return rc;
+    if (io->params_bf16) return fail(AUV_EINVAL, "%s: a squashed policy is evaluated in exact f32 only (params_bf16 must be NULL)", who);
+    return AUV_OK;
   }
-  return AUV_OK;
-}
+  static hipError_t prepare(const auv_policy_arch_t* a, const io_t& io) { return auv_policy_squash_prepare(a->h1, a->h2, a->h3, io.obs_dim, false); }
+  static void launch(const auv_policy_arch_t* a, const io_t& io, int32_t e0, int32_t ne, hipStream_t st, long long t, long long gstep) {
+    auv_launch_policy_squash(a->h1, a->h2, a->h3, io, e0, ne, st, t, gstep);
+  }
+};
 
-static int policy_act_stacked_impl(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* io, const auv_policy_arch_t* a,
-                                   void* stream, const char* who) {
+// frame-stacked observations (include/auv_hip.h, auv_policy_stack; kernels: k12_policy_stacked.hip)
+struct PolicyStacked {
+  typedef auv_policy_stack_t io_t;
+  static int check(const auv_handle_t* h, int32_t e0, int32_t ne, const io_t* s, const auv_policy_arch_t* a, const char* who) {
+    if (!s) return fail(AUV_EINVAL, "%s: null io", who);
+    if (s->frames < 1 || s->frames > AUV_MAX_FRAMES) return fail(AUV_EINVAL, "%s: frames = %d outside [1, %d]", who, s->frames, AUV_MAX_FRAMES);
+    int rc = check_policy_io(h, e0, ne, &s->io, a, who);
+    if (rc) return rc;
+    if (s->io.params_bf16) return fail(AUV_EINVAL, "%s: stacked rows are evaluated in exact f32 only (params_bf16 must be NULL)", who);
+    const int64_t width = (int64_t)s->frames * s->io.obs_dim;
+    if (width > 16384 || auv_policy_stacked_lds_bytes(a->h1, a->h2, a->h3, (int)width) > 160 * 1024)
+      return fail(AUV_EINVAL, "%s: %d frames of %d columns are too wide for the policy kernel's LDS tile", who, s->frames, s->io.obs_dim);
+    if (s->frames > 1) {
+      if (!s->hist || !s->stk) return fail(AUV_EINVAL, "%s: null hist or stk", who);
+      if (((uintptr_t)s->hist & 15) || ((uintptr_t)s->stk & 7)) return fail(AUV_EINVAL, "%s: hist must be 16-byte, stk 8-byte aligned", who);
+    }
+    return AUV_OK;
+  }
+  static int check_uniform(const io_t* ios, int i, const char* who) {
+    if (ios[i].frames != ios[0].frames) return fail(AUV_EINVAL, "%s: slice %d has %d frames, slice 0 has %d", who, i, ios[i].frames, ios[0].frames);
+    return AUV_OK;
+  }
+  static hipError_t prepare(const auv_policy_arch_t* a, const io_t& s) { return auv_policy_stacked_prepare(a->h1, a->h2, a->h3, s.frames * s.io.obs_dim); }
+  static void launch(const auv_policy_arch_t* a, const io_t& s, int32_t e0, int32_t ne, hipStream_t st, long long t, long long gstep) {
+    auv_launch_policy_stacked(a->h1, a->h2, a->h3, s, e0, ne, st, t, gstep);
+  }
+  static float* actions_out(const io_t& s) { return s.io.actions_out; }
+};
+
+// running normalisation (include/auv_hip.h, auv_policy_norm; kernels: k16_policy_norm.hip)
+struct PolicyNorm {
+  typedef auv_policy_norm_t io_t;
+  static int check(const auv_handle_t* h, int32_t e0, int32_t ne, const io_t* s, const auv_policy_arch_t* a, const char* who) {
+    if (!s) return fail(AUV_EINVAL, "%s: null io", who);
+    int rc = check_policy_io(h, e0, ne, &s->io, a, who);
+    if (rc) return rc;
+    if (s->io.params_bf16) return fail(AUV_EINVAL, "%s: normalised rows are evaluated in exact f32 only (params_bf16 must be NULL)", who);
+    if (!s->table || ((uintptr_t)s->table & 7)) return fail(AUV_EINVAL, "%s: table must be an 8-byte aligned device pointer", who);
+    if (!s->part || !s->pcnt) return fail(AUV_EINVAL, "%s: null part or pcnt", who);
+    if (((uintptr_t)s->part & 3) || ((uintptr_t)s->pcnt & 3)) return fail(AUV_EINVAL, "%s: part and pcnt must be 4-byte aligned", who);
+    if (!(s->clip_obs > 0.0f)) return fail(AUV_EINVAL, "%s: clip_obs must be > 0", who);
+    const int tiles = (ne + POL_ROWS - 1) / POL_ROWS;
+    if (s->part_base < 0 || (int64_t)s->part_base + tiles > s->part_ld)
+      return fail(AUV_EINVAL, "%s: %d tiles from part_base %d do not fit part_ld = %d", who, tiles, s->part_base, s->part_ld);
+    return AUV_OK;
+  }
+  static int check_uniform(const io_t*, int, const char*) { return AUV_OK; }
+  static hipError_t prepare(const auv_policy_arch_t* a, const io_t& s) { return auv_policy_norm_prepare(a->h1, a->h2, a->h3, s.io.obs_dim); }
+  static void launch(const auv_policy_arch_t* a, const io_t& s, int32_t e0, int32_t ne, hipStream_t st, long long t, long long gstep) {
+    auv_launch_policy_norm(a->h1, a->h2, a->h3, s, e0, ne, st, t, gstep);
+  }
+  static float* actions_out(const io_t& s) { return s.io.actions_out; }
+};
+}  // namespace
+
+// one acting launch of the slice [e0, e0 + ne) on `stream`: the counters live on the device (io.ctr)
+extern "C++" template <class V>
+static int policy_act_impl(auv_handle_t* h, int32_t e0, int32_t ne, const typename V::io_t* io, const auv_policy_arch_t* a, void* stream,
+                           const char* who) {
   REQUIRE_READY(h);
-  int rc = check_policy_stack(h, e0, ne, io, a, who);
+  int rc = V::check(h, e0, ne, io, a, who);
   if (rc) return rc;
-  HIP_TRY(auv_policy_stacked_prepare(a->h1, a->h2, a->h3, io->frames * io->io.obs_dim));
-  auv_launch_policy_stacked(a->h1, a->h2, a->h3, *io, e0, ne, (hipStream_t)stream);
+  HIP_TRY(V::prepare(a, *io));
+  V::launch(a, *io, e0, ne, (hipStream_t)stream, -1, -1);
   HIP_TRY(hipGetLastError());
   return AUV_OK;
 }
-int auv_policy_act_stacked(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* io, void* stream) {
-  return policy_act_stacked_impl(h, e0, ne, io, &POLICY_ARCH_REF, stream, "auv_policy_act_stacked");
-}
-int auv_policy_act_stacked_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* io, const auv_policy_arch_t* arch,
-                                void* stream) {
-  return policy_act_stacked_impl(h, e0, ne, io, arch, stream, "auv_policy_act_stacked_arch");
-}
 
-// auv_policy_rollout's loop with the stacked launch: the same t0 / gstep0 contract, the same slices on their own streams
-static int policy_rollout_stacked_impl(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
-                                       const auv_policy_stack_t* ios, const auv_policy_arch_t* a, float* obs_dev, float* reward_dev,
-                                       uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0,
-                                       const char* who) {
+// the rollout loop with a variant's launch: the t0 / gstep0 contract above, every slice on its own stream
+extern "C++" template <class V>
+static int policy_rollout_impl(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const typename V::io_t* ios,
+                               const auv_policy_arch_t* a, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush,
+                               const int64_t* t0, const int64_t* gstep0, const char* who) {
   REQUIRE_READY(h);
   const RolloutCounters ctr = {t0, gstep0};
   int rc = check_slices(h, n_slices, bounds, streams, who);
   if (rc) return rc;
   if (!ios || n_steps < 0 || !ctr.paired()) return fail(AUV_EINVAL, "%s: bad arguments", who);
   for (int i = 0; i < n_slices; i++) {
-    rc = check_policy_stack(h, bounds[i], bounds[i + 1] - bounds[i], ios + i, a, who);
+    rc = V::check(h, bounds[i], bounds[i + 1] - bounds[i], ios + i, a, who);
     if (rc) return rc;
-    rc = check_actions(ios[i].io.actions_out, AUV_F32, who);
+    rc = check_actions(V::actions_out(ios[i]), AUV_F32, who);
     if (rc) return rc;
-    if (ios[i].frames != ios[0].frames) return fail(AUV_EINVAL, "%s: slice %d has %d frames, slice 0 has %d", who, i, ios[i].frames, ios[0].frames);
+    rc = V::check_uniform(ios, i, who);
+    if (rc) return rc;
     if (ctr.negative(i)) return fail(AUV_EINVAL, "%s: negative counter for slice %d", who, i);
   }
   PAIR_CHECK(h, obs_dev);
-  HIP_TRY(auv_policy_stacked_prepare(a->h1, a->h2, a->h3, ios[0].frames * ios[0].io.obs_dim));
+  HIP_TRY(V::prepare(a, ios[0]));
   return rollout_loop(
-      h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].io.actions_out; },
+      h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return V::actions_out(ios[i]); },
       [&](int i, int32_t k, bool) {
-        auv_launch_policy_stacked(a->h1, a->h2, a->h3, ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k),
-                                  ctr.gstep(i, k));
+        V::launch(a, ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k), ctr.gstep(i, k));
       });
 }
-int auv_policy_rollout_stacked(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_stack_t* ios,
-                               float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
-                               const int64_t* gstep0) {
-  return policy_rollout_stacked_impl(h, n_slices, bounds, streams, ios, &POLICY_ARCH_REF, obs_dev, reward_dev, done_dev, n_steps, flush, t0,
-                                     gstep0, "auv_policy_rollout_stacked");
+
+// the sixteen entries: (act, rollout) x (plain, squash, stacked, norm) x (the reference's widths, _arch), each under its own name
+int auv_policy_act(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, void* stream) {
+  return policy_act_impl<PolicyPlain>(h, e0, ne, io, &POLICY_ARCH_REF, stream, "auv_policy_act");
 }
-int auv_policy_rollout_stacked_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
-                                    const auv_policy_stack_t* ios, const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev,
-                                    uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0) {
-  return policy_rollout_stacked_impl(h, n_slices, bounds, streams, ios, arch, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0,
-                                     "auv_policy_rollout_stacked_arch");
+int auv_policy_act_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const auv_policy_arch_t* arch, void* stream) {
+  return policy_act_impl<PolicyPlain>(h, e0, ne, io, arch, stream, "auv_policy_act_arch");
+}
+int auv_policy_rollout(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios, float* obs_dev,
+    float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0) {
+  return policy_rollout_impl<PolicyPlain>(h, n_slices, bounds, streams, ios, &POLICY_ARCH_REF, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0, "auv_policy_rollout");
+}
+int auv_policy_rollout_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios, const auv_policy_arch_t* arch,
+    float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0) {
+  return policy_rollout_impl<PolicyPlain>(h, n_slices, bounds, streams, ios, arch, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0, "auv_policy_rollout_arch");
+}
+int auv_policy_act_squash(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, void* stream) {
+  return policy_act_impl<PolicySquash>(h, e0, ne, io, &POLICY_ARCH_REF, stream, "auv_policy_act_squash");
+}
+int auv_policy_act_squash_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_io_t* io, const auv_policy_arch_t* arch, void* stream) {
+  return policy_act_impl<PolicySquash>(h, e0, ne, io, arch, stream, "auv_policy_act_squash_arch");
+}
+int auv_policy_rollout_squash(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios, float* obs_dev,
+    float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0) {
+  return policy_rollout_impl<PolicySquash>(h, n_slices, bounds, streams, ios, &POLICY_ARCH_REF, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0, "auv_policy_rollout_squash");
+}
+int auv_policy_rollout_squash_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_io_t* ios, const auv_policy_arch_t* arch,
+    float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0) {
+  return policy_rollout_impl<PolicySquash>(h, n_slices, bounds, streams, ios, arch, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0, "auv_policy_rollout_squash_arch");
+}
+int auv_policy_act_stacked(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* io, void* stream) {
+  return policy_act_impl<PolicyStacked>(h, e0, ne, io, &POLICY_ARCH_REF, stream, "auv_policy_act_stacked");
+}
+int auv_policy_act_stacked_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_stack_t* io, const auv_policy_arch_t* arch, void* stream) {
+  return policy_act_impl<PolicyStacked>(h, e0, ne, io, arch, stream, "auv_policy_act_stacked_arch");
+}
+int auv_policy_rollout_stacked(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_stack_t* ios, float* obs_dev,
+    float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0) {
+  return policy_rollout_impl<PolicyStacked>(h, n_slices, bounds, streams, ios, &POLICY_ARCH_REF, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0, "auv_policy_rollout_stacked");
+}
+int auv_policy_rollout_stacked_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_stack_t* ios, const auv_policy_arch_t* arch,
+    float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0) {
+  return policy_rollout_impl<PolicyStacked>(h, n_slices, bounds, streams, ios, arch, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0, "auv_policy_rollout_stacked_arch");
+}
+int auv_policy_act_norm(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_norm_t* io, void* stream) {
+  return policy_act_impl<PolicyNorm>(h, e0, ne, io, &POLICY_ARCH_REF, stream, "auv_policy_act_norm");
+}
+int auv_policy_act_norm_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_norm_t* io, const auv_policy_arch_t* arch, void* stream) {
+  return policy_act_impl<PolicyNorm>(h, e0, ne, io, arch, stream, "auv_policy_act_norm_arch");
+}
+int auv_policy_rollout_norm(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_norm_t* ios, float* obs_dev,
+    float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0) {
+  return policy_rollout_impl<PolicyNorm>(h, n_slices, bounds, streams, ios, &POLICY_ARCH_REF, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0, "auv_policy_rollout_norm");
+}
+int auv_policy_rollout_norm_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_norm_t* ios, const auv_policy_arch_t* arch,
+    float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0) {
+  return policy_rollout_impl<PolicyNorm>(h, n_slices, bounds, streams, ios, arch, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0, "auv_policy_rollout_norm_arch");
 }
 
+// ---- the history update alone (include/auv_hip.h, auv_stack_frames; kernel: k12_policy_stacked.hip) ----
 int auv_stack_frames(int32_t device, const float* obs, const uint8_t* done, float* hist, int32_t* stk, float* out, int64_t ldx, int32_t e0,
                      int32_t ne, int32_t obs_dim, int32_t frames, int32_t advance, void* stream) {
   if (device < 0) return fail(AUV_EINVAL, "auv_stack_frames: device %d", device);
@@ -338,78 +353,7 @@ int auv_stack_frames(int32_t device, const float* obs, const uint8_t* done, floa
   return AUV_OK;
 }
 
-// ---- running normalisation in the policy launch (include/auv_hip.h, auv_policy_norm; kernels: k16_policy_norm.hip) ----
-static int check_policy_norm(const auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_norm_t* s, const auv_policy_arch_t* a,
-                             const char* who) {
-  if (!s) return fail(AUV_EINVAL, "%s: null io", who);
-  int rc = check_policy_io(h, e0, ne, &s->io, a, who);
-  if (rc) return rc;
-  if (s->io.params_bf16) return fail(AUV_EINVAL, "%s: normalised rows are evaluated in exact f32 only (params_bf16 must be NULL)", who);
-  if (!s->table || ((uintptr_t)s->table & 7)) return fail(AUV_EINVAL, "%s: table must be an 8-byte aligned device pointer", who);
-  if (!s->part || !s->pcnt) return fail(AUV_EINVAL, "%s: null part or pcnt", who);
-  if (((uintptr_t)s->part & 3) || ((uintptr_t)s->pcnt & 3)) return fail(AUV_EINVAL, "%s: part and pcnt must be 4-byte aligned", who);
-  if (!(s->clip_obs > 0.0f)) return fail(AUV_EINVAL, "%s: clip_obs must be > 0", who);
-  const int tiles = (ne + POL_ROWS - 1) / POL_ROWS;
-  if (s->part_base < 0 || (int64_t)s->part_base + tiles > s->part_ld)
-    return fail(AUV_EINVAL, "%s: %d tiles from part_base %d do not fit part_ld = %d", who, tiles, s->part_base, s->part_ld);
-  return AUV_OK;
-}
-
-static int policy_act_norm_impl(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_norm_t* io, const auv_policy_arch_t* a, void* stream,
-                                const char* who) {
-  REQUIRE_READY(h);
-  int rc = check_policy_norm(h, e0, ne, io, a, who);
-  if (rc) return rc;
-  HIP_TRY(auv_policy_norm_prepare(a->h1, a->h2, a->h3, io->io.obs_dim));
-  auv_launch_policy_norm(a->h1, a->h2, a->h3, *io, e0, ne, (hipStream_t)stream);
-  HIP_TRY(hipGetLastError());
-  return AUV_OK;
-}
-int auv_policy_act_norm(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_norm_t* io, void* stream) {
-  return policy_act_norm_impl(h, e0, ne, io, &POLICY_ARCH_REF, stream, "auv_policy_act_norm");
-}
-int auv_policy_act_norm_arch(auv_handle_t* h, int32_t e0, int32_t ne, const auv_policy_norm_t* io, const auv_policy_arch_t* arch, void* stream) {
-  return policy_act_norm_impl(h, e0, ne, io, arch, stream, "auv_policy_act_norm_arch");
-}
-
-// auv_policy_rollout's loop with the normalising launch: the same t0 / gstep0 contract, the same slices on their own streams
-static int policy_rollout_norm_impl(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_norm_t* ios,
-                                    const auv_policy_arch_t* a, float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps,
-                                    int32_t flush, const int64_t* t0, const int64_t* gstep0, const char* who) {
-  REQUIRE_READY(h);
-  const RolloutCounters ctr = {t0, gstep0};
-  int rc = check_slices(h, n_slices, bounds, streams, who);
-  if (rc) return rc;
-  if (!ios || n_steps < 0 || !ctr.paired()) return fail(AUV_EINVAL, "%s: bad arguments", who);
-  for (int i = 0; i < n_slices; i++) {
-    rc = check_policy_norm(h, bounds[i], bounds[i + 1] - bounds[i], ios + i, a, who);
-    if (rc) return rc;
-    rc = check_actions(ios[i].io.actions_out, AUV_F32, who);
-    if (rc) return rc;
-    if (ctr.negative(i)) return fail(AUV_EINVAL, "%s: negative counter for slice %d", who, i);
-  }
-  PAIR_CHECK(h, obs_dev);
-  HIP_TRY(auv_policy_norm_prepare(a->h1, a->h2, a->h3, ios[0].io.obs_dim));
-  return rollout_loop(
-      h, n_slices, bounds, streams, obs_dev, reward_dev, done_dev, n_steps, flush, [&](int i) { return ios[i].io.actions_out; },
-      [&](int i, int32_t k, bool) {
-        auv_launch_policy_norm(a->h1, a->h2, a->h3, ios[i], bounds[i], bounds[i + 1] - bounds[i], (hipStream_t)streams[i], ctr.t(i, k),
-                               ctr.gstep(i, k));
-      });
-}
-int auv_policy_rollout_norm(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams, const auv_policy_norm_t* ios,
-                            float* obs_dev, float* reward_dev, uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0,
-                            const int64_t* gstep0) {
-  return policy_rollout_norm_impl(h, n_slices, bounds, streams, ios, &POLICY_ARCH_REF, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0,
-                                  "auv_policy_rollout_norm");
-}
-int auv_policy_rollout_norm_arch(auv_handle_t* h, int32_t n_slices, const int32_t* bounds, void* const* streams,
-                                 const auv_policy_norm_t* ios, const auv_policy_arch_t* arch, float* obs_dev, float* reward_dev,
-                                 uint8_t* done_dev, int32_t n_steps, int32_t flush, const int64_t* t0, const int64_t* gstep0) {
-  return policy_rollout_norm_impl(h, n_slices, bounds, streams, ios, arch, obs_dev, reward_dev, done_dev, n_steps, flush, t0, gstep0,
-                                  "auv_policy_rollout_norm_arch");
-}
-
+// ---- running normalisation: the same expression on arbitrary rows, the fold and the return pass (kernels: k16_policy_norm.hip) ----
 static bool norm_finite(double x) { return x == x && x - x == 0.0; }
 
 int auv_norm_rows(int32_t device, const float* X, const int64_t* idx, int64_t ldx, const float* table, float clip_obs, float* out, int64_t ldo,

@@ -1,8 +1,9 @@
-// The forward pass of the policy MLP as the four fused launches run it -- k6_policy_act, k9_policy_eval, k11_population_act,
-// k12_stacked_act -- written once: the packed net's pointers, the LDS carve-up, the prefetch / layer / barrier sequence (pol_trunk),
-// the counter-based generator, the action map, log pi(a), and the frame of an ACT launch (rollout position, transition, sampling
-// epilogue, counters) that k6 and k12 share.  What stays in the kernels is what differs between them: where the input rows come from
-// and what is stored of the outputs.  (The PPO update, k8_ppo_update.hip, has its own sequence and includes auv_policy_mfma.h only.)
+// The forward pass of the policy MLP as the fused launches run it -- k6_policy_act, k9_policy_eval, k11_population_act,
+// k12_stacked_act, k16_norm_act, k17_squash_act / _eval -- written once: the packed net's pointers, the LDS carve-up, the prefetch /
+// layer / barrier sequence (pol_trunk), the counter-based generator, the action maps, log pi(a), and the whole ACT launch
+// (pol_act_body: rollout position, transition, tile, trunk, sampling epilogue, counters; its host helpers) that k6, k12, k16 and k17
+// instantiate with a Tile -- how the input tile is formed -- and a map.  What stays in a kernel file is its Tile.  (The PPO update,
+// k8_ppo_update.hip, has its own sequence and includes auv_policy_mfma.h only.)
 //
 // The order of requests and barriers in here was measured line by line (profiles/r04, profiles/policy_trunk); the library is built
 // with -ffp-contract=off and the tests compare bits across the launches.
@@ -155,8 +156,9 @@ __device__ __forceinline__ float pol_logp(const float a, const float mu, const f
   return lp;
 }
 
-// ---- the frame of an ACT launch (k6_policy_act, k12_stacked_act): grid (ceil(ne / 16), 2), blockIdx.y = 0 the policy net, 1 the
-// value net; a kernel calls pol_act_begin first, pol_act_sample behind the trunk on wave 0, pol_act_end last ----
+// ---- the frame of an ACT launch (k6_policy_act, k12_stacked_act, k16_norm_act, k17_squash_act): grid (ceil(ne / 16), 2),
+// blockIdx.y = 0 the policy net, 1 the value net; pol_act_body calls pol_act_begin first, pol_act_sample behind the trunk on wave 0,
+// pol_act_end last ----
 struct PolAct {
   bool host_counts, act, trans;
   long long t;                       // position in the rollout; t == T: the flush call after a rollout's last step
@@ -278,6 +280,97 @@ __device__ __forceinline__ void pol_act_end(const auv_policy_io_t& io, const Pol
       io.ctr[1] = (long long)(p.gstep + 1);
     }
   }
+}
+
+// ---- the act launch, written once: what an act kernel is launched with, the Tile contract, the body, the host's two helpers ----
+// IO: auv_policy_io_t, or a struct that holds one as `io` (auv_policy_stack_t, auv_policy_norm_t)
+template <class IO>
+struct PolActArgs {
+  IO io;
+  int32_t e0, ne;
+  long long t_host, gstep_host;      // >= 0: the host names the rollout position and the generator's step (auv_policy_rollout: a plain
+                                     // loop of launches); -1: both live on the device (io.ctr) and the launch moves them on itself
+};
+
+// A Tile is what differs between the act launches: how the input tile is formed.  pol_act_body calls, in this order,
+//   width()                      the net's input width K0
+//   weights(A(), nw, net, K0p)   behind pol_net_ptrs: other weight pointers than the packed f32 ones (k6's bf16 variant)
+//   Req rq(p)                    the thread's state of the step, made before `if (p.act)`; fill and finish get it back (the Tile is const)
+//   request(A(), rq, X, p, rows) AHEAD of the barrier behind the tile's zeroing: loads whose values the fill needs, into rq, and LDS
+//                                words behind the tiles (pol_tiles_end<A>: the launch's LDS size must cover what a Tile puts there)
+//   fill(A(), X, p, rq, rows)    BEHIND that barrier: the rows of the tile into X, and into the rollout's O[t] (policy workgroup).  A
+//                                fill that needs the whole raw tile before it goes on sets its own barrier (k16: one more than k6)
+//   finish(p, rq)                outside `if (p.act)`, ahead of pol_act_end: the Tile's own state, stored last
+// requests first, stores last -- the rule every kernel file's header states for its step.  The plain tile, consecutive rows of the
+// observation buffer, is the base the others derive from: a Tile names only the hooks it changes.  (The hooks take the widths as a
+// tag and X, not a pointer worked out here: a dead pol_tiles_end in the body cost the plain kernels two scalar registers --
+// profiles/policy_frame.)
+struct PolPlainTile {
+  const auv_policy_io_t& io;
+  struct Req {
+    __device__ __forceinline__ explicit Req(const PolAct&) {}
+  };
+  __device__ __forceinline__ explicit PolPlainTile(const auv_policy_io_t& io_) : io(io_) {}
+  __device__ __forceinline__ int width() const { return io.obs_dim; }
+  template <class A>
+  __device__ __forceinline__ void weights(A, PolNet&, const int, const int) const {}
+  template <class A>
+  __device__ __forceinline__ void request(A, Req&, float*, const PolAct&, const int) const {}
+  template <class A>
+  __device__ __forceinline__ void fill(A, float* X, const PolAct& p, const Req&, const int rows) const {
+    pol_act_fill_obs(X, io, p, pol_act_obs_out(io, p, io.obs_dim), rows);
+  }
+  template <class R>
+  __device__ __forceinline__ void finish(const PolAct&, const R&) const {}
+};
+
+// The launch's body, written once for every hidden-width triple A (PolArch, auv_policy_mfma.h), BF (bf16 weights), SQUASH (the map
+// actions_out gets: pol_map_of) and Tile.
+template <class A, bool BF, bool SQUASH, class IO, class Tile>
+__device__ __forceinline__ void pol_act_body(const PolActArgs<IO>& pa, const Tile& tile) {
+  extern __shared__ __align__(16) unsigned char smem[];
+  const auv_policy_io_t& io = tile.io;
+  const int tid = threadIdx.x, wave = tid / AUV_WAVE, lane = tid % AUV_WAVE;
+  const int net = blockIdx.y;
+  const int K0 = tile.width(), K0p = pol_pad16(K0);
+  float* X = (float*)smem;
+  const PolAct p = pol_act_begin(io, pa.e0, pa.ne, pa.t_host, pa.gstep_host);
+  typename Tile::Req rq(p);
+  if (p.act) {
+    PolNet nw = pol_net_ptrs<A>(io.params + (size_t)net * pol_net_floats<A>(K0), K0);
+    tile.weights(A(), nw, net, K0p);
+    PolW<A::H1 / 16, BF> w1;
+    pol_prefetch(w1, nw.W1, nw.b1, K0p, wave, lane);                 // (in flight while the tile is formed)
+    const int rows = (p.cnt - p.r0 < POL_ROWS) ? p.cnt - p.r0 : POL_ROWS;
+    tile.request(A(), rq, X, p, rows);
+    // ---- input tile -> LDS (zero padded), and into the rollout (policy workgroup) ----
+    pol_zero_tile(X, pol_ldx(K0), tid);
+    __syncthreads();
+    tile.fill(A(), X, p, rq, rows);
+    f32x4 o[1][POL_MT];
+    const float ls = pol_trunk<BF, A>(X, K0, nw, w1, (wave == 0 && net == 0) ? io.params + 2 * pol_net_floats<A>(K0) : nullptr, wave, lane, o);
+    if (wave == 0) pol_act_sample<SQUASH>(io, p, o, ls, lane);
+  }
+  tile.finish(p, rq);
+  pol_act_end(io, p);
+}
+
+// host side.  kernel_of(PolArch<..>{}): the act kernel's instantiation for that triple, `void (*)(PolActArgs<IO>)`; (h1, h2, h3) a
+// listed triple (the caller has checked).  Above 64 KB of LDS a kernel must be told before its first launch:
+template <class KernelOf>
+hipError_t pol_act_prepare(int h1, int h2, int h3, size_t lds, KernelOf kernel_of) {
+  if (lds <= 64 * 1024) return hipSuccess;
+  hipError_t e = hipErrorInvalidValue;
+  pol_arch_visit(h1, h2, h3, [&](auto a) {
+    e = hipFuncSetAttribute((const void*)kernel_of(a), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+  });
+  return e;
+}
+// grid (ceil(ne / 16), 2), POL_THREADS
+template <class IO, class KernelOf>
+void pol_act_launch(int h1, int h2, int h3, const PolActArgs<IO>& pa, size_t lds, hipStream_t st, KernelOf kernel_of) {
+  const dim3 grid((pa.ne + POL_ROWS - 1) / POL_ROWS, 2), block(POL_THREADS);
+  pol_arch_visit(h1, h2, h3, [&](auto a) { hipLaunchKernelGGL(kernel_of(a), grid, block, lds, st, pa); });
 }
 
 // ---- the frame of an EVAL launch (k9_policy_eval, k17_squash_eval): grid (ceil(M / 16), nets launched), no environment, no

@@ -3,9 +3,9 @@
 // scripts/run.py:332-357): the last `frames` observations of an environment are ONE input row, so that a feed-forward policy sees how
 // the obstacles move.
 //
-// k12_stacked_act<A> is k6_policy_act<A, false> with another input tile: both are written from the same pieces of auv_policy_forward.h --
-// the frame of an act launch (rollout position, transition, sampling epilogue, counters) and the forward pass -- and this file holds
-// only the history's step and the loader that reads the ring.  A row has frames * obs_dim columns; columns
+// k12_stacked_act<A> is k6_policy_act<A, false> with another input tile: both are pol_act_body (auv_policy_forward.h, which states the
+// Tile contract), and this file holds only StackTile -- the history's step, the loader that reads the ring, the tagged store.  A row
+// has frames * obs_dim columns; columns
 // [j * obs_dim, (j + 1) * obs_dim) hold the observation of
 // j steps ago, j = 0 the environment's observation buffer as it stands now, and zeros where the episode is younger than j steps
 // (stable-baselines zeroes the stack at a reset).  NEWEST FIRST: a column permutation of stable-baselines' newest-last order, chosen so
@@ -36,12 +36,6 @@
 #include "auv_policy_forward.h"
 
 namespace {
-
-struct StackArgs {
-  auv_policy_stack_t s;
-  int32_t e0, ne;
-  long long t_host, gstep_host;      // as k6's PolicyArgs: >= 0 the host names position and generator step, -1 they live in io.ctr
-};
 
 // the history's step for one environment: (pos, age) -> (pos', age')
 __device__ __forceinline__ void stk_advance(const int2 s, const bool done, const int F, const int tag, int& pos, int& age) {
@@ -87,55 +81,50 @@ __device__ __forceinline__ void stk_fill_ring(float* X, const int ldx, const auv
   }
 }
 
-// The launch's body, written once for every hidden-width triple A (PolArch, auv_policy_mfma.h).
-template <class A>
-__device__ __forceinline__ void stacked_act_body(const StackArgs& pa) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  const auv_policy_io_t& io = pa.s.io;
-  const int tid = threadIdx.x, wave = tid / AUV_WAVE, lane = tid % AUV_WAVE;
-  const int net = blockIdx.y;
-  const int F = pa.s.frames;
-  const int K0 = F * io.obs_dim, K0p = pol_pad16(K0);            // the net's input width
-  float* X = (float*)smem;
-  const int ldx = pol_ldx(K0);
-  int32_t* S = (int32_t*)pol_tiles_end<A>(X, K0);                            // [ROWS][2]: pos', age'
-  const PolAct p = pol_act_begin(io, pa.e0, pa.ne, pa.t_host, pa.gstep_host);
-  const int tag = (int)(p.gstep % 0x7fffffull) + 1;              // 1 .. 2^23 - 1: tag << 8 stays below 2^31, the word stays positive
-  bool keep = false;                                             // this thread stores its row's (pos', age') at the end
-  int my_pos = 0, my_age = 0;
-  if (p.act) {
-    const PolNet nw = pol_net_ptrs<A>(io.params + (size_t)net * pol_net_floats<A>(K0), K0);
-    PolW<A::H1 / 16, false> w1;
-    pol_prefetch(w1, nw.W1, nw.b1, K0p, wave, lane);               // (in flight while the tile is formed)
-    const int rows = (p.cnt - p.r0 < POL_ROWS) ? p.cnt - p.r0 : POL_ROWS;
-    // ---- the history's step of the tile's rows: requested ahead of the barrier behind the zeroing ----
+// the stacked tile (Tile contract: auv_policy_forward.h): frames * obs_dim columns, (pos', age') of the tile's rows in LDS behind
+// the tiles, the thread's own row's kept for the store at the end
+struct StackTile : PolPlainTile {
+  const auv_policy_stack_t& s;
+  struct Req {
+    bool keep = false;               // this thread stores its row's (pos', age') at the end
+    int pos = 0, age = 0, tag;       // tag 1 .. 2^23 - 1: tag << 8 stays below 2^31, the word stays positive
+    __device__ __forceinline__ explicit Req(const PolAct& p) : tag((int)(p.gstep % 0x7fffffull) + 1) {}
+  };
+  __device__ __forceinline__ explicit StackTile(const auv_policy_stack_t& s_) : PolPlainTile(s_.io), s(s_) {}
+  __device__ __forceinline__ int width() const { return s.frames * io.obs_dim; }
+  // the history's step of the tile's rows
+  template <class A>
+  __device__ __forceinline__ void request(A, Req& r, float* X, const PolAct& p, const int rows) const {
+    const int F = s.frames, tid = threadIdx.x;
+    int32_t* S = (int32_t*)pol_tiles_end<A>(X, width());           // [ROWS][2]: pos', age'
     if (F > 1 && tid < rows) {
-      const int e = pa.e0 + p.r0 + tid;
-      const int2 s = *(const int2*)(pa.s.stk + 2 * (size_t)e);
+      const int e = p.e0 + p.r0 + tid;
+      const int2 w = *(const int2*)(s.stk + 2 * (size_t)e);
       const bool d = io.done_in[e] != 0;
-      stk_advance(s, d, F, tag, my_pos, my_age);
-      S[2 * tid] = my_pos, S[2 * tid + 1] = my_age;
-      keep = net == 0;
+      stk_advance(w, d, F, r.tag, r.pos, r.age);
+      S[2 * tid] = r.pos, S[2 * tid + 1] = r.age;
+      r.keep = blockIdx.y == 0;
     }
-    // ---- input tile -> LDS (zero padded), and into the rollout (policy workgroup) ----
-    pol_zero_tile(X, ldx, tid);
-    __syncthreads();
-    float* dstO = pol_act_obs_out(io, p, K0);
-    if (F == 1) pol_act_fill_obs(X, io, p, dstO, rows);
-    else if ((io.obs_dim & 1) == 0) stk_fill_ring<float2>(X, ldx, pa.s, S, dstO, pa.e0 + p.r0, rows, net == 0, tid);
-    else stk_fill_ring<float>(X, ldx, pa.s, S, dstO, pa.e0 + p.r0, rows, net == 0, tid);
-    f32x4 o[1][POL_MT];
-    const float ls = pol_trunk<false, A>(X, K0, nw, w1, (wave == 0 && net == 0) ? io.params + 2 * pol_net_floats<A>(K0) : nullptr, wave, lane, o);
-    if (wave == 0) pol_act_sample(io, p, o, ls, lane);
   }
-  if (keep) *(int2*)(pa.s.stk + 2 * (size_t)(pa.e0 + p.r0 + tid)) = make_int2(my_pos | (tag << 8), my_age);
-  pol_act_end(io, p);
-}
+  template <class A>
+  __device__ __forceinline__ void fill(A, float* X, const PolAct& p, const Req&, const int rows) const {
+    const int K0 = width(), ldx = pol_ldx(K0), tid = threadIdx.x;
+    float* dstO = pol_act_obs_out(io, p, K0);
+    const int32_t* S = (const int32_t*)pol_tiles_end<A>(X, K0);
+    const bool store = blockIdx.y == 0;
+    if (s.frames == 1) pol_act_fill_obs(X, io, p, dstO, rows);
+    else if ((io.obs_dim & 1) == 0) stk_fill_ring<float2>(X, ldx, s, S, dstO, p.e0 + p.r0, rows, store, tid);
+    else stk_fill_ring<float>(X, ldx, s, S, dstO, p.e0 + p.r0, rows, store, tid);
+  }
+  __device__ __forceinline__ void finish(const PolAct& p, const Req& r) const {
+    if (r.keep) *(int2*)(s.stk + 2 * (size_t)(p.e0 + p.r0 + threadIdx.x)) = make_int2(r.pos | (r.tag << 8), r.age);
+  }
+};
 
 // grid (ceil(ne / 16), 2): blockIdx.y = 0 the policy net, 1 the value net
 template <class A>
-__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k12_stacked_act(StackArgs pa) {   // (two workgroups per CU, as k6)
-  stacked_act_body<A>(pa);
+__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k12_stacked_act(PolActArgs<auv_policy_stack_t> pa) {   // (two workgroups per CU, as k6)
+  pol_act_body<A, false, false>(pa, StackTile(pa.io));
 }
 
 // ---- the history update alone: stacked rows out[ne][ldx] of environments [e0, e0 + ne), no network ----
@@ -210,24 +199,16 @@ __global__ void __launch_bounds__(STK_THREADS) k12_stack_frames(FramesArgs fa) {
 // (h1, h2, h3): a listed hidden-width triple (the caller has checked)
 size_t auv_policy_stacked_lds_bytes(int h1, int h2, int h3, int width) { return stk_lds_bytes_h(h1, h2, h3, width); }
 
+static auto k12_act = [](auto a) { return k12_stacked_act<decltype(a)>; };
+
 hipError_t auv_policy_stacked_prepare(int h1, int h2, int h3, int width) {
-  const size_t b = stk_lds_bytes_h(h1, h2, h3, width);
-  if (b <= 64 * 1024) return hipSuccess;
-  hipError_t e = hipErrorInvalidValue;
-  pol_arch_visit(h1, h2, h3, [&](auto a) {
-    e = hipFuncSetAttribute((const void*)k12_stacked_act<decltype(a)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
-  });
-  return e;
+  return pol_act_prepare(h1, h2, h3, stk_lds_bytes_h(h1, h2, h3, width), k12_act);
 }
 
 void auv_launch_policy_stacked(int h1, int h2, int h3, const auv_policy_stack_t& s, int e0, int ne, hipStream_t st, long long t_host,
                                long long gstep_host) {
-  StackArgs pa;
-  pa.s = s, pa.e0 = e0, pa.ne = ne;
-  pa.t_host = t_host, pa.gstep_host = gstep_host;
-  const dim3 grid((ne + POL_ROWS - 1) / POL_ROWS, 2), block(POL_THREADS);
-  const size_t lds = stk_lds_bytes_h(h1, h2, h3, s.frames * s.io.obs_dim);
-  pol_arch_visit(h1, h2, h3, [&](auto a) { hipLaunchKernelGGL((k12_stacked_act<decltype(a)>), grid, block, lds, st, pa); });
+  const PolActArgs<auv_policy_stack_t> pa = {s, e0, ne, t_host, gstep_host};
+  pol_act_launch(h1, h2, h3, pa, stk_lds_bytes_h(h1, h2, h3, s.frames * s.io.obs_dim), st, k12_act);
 }
 
 void auv_launch_stack_frames(const float* obs, const uint8_t* done, float* hist, int32_t* stk, float* out, long long ldx, int e0, int ne,

@@ -10,8 +10,8 @@
 // leaves the moments of its RAW rows as a partial per tile; one fold behind the rollout merges the partials in a fixed order.  The
 // rewards of a rollout are scaled behind it, by the deviation that already holds that rollout's returns.
 //
-// k16_norm_act<A> is k6_policy_act<A, false> with another tile step: both are written from the same pieces of auv_policy_forward.h --
-// the frame of an act launch and the forward pass -- and this file holds only what goes between the tile's fill and the trunk.  The raw
+// k16_norm_act<A> is k6_policy_act<A, false> with another tile step: both are pol_act_body (auv_policy_forward.h, which states the
+// Tile contract), and this file holds only NormTile -- what goes between the tile's fill and the trunk.  The raw
 // tile goes to LDS (pol_act_fill_obs without the copy into O); behind a barrier thread c < obs_dim owns column c of the tile's
 // rows <= 16 rows, in row order 0 .. rows - 1 (consecutive threads on consecutive LDS words: no bank conflict):
 //   moments      s = the sequential f32 sum, m = s / rows, M2 = sum of (x_r - m)^2 sequential; every operation separately rounded
@@ -35,12 +35,6 @@
 #include "auv_policy_forward.h"
 
 namespace {
-
-struct NormArgs {
-  auv_policy_norm_t s;
-  int32_t e0, ne;
-  long long t_host, gstep_host;      // as k6's PolicyArgs: >= 0 the host names position and generator step, -1 they live in io.ctr
-};
 
 // THE normalising expression: the act launch and k16_norm_rows give the same bits
 __device__ __forceinline__ float norm_apply(const float x, const float mean, const float inv_std, const float clip) {
@@ -69,50 +63,43 @@ __device__ __forceinline__ void norm_tile_column(float* col, const int ldx, cons
   if (part_m) part_m[0] = m, part_m[K0] = M2;
 }
 
-// The launch's body, written once for every hidden-width triple A (PolArch, auv_policy_mfma.h).
-template <class A>
-__device__ __forceinline__ void norm_act_body(const NormArgs& pa) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  const auv_policy_io_t& io = pa.s.io;
-  const int tid = threadIdx.x, wave = tid / AUV_WAVE, lane = tid % AUV_WAVE;
-  const int net = blockIdx.y;
-  const int K0 = io.obs_dim, K0p = pol_pad16(K0);
-  float* X = (float*)smem;
-  const int ldx = pol_ldx(K0);
-  const PolAct p = pol_act_begin(io, pa.e0, pa.ne, pa.t_host, pa.gstep_host);
-  if (p.act) {
-    const PolNet nw = pol_net_ptrs<A>(io.params + (size_t)net * pol_net_floats<A>(K0), K0);
-    PolW<A::H1 / 16, false> w1;
-    pol_prefetch(w1, nw.W1, nw.b1, K0p, wave, lane);               // (in flight while the tile is formed)
-    const int rows = (p.cnt - p.r0 < POL_ROWS) ? p.cnt - p.r0 : POL_ROWS;
-    // (mean, inv_std) of this thread's first column: requested ahead of the barrier behind the zeroing
-    float2 tb = make_float2(0.0f, 1.0f);
-    if (tid < K0) tb = *(const float2*)(pa.s.table + 2 * tid);
-    // ---- raw tile -> LDS (zero padded) ----
-    pol_zero_tile(X, ldx, tid);
-    __syncthreads();
+// the normalising tile (Tile contract: auv_policy_forward.h): the plain tile, raw, and behind a barrier of its own the column step
+struct NormTile : PolPlainTile {
+  const auv_policy_norm_t& s;
+  struct Req {
+    float2 tb;                       // (mean, inv_std) of this thread's first column
+    __device__ __forceinline__ explicit Req(const PolAct&) {}
+  };
+  __device__ __forceinline__ explicit NormTile(const auv_policy_norm_t& s_) : PolPlainTile(s_.io), s(s_) {}
+  template <class A>
+  __device__ __forceinline__ void request(A, Req& r, float*, const PolAct&, const int) const {
+    const int tid = threadIdx.x;
+    r.tb = make_float2(0.0f, 1.0f);
+    if (tid < io.obs_dim) r.tb = *(const float2*)(s.table + 2 * tid);
+  }
+  template <class A>
+  __device__ __forceinline__ void fill(A, float* X, const PolAct& p, const Req& r, const int rows) const {
+    const int K0 = io.obs_dim, ldx = pol_ldx(K0), tid = threadIdx.x, net = blockIdx.y;
+    // ---- raw tile -> LDS ----
     pol_act_fill_obs(X, io, p, nullptr, rows);
     __syncthreads();
     // ---- moments of the raw rows, the normalised rows into the tile and the rollout ----
+    float2 tb = r.tb;
     float* dstO = pol_act_obs_out(io, p, K0);
-    const size_t slot = (size_t)p.t * (size_t)pa.s.part_ld + (size_t)pa.s.part_base + blockIdx.x;
-    float* part_m = net == 0 ? pa.s.part + slot * 2 * (size_t)K0 : nullptr;
+    const size_t slot = (size_t)p.t * (size_t)s.part_ld + (size_t)s.part_base + blockIdx.x;
+    float* part_m = net == 0 ? s.part + slot * 2 * (size_t)K0 : nullptr;
     for (int c = tid; c < K0; c += POL_THREADS) {
-      if (c != tid) tb = *(const float2*)(pa.s.table + 2 * c);
-      norm_tile_column(X + c, ldx, rows, K0, tb, pa.s.clip_obs, dstO ? dstO + c : nullptr, part_m ? part_m + c : nullptr);
+      if (c != tid) tb = *(const float2*)(s.table + 2 * c);
+      norm_tile_column(X + c, ldx, rows, K0, tb, s.clip_obs, dstO ? dstO + c : nullptr, part_m ? part_m + c : nullptr);
     }
-    if (net == 0 && tid == 0) pa.s.pcnt[slot] = rows;
-    f32x4 o[1][POL_MT];
-    const float ls = pol_trunk<false, A>(X, K0, nw, w1, (wave == 0 && net == 0) ? io.params + 2 * pol_net_floats<A>(K0) : nullptr, wave, lane, o);
-    if (wave == 0) pol_act_sample(io, p, o, ls, lane);
+    if (net == 0 && tid == 0) s.pcnt[slot] = rows;
   }
-  pol_act_end(io, p);
-}
+};
 
 // grid (ceil(ne / 16), 2): blockIdx.y = 0 the policy net, 1 the value net
 template <class A>
-__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k16_norm_act(NormArgs pa) {   // (two workgroups per CU, as k6)
-  norm_act_body<A>(pa);
+__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k16_norm_act(PolActArgs<auv_policy_norm_t> pa) {   // (two workgroups per CU, as k6)
+  pol_act_body<A, false, false>(pa, NormTile(pa.io));
 }
 
 // ---- the normalising expression on arbitrary rows, no network: out[j][c] = norm(X[idx ? idx[j] : j][c]) ----
@@ -234,24 +221,16 @@ __global__ void __launch_bounds__(256) k16_return_scale(const float* R, float* o
 }  // namespace
 
 // (h1, h2, h3): a listed hidden-width triple (the caller has checked); the LDS is k6's (auv_policy_lds_bytes)
+static auto k16_act = [](auto a) { return k16_norm_act<decltype(a)>; };
+
 hipError_t auv_policy_norm_prepare(int h1, int h2, int h3, int obs_dim) {
-  const size_t b = pol_lds_bytes_h(h1, h2, h3, obs_dim);
-  if (b <= 64 * 1024) return hipSuccess;
-  hipError_t e = hipErrorInvalidValue;
-  pol_arch_visit(h1, h2, h3, [&](auto a) {
-    e = hipFuncSetAttribute((const void*)k16_norm_act<decltype(a)>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
-  });
-  return e;
+  return pol_act_prepare(h1, h2, h3, pol_lds_bytes_h(h1, h2, h3, obs_dim), k16_act);
 }
 
 void auv_launch_policy_norm(int h1, int h2, int h3, const auv_policy_norm_t& s, int e0, int ne, hipStream_t st, long long t_host,
                             long long gstep_host) {
-  NormArgs pa;
-  pa.s = s, pa.e0 = e0, pa.ne = ne;
-  pa.t_host = t_host, pa.gstep_host = gstep_host;
-  const dim3 grid((ne + POL_ROWS - 1) / POL_ROWS, 2), block(POL_THREADS);
-  const size_t lds = pol_lds_bytes_h(h1, h2, h3, s.io.obs_dim);
-  pol_arch_visit(h1, h2, h3, [&](auto a) { hipLaunchKernelGGL((k16_norm_act<decltype(a)>), grid, block, lds, st, pa); });
+  const PolActArgs<auv_policy_norm_t> pa = {s, e0, ne, t_host, gstep_host};
+  pol_act_launch(h1, h2, h3, pa, pol_lds_bytes_h(h1, h2, h3, s.io.obs_dim), st, k16_act);
 }
 
 void auv_launch_norm_rows(const float* X, const int64_t* idx, long long ldx, const float* table, float clip_obs, float* out, long long ldo,

@@ -27,53 +27,28 @@
 
 namespace {
 
-// (LDS: pol_lds_x_floats / pol_lds_bytes in auv_policy_mfma.h; the forward pass and the frame of an act launch -- rollout position,
-// transition, sampling epilogue, counters: auv_policy_forward.h, shared with k9, k11 and k12)
-struct PolicyArgs {
-  auv_policy_io_t io;
-  int32_t e0, ne;
-  long long t_host, gstep_host;      // >= 0: the host names the rollout position and the generator's step (auv_policy_rollout: a plain
-                                     // loop of launches); -1: both live on the device (io.ctr) and the launch moves them on itself
-};
-
-// The launch's body, written once for every hidden-width triple A (PolArch, auv_policy_mfma.h).
-template <class A, bool BF>
-__device__ __forceinline__ void policy_act_body(const PolicyArgs& pa) {
-  extern __shared__ __align__(16) unsigned char smem[];
-  const auv_policy_io_t& io = pa.io;
-  const int tid = threadIdx.x, wave = tid / AUV_WAVE, lane = tid % AUV_WAVE;
-  const int net = blockIdx.y;
-  const int K0 = io.obs_dim, K0p = pol_pad16(K0);
-  float* X = (float*)smem;
-  const PolAct p = pol_act_begin(io, pa.e0, pa.ne, pa.t_host, pa.gstep_host);
-  if (p.act) {
-    PolNet nw = pol_net_ptrs<A>(io.params + (size_t)net * pol_net_floats<A>(K0), K0);
+// (LDS: pol_lds_x_floats / pol_lds_bytes in auv_policy_mfma.h; the forward pass, the body of an act launch and its Tile contract:
+// auv_policy_forward.h.  This launch forms the plain tile; all this file adds is where the bf16 weights lie.)
+template <bool BF>
+struct PolicyTile : PolPlainTile {
+  using PolPlainTile::PolPlainTile;
+  template <class A>
+  __device__ __forceinline__ void weights(A, PolNet& nw, const int net, const int K0p) const {
     if (BF) {
       // bf16 weights: the four matrices of a net back to back, half the floats each (biases and log_std stay in `params`)
-      const float* Q = (const float*)io.params_bf16 + (size_t)net * (pol_net_floats<A>(K0) - A::H1 - A::H2 - A::H3 - POL_OUT) / 2;
+      const float* Q = (const float*)io.params_bf16 + (size_t)net * (pol_net_floats<A>(io.obs_dim) - A::H1 - A::H2 - A::H3 - POL_OUT) / 2;
       nw.W1 = Q;
       nw.W2 = nw.W1 + (size_t)A::H1 * K0p / 2;
       nw.W3 = nw.W2 + (size_t)A::H2 * A::H1 / 2;
       nw.W4 = nw.W3 + (size_t)A::H3 * A::H2 / 2;
     }
-    PolW<A::H1 / 16, BF> w1;
-    pol_prefetch(w1, nw.W1, nw.b1, K0p, wave, lane);                 // (in flight while the observation tile is fetched)
-    // ---- observation tile -> LDS (zero padded), and into the rollout (policy workgroup) ----
-    const int rows = (p.cnt - p.r0 < POL_ROWS) ? p.cnt - p.r0 : POL_ROWS;
-    pol_zero_tile(X, pol_ldx(K0), tid);
-    __syncthreads();
-    pol_act_fill_obs(X, io, p, pol_act_obs_out(io, p, K0), rows);
-    f32x4 o[1][POL_MT];
-    const float ls = pol_trunk<BF, A>(X, K0, nw, w1, (wave == 0 && net == 0) ? io.params + 2 * pol_net_floats<A>(K0) : nullptr, wave, lane, o);
-    if (wave == 0) pol_act_sample(io, p, o, ls, lane);
   }
-  pol_act_end(io, p);
-}
+};
 
 // grid (ceil(ne / 16), 2): blockIdx.y = 0 the policy net, 1 the value net.  BF (bf16 weights) is instantiated for the reference's triple only
 template <class A, bool BF>
-__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k6_policy_act(PolicyArgs pa) {   // (two workgroups per CU)
-  policy_act_body<A, BF>(pa);
+__global__ void __launch_bounds__(POL_THREADS, (POL_WAVES >= 8 ? 4 : 2)) k6_policy_act(PolActArgs<auv_policy_io_t> pa) {   // (two workgroups per CU)
+  pol_act_body<A, BF, false>(pa, PolicyTile<BF>(pa.io));
 }
 
 // Generalised advantage estimation over a rollout (what stable-baselines' PPO2 runner does on the host after n_steps,
@@ -109,26 +84,19 @@ size_t auv_policy_param_floats_impl(int h1, int h2, int h3, int obs_dim) { retur
 size_t auv_policy_lds_bytes(int h1, int h2, int h3, int obs_dim) { return pol_lds_bytes_h(h1, h2, h3, obs_dim); }
 
 // (the reference's triple also runs on bf16 weights: the launch picks that variant by io.params_bf16, which is NULL for every other triple)
+static auto k6_f32 = [](auto a) { return k6_policy_act<decltype(a), false>; };
+static auto k6_bf16 = [](auto) { return k6_policy_act<PolArchRef, true>; };
+
 hipError_t auv_policy_prepare(int h1, int h2, int h3, int obs_dim) {
   const size_t b = pol_lds_bytes_h(h1, h2, h3, obs_dim);
-  if (b <= 64 * 1024) return hipSuccess;
-  hipError_t e = hipErrorInvalidValue;
-  pol_arch_visit(h1, h2, h3, [&](auto a) {
-    e = hipFuncSetAttribute((const void*)k6_policy_act<decltype(a), false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
-  });
+  const hipError_t e = pol_act_prepare(h1, h2, h3, b, k6_f32);
   if (e != hipSuccess || !pol_arch_is_ref(h1, h2, h3)) return e;
-  return hipFuncSetAttribute((const void*)k6_policy_act<PolArchRef, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)b);
+  return pol_act_prepare(h1, h2, h3, b, k6_bf16);
 }
 
 void auv_launch_policy(int h1, int h2, int h3, const auv_policy_io_t& io, int e0, int ne, hipStream_t st, long long t_host, long long gstep_host) {
-  PolicyArgs pa;
-  pa.io = io, pa.e0 = e0, pa.ne = ne;
-  pa.t_host = t_host, pa.gstep_host = gstep_host;
-  const dim3 grid((ne + POL_ROWS - 1) / POL_ROWS, 2), block(POL_THREADS);
+  const PolActArgs<auv_policy_io_t> pa = {io, e0, ne, t_host, gstep_host};
   const size_t lds = pol_lds_bytes_h(h1, h2, h3, io.obs_dim);
-  if (io.params_bf16 && pol_arch_is_ref(h1, h2, h3)) {
-    hipLaunchKernelGGL((k6_policy_act<PolArchRef, true>), grid, block, lds, st, pa);
-    return;
-  }
-  pol_arch_visit(h1, h2, h3, [&](auto a) { hipLaunchKernelGGL((k6_policy_act<decltype(a), false>), grid, block, lds, st, pa); });
+  if (io.params_bf16 && pol_arch_is_ref(h1, h2, h3)) pol_act_launch(h1, h2, h3, pa, lds, st, k6_bf16);
+  else pol_act_launch(h1, h2, h3, pa, lds, st, k6_f32);
 }

@@ -469,6 +469,14 @@ class FusedActorCritic:
                     s.io = self._ios[i]
                     s.table, s.part, s.pcnt = normalize.table.data_ptr(), normalize.part.data_ptr(), normalize.pcnt.data_ptr()
                     s.part_ld, s.part_base, s.clip_obs = normalize.part_ld, normalize.part_base[i], normalize.clip_obs
+        # the entries act() and rollout() call, resolved once: squash first, then norm, then stacked, then plain; the _arch entries
+        # (with the widths as one more argument behind the io block) only for other widths than the default, or on request
+        variant, self._io = (("_squash", self._ios) if self.squash else ("_norm", self._nios) if self._nios is not None
+                             else ("_stacked", self._sios) if self.frames > 1 else ("", self._ios))
+        suffix = variant + ("_arch" if self._arch is not None else "")
+        self._act_name, self._rollout_name = "auv_policy_act" + suffix, "auv_policy_rollout" + suffix
+        self._act_fn, self._rollout_fn = getattr(_LIB, self._act_name), getattr(_LIB, self._rollout_name)
+        self._arch_arg = () if self._arch is None else (C.byref(self._arch),)
         self.refresh()
 
     # ------------------------------------------------------------------------------ weights
@@ -506,29 +514,7 @@ class FusedActorCritic:
         slice's rows of `self.actions` and the transition at the chain's position t, then moves t on."""
         lo, cnt = self.slices[i]
         st = self.env._sub_streams[i] if stream is None else stream
-        if self.squash:
-            if self._arch is not None:
-                _check(_LIB.auv_policy_act_squash_arch(self.env._h, lo, cnt, C.byref(self._ios[i]), C.byref(self._arch), C.c_void_p(st.cuda_stream)),
-                       "auv_policy_act_squash_arch")
-            else:
-                _check(_LIB.auv_policy_act_squash(self.env._h, lo, cnt, C.byref(self._ios[i]), C.c_void_p(st.cuda_stream)), "auv_policy_act_squash")
-        elif self._nios is not None:
-            if self._arch is not None:
-                _check(_LIB.auv_policy_act_norm_arch(self.env._h, lo, cnt, C.byref(self._nios[i]), C.byref(self._arch), C.c_void_p(st.cuda_stream)),
-                       "auv_policy_act_norm_arch")
-            else:
-                _check(_LIB.auv_policy_act_norm(self.env._h, lo, cnt, C.byref(self._nios[i]), C.c_void_p(st.cuda_stream)), "auv_policy_act_norm")
-        elif self._arch is not None:
-            a = C.byref(self._arch)
-            if self.frames > 1:
-                _check(_LIB.auv_policy_act_stacked_arch(self.env._h, lo, cnt, C.byref(self._sios[i]), a, C.c_void_p(st.cuda_stream)),
-                       "auv_policy_act_stacked_arch")
-            else:
-                _check(_LIB.auv_policy_act_arch(self.env._h, lo, cnt, C.byref(self._ios[i]), a, C.c_void_p(st.cuda_stream)), "auv_policy_act_arch")
-        elif self.frames > 1:
-            _check(_LIB.auv_policy_act_stacked(self.env._h, lo, cnt, C.byref(self._sios[i]), C.c_void_p(st.cuda_stream)), "auv_policy_act_stacked")
-        else:
-            _check(_LIB.auv_policy_act(self.env._h, lo, cnt, C.byref(self._ios[i]), C.c_void_p(st.cuda_stream)), "auv_policy_act")
+        _check(self._act_fn(self.env._h, lo, cnt, C.byref(self._io[i]), *self._arch_arg, C.c_void_p(st.cuda_stream)), self._act_name)
         self._t[i] = min(self._t[i] + 1, self.T + 1)
         self._g[i] += 1
 
@@ -540,43 +526,9 @@ class FusedActorCritic:
         env = self.env
         k = len(self.slices)
         t0, g0 = (C.c_int64 * k)(*self._t), (C.c_int64 * k)(*self._g)
-        if self.squash:
-            tail = (C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()), int(n_steps),
-                    int(bool(flush)), t0, g0)
-            if self._arch is not None:
-                _check(_LIB.auv_policy_rollout_squash_arch(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._ios,
-                                                           C.byref(self._arch), *tail), "auv_policy_rollout_squash_arch")
-            else:
-                _check(_LIB.auv_policy_rollout_squash(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._ios, *tail),
-                       "auv_policy_rollout_squash")
-        elif self._nios is not None:
-            tail = (C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()), int(n_steps),
-                    int(bool(flush)), t0, g0)
-            if self._arch is not None:
-                _check(_LIB.auv_policy_rollout_norm_arch(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._nios,
-                                                         C.byref(self._arch), *tail), "auv_policy_rollout_norm_arch")
-            else:
-                _check(_LIB.auv_policy_rollout_norm(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._nios, *tail),
-                       "auv_policy_rollout_norm")
-        elif self._arch is not None:
-            a = C.byref(self._arch)
-            tail = (C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()), int(n_steps),
-                    int(bool(flush)), t0, g0)
-            if self.frames > 1:
-                _check(_LIB.auv_policy_rollout_stacked_arch(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._sios, a, *tail),
-                       "auv_policy_rollout_stacked_arch")
-            else:
-                _check(_LIB.auv_policy_rollout_arch(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._ios, a, *tail),
-                       "auv_policy_rollout_arch")
-        elif self.frames > 1:
-            _check(_LIB.auv_policy_rollout_stacked(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._sios,
-                                                   C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()),
-                                                   C.c_void_p(env.done.data_ptr()), int(n_steps), int(bool(flush)), t0, g0),
-                   "auv_policy_rollout_stacked")
-        else:
-            _check(_LIB.auv_policy_rollout(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._ios,
-                                           C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()),
-                                           C.c_void_p(env.done.data_ptr()), int(n_steps), int(bool(flush)), t0, g0), "auv_policy_rollout")
+        _check(self._rollout_fn(env._h, env.sub_batches, env._bounds_c, env._streams_c, self._io, *self._arch_arg,
+                                C.c_void_p(env.obs.data_ptr()), C.c_void_p(env.reward.data_ptr()), C.c_void_p(env.done.data_ptr()),
+                                int(n_steps), int(bool(flush)), t0, g0), self._rollout_name)
         n_launch = int(n_steps) + int(bool(flush))
         for i in range(k):
             self._t[i] = min(self._t[i] + n_launch, self.T + 1)

@@ -183,7 +183,7 @@ def _by_arch(kernels, body):
     out = {}
     for h in cases.HIDDEN:
         tag = "PolArchILi%dELi%dELi%dEE" % h
-        k = [x for x in kernels if body in x["name"] and tag in x["name"] and "Lb1EEEvNS_10PolicyArgs" not in x["name"]]
+        k = [x for x in kernels if body in x["name"] and tag in x["name"] and "EEELb1E" not in x["name"]]
         assert len(k) == 1, (body, h, [x["name"] for x in kernels])
         out[h] = k[0]
     return out
